@@ -7,7 +7,10 @@ level) -> Gene_counts -> EM #1 -> exon->gene hand-off -> EM #2 -> abundances.
 N > 1: one process per GPU (torchrun), every rank types its own synthetic sample of the same locus (weak
 scaling, no data-path collective); the shared locus index is broadcast once from rank 0 over RCCL.
 
-Prints ONE JSON line on rank 0 (see DESIGN.md section 6 for the byte model behind `roofline`).
+Prints ONE JSON line on rank 0 (see DESIGN.md section 6 for the byte model behind `roofline`).  A plain run sets up, warms up,
+times the steps and prints the line; `--full` adds everything else the benchmark measures or checks (the host front end's batch
+against the device's, the file -> result legs, cpu_baseline, samples in flight, the bit-identical EM, the other workloads).
+`--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (float64).
 """
 import argparse
 import json
@@ -98,7 +101,7 @@ def parse_args():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-e2e", action="store_true", help="skip the file -> result measurements (SAM text and BAM; the N-process leg; the workloads' file legs)")
     ap.add_argument("--e2e-procs", default="1,2,4,8",
-                    help="file -> result with N processes sharing GPU 0 (one sample stream each): the host-scaling leg of the default run; '' skips it")
+                    help="file -> result with N processes sharing GPU 0 (one sample stream each): the host-scaling leg of the --full run; '' skips it")
     ap.add_argument("--e2e-child", default=None, help=argparse.SUPPRESS)      # internal: one process of that leg (a JSON job description)
     ap.add_argument("--no-kernel-timing", action="store_true", help="skip the per-launch HIP events (profiling runs)")
     ap.add_argument("--workload", choices=["configs1", "class1", "panel64", "config0_dropin", "codis_dropin", "sample6"], default="configs1",
@@ -119,7 +122,7 @@ def parse_args():
                     help="class1: every rank of a sharded locus also types the whole locus alone and compares (`sharded_equals_unsharded`)")
     ap.add_argument("--no-in-flight", action="store_true", help="skip the side measurement with 2 / 3 samples in flight")
     ap.add_argument("--no-workloads", action="store_true", help="default workload only: skip the class1 / panel64 runs that follow it")
-    ap.add_argument("--workloads", action="store_true", help="run class1 / panel64 behind the default workload also with more than one rank "
+    ap.add_argument("--workloads", action="store_true", help="--full: run class1 / panel64 behind the default workload also with more than one rank "
                                                                "(by default they are N = 1 legs, like cpu_baseline and e2e: the scaling run is about `value`)")
     ap.add_argument("--wl-steps", type=int, default=10, help="timed steps of the class1 / panel64 runs that follow the default workload")
     ap.add_argument("--em-exact", action="store_true",
@@ -131,7 +134,18 @@ def parse_args():
     ap.add_argument("--inflight", type=int, default=1,
                     help="samples typed concurrently per GPU (host threads with their own streams and class-row buffers; "
                          "the EM of one sample is a chain of short launches that leaves the GPU to the scoring of the next)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="configs1: also run what the headline does not need -- the host front end's check of the device batch, the "
+                         "file -> result legs (incl. --e2e-procs), cpu_baseline, samples in flight, the bit-identical EM and the other "
+                         "workloads (the --no-* options above switch single legs off again)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="configs1: write what the last timed step returned (counts, both EMs, gene_prob) as DIR/<name>.npy in float64")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.workload != "configs1":
+        ap.error("--dump-outputs covers the default workload (configs1) only")
+    return args
 
 
 COMM_FORCE = "auto"      # --comm: which exchange object the ranks of a sharded locus get (make_comm)
@@ -141,9 +155,10 @@ EM_MODE = False          # --em-exact: -1 = the reference's order of operations 
 
 def step(pl, batch, db, ev=None, stream=None, gate=None):
     """One pass of the hot path on `stream` (None = the default stream): ONE call into libhgx (hgx_type_dbatch) over the
-    piece batch resident in HBM.  `ev` = (compat begin, compat end, pairs begin, pairs end) events.  Returns the LocusResult."""
+    piece batch resident in HBM (`db`; the host `batch` may be None).  `ev` = (compat begin, compat end, pairs begin, pairs end)
+    events.  Returns the LocusResult."""
     res = htyping.LocusResult()
-    res.num_reads, res.num_pairs = batch.n_reads, batch.n_pairs
+    res.num_reads, res.num_pairs = db.n_reads, db.n_pairs
     return htyping._type_batch(pl, batch, res, True, dbatch=db, stream=stream, overlap=True, gate=gate, events=ev, em_fast=EM_MODE)
 
 
@@ -197,6 +212,23 @@ def run_steps(pl, batch, db, inflight, n_steps, ev_list, timing, local_rank):
     if state["err"] is not None:
         raise state["err"]
     return state["res"], state["t_em"], state["n_iter"], state["timing"]
+
+
+def dump_outputs(out_dir, res, pl):
+    """--dump-outputs: the LocusResult of the last timed step as float64 arrays, allele names as indices into pl.names (a few
+    hundred KB at configs[1])."""
+    os.makedirs(out_dir, exist_ok=True)
+    aidx = {n: i for i, n in enumerate(pl.names)}
+    arrs = {"reads_pairs": [res.num_reads, res.num_pairs],
+            "counts": res.counts,                                  # Gene_counts per allele index
+            "counts_order": res.counts_order,                      # allele indices in the reference's print order
+            "gene_prob_allele": [aidx[a] for a, _ in res.gene_prob], "gene_prob": [p for _, p in res.gene_prob]}
+    for k, em in enumerate(res.em):
+        arrs["em%d_stats" % k] = [em["n_classes"], em["n_iter"], em["remove_low"], em["use_length"]]
+        arrs["em%d_allele" % k] = [aidx[a] for a, _ in em["result"]]
+        arrs["em%d_abundance" % k] = [p for _, p in em["result"]]
+    for name, a in arrs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def cpu_baseline(loc, sam, n_pairs):
@@ -1381,7 +1413,8 @@ def main():
             dist.init_process_group("gloo")
         assert dist.get_world_size() == world
     pre = None
-    if (args.workload == "configs1" and world == 1 and not use_dist and not args.no_e2e and not args.no_cpu_baseline and args.e2e_procs.strip()):
+    if (args.full and args.workload == "configs1" and world == 1 and not use_dist and not args.no_e2e and not args.no_cpu_baseline
+            and args.e2e_procs.strip()):
         # the N-process host-scaling leg comes FIRST: its children start before this process has touched the GPU.  The sample
         # it makes is the one the rest of the run uses.
         loc0 = synth.make_hla_like_locus(n_alleles=args.alleles, n_vars=args.vars, seed=101)
@@ -1429,26 +1462,29 @@ def main():
         pl.index()
     sample = synth.pick_sample(loc, 101 + rank)
     sam = pre[1] if pre else synth.simulate_sam_fast(loc, sample, args.pairs, err_rate=args.err, seed=100 + rank)
-    t0 = time.perf_counter()
-    batch = pl.parse_sam(sam)                               # host front end: the pinned checker of the device front end
-    t_parse = time.perf_counter() - t0
+    batch, t_parse, fe_same = None, None, None
+    if args.full:
+        t0 = time.perf_counter()
+        batch = pl.parse_sam(sam)                           # host front end: the pinned checker of the device front end
+        t_parse = time.perf_counter() - t0
     # the batch the timed steps read is the one the DEVICE front end builds in HBM (record route); it must be the host's, byte for byte
     pl.parse_sam_dev(sam).close()                           # (warm-up: staging memory, locus tables)
     t0 = time.perf_counter()
     db = pl.parse_sam_dev(sam)
     t_parse_dev = time.perf_counter() - t0
     fe_route, fe_code = engine.front_last()
-    hb = db.to_host()
-    fe_same = all(getattr(hb, k).tobytes() == getattr(batch, k).tobytes() for k in ("pieces", "masks", "pair_off", "pair_ref")) and \
-        hb.n_reads == batch.n_reads
-    del hb
+    if batch is not None:
+        hb = db.to_host()
+        fe_same = all(getattr(hb, k).tobytes() == getattr(batch, k).tobytes() for k in ("pieces", "masks", "pair_off", "pair_ref")) and \
+            hb.n_reads == batch.n_reads
+        del hb
     inflight = max(1, args.inflight)
-    if rank != 0 or args.no_cpu_baseline or use_dist:
+    if rank != 0 or args.no_cpu_baseline or use_dist or not args.full:
         sam_keep = None
     else:
         sam_keep = sam
     rank_bam = None
-    if use_dist and not args.no_e2e:
+    if use_dist and args.full and not args.no_e2e:
         # every rank's own sample as a coordinate-sorted BAM file: the file -> result leg of the N-GPU line (below)
         import tempfile
         from hisatgenotype_amd import bamio
@@ -1476,11 +1512,13 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device=DIST_DEV)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
-        rr = torch.tensor([float(batch.n_reads)], dtype=torch.float64, device=DIST_DEV)
+        rr = torch.tensor([float(db.n_reads)], dtype=torch.float64, device=DIST_DEV)
         dist.all_reduce(rr, op=dist.ReduceOp.SUM)
         total_reads = float(rr.item())
     else:
-        total_reads = float(batch.n_reads)
+        total_reads = float(db.n_reads)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res, pl)
     e2e_ranks = None
     if rank_bam is not None:
         # N ranks, N GPUs, ONE host: every rank types its own BAM file through hgx_type_file, all at the same time
@@ -1513,7 +1551,7 @@ def main():
     # scale is a pool of processes over samples (/root/reference/hisatgenotype:613-665); one sample's step is a chain of ~70 short
     # dependent launches that leaves most of the chip idle, the next sample's scoring fills it.  Reported beside `value`, never as it.
     in_flight = None
-    if inflight == 1 and dist is None and not args.no_workloads and not args.no_in_flight:
+    if args.full and inflight == 1 and dist is None and not args.no_workloads and not args.no_in_flight:
         in_flight = {}
         for nf in (2, 3):
             n_st = 10 * nf
@@ -1523,12 +1561,12 @@ def main():
             run_steps(pl, batch, db, nf, n_st, None, False, local_rank)
             capi.sync()
             dt = time.perf_counter() - t0
-            in_flight[str(nf)] = {"steps": n_st, "ms_per_step": round(dt / n_st * 1e3, 3), "value": round(batch.n_reads * n_st / dt, 1)}
+            in_flight[str(nf)] = {"steps": n_st, "ms_per_step": round(dt / n_st * 1e3, 3), "value": round(db.n_reads * n_st / dt, 1)}
     # the same steps in the OTHER EM arithmetic, a few of them outside the timed region: `value` times the library's default (reference
     # order up to 4 096 classes, table lookups <= 1e-9 beyond: EM #1 of this sample); em_fast = -1 is the reference's order at every
     # size, bit-identical abundances (say what the bit-identical form costs NEXT to `value`)
     exact_em = None
-    if inflight == 1 and dist is None and not args.no_workloads and not args.em_exact:
+    if args.full and inflight == 1 and dist is None and not args.no_workloads and not args.em_exact:
         EM_MODE = -1
         try:
             run_steps(pl, batch, db, 1, 1, None, False, local_rank)
@@ -1537,7 +1575,7 @@ def main():
             res_x, _, _, _ = run_steps(pl, batch, db, 1, 3, None, False, local_rank)
             capi.sync()
             dt = (time.perf_counter() - t0) / 3
-            exact_em = {"ms_per_step": round(dt * 1e3, 3), "value": round(batch.n_reads / dt, 1), "steps": 3,
+            exact_em = {"ms_per_step": round(dt * 1e3, 3), "value": round(db.n_reads / dt, 1), "steps": 3,
                         "same_top2": [a for a, _ in res_x.gene_prob[:2]] == [a for a, _ in res.gene_prob[:2]],
                         "max_abs_abundance_difference_to_the_timed_form": max([abs(p - q) for (_, p), (_, q) in zip(res_x.gene_prob, res.gene_prob)] or [0.0])}
         except Exception as e:
@@ -1554,8 +1592,8 @@ def main():
         n_gene_refs = db.n_gene_refs
         # fused gene-level launch (hgx_pair_classes_dedup): the pairs' gene-level compat rows read, one representative row read
         # per pair for the exact compare (in place of the row + hash the unfused form wrote), refs / offsets, slot index written
-        pc_bytes = n_gene_refs * row + 4 * batch.n_refs + 4 * (batch.n_pairs + 1) + batch.n_pairs * (row + 4)
-        cp_bytes = db.sum_piece_words * pl.a_pad * 4 + batch.n_pieces * (row + 8) + db.sum_piece_words * 8
+        pc_bytes = n_gene_refs * row + 4 * db.n_refs + 4 * (db.n_pairs + 1) + db.n_pairs * (row + 4)
+        cp_bytes = db.sum_piece_words * pl.a_pad * 4 + db.n_pieces * (row + 8) + db.sum_piece_words * 8
         pc_ms = sum(e[2].elapsed_ms(e[3]) for e in ev) / len(ev)
         cp_ms = sum(e[0].elapsed_ms(e[1]) for e in ev) / len(ev)
         gbs = lambda b, ms: (b / (ms * 1e-3) / 1e9) if ms > 0 else 0.0
@@ -1573,8 +1611,8 @@ def main():
         # piece, the value-id tables of the window words read per group of 64 pieces (L2-resident: 1 B per allele and word at
         # HLA-A) and the piece table.  Priced against HBM (the rows are the kernel's only large stream); the kernel itself is
         # bound by the transposes' VALU issue and by launch width (996 groups of 64 pieces), not by bandwidth.
-        n_groups = (batch.n_pieces + 63) // 64
-        cp_bytes = batch.n_pieces * (row + 8) + db.sum_piece_words * 8 + n_groups * 8 * pl.a_pad
+        n_groups = (db.n_pieces + 63) // 64
+        cp_bytes = db.n_pieces * (row + 8) + db.sum_piece_words * 8 + n_groups * 8 * pl.a_pad
         kernels["k_piece_compat"] = {"launches": args.steps, "alg_bytes_per_launch": int(cp_bytes), "avg_ms": round(cp_ms, 4),
                                      "total_ms_per_step": round(cp_ms, 4), "GBps": round(gbs(cp_bytes, cp_ms), 1)}
         for k in kernels:
@@ -1592,7 +1630,7 @@ def main():
         if os.path.exists(tf):
             try:
                 tj = json.load(open(tf))
-                if tj.get("n_pairs") == batch.n_pairs and tj.get("a_pad") == pl.a_pad:
+                if tj.get("n_pairs") == db.n_pairs and tj.get("a_pad") == pl.a_pad:
                     traffic = tj["hbm_bytes_per_launch"].get(dom)
             except Exception:
                 traffic = None
@@ -1600,13 +1638,13 @@ def main():
         # scoring: piece compat + the gene-level per-pair launch (above) + the exon level per DISTINCT ref list (rows read per ref, one
         # class row + hash written per group); dedup: every row hashed / inserted once and read once more by the exact verify, at both
         # levels; Gene_counts: the gene class matrix once; EM: every executed mat-vec pass streams its compact bit matrix + vectors
-        n_exon_refs = batch.n_refs - n_gene_refs
+        n_exon_refs = db.n_refs - n_gene_refs
         try:
             n_exon_groups = engine.Groups(db, 0).n_groups
         except Exception:
-            n_exon_groups = batch.n_pairs
-        exon_bytes = n_exon_refs * row // max(batch.n_pairs // max(n_exon_groups, 1), 1) + n_exon_groups * (row + 12)
-        dedup_bytes = 2 * batch.n_pairs * (row + 8) + 2 * n_exon_groups * (row + 8)
+            n_exon_groups = db.n_pairs
+        exon_bytes = n_exon_refs * row // max(db.n_pairs // max(n_exon_groups, 1), 1) + n_exon_groups * (row + 12)
+        dedup_bytes = 2 * db.n_pairs * (row + 8) + 2 * n_exon_groups * (row + 8)
         n_gene_cls = res.em[1]["n_classes"] if len(res.em) > 1 else 0
         em_bytes = sum(by / max(min(N_TIMED_STEPS, args.steps), 1) for (_ms, _n, _ex, by) in em_timing.values())
         step_alg_bytes = int(cp_bytes + pc_bytes + exon_bytes + dedup_bytes + em_bytes)
@@ -1616,7 +1654,7 @@ def main():
         if os.path.exists(sp):
             try:
                 sj = json.load(open(sp))
-                if sj.get("n_pairs") == batch.n_pairs and sj.get("a_pad") == pl.a_pad:
+                if sj.get("n_pairs") == db.n_pairs and sj.get("a_pad") == pl.a_pad:
                     step_profile = sj["per_step"]
                     step_profile["source"] = sj["source"]
             except Exception:
@@ -1638,8 +1676,8 @@ def main():
             "em_iters_per_s": round(n_em_iter / max(t_em, 1e-9), 1),
             "config": {
                 "workload": "configs[1]: HLA-A-like locus, %d simulated 2x150bp reads per GPU, %d alleles, %d variants" % (
-                    batch.n_reads, pl.n_alleles, pl.n_vars),
-                "pairs_per_gpu": batch.n_pairs, "distinct_pieces": batch.n_pieces, "piece_refs": batch.n_refs,
+                    db.n_reads, pl.n_alleles, pl.n_vars),
+                "pairs_per_gpu": db.n_pairs, "distinct_pieces": db.n_pieces, "piece_refs": db.n_refs,
                 "exon_classes": res.em[0]["n_classes"] if res.em else 0,
                 "gene_classes_after_handoff": res.em[1]["n_classes"] if len(res.em) > 1 else 0,
                 "em_outer_iterations_per_step": n_em_iter // max(args.steps, 1),
@@ -1648,10 +1686,11 @@ def main():
                 "top2": [a for a, _ in res.gene_prob[:2]], "true_alleles": sample,
                 "parallelism": "samples/loci shard over GPUs with no data-path collective; %d sample(s) in flight per GPU" % inflight,
                 "comm_kind": comm_kind, "index_broadcast_bytes": bcast_bytes, "shared_gpu": bool(args.share_gpu),
-                "input": "piece batch built in HBM by the device front end from the SAM text (route %d, decline code %d: %.1f ms, not timed; "
-                         "identical to the host front end's batch: %s -- the host takes %.1f ms on %d host threads)" % (
-                             fe_route, fe_code, t_parse_dev * 1e3, fe_same, t_parse * 1e3, os.cpu_count() or 1),
-                "device_front_end_batch_identical_to_host": bool(fe_same),
+                "input": "piece batch built in HBM by the device front end from the SAM text (route %d, decline code %d: %.1f ms, not timed; %s)" % (
+                             fe_route, fe_code, t_parse_dev * 1e3,
+                             "identical to the host front end's batch: %s -- the host takes %.1f ms on %d host threads" % (
+                                 fe_same, t_parse * 1e3, os.cpu_count() or 1) if batch is not None else "compared with the host front end's batch under --full"),
+                "device_front_end_batch_identical_to_host": bool(fe_same) if fe_same is not None else None,
                 "setup_s": round(t_setup, 1),
             },
             "roofline": {
@@ -1690,19 +1729,19 @@ def main():
         if sam_keep is not None:
             if not args.no_e2e:
                 out["e2e"] = end_to_end(pl, loc, sam_keep, res)
-            cb, _ = cpu_baseline(loc, sam_keep, min(args.cpu_pairs, batch.n_pairs))
+            cb, _ = cpu_baseline(loc, sam_keep, min(args.cpu_pairs, db.n_pairs))
             out["cpu_baseline"] = cb
             t_fe = (out.get("e2e") or {}).get("bam", {}).get("host_front_end_one_thread_s")
             if t_fe:
-                t_cpu = t_fe + batch.n_reads / cb["value"]
+                t_cpu = t_fe + db.n_reads / cb["value"]
                 out["e2e"]["cpu_baseline"] = {
-                    "value": round(batch.n_reads / t_cpu, 1), "unit": "reads/s", "cores": 1, "kind": "port",
+                    "value": round(db.n_reads / t_cpu, 1), "unit": "reads/s", "cores": 1, "kind": "port",
                     "sample": "the same BAM file: host front end (read, inflate, walk, sort, decode; libhgx's C++ host stages, n_threads = 1) %.2f s "
                               "measured on the whole file + scoring / dedup / EM at the C oracle's rate (cpu_baseline: %.0f reads/s on its bounded "
-                              "sample) = %.1f s for %d reads" % (t_fe, cb["value"], t_cpu, batch.n_reads),
-                    "gpu_over_cpu": {k: round((batch.n_reads / (out["e2e"][k]["ms"] * 1e-3)) / (batch.n_reads / t_cpu), 1) for k in ("sam", "bam")}}
+                              "sample) = %.1f s for %d reads" % (t_fe, cb["value"], t_cpu, db.n_reads),
+                    "gpu_over_cpu": {k: round((db.n_reads / (out["e2e"][k]["ms"] * 1e-3)) / (db.n_reads / t_cpu), 1) for k in ("sam", "bam")}}
     # ---- the other BASELINE.json workloads, driver-timed in the same run: configs[2] (class1) and configs[3] (panel64) --------
-    if not args.no_workloads and (world == 1 or args.workloads):
+    if args.full and not args.no_workloads and (world == 1 or args.workloads):
         del batch, db
         import copy
         wl = {}

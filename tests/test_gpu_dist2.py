@@ -144,7 +144,7 @@ def test_bench_body_with_ranks_sharing_the_gpu(n):
     the ranks itself, rank 0's index is broadcast, every rank types its own sample, the time is the max over ranks, the reads are
     summed, every rank's file -> result leg runs at the same time as the others'.  (RCCL refuses two ranks on one device; the nccl
     form of the same body differs in make_comm() only.)"""
-    line = _bench(["--gpus", str(n), "--backend", "gloo", "--share-gpu", "--pairs", "20000", "--steps", "2", "--warmup", "1", "--no-workloads"])
+    line = _bench(["--gpus", str(n), "--backend", "gloo", "--share-gpu", "--pairs", "20000", "--steps", "2", "--warmup", "1", "--no-workloads", "--full"])
     assert line["n_gpus"] == n and line["steps"] == 2 and line["scaling"] == "weak"
     cfg = line["config"]
     assert cfg["shared_gpu"] is True and cfg["comm_kind"].startswith("torch-gloo") and cfg["index_broadcast_bytes"] > 1_000_000
@@ -191,7 +191,7 @@ def test_bench_nccl_body_with_a_world_of_one():
     """The nccl form of the multi-rank body on the one GPU there is: torch.distributed over RCCL with ONE rank (HGX_FORCE_DIST) -- process
     group on the device, the index broadcast on a tensor aliasing the index block, the max / sum reductions on device tensors, the
     per-rank file -> result leg."""
-    line = _bench_nccl_world1(["--pairs", "20000", "--steps", "2", "--warmup", "1", "--no-workloads"], "1")
+    line = _bench_nccl_world1(["--pairs", "20000", "--steps", "2", "--warmup", "1", "--no-workloads", "--full"], "1")
     cfg = line["config"]
     assert line["n_gpus"] == 1 and cfg["comm_kind"].startswith("torch-nccl") and cfg["index_broadcast_bytes"] > 1_000_000
     assert sorted(cfg["top2"]) == sorted(cfg["true_alleles"]) and cfg["device_front_end_batch_identical_to_host"] is True

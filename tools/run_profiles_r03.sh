@@ -6,7 +6,7 @@ D=gpurun_out/$1
 mkdir -p $D
 R=$(pwd)
 cd /tmp && export TMPDIR=/tmp && cd $R
-python3 bench.py > $D/bench_default.json 2> $D/bench_default.err
+python3 bench.py --full > $D/bench_default.json 2> $D/bench_default.err
 python3 bench.py --workload panel64 --em-exact --no-cpu-baseline --steps 6 --warmup 2 > $D/bench_panel64_em_exact.json 2>> $D/bench_default.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $D/stats -o r03 -- python3 bench.py --no-cpu-baseline --no-e2e --no-workloads > $D/bench_under_rocprof.json 2> $D/stats.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $D/stats_panel -o r03p -- python3 bench.py --workload panel64 --no-cpu-baseline --steps 8 --warmup 2 > $D/panel_under_rocprof.json 2> $D/stats_panel.err

@@ -8,8 +8,8 @@ R=$(pwd)
 cd /tmp && export TMPDIR=/tmp && cd $R
 # a fresh box's FIRST process runs its multi-threaded phases slower (class1 5.7 instead of 4.4 ms per step, the single sample 2.13
 # instead of 2.06: the image is still paging in): a throw-away run first, so that the committed line is the steady state
-python3 bench.py --no-cpu-baseline --no-e2e --wl-steps 4 > $D/bench_first_process.json 2> /dev/null
-python3 bench.py > $D/bench_default.json 2> $D/bench_default.err
+python3 bench.py --full --no-cpu-baseline --no-e2e --wl-steps 4 > $D/bench_first_process.json 2> /dev/null
+python3 bench.py --full > $D/bench_default.json 2> $D/bench_default.err
 python3 bench.py --workload panel64 --em-exact --no-cpu-baseline --steps 6 --warmup 2 > $D/bench_panel64_em_exact.json 2>> $D/bench_default.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $D/stats -o r05 -- python3 bench.py --no-cpu-baseline --no-e2e --no-workloads > $D/bench_under_rocprof.json 2> $D/stats.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $D/stats_panel -o r05p -- python3 bench.py --workload panel64 --no-cpu-baseline --steps 8 --warmup 2 > $D/panel_under_rocprof.json 2> $D/stats_panel.err

@@ -8,8 +8,8 @@ R=$(pwd)
 cd /tmp && export TMPDIR=/tmp && cd $R
 # a fresh box's FIRST process runs its multi-threaded phases slower (class1 5.7 instead of 4.4 ms per step, the single sample 2.13
 # instead of 2.06: the image is still paging in): a throw-away run first, so that the committed line is the steady state
-python3 bench.py --no-cpu-baseline --no-e2e --wl-steps 4 > $D/bench_first_process.json 2> /dev/null
-python3 bench.py > $D/bench_default.json 2> $D/bench_default.err
+python3 bench.py --full --no-cpu-baseline --no-e2e --wl-steps 4 > $D/bench_first_process.json 2> /dev/null
+python3 bench.py --full > $D/bench_default.json 2> $D/bench_default.err
 python3 bench.py --workload panel64 --em-exact --no-cpu-baseline --steps 6 --warmup 2 > $D/bench_panel64_em_exact.json 2>> $D/bench_default.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $D/stats -o r06 -- python3 bench.py --no-cpu-baseline --no-e2e --no-workloads > $D/bench_under_rocprof.json 2> $D/stats.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $D/stats_panel -o r06p -- python3 bench.py --workload panel64 --no-cpu-baseline --steps 8 --warmup 2 > $D/panel_under_rocprof.json 2> $D/stats_panel.err
@@ -44,7 +44,7 @@ INF_FORM=inflate_prof python3 tools/inflate_probe.py run 2>&1 | grep "k_bgzf_inf
 # ---- round 6 additions --------------------------------------------------------------------------------------------------------
 # the multi-rank bench BODY on this one GPU (control plane over gloo; RCCL refuses two ranks on one device): configs1 with 2 ranks,
 # class1 with 4 ranks (HLA-A's pairs sharded over ranks 0-1: device front end per shard, pileup all-reduce, class-table gather per step)
-python3 bench.py --gpus 2 --backend gloo --share-gpu --pairs 100000 --steps 5 --warmup 2 --no-workloads > $D/bench_2ranks_shared_gpu.json 2> $D/bench_2ranks.err
+python3 bench.py --gpus 2 --backend gloo --share-gpu --pairs 100000 --steps 5 --warmup 2 --no-workloads --full > $D/bench_2ranks_shared_gpu.json 2> $D/bench_2ranks.err
 python3 bench.py --gpus 4 --backend gloo --share-gpu --workload class1 --pairs 100000 --steps 5 --warmup 2 --check-unsharded --no-cpu-baseline > $D/bench_class1_4ranks_shared_gpu.json 2> $D/bench_class1_4ranks.err
 # stream placement: what the hardware does with streams (queues per priority, lanes), and the A/B of the measured placement
 python3 tools/stream_probe.py 12 HHHHHHHHHHHH > $D/stream_probe.txt 2>&1
