@@ -41,8 +41,14 @@ enum {
     S_NCOLS = 7,
     S_NPRES = 8,     // alleles still in the estimate after the last advance
     S_TAIL = 9,      // 1 = the compact tail kernel finished the EM, -1 = it could not take over
-    S_N = 10
+    S_NEAR = 10,     // decisions taken within EM_NEAR_REL of their threshold so far (pruning p >= max / 10, stopping diff > 0.0001)
+    S_N = 11
 };
+
+// Relative distance below which a value of the table-lookup path (good to ~1e-11) cannot tell which side of a threshold, or of a
+// neighbour, the reference's own value lies on (see em_impl)
+constexpr double EM_NEAR_REL = 1e-8;
+__device__ __forceinline__ bool near_threshold(double v, double thr) { return fabs(v - thr) <= EM_NEAR_REL * thr; }
 
 constexpr int BLOCK = 1024;
 constexpr int NWAVE = BLOCK / 64;
@@ -221,11 +227,14 @@ __global__ __launch_bounds__(BLOCK) void k_em_advance(double *__restrict__ p, ui
     const double td = d[0];
     const int iter = (int)it_d;
     const bool prune = remove_low && iter >= 10;
-    double kept[1] = {0.0};
+    double kept[2] = {0.0, 0.0};                 // survivors, pruning decisions on the threshold
     auto store = [&](int a, bool an, double xn) {
         const double pn = an ? xn / tot : 0.0;
         bool keep = an;
-        if (prune && keep) keep = pn >= tm / 10.0;
+        if (prune && keep) {
+            if (near_threshold(pn, tm / 10.0)) kept[1] += 1.0;
+            keep = pn >= tm / 10.0;
+        }
         pres[a] = keep ? 1 : 0;
         p[a] = keep ? pn : 0.0;
         if (keep) kept[0] += 1.0;
@@ -236,9 +245,10 @@ __global__ __launch_bounds__(BLOCK) void k_em_advance(double *__restrict__ p, ui
     } else {
         for (int a = threadIdx.x; a < a_pad; a += BLOCK) store(a, prn[a], qn[a]);
     }
-    block_sum_n<1>(kept, sh);
+    block_sum_n<2>(kept, sh);
     if (threadIdx.x == 0) {
         scal[S_NPRES] = kept[0];
+        scal[S_NEAR] += kept[1] + (near_threshold(td, 0.0001) ? 1.0 : 0.0);
         scal[S_DIFF] = td;
         scal[S_ITER] = (double)(iter + 1);
         if (!(td > 0.0001) || iter + 1 >= 1000) scal[S_DONE] = 1.0;
@@ -254,20 +264,25 @@ __global__ __launch_bounds__(BLOCK) void k_em_init_norm(double *__restrict__ p, 
     for (int a = threadIdx.x; a < a_pad; a += BLOCK) p[a] = pres[a] ? p[a] / tot : 0.0;
 }
 
-// final select_alleles + normalise (common:1402-1407); out = -1 for alleles not in the dict
+// final select_alleles + normalise (common:1402-1407); out = -1 for alleles not in the dict; out[a_pad] = the EM's decisions on a
+// threshold (scal[S_NEAR] + this selection's): it comes back with the result
 __global__ __launch_bounds__(BLOCK) void k_em_finish(const double *__restrict__ p, const uint8_t *__restrict__ pres,
                                                      const double *__restrict__ len, int a_pad, int prune,
-                                                     double *__restrict__ out) {
+                                                     double *__restrict__ out, const double *__restrict__ scal) {
     __shared__ double sh[NWAVE];
+    __shared__ double sh2[2][NWAVE];
     double mx = 0.0;
     for (int a = threadIdx.x; a < a_pad; a += BLOCK) if (pres[a]) mx = fmax(mx, p[a]);
     const double tm = block_max(mx, sh);
-    double s = 0.0;
+    double s[2] = {0.0, 0.0};                   // sum, pruning decisions on the threshold
     for (int a = threadIdx.x; a < a_pad; a += BLOCK) {
+        if (prune && pres[a] && near_threshold(p[a], tm / 10.0)) s[1] += 1.0;
         const bool keep = pres[a] && (!prune || p[a] >= tm / 10.0);
-        if (keep) s += len ? p[a] / len[a] : p[a];
+        if (keep) s[0] += len ? p[a] / len[a] : p[a];
     }
-    const double tot = block_sum(s, sh);
+    block_sum_n<2>(s, sh2);
+    const double tot = s[0];
+    if (threadIdx.x == 0) out[a_pad] = scal[S_NEAR] + s[1];
     for (int a = threadIdx.x; a < a_pad; a += BLOCK) {
         const bool keep = pres[a] && (!prune || p[a] >= tm / 10.0);
         out[a] = keep ? (len ? p[a] / len[a] / tot : p[a] / tot) : -1.0;
@@ -340,6 +355,7 @@ __device__ __forceinline__ void wave_em_run(const WaveEM &E, double p, bool pr, 
     bool pr1, pr2, pr3;
     double diff = 1.0;
     bool keyerr = false;
+    double near = 0.0;                                   // (lane 0 also counts the stopping decisions)
     while (diff > 0.0001 && iter < 1000) {
         const double q1 = wave_map(E, p, pr, 1.0, false, use_len, pr1);
         const double tot1 = wave_sum_f64(pr1 ? q1 : 0.0);
@@ -370,16 +386,22 @@ __device__ __forceinline__ void wave_em_run(const WaveEM &E, double p, bool pr, 
         diff = wave_sum_f64(pr ? (prn ? fabs(p - pn) : p) : 0.0);
         const double mx = wave_max_f64(prn ? pn : 0.0);
         bool keep = prn;
-        if (remove_low && iter >= 10 && keep) keep = pn >= mx / 10.0;
+        if (remove_low && iter >= 10 && keep) {
+            if (near_threshold(pn, mx / 10.0)) near += 1.0;
+            keep = pn >= mx / 10.0;
+        }
+        if (lane == 0 && near_threshold(diff, 0.0001)) near += 1.0;
         pr = keep;
         p = keep ? pn : 0.0;
         iter += 1;
     }
     const double mx = wave_max_f64(pr ? p : 0.0);
     const bool keep = pr && (!remove_low || p >= mx / 10.0);
+    if (remove_low && pr && near_threshold(p, mx / 10.0)) near += 1.0;
     const double tl = wave_sum_f64(keep ? (use_len ? p / E.len : p) : 0.0);
+    near = wave_sum_f64(near);
     if (lane < E.A1 && keep) out[g] = use_len ? p / E.len / tl : p / tl;
-    if (lane == 0) { scal[S_ITER] = (double)iter; scal[S_KEYERR] = keyerr ? 1.0 : 0.0; scal[S_DONE] = 1.0; }
+    if (lane == 0) { scal[S_ITER] = (double)iter; scal[S_KEYERR] = keyerr ? 1.0 : 0.0; scal[S_DONE] = 1.0; scal[S_NEAR] += near; }
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1189,20 +1211,24 @@ __global__ __launch_bounds__(BLOCK) void k_lut_rows_fused(const uint64_t *__rest
         const double td = d[0];
         const int iter = (int)it_d;
         const bool prune = fz.remove_low && iter >= 10;
-        double kept[1] = {0.0};
+        double kept[2] = {0.0, 0.0};             // survivors, pruning decisions on the threshold
 #pragma unroll
         for (int k = 0; k < EPT; ++k) {
             const bool an = ext ? fb[k] : f1[k];
             const double pn = an ? (ext ? vb[k] : v1[k]) / tot : 0.0;
             bool keep = an;
-            if (prune && keep) keep = pn >= tm / 10.0;
+            if (prune && keep) {
+                if (near_threshold(pn, tm / 10.0)) kept[1] += 1.0;
+                keep = pn >= tm / 10.0;
+            }
             if (keep) kept[0] += 1.0;
         }
-        block_sum_n<1>(kept, shf);
+        block_sum_n<2>(kept, shf);
         const bool done = !(td > 0.0001) || iter + 1 >= 1000;
         if (lead) {
             carry_state();
             fz.scal_out[S_NPRES] = kept[0];
+            fz.scal_out[S_NEAR] = fz.scal_in[S_NEAR] + kept[1] + (near_threshold(td, 0.0001) ? 1.0 : 0.0);
             fz.scal_out[S_DIFF] = td;
             fz.scal_out[S_ITER] = (double)(iter + 1);
             if (done) fz.scal_out[S_DONE] = 1.0;
@@ -1510,6 +1536,8 @@ static int hgx_ensure_compact(hgx_classes *c, hipStream_t st) {
 // 1 if the calling thread's last EM (hgx_em / hgx_em_ordered / hgx_em_masked) ran on the single-wavefront path in the reference's
 // own order of floating-point operations (its abundances are then the reference's, bit for bit), 0 otherwise
 static thread_local int g_last_exact = 0;
+static thread_local long long g_last_near = 0;   // the last table-lookup EM's decisions within EM_NEAR_REL of their threshold (S_NEAR)
+static thread_local bool g_tie_prefix = false;   // em_tie_prefix_scope: near-ties are looked for in the report's prefix only
 static thread_local std::vector<int32_t> g_last_order;     // per allele: position in the returned dict's insertion order (hgx_em_last_order)
 static thread_local int g_em_fast = 0;           // hgx_em_set_fast: 1 = table-lookup arithmetic on the one-workgroup path (k_emx), -1 = the
                                                  // reference's order at every size (k_emx also beyond 4096 classes)
@@ -1576,9 +1604,16 @@ extern "C" int hgx_em_ordered(const hgx_classes *cc, int32_t n_alleles, int32_t 
 // reference's own order of operations (k_emx at any size, a lone big problem in cluster mode: bit-identical abundances, ~15x the
 // time; rare: alleles the data cannot tell apart have identical columns and are exact ties on both paths, and distinct columns
 // agreeing to eight digits takes a symmetric construction), and that result is returned as exact.
-constexpr double EM_NEAR_REL = 1e-8;
+// The same holds for the hard decisions the EM itself takes on its values: the pruning test p >= max / 10 (common:1338-1346, 1402) and
+// the stopping rule diff > 0.0001 (common:1351).  The kernels count the decisions taken within EM_NEAR_REL of their threshold (S_NEAR,
+// in the state words the host reads anyway); a non-zero count re-runs the EM the same way.  (Exact ratios such as 10 : 1 between
+// alleles that only their own reads support are ordinary data, not a construction.)
 static std::atomic<long long> g_tie_reruns{0};
 extern "C" long long hgx_em_tie_reruns(void) { return g_tie_reruns.load(); }
+// Library-internal (not part of the C ABI): the typing chain reads only the report's prefix and the hand-off's of its EM lists.
+int em_tie_prefix_scope(int on) { const int old = g_tie_prefix ? 1 : 0; g_tie_prefix = on != 0; return old; }
+int em_fast_mode() { return g_em_fast; }
+void em_count_rerun() { g_tie_reruns.fetch_add(1); }
 
 // rows of the transposed class matrix (allele-major) gathered into one contiguous block: the near-tie check compares them on the host
 __global__ void k_gather_rows(const uint64_t *__restrict__ bitsT, int c64, const int32_t *__restrict__ ids, int n, uint64_t *__restrict__ out) {
@@ -1592,13 +1627,14 @@ static int em_uncertain_near_tie(hgx_classes *c, int32_t n_alleles, const double
     std::vector<int32_t> al;
     for (int32_t a = 0; a < n_alleles; ++a) if (prob[a] > 0.0) al.push_back(a);
     std::sort(al.begin(), al.end(), [&](int32_t x, int32_t y) { return prob[x] > prob[y]; });
-    // Only an order somebody reads is worth a ~15x slower exact run: the report prints abundances >= 0.01 and at most 20
-    // alleles (typing_core.py:2081, 2118-2121), the exon -> gene hand-off walks the ranking until `rank >= 10 and p < 0.03`
-    // (core:1739-1749).  Neighbours below rank 32 AND below 0.005 are vanishing residues whose relative order reaches no output.
+    // In the typing chain (em_tie_prefix_scope) only an order somebody reads is worth a ~15x slower exact run: the report
+    // prints abundances >= 0.01 and at most 20 alleles (typing_core.py:2081, 2118-2121), the exon -> gene hand-off walks the ranking
+    // until `rank >= 10 and p < 0.03` (core:1739-1749); neighbours below rank 32 AND below 0.005 reach none of its outputs.  The
+    // drop-in single_abundance returns the whole list: every neighbour counts there.
     std::vector<std::pair<int32_t, int32_t>> pairs;
     for (size_t i = 0; i + 1 < al.size(); ++i) {
         const double hi = prob[al[i]], lo = prob[al[i + 1]];
-        if (i >= 32 && hi < 0.005) break;
+        if (g_tie_prefix && i >= 32 && hi < 0.005) break;
         if (hi != lo && hi - lo <= EM_NEAR_REL * hi) pairs.emplace_back(al[i], al[i + 1]);
     }
     if (pairs.empty()) return HGX_OK;
@@ -1632,8 +1668,8 @@ static int em_impl(const hgx_classes *cc, int32_t n_alleles, int32_t remove_low,
     if (!c->h_rank || c->n_classes > HGX_EMX_HARD_MAX_CLASSES || c->w64 > 128 || hgx_switch_has("em_skip", "exact") ||
         hgx_switch_has("em_skip", "emx") || hgx_switch_has("em_skip", "tie_rerun"))
         return rc;                                                          // (the reference's order is not available for this problem)
-    bool uncertain = false;
-    rc = em_uncertain_near_tie(c, n_alleles, prob_host, (hipStream_t)stream, &uncertain);
+    bool uncertain = g_last_near > 0;                                       // a pruning or stopping decision on its threshold
+    if (!uncertain) rc = em_uncertain_near_tie(c, n_alleles, prob_host, (hipStream_t)stream, &uncertain);
     if (rc || !uncertain) return rc;
     g_tie_reruns.fetch_add(1);
     const int old = g_em_fast;
@@ -1647,6 +1683,7 @@ static int em_impl_inner(const hgx_classes *cc, int32_t n_alleles, int32_t remov
                          int32_t *first_host, int32_t *n_iter_host, void *stream) {
     ARGCHK(cc && prob_host && n_alleles > 0 && n_alleles <= cc->a_pad);
     g_last_exact = 0;
+    g_last_near = 0;
     g_last_order.clear();
     hgx_classes_order_after(cc, (hipStream_t)stream);
     if (first_host) for (int a = 0; a < n_alleles; ++a) first_host[a] = -1;
@@ -1768,7 +1805,7 @@ static int em_impl_inner(const hgx_classes *cc, int32_t n_alleles, int32_t remov
     A = c->a1p;
     const int w64c = A / 64;
     DevBuf b_p, b_q1, b_q2, b_q3, b_wc, b_pr, b_pr1, b_pr2, b_pr3, b_len, b_scal, b_out;
-    ALLOC(b_p, A * 8); ALLOC(b_q1, A * 8); ALLOC(b_q2, A * 8); ALLOC(b_q3, A * 8); ALLOC(b_out, A * 8);
+    ALLOC(b_p, A * 8); ALLOC(b_q1, A * 8); ALLOC(b_q2, A * 8); ALLOC(b_q3, A * 8); ALLOC(b_out, (A + 1) * 8);   // (+ k_em_finish's count)
     const size_t n_cnt_all = (size_t)std::max((C + BLOCK - 1) / BLOCK, (A + BLOCK - 1) / BLOCK);
     ALLOC(b_wc, (size_t)C * 8); ALLOC(b_pr, A); ALLOC(b_pr1, A); ALLOC(b_pr2, A); ALLOC(b_pr3, A); ALLOC(b_scal, S_N * 8 + n_cnt_all * 4);       // (scalars + the passes' slab counters: one block, one memset)
     double *d_len = nullptr;
@@ -1877,7 +1914,7 @@ static int em_impl_inner(const hgx_classes *cc, int32_t n_alleles, int32_t remov
     }
     double h_scal[S_N];
     int h_abort = 0;
-    std::vector<double> out(A);
+    std::vector<double> out(A + 1);
     bool results_fetched = false;         // the speculative tail's results came back with its status word
     const int batch = 4;
     int launched_iters = 0;
@@ -2069,13 +2106,14 @@ static int em_impl_inner(const hgx_classes *cc, int32_t n_alleles, int32_t remov
         hgx_set_error("EM: allele missing from the next estimate (the reference raises KeyError here, common:1365-1369)");
         return HGX_EKEY;
     }
-    if (!tail_done) hipLaunchKernelGGL(k_em_finish, dim3(1), dim3(BLOCK), 0, st, p, pr, d_len, A, remove_low ? 1 : 0, b_out.as<double>());
+    if (!tail_done) hipLaunchKernelGGL(k_em_finish, dim3(1), dim3(BLOCK), 0, st, p, pr, d_len, A, remove_low ? 1 : 0, b_out.as<double>(), scal);
     HIPCHK(hipGetLastError());
     if (!results_fetched) {
         if (first_host) { int rc_ = hgx_d2h(h_fc.data(), b_fc.p, (size_t)A * 4, st); if (rc_) return rc_; }
-        { int rc_ = hgx_d2h(out.data(), b_out.p, A * 8, st); if (rc_) return rc_; }
+        { int rc_ = hgx_d2h(out.data(), b_out.p, (size_t)(tail_done ? A : A + 1) * 8, st); if (rc_) return rc_; }
         { int rc_ = hgx_sync(st); if (rc_) return rc_; }
     }
+    g_last_near = (long long)(tail_done ? h_scal[S_NEAR] : out[A]);      // (the tail kernel counted into the state words)
     for (int a = 0; a < n_alleles; ++a) prob_host[a] = -1.0;
     for (int j = 0; j < c->n_act; ++j) if (c->h_act[j] < n_alleles) prob_host[c->h_act[j]] = out[j];
     if (first_host) for (int j = 0; j < c->n_act; ++j) if (c->h_act[j] < n_alleles) first_host[c->h_act[j]] = h_fc[j];

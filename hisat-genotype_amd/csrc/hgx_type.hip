@@ -32,6 +32,9 @@
 #include "hgx_internal.hpp"
 
 extern "C" int hgx_em_set_fast(int on);
+int em_tie_prefix_scope(int on);       // hgx_em.hip (library-internal)
+int em_fast_mode();
+void em_count_rerun();
 extern "C" int hgx_em_last_order(int32_t *order_host, int32_t n);
 
 struct hgx_gate { std::mutex mu; };
@@ -358,10 +361,10 @@ double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock:
 inline int em_mode_one(int em_fast) { return em_fast == 2 ? 0 : em_fast; }
 inline int em_mode_many(int em_fast) { return em_fast == 0 ? 1 : (em_fast == 2 ? 0 : em_fast); }
 
-struct EmFastScope {                 // hgx_type_opts.em_fast for the EMs of this call (this thread)
-    int old;
-    explicit EmFastScope(int on) : old(hgx_em_set_fast(on)) {}
-    ~EmFastScope() { hgx_em_set_fast(old); }
+struct EmFastScope {                 // hgx_type_opts.em_fast for the EMs of this call (this thread); near-ties of the table-lookup
+    int old, old_prefix;             // EM are looked for in the prefix the chain reads (hgx_em.hip em_uncertain_near_tie)
+    explicit EmFastScope(int on) : old(hgx_em_set_fast(on)), old_prefix(em_tie_prefix_scope(1)) {}
+    ~EmFastScope() { hgx_em_set_fast(old); em_tie_prefix_scope(old_prefix); }
 };
 
 }   // namespace
@@ -517,6 +520,48 @@ int gene_rank(hgx_classes *gcl, int32_t A, int32_t a_pad, hipStream_t st, GeneSi
     return HGX_OK;
 }
 
+// ---- decisions of the chain on a table-lookup EM #1 ----------------------------------------------------------------------------
+// EM #1 beyond 4096 classes runs on table lookups by default (good to ~1e-11; the EM's own near-ties, pruning and stopping decisions
+// are re-run in hgx_em.hip).  The chain then takes hard decisions on its values: the hand-off cut `i >= 10 and p < 0.03`
+// (core:1742-1743), the report cut `p < 0.01`, the report's `"%.2f%%" % (p * 100)` (core:2097-2121) and the order of the combined
+// list (core:1771-1782).  Where a value lies within CHAIN_NEAR_REL of such a line, the reference's own value may lie on the other
+// side: EM #1 is run again in the reference's order (em_fast -1) and the hand-off redone.  Callers that chose table lookups
+// (em_fast 1, the many-task default) keep their values.
+constexpr double CHAIN_NEAR_REL = 1e-8;
+bool chain_near(double v, double thr) { return std::fabs(v - thr) <= CHAIN_NEAR_REL * std::fabs(thr); }
+
+// (the same availability test as hgx_em.hip em_impl: the reference's order must exist for this problem)
+bool em1_may_rerun(const EmOut &e1, const hgx_classes *ecl) {
+    return !e1.exact && em_fast_mode() == 0 && ecl->h_rank && ecl->n_classes <= HGX_EMX_HARD_MAX_CLASSES && ecl->w64 <= 128 &&
+           !hgx_switch_has("em_skip", "tie_rerun") && !hgx_switch_has("em_skip", "exact") && !hgx_switch_has("em_skip", "emx");
+}
+// an EM #1 value at rank >= 10 on the 0.03 line
+bool handoff_uncertain(const EmOut &e1) {
+    for (size_t i = 10; i < e1.prob.size(); ++i) {
+        if (chain_near(e1.prob[i], 0.03)) return true;
+        if (e1.prob[i] < 0.03) break;
+    }
+    return false;
+}
+// the report's lines (at most 20, p >= 0.01): a value on the 0.01 line or on a rounding boundary (k + 0.5) / 10^4, or two neighbours
+// of different origin (exon level / EM #2 times exon_prob_sum) too close to order
+bool report_uncertain(const EmOut &gp, const std::vector<uint8_t> &from_em2) {
+    const size_t n = std::min(gp.prob.size(), (size_t)20);
+    for (size_t i = 0; i < n; ++i) {
+        const double p = gp.prob[i];
+        if (chain_near(p, 0.01)) return true;
+        if (p < 0.01) break;
+        const double x = p * 1e4;
+        if (chain_near(x, std::floor(x) + 0.5) || chain_near(x, std::ceil(x) - 0.5)) return true;
+        if (i + 1 < gp.prob.size() && !from_em2.empty() && from_em2[gp.allele[i]] != from_em2[gp.allele[i + 1]] &&
+            p - gp.prob[i + 1] <= CHAIN_NEAR_REL * p)
+            return true;
+    }
+    return false;
+}
+// EM #1 again, in the reference's own order of operations (k_emx at any size); replaces t->em
+int em1_exact_again(hgx_typing *t, hgx_classes *ecl, const hgx_locus *loc, int32_t remove_low, hipStream_t st);
+
 int run_em(hgx_classes *cl, const hgx_locus *loc, int32_t remove_low, const int32_t *lengths, hipStream_t st, hgx_typing *t) {
     const int32_t A = loc->A;
     std::vector<double> prob((size_t)A);
@@ -539,6 +584,13 @@ int run_em(hgx_classes *cl, const hgx_locus *loc, int32_t remove_low, const int3
     sorted_result(prob, first, loc->name_rank.data(), A, o);
     t->em.push_back(std::move(o));
     return HGX_OK;
+}
+
+int em1_exact_again(hgx_typing *t, hgx_classes *ecl, const hgx_locus *loc, int32_t remove_low, hipStream_t st) {
+    em_count_rerun();
+    EmFastScope exact(-1);
+    t->em.clear();
+    return run_em(ecl, loc, remove_low, nullptr, st, t);
 }
 
 // exon_alleles (core:1739-1749): the members of the exon groups of the leading representatives of EM #1's result
@@ -570,50 +622,68 @@ void combine_levels(hgx_typing *t, EmOut &&e2, const std::vector<uint8_t> &in_ex
     t->gene_prob.prob = comb.prob;
 }
 
-// EM #1 on the exon-level classes, exon_alleles, hand-off and EM #2 on the gene classes, combination (core:1732-1782).
-// `gene_ready` delivers the gene-level class set (and the counts in `t`) when the exon-level EM is done -- the gene side may
-// still be running beside it until then.
+// Everything after EM #1 of an HLA-like locus for one task (core:1739-1782): exon_alleles, the hand-off EM #2 on the gene classes
+// (hgx_em_masked) and the combined list -- with the chain's decisions checked on a table-lookup EM #1 (above): a hand-off cut or a
+// report line on its line runs EM #1 again in the reference's order (once) and redoes the rest.  Used by the one-task chain and by
+// the many-task tasks whose EM #1 went through the one-task EM.
+int chain_after_em1(hgx_typing *t, const hgx_locus *loc, hgx_classes *ecl, int32_t remove_low, hgx_classes *gcl, hipStream_t em_stream,
+                    hipStream_t stream) {
+    const int32_t A = loc->A;
+    const int w64 = loc->a_pad / 64;
+    for (int pass = 0;; ++pass) {                 // pass 1: after EM #1 was run again in the reference's order
+        const bool may_rerun = pass == 0 && em1_may_rerun(t->em[0], ecl);
+        if (may_rerun && handoff_uncertain(t->em[0])) {
+            if (int rc = em1_exact_again(t, ecl, loc, remove_low, em_stream)) return rc;
+            continue;
+        }
+        std::vector<uint8_t> in_exon;
+        double psum = 0.0;
+        const bool any = exon_alleles_of(t->em[0], loc, in_exon, psum);
+        t->gene_prob = t->em[0];
+        if (any) {                                                                           // core:1752-1782
+            std::vector<uint64_t> mask((size_t)w64, 0);
+            for (int32_t a = 0; a < A; ++a) if (in_exon[a]) mask[a >> 6] |= 1ull << (a & 63);
+            std::vector<double> prob2((size_t)A);
+            std::vector<int32_t> first2((size_t)A);
+            int32_t it2 = 0, ncls2 = 0;
+            const double t0 = now_s();
+            int rc = hgx_classes_set_allele_rank(gcl, loc->name_rank.data(), A);
+            // Gene_cmpt2 (gene classes filtered to exon_alleles, merged) and EM #2 in one call
+            if (!rc) rc = hgx_em_masked(gcl, mask.data(), A, 1, loc->allele_len.data(), prob2.data(), first2.data(), &it2, &ncls2, stream);
+            t->t_em += now_s() - t0;
+            if (rc) return rc;
+            EmOut e2;
+            e2.exact = hgx_em_last_exact() != 0;
+            e2.n_classes = ncls2; e2.n_iter = it2; e2.remove_low = 1; e2.use_length = 1;
+            sorted_result(prob2, first2, loc->name_rank.data(), A, e2);
+            combine_levels(t, std::move(e2), in_exon, psum);
+        }
+        if (may_rerun && report_uncertain(t->gene_prob, any ? in_exon : std::vector<uint8_t>())) {
+            if (int rc = em1_exact_again(t, ecl, loc, remove_low, em_stream)) return rc;
+            continue;
+        }
+        return HGX_OK;
+    }
+}
+
+// EM #1 on the exon-level classes, then the rest of the chain (core:1732-1782).  `gene_ready` delivers the gene-level class set (and
+// the counts in `t`) when the exon-level EM is done -- the gene side may still be running beside it until then.
 template <class GeneReady>
 int finish_hla(hgx_typing *t, const hgx_locus *loc, hgx_classes *ecl, const hgx_type_opts *opts, hipStream_t em_stream, hipStream_t stream,
                GeneReady gene_ready) {
-    const int32_t A = loc->A;
-    const int w64 = loc->a_pad / 64;
-    int rc;
     const bool prof = getenv("HGX_TYPE_PROFILE") != nullptr;
     const double tp0 = now_s();
-    rc = run_em(ecl, loc, opts->remove_low, nullptr, em_stream, t);                          // core:1732-1737
+    int rc = run_em(ecl, loc, opts->remove_low, nullptr, em_stream, t);                      // core:1732-1737
     if (rc) return rc;
     const double tp1 = now_s();
     hgx_classes *gcl = nullptr;
     rc = gene_ready(&gcl);
     if (rc) return rc;
     const double tp2 = now_s();
-    const EmOut &e1 = t->em[0];
-    std::vector<uint8_t> in_exon;
-    double psum = 0.0;
-    const bool any = exon_alleles_of(e1, loc, in_exon, psum);
-    t->gene_prob = e1;
-    if (any) {                                                                               // core:1752-1782
-        std::vector<uint64_t> mask((size_t)w64, 0);
-        for (int32_t a = 0; a < A; ++a) if (in_exon[a]) mask[a >> 6] |= 1ull << (a & 63);
-        std::vector<double> prob2((size_t)A);
-        std::vector<int32_t> first2((size_t)A);
-        int32_t it2 = 0, ncls2 = 0;
-        const double t0 = now_s();
-        rc = hgx_classes_set_allele_rank(gcl, loc->name_rank.data(), A);
-        // Gene_cmpt2 (gene classes filtered to exon_alleles, merged) and EM #2 in one call
-        if (!rc) rc = hgx_em_masked(gcl, mask.data(), A, 1, loc->allele_len.data(), prob2.data(), first2.data(), &it2, &ncls2, stream);
-        t->t_em += now_s() - t0;
-        if (rc) return rc;
-        if (prof) fprintf(stderr, "[finish_hla] EM#1 %.1f us | wait gene %.1f | exon_alleles+mask %.1f | EM#2 call %.1f\n", (tp1 - tp0) * 1e6,
-                          (tp2 - tp1) * 1e6, (t0 - tp2) * 1e6, (now_s() - t0) * 1e6);
-        EmOut e2;
-        e2.exact = hgx_em_last_exact() != 0;
-        e2.n_classes = ncls2; e2.n_iter = it2; e2.remove_low = 1; e2.use_length = 1;
-        sorted_result(prob2, first2, loc->name_rank.data(), A, e2);
-        combine_levels(t, std::move(e2), in_exon, psum);
-    }
-    return HGX_OK;
+    rc = chain_after_em1(t, loc, ecl, opts->remove_low, gcl, em_stream, stream);
+    if (prof) fprintf(stderr, "[finish_hla] EM#1 %.1f us | wait gene %.1f | hand-off + EM#2 %.1f\n", (tp1 - tp0) * 1e6, (tp2 - tp1) * 1e6,
+                      (now_s() - tp2) * 1e6);
+    return rc;
 }
 
 // non-HLA bases (core:1784-1789): the EM on the gene classes, no pruning, no lengths; a single class is the reference's quirk Q3
@@ -1267,6 +1337,7 @@ struct ManyRun {
     std::vector<uint64_t> masks;
     size_t job_lo = 0, job_hi = 0, job2_lo = 0, job2_hi = 0;     // this locus' ranges in the callers' job lists
     std::vector<int> job_task, job2_task;
+    std::vector<int32_t> one_task;     // per task: EM #1's class count if the task finishes through chain_after_em1, else -1
 
     ~ManyRun() {
         if (st || active) (void)hipStreamSynchronize(st);
@@ -1419,6 +1490,7 @@ struct ManyRun {
         job2_lo = job2_hi = jobs2.size();
         if (!active) return HGX_OK;
         int rc = HGX_OK;
+        one_task.assign((size_t)n, -1);
         for (size_t k = job_lo; k < job_hi; ++k) {
             const int t = job_task[k - job_lo];
             hgx_typing *ty = res[t];
@@ -1433,7 +1505,10 @@ struct ManyRun {
             if (J.status == 1) {                                // beyond the batched kernel's limits: this task's EM through the one-task path
                 ClassesView v(cl1(), off1()[t], J.C);
                 rc = run_em(&v.c, loc, J.remove_low, nullptr, st, ty);
-                if (rc) { rc = fail_task(t, rc); if (rc) return rc; }
+                if (rc) { rc = fail_task(t, rc); if (rc) return rc; continue; }
+                // a table-lookup EM #1 of an HLA-like locus in the reference-order mode: the rest of its chain goes through the
+                // one-task chain (chain_after_em1, in finish), which checks the decisions taken on its values
+                if (hla && !ty->em[0].exact && em_fast_mode() == 0) one_task[t] = J.C;
                 continue;
             }
             EmOut o;
@@ -1452,6 +1527,7 @@ struct ManyRun {
             hgx_typing *ty = res[t];
             if (!ty || ty->em.empty()) continue;
             ty->gene_prob = ty->em[0];
+            if (one_task[t] >= 0) continue;                 // (finish)
             if (!exon_alleles_of(ty->em[0], loc, in_exon[t], psum[t])) continue;
             uint64_t *mk = &masks[(size_t)t * w64];
             for (int32_t a = 0; a < A; ++a) if (in_exon[t][a]) mk[a >> 6] |= 1ull << (a & 63);
@@ -1497,6 +1573,13 @@ struct ManyRun {
                 em_out_from(J, recs2, loc, 1, e2, false);      // (as the one-task path's hand-off kernel orders its result)
             }
             combine_levels(ty, std::move(e2), in_exon[t], psum[t]);
+        }
+        for (int t = 0; t < (int)one_task.size(); ++t) {
+            if (one_task[t] < 0 || !res[t]) continue;
+            ClassesView ev(ecl, e_off[t], one_task[t]), gv(gcl, g_off[t], g_off[t + 1] - g_off[t]);
+            rc = hgx_classes_set_allele_rank(&ev.c, loc->name_rank.data(), A);
+            if (!rc) rc = chain_after_em1(res[t], loc, &ev.c, opts->remove_low, &gv.c, st, st);
+            if (rc) { rc = fail_task(t, rc); if (rc) return rc; }
         }
         for (int t = 0; t < n; ++t) out[t] = res[t];
         res.clear();

@@ -116,7 +116,8 @@ class LocusResult:
         self.counts = None          # Gene_counts per allele index
         self.exon_classes = None    # (bits[C][w64], counts[C]) host copies, first-seen order
         self.gene_classes = None
-        self.em = []                # [{'n_classes', 'remove_low', 'use_length', 'result', 'n_iter'}]
+        self.em = []                # [{'n_classes', 'remove_low', 'use_length', 'result', 'n_iter'}]; beyond rank 32 below 0.005 the
+                                    # order of a table-lookup EM's list (EM #1 above 4096 classes) is not reference-exact
         self.gene_prob = []         # final [[allele name, prob]] (core:1732-1789)
         self.n_pieces = self.n_refs = 0
         self.t_em = 0.0             # seconds spent inside the EM calls (bench)
@@ -132,7 +133,9 @@ class LocusResult:
 def _em_mode(em_fast):
     """hgx_type_opts.em_fast: None = the entry point's default (one-task calls: the reference's order where the one-workgroup kernel
     takes the problem; many-task calls: table lookups), False = the reference's order (2: also in the many-task calls), True / 1 =
-    table lookups, -1 = the reference's order at every size (validation mode: slow beyond 4096 classes)."""
+    table lookups, -1 = the reference's order at every size (validation mode: slow beyond 4096 classes).  Where table lookups were
+    chosen (True / 1, and the many-task default), decisions on a threshold -- pruning, stopping, the hand-off cut, the report's cut
+    and rounding -- are taken on those values and are not reference-exact."""
     if em_fast is None:
         return 0
     if em_fast is False or (em_fast is not True and int(em_fast) == 0):      # False, 0, numpy.bool_(False): all mean "the reference's order"

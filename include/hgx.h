@@ -462,12 +462,21 @@ typedef struct hgx_type_opts {
                                       reference's own order of floating-point operations -- abundances, pruning and stopping decisions
                                       bit-identical to typing_common.py:1282-1410; the MANY-TASK calls (hgx_type_many / _many_loci: the
                                       throughput API) run table-lookup arithmetic on the same kernel: ~3x faster per panel, abundances
-                                      within 1e-8 of the reference (typically 1e-11; bar 1e-5), same stopping and pruning rules;
-                                   1  table lookups in the one-task calls too;
+                                      within 1e-8 of the reference (typically 1e-11; bar 1e-5), same stopping and pruning rules --
+                                      but decisions on a threshold (pruning at max / 10, stopping at 0.0001, the hand-off cut 0.03, the
+                                      report's 0.01 and rounding) are taken on those values and are not reference-exact there;
+                                   1  table lookups in the one-task calls too (same caveat);
                                    2  the reference's order in the many-task calls too (bit-identical; the hand-off EM always is);
                                   -1  the reference's order at EVERY size (k_emx up to 32768 classes, in cluster mode for a lone large
                                       problem: 33 ms per step for a 1 M-read sample with a 16 000-class EM #1 instead of 2 ms).
-                                 Larger problems (EM #1 of a deep sample) take the chip-wide table-lookup path (<= 1e-9) unless -1. */
+                                 Larger problems (EM #1 of a deep sample) take the chip-wide table-lookup path (<= 1e-9) unless -1.
+                                 In the reference-order modes (0 in the one-task calls, 2 in the many-task calls) its decisions stay
+                                 the reference's: a pruning or stopping decision, an EM #1 value at rank
+                                 >= 10 on the hand-off's 0.03 line, or a report line (at most 20, >= 0.01) on the 0.01 line, on a
+                                 rounding boundary or nearly tied with a neighbour of the other level -- within 1e-8 relative -- runs
+                                 EM #1 again in the reference's order (where it exists: <= 32768 classes over <= 8192 alleles).  Near-ties inside an EM list are checked up to rank 32 or
+                                 0.005, the prefix the chain reads: beyond it, the order of the result's EM lists (LocusResult.em,
+                                 hgx_typing_em) is not reference-exact on this path. */
 } hgx_type_opts;
 
 int hgx_dbatch_create(hgx_dbatch **out, const hgx_batch *b, void *stream);     /* upload; returns when the copy is complete */
@@ -647,8 +656,10 @@ int hgx_stream_probe_chain(void *light_stream, void *other_stream, int32_t mode,
 int hgx_stream_sets_streams(void **streams /* em, gene per free set */, int32_t cap, int32_t *n_sets);
 int hgx_stream_sets_info(int32_t *n_sets, int32_t *n_classes, int32_t *n_probes, double *probe_ms, int32_t *classes, int32_t cap);
 /* hgx_em / hgx_em_ordered calls (default arithmetic) whose table-lookup result held two alleles of DIFFERENT class membership closer
- * than 1e-8 relative and was therefore recomputed in the reference's own order of operations (common:1282-1410: a plain stable
- * sort on the reference's own doubles decides such an order), since the library was loaded.                                    */
+ * than 1e-8 relative, or that took a pruning (p >= max / 10) or stopping (diff > 0.0001) decision within 1e-8 relative of its
+ * threshold, and were therefore recomputed in the reference's own order of operations (common:1282-1410: the reference decides
+ * these on its own doubles), plus the typing calls that ran EM #1 again for the same reason (hand-off cut, report lines), since the
+ * library was loaded.  A direct hgx_em call checks the whole result list; the typing calls check the prefix they read.          */
 long long hgx_em_tie_reruns(void);
 int hgx_em_get_timing(int slot, double *ms_total, int64_t *launches, int64_t *executed, int64_t *bytes_total);
 

@@ -137,7 +137,9 @@ def test_config1_one_million_reads_equals_the_oracle():
     th.start()
     try:
         pl = hl.PackedLocus.from_synth(loc)
+        n_rerun = engine.em_tie_reruns()
         res = hgx.type_locus(pl, sam, keep_classes=True)
+        print("configs[1] default path: %d exact re-run(s) of an EM" % (engine.em_tie_reruns() - n_rerun))
         assert engine.front_last() == (2, 0), engine.front_last()          # the kernels took the records themselves
         res_x = hgx.type_locus(pl, sam, em_fast=-1)
         assert engine.front_last() == (2, 0)
@@ -162,6 +164,8 @@ def test_config1_one_million_reads_equals_the_oracle():
         assert [(a, p) for a, p in got["result"]] == [(a, p) for a, p in r]
     assert [(a, p) for a, p in res_x.gene_prob] == [(a, p) for a, p in exp["gene_prob"]]
     assert res_x.counts_sorted == res.counts_sorted
+    # the default path's report: the reference's text, line for line (res_x is the reference's, bit for bit)
+    assert hgx.report_lines(res) == hgx.report_lines(res_x)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
