@@ -76,6 +76,9 @@ SYMBOLS = [
     "hgx_many_from_dbatch", "hgx_alignment_open", "hgx_alignment_dims", "hgx_alignment_parse_dev", "hgx_alignment_close", "hgx_stream_sets_info", "hgx_stream_create_placed", "hgx_stream_probe_matrix", "hgx_stream_probe_pair", "hgx_stream_probe_chain", "hgx_stream_sets_streams",
     "hgx_parse_sam_dev", "hgx_parse_alignment_file_dev", "hgx_front_last", "hgx_front_last_parts", "hgx_dbatch_to_host",
     "hgx_emx_cluster_stats", "hgx_em_tie_reruns",
+    "hgx_linear_locus_create", "hgx_linear_locus_destroy", "hgx_linear_type_sam", "hgx_linear_type_file", "hgx_linear_dims",
+    "hgx_linear_counts", "hgx_linear_classes", "hgx_linear_extra_names", "hgx_linear_destroy",
+    "hgx_linear_input_open", "hgx_linear_input_dims", "hgx_linear_type_input", "hgx_linear_input_close",
 ]
 
 _lib = None

@@ -1103,7 +1103,7 @@ int hgx_read_alignment_lines(const char *path, const char *regions, int n_thread
     lap("decode / split");
     // an aligner writes its records grouped by read already: a stable sort would not move anything
     bool sorted = true;
-    {
+    if (!out.file_order) {
         std::vector<int> unsorted(n_threads, 0);
         par_for(lines.size() > 100000 ? n_threads : 1, lines.size(), [&](int t, size_t b, size_t e) {
             for (size_t i = std::max<size_t>(b, 1); i < e; ++i)

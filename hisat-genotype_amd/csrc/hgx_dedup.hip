@@ -121,6 +121,16 @@ static int scan_u32(const uint32_t *in, uint32_t *out, long n, void *scratch, ui
     HIPCHK(hipGetLastError());
     return HGX_OK;
 }
+// the same for other translation units (hgx_linear.hip): scratch of hgx_scan_u32_scratch_bytes(n) from the caller (re-zeroed
+// here on `st`, so one scratch serves consecutive scans of up to n items on one stream)
+size_t hgx_scan_u32_scratch_bytes(long n) { return scan_scratch_bytes(std::max(n, 1L)); }
+int hgx_scan_u32_dev(const uint32_t *in, uint32_t *out, long n, void *scratch, uint32_t *total_dev, hipStream_t st) {
+    if (n <= 0) {
+        if (total_dev) HIPCHK(hipMemsetAsync(total_dev, 0, 4, st));
+        return HGX_OK;
+    }
+    return scan_u32(in, out, n, scratch, total_dev, st);
+}
 
 // ------------------------------------------------------------------------------------------------
 // Hash-table form of the dedup (default).  Sorting 500 k 64-bit keys costs ~25 short library launches; the dict

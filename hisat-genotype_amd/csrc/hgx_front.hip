@@ -2685,6 +2685,10 @@ extern "C" int hgx_front_last_parts(int32_t *parts) {
     *parts = g_last_parts;
     return HGX_OK;
 }
+// the linear-index route (hgx_linear.hip) reports through hgx_front_last too
+void hgx_front_set_last(int route, int decline, long long bytes) {
+    g_last_route = route; g_last_decline = decline; g_last_device = route == 2; g_last_bytes = bytes; g_last_parts = 0;
+}
 extern "C" int hgx_front_last(int32_t *route, int32_t *decline_code, int64_t *bytes_to_device) {
     if (route) *route = g_last_device ? g_last_route : 0;
     if (decline_code) *decline_code = g_last_decline;

@@ -204,6 +204,9 @@ struct hgx_align_lines {
     // in: the caller can walk / filter / sort BAM records itself (the device front end) when the inflated stream has at least
     // defer_min_bytes and at most one region was asked for; out: `deferred.on` -- `lines` is empty then
     bool defer_walk = false;
+    // in: keep the records in file order (per region, regions one after the other), no name sort -- `samtools view <file> [region]`
+    // without the `sort -k 1,1 -s` behind it, what the linear branch reads (typing_core.py:1597-1599)
+    bool file_order = false;
     bool defer_text = false;             // ... and SAM text without a line table (the device front end scans the lines itself)
     size_t defer_min_bytes = 0;
     hgx_bam_deferred deferred;

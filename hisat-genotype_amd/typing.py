@@ -82,8 +82,13 @@ def _keys_to_classes(keys):
 
 def single_abundance(Gene_cmpt, remove_low_abundance_allele=False, Gene_length={}):
     """EM abundance of alleles from compatibility classes ``{'a-b-c': count}`` (drop-in, GPU)."""
+    return _single_abundance(Gene_cmpt, remove_low_abundance_allele, Gene_length)[0]
+
+
+def _single_abundance(Gene_cmpt, remove_low_abundance_allele=False, Gene_length={}):
+    """single_abundance and the number of outer EM iterations it took."""
     if len(Gene_cmpt) == 0:
-        return []
+        return [], 0
     names, bits, ap, rank = _keys_to_classes(list(Gene_cmpt.keys()))
     A = len(names)
     counts = np.fromiter(Gene_cmpt.values(), np.int64, len(Gene_cmpt))
@@ -94,7 +99,7 @@ def single_abundance(Gene_cmpt, remove_low_abundance_allele=False, Gene_length={
     try:
         if rank is not None:                               # keys as the reference builds them: '-'.join(sorted(names))
             cl.set_allele_rank(rank)
-        prob, _ = cl.em(A, bool(remove_low_abundance_allele), lengths)
+        prob, n_iter = cl.em(A, bool(remove_low_abundance_allele), lengths)
         exact = bool(capi.lib().hgx_em_last_exact())
         order = engine.em_last_order(A) if exact else None
     finally:
@@ -105,7 +110,7 @@ def single_abundance(Gene_cmpt, remove_low_abundance_allele=False, Gene_length={
     if order is not None:
         idx.sort(key=lambda a: int(order[a]))
     res = [[names[a], float(prob[a])] for a in idx]
-    return _stable_desc(res, exact)
+    return _stable_desc(res, exact), int(n_iter)
 
 
 class LocusResult:
@@ -414,6 +419,158 @@ def report_lines(res, simulation=False, true_alleles=(), output_allele_counts=Fa
     return out, success
 
 
+class LinearOpts(C.Structure):
+    """hgx_linear_opts (include/hgx.h)."""
+    _fields_ = [("aligner", C.c_int32), ("is_hla", C.c_int32), ("gene", C.c_char_p)]
+
+
+LINEAR_ALIGNERS = {"hisat2": 0, "bowtie2": 1}
+
+
+class LinearResult:
+    """What the linear branch computes for one locus (typing_core.py:1597-1677, 1791-1797)."""
+    def __init__(self):
+        self.counts = {}            # Gene_counts in dict order; keys may lie outside the locus (the final trigger, core:1600-1604)
+        self.classes = {}           # Gene_cmpt in dict order: '-'.join(sorted(names)) -> count
+        self.gene_prob = []
+        self.n_iter = 0
+        self.error = None           # the exception the abundance step raises (one class, non-HLA: TypeError, core:1795)
+        self.route = self.decline = 0
+        self.n_groups = 0
+
+    @property
+    def counts_sorted(self):
+        """core:1650-1651: by count, descending, stable over dict order."""
+        return sorted([[a, c] for a, c in self.counts.items()], key=lambda x: x[1], reverse=True)
+
+
+def _linear_locus(pl):
+    """The packed locus' hgx_linear_locus (allele names, name order, device name hash): made once, kept with the locus."""
+    h = getattr(pl, "_linear_h", None)
+    if h is None:
+        import weakref
+        L = capi.lib()
+        pool = b"".join(n.encode() + b"\0" for n in pl.names)
+        h = C.c_void_p()
+        capi.check(L.hgx_linear_locus_create(C.byref(h), pool, C.c_size_t(len(pool)), C.c_int32(len(pl.names))))
+        pl._linear_h = h
+        weakref.finalize(pl, L.hgx_linear_locus_destroy, h)
+    return h
+
+
+class LinearInput:
+    """An alignment file's records for the linear route, read once (hgx_linear_input_open: file order, region-filtered, a BAM
+    kept binary) and, from the first device-route call on, resident on the device: every locus and aligner section of a
+    typing() call types from it."""
+    def __init__(self, path, regions=None):
+        if regions is not None and not isinstance(regions, (str, bytes)):
+            regions = "\n".join(regions)
+        reg = regions.encode() if isinstance(regions, str) else regions
+        self.h = C.c_void_p()
+        capi.check(capi.lib().hgx_linear_input_open(C.byref(self.h), path.encode(), reg))
+        import weakref
+        self._fin = weakref.finalize(self, capi.lib().hgx_linear_input_close, self.h)      # (also when typing() raises)
+        n, bam = C.c_int64(), C.c_int32()
+        capi.check(capi.lib().hgx_linear_input_dims(self.h, C.byref(n), C.byref(bam), None))
+        self.n_records, self.is_bam = n.value, bool(bam.value)
+
+    def close(self):
+        self._fin()
+        self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def type_locus_linear(pl, sam_text=None, aligner="hisat2", alignment_file=None, regions=None, stream=None, linear_input=None):
+    """Linear-index typing of one locus (the reference's `index_type == "linear"` branch, typing_core.py:1597-1677 and
+    1791-1797): `sam_text` (the record stream in file order) or `alignment_file` (SAM / BAM, read in file order; `regions` =
+    samtools region strings, set in genotype-genome mode, core:436-440).  Record pass, groups, accept flags, class dedup and
+    Gene_counts run as kernels (hgx_linear_*; small inputs and the declines of include/hgx.h on the host route); the abundance is
+    the existing EM (single_abundance).  Raises what the reference raises (AssertionError: a kept record without AS; ValueError);
+    the abundance step's TypeError of a non-HLA locus with one class is kept in `.error` (the counts are printed before it)."""
+    res = linear_counts(pl, sam_text, aligner, alignment_file, regions, stream, linear_input)
+    # core:1681-1797 in the linear branch: HLA -> single_abundance(Gene_exons_cmpt = {}) = []; otherwise single_abundance(Gene_cmpt)
+    # with the default flags, and a single class raises (Gene_cmpt.keys()[0] under Python 3, core:1795)
+    if pl.base_fname == "hla":
+        res.gene_prob = []
+    elif len(res.classes) == 1:
+        res.error = TypeError("'dict_keys' object is not subscriptable (reference quirk, typing_core.py:1795)")
+    elif len(res.classes) > 1:
+        res.gene_prob, res.n_iter = _single_abundance(res.classes)
+    return res
+
+
+def linear_counts(pl, sam_text=None, aligner="hisat2", alignment_file=None, regions=None, stream=None, linear_input=None):
+    """type_locus_linear up to the abundance step: Gene_counts and Gene_cmpt (LinearResult without gene_prob).  The records come
+    from `linear_input` (LinearInput: a file read once), `alignment_file` (read for this call) or `sam_text`."""
+    L = capi.lib()
+    ll = _linear_locus(pl)
+    o = LinearOpts(LINEAR_ALIGNERS.get(aligner, 2), int(pl.base_fname == "hla"), pl.gene.encode())
+    h = C.c_void_p()
+    if linear_input is not None:
+        rc = L.hgx_linear_type_input(C.byref(h), linear_input.h, ll, C.byref(o), stream)
+    elif alignment_file is not None:
+        if regions is not None and not isinstance(regions, (str, bytes)):
+            regions = "\n".join(regions)
+        reg = regions.encode() if isinstance(regions, str) else regions
+        rc = L.hgx_linear_type_file(C.byref(h), ll, alignment_file.encode(), reg or None, C.byref(o), stream)
+    else:
+        if isinstance(sam_text, str):
+            sam_text = sam_text.encode()
+        rc = L.hgx_linear_type_sam(C.byref(h), ll, sam_text, C.c_size_t(len(sam_text)), C.byref(o), stream)
+    if rc == -6:                                               # HGX_EPARSE: the reference's own exception
+        msg = L.hgx_last_error().decode(errors="replace")
+        if msg.startswith("AssertionError"):
+            raise AssertionError(msg)
+        raise ValueError(msg)
+    capi.check(rc)
+    res = LinearResult()
+    try:
+        nc, ncl, nids, nx, xb, ng = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int32(), C.c_size_t(), C.c_int64()
+        capi.check(L.hgx_linear_dims(h, C.byref(nc), C.byref(ncl), C.byref(nids), C.byref(nx), C.byref(xb), C.byref(ng)))
+        pool = C.create_string_buffer(max(xb.value, 1))
+        capi.check(L.hgx_linear_extra_names(h, pool))
+        names = list(pl.names) + (pool.raw[:xb.value].decode().split("\0")[:-1] if xb.value else [])
+        ids, cnt = np.zeros(max(nc.value, 1), np.int32), np.zeros(max(nc.value, 1), np.int64)
+        capi.check(L.hgx_linear_counts(h, capi.ptr(ids), capi.ptr(cnt)))
+        res.counts = {names[a]: int(c) for a, c in zip(ids[:nc.value].tolist(), cnt[:nc.value].tolist())}
+        off = np.zeros(ncl.value + 1, np.int64)
+        cid = np.zeros(max(nids.value, 1), np.int32)
+        ccnt = np.zeros(max(ncl.value, 1), np.int64)
+        capi.check(L.hgx_linear_classes(h, capi.ptr(off), capi.ptr(cid), capi.ptr(ccnt)))
+        cid, off = cid.tolist(), off.tolist()
+        res.classes = {"-".join(names[a] for a in cid[off[c]:off[c + 1]]): int(ccnt[c]) for c in range(ncl.value)}
+        res.n_groups = ng.value
+    finally:
+        L.hgx_linear_destroy(h)
+    res.route, res.decline = engine.front_last()[:2]
+    return res
+
+
+def report_lines_linear(res, output_allele_counts=False, best_alleles=False):
+    """Report body of one locus in the linear branch (core:1650-1672, 2076-2121): no 'reads and pairs are aligned' line (that is
+    graph-only, core:1593), no skip of a locus without reads, counted names that may lie outside the locus."""
+    out = []
+    for i, (a, c) in enumerate(res.counts_sorted):
+        out.append("\t\t\t\t%d %s (count: %d)" % (i + 1, a, c))
+        if i >= 9 and not output_allele_counts:
+            break
+    out.append("\n")
+    for i, (a, p) in enumerate(res.gene_prob):
+        if p < 0.01:
+            break
+        out.append("\t\t\t\t%d ranked %s (abundance: %.2f%%)" % (i + 1, a, p * 100.0))
+        if best_alleles and i < 2:
+            out.append("SingleModel %s (abundance: %.2f%%)" % (a, p * 100.0))
+        if i >= 9:
+            break
+    return out
+
+
 def read_alignment_text(alignment_fname, regions=None, n_threads=0, native=True):
     """The record stream the reference's loop consumes: ``samtools view F [chr:l-r] ref_allele`` piped through
     ``sort -k1,1 -s`` (core:436-468), as bytes.  SAM text and BAM files are read by the native reader of libhgx
@@ -491,9 +648,37 @@ def typing(simulation, full_path_base_fname, locus_list, genotype_genome, partia
         say("# HISAT-genotype hot path: hgx %s (MI355X)" % __import__("hisatgenotype_amd").__version__)
         say("# Database - %s" % dbversion)
         say("# COMMAND:\n%s" % " ".join(sys.argv))
+        linear_inputs = {}                                 # region list -> LinearInput (the linear sections' one read of the file)
         for aligner, index_type in aligners:
+            if index_type == "linear":
+                if simulation or alignment_fname == "":
+                    raise NotImplementedError("a linear index without an alignment file (simulation mode, or reads to align) "
+                                              "needs an aligner run: outside the accelerated path")
+                say("\n\t\t%s %s" % (aligner, index_type))
+                # core:370 + 1597-1677: every locus of the list over the same alignment file, in file order.  The file is read
+                # once for all loci and aligner sections (LinearInput); in genotype-genome mode once per distinct locus region
+                for test_Gene_names in locus_list:
+                    gene = test_Gene_names
+                    pl = PackedLocus.cached_from_reference_dicts(gene, base_fname, refGenes, Genes, Gene_names, Gene_lengths,
+                                                                 refGene_loci, Vars, Var_list, Links)
+                    regions = None
+                    if genotype_genome != "":
+                        _, chr_, left, right = refGene_loci[gene][:4]
+                        regions = ["%s:%d-%d" % (chr_, left + 1, right + 1)]
+                    key = tuple(regions or ())
+                    if key not in linear_inputs:
+                        linear_inputs[key] = LinearInput(alignment_fname, regions)
+                    try:
+                        res = type_locus_linear(pl, None, aligner, linear_input=linear_inputs[key])
+                    finally:
+                        if not getattr(pl, "cached", False):
+                            pl.close()
+                    say("\n".join(report_lines_linear(res, output_allele_counts, best_alleles)))
+                    if res.error is not None:                      # the counts are printed before the abundance step raises
+                        raise res.error
+                continue
             if index_type != "graph":
-                raise NotImplementedError("only graph alignments are on the accelerated path")
+                raise NotImplementedError("index type %r is not on the accelerated path" % (index_type,))
             say("\n\t\t%s %s" % (aligner, index_type))
             remove_alignment_file = False
             if alignment_fname == "":                     # core:346-367: align the reads first
@@ -658,5 +843,7 @@ def typing(simulation, full_path_base_fname, locus_list, genotype_genome, partia
                 for f in [alignment_fname] + [alignment_fname + ext for ext in (".bai", ".unsorted")]:
                     if os.path.exists(f):
                         os.remove(f)
+        for li in linear_inputs.values():
+            li.close()
     if simulation:
         return test_passed

@@ -663,6 +663,56 @@ int hgx_stream_sets_info(int32_t *n_sets, int32_t *n_classes, int32_t *n_probes,
 long long hgx_em_tie_reruns(void);
 int hgx_em_get_timing(int slot, double *ms_total, int64_t *launches, int64_t *executed, int64_t *bytes_total);
 
+/* ---- linear-index typing (--linear-index, --aligners hisat2.linear / bowtie2.linear) --------------------------------------
+ * Replaces the reference's `index_type == "linear"` branch (typing_core.py:1597-1649): the records of `samtools view <file>
+ * [region]` in FILE order; a record is skipped iff flag & 0x4, its RNAME does not start with the gene or contains "BACKBONE";
+ * AS = the last cols[11:] column starting with "AS"; a group = a run of kept records with one read id; a record joins the
+ * group's class iff its AS >= the max AS before it in the group; a flushed group counts iff aligner == hisat2, or bowtie2 with
+ * < 10 names; the last group always counts.  Gene_counts[allele] takes the RNAME of the NEXT group's first kept record (the
+ * loop's free variable, core:1600-1604), or for the last group that of the last line read -- which may be a name outside the
+ * locus ("*", another gene, the backbone): such names get ids >= n_alleles (hgx_linear_extra_names).
+ * hgx_linear_locus_create: the allele names of a locus ('\0'-separated, allele index order), their name order and (on first
+ * device use) their device hash; keep it with the packed locus.  hgx_linear_type_sam types SAM text in memory,
+ * hgx_linear_type_file a file (SAM text or BAM, records in file order; regions as hgx_read_alignments, one region is what the
+ * reference passes in genotype-genome mode, core:436-440), hgx_linear_type_input a file opened once (below).  Route: the device route (csrc/hgx_linear.hip) from
+ * 1 000 records on (front=device forces it, front=host forbids it); unknown in-gene names, non-integer or missing AS, lines the
+ * reference would raise on and 64-bit class-key collisions decline to the host route, which gives the same result or words the
+ * reference's error (HGX_EPARSE; AssertionError / ValueError in the message).  hgx_front_last reports the route as the front end
+ * does (2 = device, 0 = host; decline code HGX_LIN_DECLINE_* of csrc/hgx_linear.hpp).
+ * Results: hgx_linear_dims, hgx_linear_counts (Gene_counts in dict order), hgx_linear_classes (Gene_cmpt in dict order: per
+ * class its name ids in name order, CSR), hgx_linear_extra_names.  The abundance (single_abundance, core:1791-1797) is the
+ * existing EM on those classes.                                                                                            */
+typedef struct hgx_linear_opts {
+    int32_t aligner;          /* 0 = hisat2, 1 = bowtie2, 2 = any other aligner name (core:1632-1635) */
+    int32_t is_hla;           /* base_fname == "hla" (the caller's abundance step: Gene_exons_cmpt is empty there) */
+    const char *gene;         /* the RNAME prefix test of core:1620 */
+} hgx_linear_opts;
+typedef struct hgx_linear_locus hgx_linear_locus;
+typedef struct hgx_linear hgx_linear;
+int hgx_linear_locus_create(hgx_linear_locus **out, const char *name_pool, size_t n_bytes, int32_t n_names);
+int hgx_linear_locus_destroy(hgx_linear_locus *ll);
+int hgx_linear_type_sam(hgx_linear **out, hgx_linear_locus *ll, const char *sam, size_t n_bytes, const hgx_linear_opts *opts,
+                        void *stream);
+int hgx_linear_type_file(hgx_linear **out, hgx_linear_locus *ll, const char *path, const char *regions_or_null,
+                         const hgx_linear_opts *opts, void *stream);
+/* The records of one alignment file, read once for every locus and aligner section of a typing() call (typing_core.py:370 runs
+ * `samtools view <file> [region]` once per locus, core:436-440): opened = read, inflated and walked on the host in file order
+ * (region-filtered), uploaded to the device on the first device-route call and kept there until closed.  A BAM stays binary:
+ * the device route reads RNAME through a per-refID table made from the header and AS from the aux data (integer types; f / Z /
+ * A / H / B or no AS decline to the host route, which decodes the records to text once).  hgx_linear_type_file = open + type +
+ * close. */
+typedef struct hgx_linear_input hgx_linear_input;
+int hgx_linear_input_open(hgx_linear_input **out, const char *path, const char *regions_or_null);
+int hgx_linear_input_dims(const hgx_linear_input *in, int64_t *n_records, int32_t *is_bam, size_t *n_bytes);
+int hgx_linear_type_input(hgx_linear **out, hgx_linear_input *in, hgx_linear_locus *ll, const hgx_linear_opts *opts, void *stream);
+int hgx_linear_input_close(hgx_linear_input *in);
+int hgx_linear_dims(const hgx_linear *r, int32_t *n_counted, int32_t *n_classes, int64_t *n_class_ids, int32_t *n_extra,
+                    size_t *extra_bytes, int64_t *n_groups);
+int hgx_linear_counts(const hgx_linear *r, int32_t *name_id, int64_t *count);
+int hgx_linear_classes(const hgx_linear *r, int64_t *offsets /* [n_classes + 1] */, int32_t *name_ids, int64_t *count);
+int hgx_linear_extra_names(const hgx_linear *r, char *pool /* '\0'-terminated names, extra_bytes */);
+int hgx_linear_destroy(hgx_linear *r);
+
 #ifdef __cplusplus
 }
 #endif
