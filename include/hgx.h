@@ -713,6 +713,42 @@ int hgx_linear_classes(const hgx_linear *r, int64_t *offsets /* [n_classes + 1] 
 int hgx_linear_extra_names(const hgx_linear *r, char *pool /* '\0'-terminated names, extra_bytes */);
 int hgx_linear_destroy(hgx_linear *r);
 
+/* ---- read extraction (stage 1 of a real-data run: hisatgenotype --base ... -1 ... -2 ...) ---------------------------------------
+ * Replaces the loop of extract_reads over the aligner's SAM stream (typing_process.py:1630-1745): lines starting with '@' are
+ * skipped; columns by str.split(); a group = a run of records with one read name (the text before '|' with `simulation`); a
+ * record is a hit iff flag & 4 == 0 and (aligner == hisat2 and NH == 1) or ((aligner == bowtie2 and AS > XS and read1_first) if
+ * (flag & 0x40 or not paired) else read2_first), exactly as Python parses process:1678-1684; a hit adds the family of the first
+ * region of its chromosome with left <= pos - 1 < right; read 1 = the group's first left record, read 2 = its LAST right record,
+ * reverse-complemented with reversed qualities under flag & 0x10; at the end of a group the pair is written once per family.
+ * hgx_extract_open (process:1364-1380, 1496-1539): the region table in .locus order -- per region its family index, its chromosome
+ * name ('\0'-separated pool), left and right -- and the mode (hgx_extract_opts).
+ * hgx_extract_feed (process:1630-1760): the next bytes of the stream, cut anywhere; the library runs every group known to be
+ * complete (a later record with another name has been seen) and carries the rest to the next call; `last` != 0 ends the stream
+ * (process:1747-1760).  One chunk is in flight at a time.  Route per chunk: the device route (csrc/hgx_extract.hip) from 2 000
+ * records on (front=device forces it, front=host forbids it); lines the reference would raise on, values int() takes but a
+ * 32-bit parse does not, more than 64 families decline to the host route (csrc/hgx_extract_host.cpp) for that chunk, which gives
+ * the same bytes or words the reference's error: HGX_EPARSE, with hgx_extract_stats' error_kind = 1 ValueError, 2 AssertionError,
+ * 3 SystemExit(1), 4 IndexError, 5 TypeError; the text written before the error stays takeable.
+ * hgx_extract_file (process:1468-1488, the aligner's stdout as a file): SAM text in 64 MB blocks through hgx_extract_feed, or a
+ * BAM in one piece through the alignment reader (a worded error beyond 1 GB of records).
+ * hgx_extract_take (write_read, process:1309-1322): the FASTQ / FASTA text of one family and mate (0 / 1) ready since the last
+ * take; the pointer holds until the next take of the same family and mate, or the close.
+ * hgx_extract_stats: records and groups read, pairs written per family, route (2 = every chunk on the device, 0 = a chunk on the
+ * host) and the last decline code (HGX_EXT_DECLINE_* of csrc/hgx_extract.hpp) as hgx_front_last reports them per chunk.       */
+typedef struct hgx_extract_opts {
+    int32_t aligner;          /* 0 = hisat2, 1 = bowtie2, 2 = any other aligner name */
+    int32_t paired, simulation, fastq;
+} hgx_extract_opts;
+typedef struct hgx_extract hgx_extract;
+int hgx_extract_open(hgx_extract **out, int32_t n_regions, const int32_t *family, const char *chrom_pool, size_t chrom_bytes,
+                     const int64_t *left, const int64_t *right, int32_t n_families, const hgx_extract_opts *opts);
+int hgx_extract_feed(hgx_extract *h, const char *bytes, size_t n_bytes, int32_t last, void *stream);
+int hgx_extract_file(hgx_extract *h, const char *path, void *stream);
+int hgx_extract_take(hgx_extract *h, int32_t family, int32_t mate, const char **text, size_t *n_bytes);
+int hgx_extract_stats(const hgx_extract *h, int64_t *records, int64_t *groups, int64_t *written /* [n_families] */, int32_t *route,
+                      int32_t *decline, int32_t *error_kind, int64_t *chunks_device, int64_t *chunks_host);
+int hgx_extract_close(hgx_extract *h);
+
 #ifdef __cplusplus
 }
 #endif
