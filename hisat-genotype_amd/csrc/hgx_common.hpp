@@ -169,6 +169,13 @@ int hgx_pair_classes_fused_launch(const hgx_index *ix, const uint64_t *compat, c
                                   int32_t n_pairs, int32_t level, unsigned long long *keys, uint32_t tmask, uint32_t *rep,
                                   uint32_t *slot_of, int *bad, uint64_t *rows, hipStream_t st);
 
+// exclusive scan of n uint32 values for other translation units (hgx_dedup.hip): scratch of hgx_scan_u32_scratch_bytes(n)
+// from the caller, the total left at total_dev
+int hgx_scan_u32_dev(const uint32_t *in, uint32_t *out, long n, void *scratch, uint32_t *total_dev, hipStream_t st);
+size_t hgx_scan_u32_scratch_bytes(long n);
+// what hgx_front_last reports for the call just made (hgx_front.hip): route, decline code, bytes uploaded
+void hgx_front_set_last(int route, int decline, long long bytes);
+
 int hgx_pair_classes_dedup_ev(hgx_classes **out, const hgx_index *ix, const uint64_t *compat, const int32_t *pair_off, const uint32_t *refs,
                               int32_t n_pairs, int32_t level, uint64_t *rows_scratch, void *stream, void *ev_begin, void *ev_end);
 

@@ -121,7 +121,7 @@ static int scan_u32(const uint32_t *in, uint32_t *out, long n, void *scratch, ui
     HIPCHK(hipGetLastError());
     return HGX_OK;
 }
-// the same for other translation units (hgx_linear.hip): scratch of hgx_scan_u32_scratch_bytes(n) from the caller (re-zeroed
+// the same for other translation units (declared in hgx_common.hpp): scratch of hgx_scan_u32_scratch_bytes(n) from the caller (re-zeroed
 // here on `st`, so one scratch serves consecutive scans of up to n items on one stream)
 size_t hgx_scan_u32_scratch_bytes(long n) { return scan_scratch_bytes(std::max(n, 1L)); }
 int hgx_scan_u32_dev(const uint32_t *in, uint32_t *out, long n, void *scratch, uint32_t *total_dev, hipStream_t st) {

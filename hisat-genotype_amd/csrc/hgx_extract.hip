@@ -3,13 +3,13 @@
 //
 // The reference walks the aligner's SAM over the whole genotype genome and writes, per locus family, the read pairs with a hit
 // in one of the family's regions.  The stream arrives in chunks cut on group boundaries (ext_feed); per chunk, in order:
-//   k_ext_records   one thread per line: columns as str.split() cuts them, FLAG, POS - 1, RNAME -> chromosome (device hash of the
-//                   region table's chromosome names, exact byte compare) -> the family of the first region of that chromosome
-//                   holding the position, AS / XS / NH (cols[11:] by their first two characters, last one wins), the hash of the
-//                   read name (up to '|' in simulation mode), and where QNAME, SEQ and QUAL lie; anything the host route has to
-//                   word (a short line, a value int() refuses) declines
-//   k_ext_heads     a record opens a group where its name differs from the previous record's (hash, then bytes)
-//   scan + k_ext_gstart      group extents (k_scan_u32)
+//   k_ext_records   one thread per line: columns as str.split() cuts them, FLAG, POS - 1, RNAME -> chromosome (name_lookup of
+//                   hgx_records.hpp: device hash of the region table's chromosome names, exact byte compare) -> the family of
+//                   the first region of that chromosome holding the position, AS / XS / NH (cols[11:] by their first two
+//                   characters, last one wins), the hash of the read name (up to '|' in simulation mode), and where QNAME, SEQ
+//                   and QUAL lie; anything the host route has to word (a short line, a value int() refuses) declines
+//   k_rec_heads     a record opens a group where its name differs from the previous record's (hash, then bytes)
+//   scan + k_rec_gstart      group extents (k_scan_u32; both kernels shared with the linear route: hgx_records.hpp)
 //   k_ext_groups    one thread per group: read1_first / read2_first carried in record order, the hit condition as Python parses
 //                   it, the family bit set (<= 64 families), read 1 = the first left record, read 2 = the LAST right record
 //   scan + k_ext_hits        the groups with a family, in order
@@ -26,16 +26,7 @@
 #include "hgx_common.hpp"
 #include "hgx_internal.hpp"
 #include "hgx_extract.hpp"
-
-int hgx_scan_u32_dev(const uint32_t *in, uint32_t *out, long n, void *scratch, uint32_t *total_dev, hipStream_t st);
-size_t hgx_scan_u32_scratch_bytes(long n);
-void hgx_front_set_last(int route, int decline, long long bytes);
-
-__host__ __device__ static inline uint64_t ext_fnv(const char *p, size_t n) {
-    uint64_t h = 1469598103934665603ull;
-    for (size_t i = 0; i < n; ++i) h = (h ^ (uint8_t)p[i]) * 1099511628211ull;
-    return h;
-}
+#include "hgx_records.hpp"
 
 __device__ static inline bool ext_sp(char c) { return c == ' ' || (c >= '\t' && c <= '\r') || (c >= 0x1c && c <= 0x1f); }
 
@@ -63,8 +54,7 @@ struct ExtRec {                         // per record, structure of arrays
 constexpr uint32_t EXT_HAS_AS = 1, EXT_HAS_XS = 2, EXT_HAS_NH = 4;
 
 __global__ void k_ext_records(const char *__restrict__ text, const uint32_t *__restrict__ ls, const uint32_t *__restrict__ le, long N,
-                              const char *__restrict__ cpool, const uint32_t *__restrict__ coff, const int32_t *__restrict__ cslot,
-                              uint32_t cmask, const uint32_t *__restrict__ creg, const int32_t *__restrict__ rfam,
+                              const hgx_name_view chroms, const uint32_t *__restrict__ creg, const int32_t *__restrict__ rfam,
                               const long long *__restrict__ rl, const long long *__restrict__ rr, int simulation, ExtRec R,
                               uint32_t *__restrict__ decline) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -115,18 +105,10 @@ __global__ void k_ext_records(const char *__restrict__ text, const uint32_t *__r
     const long long p0 = p1 - 1;
     int32_t fam = -1;
     if (!(flag & 0x4)) {
-        const char *r = text + r0;
-        for (uint32_t s = (uint32_t)ext_fnv(r, rn) & cmask;; s = (s + 1) & cmask) {
-            const int32_t c = cslot[s];
-            if (c < 0) break;
-            const uint32_t b = coff[c], n = coff[c + 1] - b;
-            if (n != rn) continue;
-            uint32_t k = 0;
-            while (k < n && cpool[b + k] == r[k]) ++k;
-            if (k != n) continue;
+        const int32_t c = name_lookup(chroms, text + r0, rn);
+        if (c >= 0) {
             for (uint32_t x = creg[c]; x < creg[c + 1]; ++x)
                 if (p0 >= rl[x] && p0 < rr[x]) { fam = rfam[x]; break; }
-            break;
         }
     }
     const char *q = text + q0;
@@ -140,30 +122,10 @@ __global__ void k_ext_records(const char *__restrict__ text, const uint32_t *__r
     R.tags[i] = tags;
     R.fam[i] = fam;
     R.as[i] = (int32_t)v_as; R.xs[i] = (int32_t)v_xs; R.nh[i] = (int32_t)v_nh;
-    R.kh[i] = ext_fnv(q, kn);
+    R.kh[i] = fnv1a(q, kn);
     R.qoff[i] = q0; R.qlen[i] = qn; R.klen[i] = kn;
     R.soff[i] = s0; R.slen[i] = sn;
     R.loff[i] = l0; R.llen[i] = ln;
-}
-
-__global__ void k_ext_heads(const char *__restrict__ text, const uint64_t *__restrict__ kh, const uint32_t *__restrict__ qoff,
-                            const uint32_t *__restrict__ klen, long N, uint32_t *__restrict__ head) {
-    const long j = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= N) return;
-    uint32_t h = 1;
-    if (j > 0 && kh[j] == kh[j - 1] && klen[j] == klen[j - 1]) {
-        const char *a = text + qoff[j], *b = text + qoff[j - 1];
-        uint32_t k = 0;
-        const uint32_t n = klen[j];
-        while (k < n && a[k] == b[k]) ++k;
-        h = k == n ? 0u : 1u;
-    }
-    head[j] = h;
-}
-
-__global__ void k_ext_gstart(const uint32_t *__restrict__ head, const uint32_t *__restrict__ gid, long N, uint32_t *__restrict__ gstart) {
-    const long j = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < N && head[j]) gstart[gid[j]] = (uint32_t)j;
 }
 
 // The loop body of process:1678-1713 for one group, in record order.
@@ -308,70 +270,28 @@ __global__ void __launch_bounds__(64) k_ext_emit(const char *__restrict__ text, 
     if (tail0 + lane < end) dst[tail0 + lane - pad] = s_img[tail0 + lane];
 }
 
-namespace {
-struct DevBufs {                         // the call's device arrays, from the library's pool (no hipMalloc per array)
-    std::vector<void *> ps;
-    ~DevBufs() { for (void *p : ps) hgx_pool_free(p); }
-    template <class T> int get(T *&p, size_t n) {
-        void *q = hgx_pool_alloc(std::max<size_t>(n, 1) * sizeof(T));
-        if (!q) {
-            hgx_set_error("extract route: device allocation of %zu bytes failed", n * sizeof(T));
-            return HGX_ENOMEM;
-        }
-        ps.push_back(q);
-        p = (T *)q;
-        return HGX_OK;
-    }
-};
-}  // namespace
-
-#define XCHK(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
-
 static void ext_free_table(hgx_extract &h) {
-    if (h.dev < 0) return;
-    int cur = 0;
-    const bool switched = hipGetDevice(&cur) == hipSuccess && cur != h.dev && hipSetDevice(h.dev) == hipSuccess;
-    for (void **p : {&h.d_cpool, &h.d_coff, &h.d_cslot, &h.d_creg, &h.d_rfam, &h.d_rl, &h.d_rr}) {
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-    }
-    if (switched) (void)hipSetDevice(cur);
-    h.dev = -1;
+    free_on_device(h.dev, {h.d_chrom.pool, h.d_chrom.off, h.d_chrom.slot, h.d_creg, h.d_rfam, h.d_rl, h.d_rr});
+    h.d_chrom = hgx_name_view();
+    h.d_creg = nullptr; h.d_rfam = nullptr; h.d_rl = h.d_rr = nullptr;
 }
 
 static int ext_upload_table(hgx_extract &h) {
     int dev = 0;
     HIPCHK(hipGetDevice(&dev));
-    if (h.d_cslot && h.dev == dev) return HGX_OK;
+    if (h.d_chrom.slot && h.dev == dev) return HGX_OK;
     ext_free_table(h);
-    const size_t C = h.chrom.size(), NR = h.reg_fam.size();
-    uint32_t ns = 16;
-    while (ns < 2 * C + 16) ns <<= 1;
-    std::vector<int32_t> slot(ns, -1);
-    std::vector<char> pool;
-    std::vector<uint32_t> off(1, 0);
-    for (size_t c = 0; c < C; ++c) {
-        uint32_t s = (uint32_t)ext_fnv(h.chrom[c].data(), h.chrom[c].size()) & (ns - 1);
-        while (slot[s] >= 0) s = (s + 1) & (ns - 1);
-        slot[s] = (int32_t)c;
-        pool.insert(pool.end(), h.chrom[c].begin(), h.chrom[c].end());
-        off.push_back((uint32_t)pool.size());
-    }
+    const size_t NR = h.reg_fam.size();
     h.dev = dev;
-    auto up = [&](void **d, const void *src, size_t n) {
-        if (hipMalloc(d, std::max<size_t>(n, 16)) != hipSuccess) return false;
-        return n == 0 || hipMemcpy(*d, src, n, hipMemcpyHostToDevice) == hipSuccess;
-    };
-    const bool ok = up(&h.d_cpool, pool.data(), pool.size()) && up(&h.d_coff, off.data(), off.size() * 4) && up(&h.d_cslot, slot.data(), (size_t)ns * 4) &&
-                    up(&h.d_creg, h.creg_off.data(), h.creg_off.size() * 4) && up(&h.d_rfam, h.reg_fam.data(), NR * 4) &&
-                    up(&h.d_rl, h.reg_left.data(), NR * 8) && up(&h.d_rr, h.reg_right.data(), NR * 8);
+    const bool ok = name_table_upload(h.d_chrom, h.chrom) && upload_array(h.d_creg, h.creg_off.data(), h.creg_off.size() * 4) &&
+                    upload_array(h.d_rfam, h.reg_fam.data(), NR * 4) && upload_array(h.d_rl, h.reg_left.data(), NR * 8) &&
+                    upload_array(h.d_rr, h.reg_right.data(), NR * 8);
     if (!ok) {
         const hipError_t e = hipGetLastError();
         ext_free_table(h);
         hgx_set_error("extract route: upload of the region table failed: %s", hipGetErrorString(e));
         return HGX_EHIP;
     }
-    h.cslot_mask = ns - 1;
     return HGX_OK;
 }
 
@@ -381,57 +301,55 @@ static int ext_device(hgx_extract &h, const char *base, size_t n_bytes, const st
     *declined = 0;
     const long N = (long)ls.size();
     if (h.n_fam > 64) { *declined = HGX_EXT_DECLINE_FAMILIES; return HGX_OK; }
-    XCHK(ext_upload_table(h));
-    DevBufs m;
+    RCHK(ext_upload_table(h));
+    DevBufs m("extract route");
     char *d_text, *d_scan;
     uint32_t *d_ls, *d_le, *d_head, *d_gid, *d_dec, *d_tot;
     unsigned long long *d_or;
     ExtRec R;
-    XCHK(m.get(d_text, n_bytes + 64));
-    XCHK(m.get(d_ls, N)); XCHK(m.get(d_le, N)); XCHK(m.get(d_head, N)); XCHK(m.get(d_gid, N));
-    XCHK(m.get(R.flag, N)); XCHK(m.get(R.tags, N)); XCHK(m.get(R.qoff, N)); XCHK(m.get(R.qlen, N)); XCHK(m.get(R.klen, N));
-    XCHK(m.get(R.soff, N)); XCHK(m.get(R.slen, N)); XCHK(m.get(R.loff, N)); XCHK(m.get(R.llen, N));
-    XCHK(m.get(R.fam, N)); XCHK(m.get(R.as, N)); XCHK(m.get(R.xs, N)); XCHK(m.get(R.nh, N)); XCHK(m.get(R.kh, N));
-    XCHK(m.get(d_dec, 4)); XCHK(m.get(d_tot, 4 + 2 * 64)); XCHK(m.get(d_or, 2 + 64));
-    XCHK(m.get(d_scan, hgx_scan_u32_scratch_bytes(N)));
+    RCHK(m.get(d_text, n_bytes + 64));
+    RCHK(m.get(d_ls, N)); RCHK(m.get(d_le, N)); RCHK(m.get(d_head, N)); RCHK(m.get(d_gid, N));
+    RCHK(m.get(R.flag, N)); RCHK(m.get(R.tags, N)); RCHK(m.get(R.qoff, N)); RCHK(m.get(R.qlen, N)); RCHK(m.get(R.klen, N));
+    RCHK(m.get(R.soff, N)); RCHK(m.get(R.slen, N)); RCHK(m.get(R.loff, N)); RCHK(m.get(R.llen, N));
+    RCHK(m.get(R.fam, N)); RCHK(m.get(R.as, N)); RCHK(m.get(R.xs, N)); RCHK(m.get(R.nh, N)); RCHK(m.get(R.kh, N));
+    RCHK(m.get(d_dec, 4)); RCHK(m.get(d_tot, 4 + 2 * 64)); RCHK(m.get(d_or, 2 + 64));
+    RCHK(m.get(d_scan, hgx_scan_u32_scratch_bytes(N)));
     HIPCHK(hipMemcpyAsync(d_text, base, n_bytes, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(d_text + n_bytes, 0, 64, st));
     HIPCHK(hipMemcpyAsync(d_ls, ls.data(), (size_t)N * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_le, le.data(), (size_t)N * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(d_dec, 0, 16, st));
     HIPCHK(hipMemsetAsync(d_or, 0, (2 + 64) * 8, st));
-    hipLaunchKernelGGL(k_ext_records, dim3(nblk(N, 256)), dim3(256), 0, st, d_text, d_ls, d_le, N, (const char *)h.d_cpool,
-                       (const uint32_t *)h.d_coff, (const int32_t *)h.d_cslot, h.cslot_mask, (const uint32_t *)h.d_creg,
-                       (const int32_t *)h.d_rfam, (const long long *)h.d_rl, (const long long *)h.d_rr, h.simulation, R, d_dec);
+    hipLaunchKernelGGL(k_ext_records, dim3(nblk(N, 256)), dim3(256), 0, st, d_text, d_ls, d_le, N, h.d_chrom, h.d_creg,
+                       h.d_rfam, h.d_rl, h.d_rr, h.simulation, R, d_dec);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_ext_heads, dim3(nblk(N, 256)), dim3(256), 0, st, d_text, R.kh, R.qoff, R.klen, N, d_head);
+    hipLaunchKernelGGL(k_rec_heads<uint32_t>, dim3(nblk(N, 256)), dim3(256), 0, st, d_text, R.kh, R.qoff, R.klen, N, d_head);
     HIPCHK(hipGetLastError());
-    XCHK(hgx_scan_u32_dev(d_head, d_gid, N, d_scan, d_tot, st));
+    RCHK(hgx_scan_u32_dev(d_head, d_gid, N, d_scan, d_tot, st));
     uint32_t h_dec = 0, G = 0;
     HIPCHK(hipMemcpyAsync(&h_dec, d_dec, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(&G, d_tot, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    auto first_bit = [](uint32_t d) { for (int b = 1; b < 32; ++b) if (d & (1u << b)) return b; return 0; };
-    if (h_dec) { *declined = first_bit(h_dec); return HGX_OK; }
+    if (h_dec) { *declined = first_decline(h_dec); return HGX_OK; }
     uint32_t *d_gstart, *d_r1, *d_r2, *d_ghit, *d_hpos;
     unsigned long long *d_gbits;
-    XCHK(m.get(d_gstart, (size_t)G + 1)); XCHK(m.get(d_r1, G)); XCHK(m.get(d_r2, G)); XCHK(m.get(d_ghit, G)); XCHK(m.get(d_hpos, G));
-    XCHK(m.get(d_gbits, G));
-    hipLaunchKernelGGL(k_ext_gstart, dim3(nblk(N, 256)), dim3(256), 0, st, d_head, d_gid, N, d_gstart);
+    RCHK(m.get(d_gstart, (size_t)G + 1)); RCHK(m.get(d_r1, G)); RCHK(m.get(d_r2, G)); RCHK(m.get(d_ghit, G)); RCHK(m.get(d_hpos, G));
+    RCHK(m.get(d_gbits, G));
+    hipLaunchKernelGGL(k_rec_gstart, dim3(nblk(N, 256)), dim3(256), 0, st, d_head, d_gid, N, d_gstart);
     HIPCHK(hipGetLastError());
     const uint32_t n32 = (uint32_t)N;
     HIPCHK(hipMemcpyAsync(d_gstart + G, &n32, 4, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_ext_groups, dim3(nblk(G, 256)), dim3(256), 0, st, d_gstart, (long)G, R, h.aligner, h.paired, d_gbits, d_r1, d_r2,
                        d_ghit, d_or, d_dec);
     HIPCHK(hipGetLastError());
-    XCHK(hgx_scan_u32_dev(d_ghit, d_hpos, G, d_scan, d_tot + 1, st));
+    RCHK(hgx_scan_u32_dev(d_ghit, d_hpos, G, d_scan, d_tot + 1, st));
     uint32_t H = 0;
     unsigned long long fam_or = 0;
     HIPCHK(hipMemcpyAsync(&h_dec, d_dec, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(&H, d_tot + 1, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(&fam_or, d_or, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    if (h_dec) { *declined = first_bit(h_dec); return HGX_OK; }
+    if (h_dec) { *declined = first_decline(h_dec); return HGX_OK; }
     h.up_bytes += (long long)n_bytes + 8ll * N;
     if (H == 0) { h.n_groups += G; return HGX_OK; }
     std::vector<int> fams;
@@ -440,15 +358,15 @@ static int ext_device(hgx_extract &h, const char *base, size_t n_bytes, const st
     const size_t F = fams.size();
     uint32_t *d_hg, *d_sz, *d_off;
     const size_t Hp = ((size_t)H + 3) & ~(size_t)3;                     // k_scan_u32 reads and writes 16 bytes at a time: aligned rows
-    XCHK(m.get(d_hg, H)); XCHK(m.get(d_sz, 2 * Hp)); XCHK(m.get(d_off, 2 * F * Hp));
+    RCHK(m.get(d_hg, H)); RCHK(m.get(d_sz, 2 * Hp)); RCHK(m.get(d_off, 2 * F * Hp));
     hipLaunchKernelGGL(k_ext_hits, dim3(nblk(G, 256)), dim3(256), 0, st, d_ghit, d_hpos, (long)G, d_hg);
     HIPCHK(hipGetLastError());
     for (size_t k = 0; k < F; ++k) {
         hipLaunchKernelGGL(k_ext_sizes, dim3(nblk(H, 256)), dim3(256), 0, st, d_hg, (long)H, d_gbits, fams[k], d_gstart, d_r1, d_r2, R,
                            h.paired, h.fastq, d_sz, d_sz + Hp, d_or + 1, d_or + 2 + k);
         HIPCHK(hipGetLastError());
-        XCHK(hgx_scan_u32_dev(d_sz, d_off + (2 * k) * Hp, H, d_scan, d_tot + 4 + 2 * k, st));
-        XCHK(hgx_scan_u32_dev(d_sz + Hp, d_off + (2 * k + 1) * Hp, H, d_scan, d_tot + 4 + 2 * k + 1, st));
+        RCHK(hgx_scan_u32_dev(d_sz, d_off + (2 * k) * Hp, H, d_scan, d_tot + 4 + 2 * k, st));
+        RCHK(hgx_scan_u32_dev(d_sz + Hp, d_off + (2 * k + 1) * Hp, H, d_scan, d_tot + 4 + 2 * k + 1, st));
     }
     std::vector<uint32_t> tot(2 * F);
     std::vector<unsigned long long> cnt(1 + F);                          // all bytes, then reads per family
@@ -460,7 +378,7 @@ static int ext_device(hgx_extract &h, const char *base, size_t n_bytes, const st
     std::vector<size_t> part(2 * F + 1, 0);
     for (size_t k = 0; k < 2 * F; ++k) part[k + 1] = part[k] + (((size_t)tot[k] + 15) & ~(size_t)15);
     char *d_out;
-    XCHK(m.get(d_out, part[2 * F] + 16));
+    RCHK(m.get(d_out, part[2 * F] + 16));
     for (size_t k = 0; k < F; ++k) {
         hipLaunchKernelGGL(k_ext_emit, dim3(2 * H), dim3(64), 0, st, d_text, d_hg, (long)H, d_gbits, fams[k], d_gstart, d_r1, d_r2, R, h.fastq,
                            d_off + (2 * k) * Hp, d_off + (2 * k + 1) * Hp, d_out + part[2 * k], h.paired ? d_out + part[2 * k + 1] : (char *)nullptr);
@@ -476,6 +394,22 @@ static int ext_device(hgx_extract &h, const char *base, size_t n_bytes, const st
     }
     h.n_groups += G;
     return HGX_OK;
+}
+
+// Index of the first record of the last group of lines [0, n), n > 0 (a name counts up to '|' in simulation mode).
+static size_t ext_last_group(const hgx_extract &h, const char *base, const std::vector<uint32_t> &ls, const std::vector<uint32_t> &le, size_t n) {
+    const char *nm, *pn;
+    uint32_t nn, kn, pnn, pkn;
+    size_t j = n - 1;
+    hgx_extract_name(base + ls[j], le[j] - ls[j], nm, nn, kn);
+    if (!h.simulation) kn = nn;
+    while (j > 0) {
+        hgx_extract_name(base + ls[j - 1], le[j - 1] - ls[j - 1], pn, pnn, pkn);
+        if (!h.simulation) pkn = pnn;
+        if (pkn != kn || memcmp(pn, nm, kn) != 0) break;
+        --j;
+    }
+    return j;
 }
 
 // One chunk: lines [0, n) of `base`, all of whose groups are complete.
@@ -498,18 +432,10 @@ static int ext_chunk(hgx_extract &h, const char *base, size_t n_bytes, std::vect
         return hgx_extract_host(h, base, ls.data(), le.data(), n);
     }
     // what the loop holds behind the chunk: the last group's first name; the chk_line test is over (hgx_extract_chk passed it)
-    size_t j = n - 1;
-    const char *nm, *pn;
-    uint32_t nn, kn, pnn, pkn;
+    const size_t j = ext_last_group(h, base, ls, le, n);
+    const char *nm;
+    uint32_t nn, kn;
     hgx_extract_name(base + ls[j], le[j] - ls[j], nm, nn, kn);
-    if (!h.simulation) kn = nn;
-    while (j > 0) {
-        hgx_extract_name(base + ls[j - 1], le[j - 1] - ls[j - 1], pn, pnn, pkn);
-        if (!h.simulation) pkn = pnn;
-        if (pkn != kn || memcmp(pn, nm, kn) != 0) break;
-        --j;
-        nm = pn; nn = pnn;
-    }
     h.prev_name.assign(nm, nn);
     h.chk_line = false;
     h.n_records += (int64_t)n;
@@ -533,19 +459,8 @@ static int ext_run(hgx_extract &h, bool last, hipStream_t st) {
     size_t keep_from = nb;                               // first byte carried over
     if (!last && n > 0) {
         // the last group may go on in the next bytes: it is complete once a record with another name has been seen
-        const char *nm, *pn;
-        uint32_t nn, kn, pnn, pkn;
-        size_t j = n - 1;
-        hgx_extract_name(base + ls[j], le[j] - ls[j], nm, nn, kn);
-        if (!h.simulation) kn = nn;
-        while (j > 0) {
-            hgx_extract_name(base + ls[j - 1], le[j - 1] - ls[j - 1], pn, pnn, pkn);
-            if (!h.simulation) pkn = pnn;
-            if (pkn != kn || memcmp(pn, nm, kn) != 0) break;
-            --j;
-        }
-        n = j;
-        keep_from = ls[j];
+        n = ext_last_group(h, base, ls, le, n);
+        keep_from = ls[n];
     }
     int rc = HGX_OK;
     if (n > 0) rc = ext_chunk(h, base, keep_from, ls, le, n, st);
@@ -606,7 +521,7 @@ extern "C" int hgx_extract_feed(hgx_extract *h, const char *bytes, size_t n_byte
         h->buf.insert(h->buf.end(), bytes + p, bytes + p + take);
         p += take;
         const bool fin = last && p == n_bytes;
-        XCHK(ext_run(*h, fin, (hipStream_t)stream));
+        RCHK(ext_run(*h, fin, (hipStream_t)stream));
         if (fin) h->finished = true;
     } while (p < n_bytes);
     return HGX_OK;
@@ -622,21 +537,13 @@ extern "C" int hgx_extract_file(hgx_extract *h, const char *path, void *stream) 
         // BAM (BGZF): the existing reader inflates and walks the file in one piece, records in file order, as the text
         // `samtools view` prints; that text is the stream
         fclose(f);
-        hgx_align_lines t;
-        t.file_order = true;
-        XCHK(hgx_read_alignment_lines(path, nullptr, 0, t));
-        size_t tot = 0;
-        for (size_t i = 0; i < t.lines.size(); ++i) tot += (size_t)t.lines[i].len + 1;
+        std::vector<char> text;
+        size_t tot;
+        RCHK(bam_as_sam_text(path, nullptr, EXT_MAX_BUF, text, tot));
         if (tot > EXT_MAX_BUF) {
             hgx_set_error("hgx_extract_file: %s holds %zu bytes of records; a BAM is read in one piece of at most %zu (feed it as SAM text)",
                           path, tot, EXT_MAX_BUF);
             return HGX_EINVAL;
-        }
-        std::vector<char> text;
-        text.reserve(tot);
-        for (size_t i = 0; i < t.lines.size(); ++i) {
-            text.insert(text.end(), t.lines[i].p, t.lines[i].p + t.lines[i].len);
-            text.push_back('\n');
         }
         return hgx_extract_feed(h, text.data(), text.size(), 1, stream);
     }

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "hgx.h"
+#include "hgx_records.hpp"
 
 enum {
     HGX_EXT_DECLINE_NONE = 0,
@@ -49,8 +50,10 @@ struct hgx_extract {
     std::vector<int64_t> written;                                // pairs (reads) written per family
     std::vector<std::string> out, taken;                         // [n_fam * 2]: text not yet taken / the block handed out last
     // device copies of the region table (hgx_extract.hip)
-    void *d_cpool = nullptr, *d_coff = nullptr, *d_cslot = nullptr, *d_creg = nullptr, *d_rfam = nullptr, *d_rl = nullptr, *d_rr = nullptr;
-    uint32_t cslot_mask = 0;
+    hgx_name_view d_chrom;
+    uint32_t *d_creg = nullptr;
+    int32_t *d_rfam = nullptr;
+    long long *d_rl = nullptr, *d_rr = nullptr;
     int dev = -1;
 };
 

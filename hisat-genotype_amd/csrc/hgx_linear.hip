@@ -2,12 +2,13 @@
 //
 // The reference reads `samtools view <file> [region]` in file order; a class is the set of alleles a read aligned to with its
 // best AS so far (HISAT2 / Bowtie2 against an index of allele sequences, -k 10: common:1003-1016).  Kernels, in order:
-//   k_lin_records   one thread per line: columns as str.split() cuts them, FLAG, RNAME -> allele id (device hash of the locus'
-//                   names, exact byte compare), the filters of core:1618-1623, AS (last cols[11:] column starting "AS"), the
-//                   read-id hash; anything the host route has to word (unknown in-gene name, no integer AS, a short line) declines
+//   k_lin_records   one thread per line: columns as str.split() cuts them, FLAG, RNAME -> allele id (name_lookup of
+//                   hgx_records.hpp: device hash of the locus' names, exact byte compare), the filters of core:1618-1623, AS
+//                   (last cols[11:] column starting "AS"), the read-id hash; anything the host route has to word (unknown
+//                   in-gene name, no integer AS, a short line) declines
 //   scan + k_lin_compact     the kept records, in order (k_scan_u32)
-//   k_lin_heads     a record opens a group where its read id differs from the previous kept record's (hash, then bytes)
-//   scan + k_lin_gstart      group extents
+//   k_rec_heads     a record opens a group where its read id differs from the previous kept record's (hash, then bytes)
+//   scan + k_rec_gstart      group extents (both kernels shared with the extract route: hgx_records.hpp)
 //   k_lin_groups    one thread per group: the segmented exclusive prefix max of AS (accept flags), the accepted ids in name
 //                   order without repeats, the bowtie2 size rule, the class key, and Gene_counts of the group's trigger (the
 //                   NEXT group's first kept RNAME, core:1600-1604) with its first-seen group for the dict order
@@ -23,19 +24,7 @@
 #include "hgx_common.hpp"
 #include "hgx_internal.hpp"
 #include "hgx_linear.hpp"
-
-int hgx_scan_u32_dev(const uint32_t *in, uint32_t *out, long n, void *scratch, uint32_t *total_dev, hipStream_t st);
-size_t hgx_scan_u32_scratch_bytes(long n);
-
-void hgx_front_set_last(int route, int decline, long long bytes);
-
-static constexpr uint64_t LIN_EMPTY = ~0ull;
-
-__host__ __device__ static inline uint64_t lin_fnv(const char *p, size_t n) {
-    uint64_t h = 1469598103934665603ull;
-    for (size_t i = 0; i < n; ++i) h = (h ^ (uint8_t)p[i]) * 1099511628211ull;
-    return h;
-}
+#include "hgx_records.hpp"
 
 __device__ static inline bool lin_sp(char c) { return c == ' ' || c == '\t' || c == '\n' || c == '\r' || c == '\v' || c == '\f'; }
 
@@ -55,11 +44,9 @@ __device__ static inline bool lin_int(const char *p, long n, int64_t &v) {
 }
 
 __global__ void k_lin_records(const char *__restrict__ text, const uint64_t *__restrict__ ls, const uint64_t *__restrict__ le, long N,
-                              const char *__restrict__ gene, int gene_len, const char *__restrict__ pool,
-                              const uint32_t *__restrict__ poff, const int32_t *__restrict__ slot, uint32_t mask,
-                              uint32_t *__restrict__ keep, int32_t *__restrict__ aid, int32_t *__restrict__ as_out,
-                              uint64_t *__restrict__ qh, uint64_t *__restrict__ qoff, uint32_t *__restrict__ qlen,
-                              uint32_t *__restrict__ decline) {
+                              const char *__restrict__ gene, int gene_len, const hgx_name_view names, uint32_t *__restrict__ keep,
+                              int32_t *__restrict__ aid, int32_t *__restrict__ as_out, uint64_t *__restrict__ qh,
+                              uint64_t *__restrict__ qoff, uint32_t *__restrict__ qlen, uint32_t *__restrict__ decline) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N) return;
     keep[i] = 0;
@@ -97,22 +84,12 @@ __global__ void k_lin_records(const char *__restrict__ text, const uint64_t *__r
         atomicOr(decline, 1u << HGX_LIN_DECLINE_AS);
         return;
     }
-    int32_t id = -1;
-    for (uint32_t s = (uint32_t)lin_fnv(r, rn) & mask;; s = (s + 1) & mask) {
-        const int32_t c = slot[s];
-        if (c < 0) break;
-        const uint32_t b = poff[c], n = poff[c + 1] - b;
-        if (n == rn) {
-            uint32_t k = 0;
-            while (k < n && pool[b + k] == r[k]) ++k;
-            if (k == n) { id = c; break; }
-        }
-    }
+    const int32_t id = name_lookup(names, r, rn);
     if (id < 0) { atomicOr(decline, 1u << HGX_LIN_DECLINE_UNKNOWN_NAME); return; }
     keep[i] = 1;
     aid[i] = id;
     as_out[i] = (int32_t)asv;
-    qh[i] = lin_fnv(text + q0, qn);
+    qh[i] = fnv1a(text + q0, qn);
     qoff[i] = q0;
     qlen[i] = qn;
 }
@@ -193,7 +170,7 @@ __global__ void k_lin_bam_records(const char *__restrict__ raw, const uint64_t *
     keep[i] = 1;
     aid[i] = id;
     as_out[i] = (int32_t)asv;
-    qh[i] = lin_fnv(r + 32, l_rn - 1);
+    qh[i] = fnv1a(r + 32, l_rn - 1);
     qoff[i] = rs[i] + 32;
     qlen[i] = l_rn - 1;
 }
@@ -211,26 +188,6 @@ __global__ void k_lin_compact(const uint32_t *__restrict__ keep, const uint32_t 
     c_qh[j] = qh[i];
     c_qoff[j] = qoff[i];
     c_qlen[j] = qlen[i];
-}
-
-__global__ void k_lin_heads(const char *__restrict__ text, const uint64_t *__restrict__ qh, const uint64_t *__restrict__ qoff,
-                            const uint32_t *__restrict__ qlen, long M, uint32_t *__restrict__ head) {
-    const long j = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= M) return;
-    uint32_t h = 1;
-    if (j > 0 && qh[j] == qh[j - 1] && qlen[j] == qlen[j - 1]) {
-        const char *a = text + qoff[j], *b = text + qoff[j - 1];
-        uint32_t k = 0;
-        const uint32_t n = qlen[j];
-        while (k < n && a[k] == b[k]) ++k;
-        h = k == n ? 0u : 1u;
-    }
-    head[j] = h;
-}
-
-__global__ void k_lin_gstart(const uint32_t *__restrict__ head, const uint32_t *__restrict__ gid, long M, uint32_t *__restrict__ gstart) {
-    const long j = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < M && head[j]) gstart[gid[j]] = (uint32_t)j;
 }
 
 __global__ void k_lin_groups(const uint32_t *__restrict__ gstart, long G, const int32_t *__restrict__ aid, const int32_t *__restrict__ as_in,
@@ -265,7 +222,7 @@ __global__ void k_lin_groups(const uint32_t *__restrict__ gstart, long G, const 
     uint64_t h = 1469598103934665603ull ^ nd;
     for (uint32_t x = 0; x < nd; ++x) h = (h ^ (uint32_t)acc[s + x]) * 1099511628211ull;
     if (collide) h &= 7ull;                     // test switch linear_collide: every class on a handful of keys
-    if (h == LIN_EMPTY) h = 0;
+    if (h == HGX_EMPTY_KEY) h = 0;
     glen[g] = nd;
     ghash[g] = h;
     counted[g] = c ? 1u : 0u;
@@ -283,8 +240,8 @@ __global__ void k_lin_insert(const uint64_t *__restrict__ ghash, const uint32_t 
     if (g >= G || !counted[g]) return;
     const unsigned long long h = ghash[g];
     for (uint32_t s = (uint32_t)(h ^ (h >> 32)) & tmask;; s = (s + 1) & tmask) {
-        const unsigned long long prev = atomicCAS(&tkey[s], (unsigned long long)LIN_EMPTY, h);
-        if (prev == LIN_EMPTY || prev == h) {
+        const unsigned long long prev = atomicCAS(&tkey[s], (unsigned long long)HGX_EMPTY_KEY, h);
+        if (prev == HGX_EMPTY_KEY || prev == h) {
             atomicMin(&tfirst[s], (uint32_t)g);
             gslot[g] = s;
             return;
@@ -325,67 +282,26 @@ __global__ void k_lin_gather(const uint32_t *__restrict__ clen, const uint32_t *
     for (uint32_t x = 0; x < clen[c]; ++x) out[coff[c] + x] = acc[csrc[c] + x];
 }
 
-namespace {
-struct DevBufs {                         // the call's device arrays, from the library's pool (no hipMalloc per array)
-    std::vector<void *> ps;
-    ~DevBufs() { for (void *p : ps) hgx_pool_free(p); }
-    template <class T> int get(T *&p, size_t n) {
-        void *q = hgx_pool_alloc(std::max<size_t>(n, 1) * sizeof(T));
-        if (!q) {
-            hgx_set_error("linear route: device allocation of %zu bytes failed", n * sizeof(T));
-            return HGX_ENOMEM;
-        }
-        ps.push_back(q);
-        p = (T *)q;
-        return HGX_OK;
-    }
-};
-}  // namespace
-
-#define LCHK(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
-
 // the device copies of a locus' names, freed on the device that holds them
 static void lin_free_names(hgx_linear_locus &ll) {
-    if (ll.dev < 0) return;
-    int cur = 0;
-    const bool switched = hipGetDevice(&cur) == hipSuccess && cur != ll.dev && hipSetDevice(ll.dev) == hipSuccess;
-    for (void **p : {&ll.d_pool, &ll.d_off, &ll.d_slot, &ll.d_rank}) {
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-    }
-    if (switched) (void)hipSetDevice(cur);
-    ll.dev = -1;
+    free_on_device(ll.dev, {ll.d_names.pool, ll.d_names.off, ll.d_names.slot, ll.d_rank});
+    ll.d_names = hgx_name_view();
+    ll.d_rank = nullptr;
 }
 
 static int lin_upload_names(hgx_linear_locus &ll) {
     int dev = 0;
     HIPCHK(hipGetDevice(&dev));
-    if (ll.d_slot && ll.dev == dev) return HGX_OK;
+    if (ll.d_names.slot && ll.dev == dev) return HGX_OK;
     lin_free_names(ll);
-    const size_t A = ll.name.size();
-    uint32_t ns = 16;
-    while (ns < 2 * A + 16) ns <<= 1;
-    std::vector<int32_t> slot(ns, -1);
-    for (size_t a = 0; a < A; ++a) {
-        uint32_t s = (uint32_t)lin_fnv(ll.name[a].data(), ll.name[a].size()) & (ns - 1);
-        while (slot[s] >= 0) s = (s + 1) & (ns - 1);
-        slot[s] = (int32_t)a;
-    }
     ll.dev = dev;
-    bool ok = hipMalloc(&ll.d_pool, std::max<size_t>(ll.pool.size(), 1)) == hipSuccess &&
-              hipMalloc(&ll.d_off, ll.pool_off.size() * 4) == hipSuccess && hipMalloc(&ll.d_slot, (size_t)ns * 4) == hipSuccess &&
-              hipMalloc(&ll.d_rank, std::max<size_t>(A, 1) * 4) == hipSuccess;
-    ok = ok && (ll.pool.empty() || hipMemcpy(ll.d_pool, ll.pool.data(), ll.pool.size(), hipMemcpyHostToDevice) == hipSuccess) &&
-         hipMemcpy(ll.d_off, ll.pool_off.data(), ll.pool_off.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(ll.d_slot, slot.data(), (size_t)ns * 4, hipMemcpyHostToDevice) == hipSuccess &&
-         (!A || hipMemcpy(ll.d_rank, ll.rank.data(), A * 4, hipMemcpyHostToDevice) == hipSuccess);
+    const bool ok = name_table_upload(ll.d_names, ll.name) && upload_array(ll.d_rank, ll.rank.data(), ll.rank.size() * 4);
     if (!ok) {
         const hipError_t e = hipGetLastError();
         lin_free_names(ll);
         hgx_set_error("linear route: upload of the locus' names failed: %s", hipGetErrorString(e));
         return HGX_EHIP;
     }
-    ll.slot_mask = ns - 1;
     return HGX_OK;
 }
 
@@ -409,12 +325,8 @@ struct hgx_linear_input {
     std::vector<uint64_t> t_ls, t_le;
     ~hgx_linear_input() { release_dev(); }
     void release_dev() {
-        if (dev < 0) return;
-        int cur = 0;
-        const bool switched = hipGetDevice(&cur) == hipSuccess && cur != dev && hipSetDevice(dev) == hipSuccess;
-        for (void **p : {&d_raw, &d_ls, &d_le}) { if (*p) (void)hipFree(*p); *p = nullptr; }
-        if (switched) (void)hipSetDevice(cur);
-        dev = -1;
+        free_on_device(dev, {d_raw, d_ls, d_le});
+        d_raw = d_ls = d_le = nullptr;
     }
 };
 
@@ -456,7 +368,7 @@ static std::string lin_last_rname(const hgx_linear_input &in) {
 // the device route; *declined != 0: nothing in `out` is to be used, the host route takes the records
 static int lin_device(hgx_linear &out, hgx_linear_locus &ll, hgx_linear_input &in, const hgx_linear_opts &o, hipStream_t st, int *declined) {
     *declined = 0;
-    LCHK(lin_upload_names(ll));
+    RCHK(lin_upload_names(ll));
     const long N = (long)in.ls.size();
     const int A = (int)ll.name.size();
     const std::string gene = o.gene ? o.gene : "";
@@ -464,21 +376,21 @@ static int lin_device(hgx_linear &out, hgx_linear_locus &ll, hgx_linear_input &i
     out.count_id.clear(); out.count_val.clear();
     out.cls_off.assign(1, 0); out.cls_ids.clear(); out.cls_count.clear();      // no kept record: no class
     if (N == 0) return HGX_OK;
-    LCHK(lin_upload_input(in, st));
+    RCHK(lin_upload_input(in, st));
     int32_t last_trigger = hgx_linear_name_id(out, ll, lin_last_rname(in));
     if (last_trigger >= A) last_trigger = -1;              // a name outside the locus: counted on the host below
-    DevBufs m;
+    DevBufs m("linear route");
     char *d_gene;
     const char *d_text = (const char *)in.d_raw;
     uint64_t *d_qh, *d_qoff, *c_qh, *c_qoff, *d_ghash;
     uint32_t *d_keep, *d_pos, *d_qlen, *c_qlen, *d_dec, *d_tot;
     int32_t *d_aid, *d_as, *c_aid, *c_as;
     char *d_scan;
-    LCHK(m.get(d_gene, gene.size() + 1));
-    LCHK(m.get(d_keep, N)); LCHK(m.get(d_pos, N)); LCHK(m.get(d_aid, N)); LCHK(m.get(d_as, N));
-    LCHK(m.get(d_qh, N)); LCHK(m.get(d_qoff, N)); LCHK(m.get(d_qlen, N));
-    LCHK(m.get(d_dec, 1)); LCHK(m.get(d_tot, 4));
-    LCHK(m.get(d_scan, hgx_scan_u32_scratch_bytes(N)));     // one scan scratch for the four scans (each is <= N long)
+    RCHK(m.get(d_gene, gene.size() + 1));
+    RCHK(m.get(d_keep, N)); RCHK(m.get(d_pos, N)); RCHK(m.get(d_aid, N)); RCHK(m.get(d_as, N));
+    RCHK(m.get(d_qh, N)); RCHK(m.get(d_qoff, N)); RCHK(m.get(d_qlen, N));
+    RCHK(m.get(d_dec, 1)); RCHK(m.get(d_tot, 4));
+    RCHK(m.get(d_scan, hgx_scan_u32_scratch_bytes(N)));     // one scan scratch for the four scans (each is <= N long)
     if (!gene.empty()) HIPCHK(hipMemcpyAsync(d_gene, gene.data(), gene.size(), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(d_dec, 0, 4, st));
     if (in.binary) {
@@ -491,37 +403,32 @@ static int lin_device(hgx_linear &out, hgx_linear_locus &ll, hgx_linear_input &i
             else { auto it = ll.id.find(nm); tab[r] = it != ll.id.end() ? it->second : -2; }
         }
         int32_t *d_tab;
-        LCHK(m.get(d_tab, R + 1));
+        RCHK(m.get(d_tab, R + 1));
         HIPCHK(hipMemcpyAsync(d_tab, tab.data(), (R + 1) * 4, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_lin_bam_records, dim3(nblk(N, 256)), dim3(256), 0, st, d_text, (const uint64_t *)in.d_ls, (const uint64_t *)in.d_le,
                            N, d_tab, (int32_t)R, d_keep, d_aid, d_as, d_qh, d_qoff, d_qlen, d_dec);
     } else {
         hipLaunchKernelGGL(k_lin_records, dim3(nblk(N, 256)), dim3(256), 0, st, d_text, (const uint64_t *)in.d_ls, (const uint64_t *)in.d_le,
-                           N, d_gene, (int)gene.size(), (const char *)ll.d_pool, (const uint32_t *)ll.d_off, (const int32_t *)ll.d_slot,
-                           ll.slot_mask, d_keep, d_aid, d_as, d_qh, d_qoff, d_qlen, d_dec);
+                           N, d_gene, (int)gene.size(), ll.d_names, d_keep, d_aid, d_as, d_qh, d_qoff, d_qlen, d_dec);
     }
     HIPCHK(hipGetLastError());
-    LCHK(hgx_scan_u32_dev(d_keep, d_pos, N, d_scan, d_tot, st));
+    RCHK(hgx_scan_u32_dev(d_keep, d_pos, N, d_scan, d_tot, st));
     uint32_t h_dec = 0, M = 0;
     HIPCHK(hipMemcpyAsync(&h_dec, d_dec, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(&M, d_tot, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    if (h_dec) {
-        for (int b = 1; b < 8; ++b)
-            if (h_dec & (1u << b)) { *declined = b; break; }
-        return HGX_OK;
-    }
+    if (h_dec) { *declined = first_decline(h_dec); return HGX_OK; }
     out.n_kept = M;
     if (M == 0) return HGX_OK;
-    LCHK(m.get(c_aid, M)); LCHK(m.get(c_as, M)); LCHK(m.get(c_qh, M)); LCHK(m.get(c_qoff, M)); LCHK(m.get(c_qlen, M));
+    RCHK(m.get(c_aid, M)); RCHK(m.get(c_as, M)); RCHK(m.get(c_qh, M)); RCHK(m.get(c_qoff, M)); RCHK(m.get(c_qlen, M));
     hipLaunchKernelGGL(k_lin_compact, dim3(nblk(N, 256)), dim3(256), 0, st, d_keep, d_pos, N, d_aid, d_as, d_qh, d_qoff, d_qlen,
                        c_aid, c_as, c_qh, c_qoff, c_qlen);
     HIPCHK(hipGetLastError());
     // group heads and extents (the N-sized scratch is reused: keep -> head, pos -> gid)
     uint32_t *d_head = d_keep, *d_gid = d_pos;
-    hipLaunchKernelGGL(k_lin_heads, dim3(nblk(M, 256)), dim3(256), 0, st, d_text, c_qh, c_qoff, c_qlen, (long)M, d_head);
+    hipLaunchKernelGGL(k_rec_heads<uint64_t>, dim3(nblk(M, 256)), dim3(256), 0, st, d_text, c_qh, c_qoff, c_qlen, (long)M, d_head);
     HIPCHK(hipGetLastError());
-    LCHK(hgx_scan_u32_dev(d_head, d_gid, M, d_scan, d_tot + 1, st));
+    RCHK(hgx_scan_u32_dev(d_head, d_gid, M, d_scan, d_tot + 1, st));
     uint32_t G = 0;
     HIPCHK(hipMemcpyAsync(&G, d_tot + 1, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -531,10 +438,10 @@ static int lin_device(hgx_linear &out, hgx_linear_locus &ll, hgx_linear_input &i
     unsigned long long *d_cnt, *d_tkey;
     uint32_t ts = 16;
     while (ts < 2 * G + 16) ts <<= 1;
-    LCHK(m.get(d_gstart, (size_t)G + 1)); LCHK(m.get(d_acc, M)); LCHK(m.get(d_glen, G)); LCHK(m.get(d_ghash, G));
-    LCHK(m.get(d_counted, G)); LCHK(m.get(d_cnt, A)); LCHK(m.get(d_firstg, A)); LCHK(m.get(d_gslot, G));
-    LCHK(m.get(d_first, G)); LCHK(m.get(d_cid, G)); LCHK(m.get(d_tkey, ts)); LCHK(m.get(d_tfirst, ts));
-    hipLaunchKernelGGL(k_lin_gstart, dim3(nblk(M, 256)), dim3(256), 0, st, d_head, d_gid, (long)M, d_gstart);
+    RCHK(m.get(d_gstart, (size_t)G + 1)); RCHK(m.get(d_acc, M)); RCHK(m.get(d_glen, G)); RCHK(m.get(d_ghash, G));
+    RCHK(m.get(d_counted, G)); RCHK(m.get(d_cnt, A)); RCHK(m.get(d_firstg, A)); RCHK(m.get(d_gslot, G));
+    RCHK(m.get(d_first, G)); RCHK(m.get(d_cid, G)); RCHK(m.get(d_tkey, ts)); RCHK(m.get(d_tfirst, ts));
+    hipLaunchKernelGGL(k_rec_gstart, dim3(nblk(M, 256)), dim3(256), 0, st, d_head, d_gid, (long)M, d_gstart);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(d_gstart + G, &M, 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(d_cnt, 0, (size_t)std::max(A, 1) * 8, st));
@@ -542,7 +449,7 @@ static int lin_device(hgx_linear &out, hgx_linear_locus &ll, hgx_linear_input &i
     HIPCHK(hipMemsetAsync(d_tkey, 0xFF, (size_t)ts * 8, st));
     HIPCHK(hipMemsetAsync(d_tfirst, 0xFF, (size_t)ts * 4, st));
     const int collide = hgx_test_switch("linear_collide") != nullptr;
-    hipLaunchKernelGGL(k_lin_groups, dim3(nblk(G, 256)), dim3(256), 0, st, d_gstart, (long)G, c_aid, c_as, (const int32_t *)ll.d_rank,
+    hipLaunchKernelGGL(k_lin_groups, dim3(nblk(G, 256)), dim3(256), 0, st, d_gstart, (long)G, c_aid, c_as, ll.d_rank,
                        (int)o.aligner, last_trigger, collide, d_acc, d_glen, d_ghash, d_counted, d_cnt, d_firstg);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(k_lin_insert, dim3(nblk(G, 256)), dim3(256), 0, st, d_ghash, d_counted, (long)G, d_tkey, d_tfirst, ts - 1, d_gslot);
@@ -550,7 +457,7 @@ static int lin_device(hgx_linear &out, hgx_linear_locus &ll, hgx_linear_input &i
     hipLaunchKernelGGL(k_lin_verify, dim3(nblk(G, 256)), dim3(256), 0, st, d_gstart, d_acc, d_glen, d_counted, d_gslot, d_tfirst,
                        (long)G, d_first, d_dec);
     HIPCHK(hipGetLastError());
-    LCHK(hgx_scan_u32_dev(d_first, d_cid, G, d_scan, d_tot + 2, st));
+    RCHK(hgx_scan_u32_dev(d_first, d_cid, G, d_scan, d_tot + 2, st));
     uint32_t C = 0;
     HIPCHK(hipMemcpyAsync(&h_dec, d_dec, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(&C, d_tot + 2, 4, hipMemcpyDeviceToHost, st));
@@ -561,19 +468,19 @@ static int lin_device(hgx_linear &out, hgx_linear_locus &ll, hgx_linear_input &i
     }
     unsigned long long *d_ccount;
     uint32_t *d_clen, *d_csrc, *d_coff;
-    LCHK(m.get(d_ccount, C)); LCHK(m.get(d_clen, C)); LCHK(m.get(d_csrc, C)); LCHK(m.get(d_coff, C));
+    RCHK(m.get(d_ccount, C)); RCHK(m.get(d_clen, C)); RCHK(m.get(d_csrc, C)); RCHK(m.get(d_coff, C));
     HIPCHK(hipMemsetAsync(d_ccount, 0, (size_t)std::max<uint32_t>(C, 1) * 8, st));
     hipLaunchKernelGGL(k_lin_class, dim3(nblk(G, 256)), dim3(256), 0, st, d_counted, d_first, d_gslot, d_tfirst, d_cid, d_glen, d_gstart,
                        (long)G, d_ccount, d_clen, d_csrc);
     HIPCHK(hipGetLastError());
     uint32_t n_ids = 0;
     if (C) {
-        LCHK(hgx_scan_u32_dev(d_clen, d_coff, C, d_scan, d_tot + 3, st));
+        RCHK(hgx_scan_u32_dev(d_clen, d_coff, C, d_scan, d_tot + 3, st));
         HIPCHK(hipMemcpyAsync(&n_ids, d_tot + 3, 4, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
     }
     int32_t *d_ids;
-    LCHK(m.get(d_ids, n_ids));
+    RCHK(m.get(d_ids, n_ids));
     if (C) {
         hipLaunchKernelGGL(k_lin_gather, dim3(nblk(C, 256)), dim3(256), 0, st, d_clen, d_csrc, d_coff, (long)C, d_acc, d_ids);
         HIPCHK(hipGetLastError());
@@ -614,18 +521,8 @@ static int lin_device(hgx_linear &out, hgx_linear_locus &ll, hgx_linear_input &i
 static int lin_host_text(hgx_linear_input &in, const char *&base, const uint64_t *&ls, const uint64_t *&le, size_t &n) {
     if (!in.binary) { base = in.base; ls = in.ls.data(); le = in.le.data(); n = in.ls.size(); return HGX_OK; }
     if (!in.host_text) {
-        hgx_align_lines t;
-        t.file_order = true;
-        LCHK(hgx_read_alignment_lines(in.path.c_str(), in.has_regions ? in.regions.c_str() : nullptr, 0, t));
-        size_t tot = 0;
-        for (size_t i = 0; i < t.lines.size(); ++i) tot += t.lines[i].len + 1;
-        in.text.reserve(tot);
-        for (size_t i = 0; i < t.lines.size(); ++i) {
-            in.t_ls.push_back(in.text.size());
-            in.text.insert(in.text.end(), t.lines[i].p, t.lines[i].p + t.lines[i].len);
-            in.t_le.push_back(in.text.size());
-            in.text.push_back('\n');
-        }
+        size_t tot;
+        RCHK(bam_as_sam_text(in.path.c_str(), in.has_regions ? in.regions.c_str() : nullptr, SIZE_MAX, in.text, tot, &in.t_ls, &in.t_le));
         in.host_text = true;
     }
     base = in.text.data(); ls = in.t_ls.data(); le = in.t_le.data(); n = in.t_ls.size();
@@ -663,15 +560,12 @@ extern "C" int hgx_linear_locus_create(hgx_linear_locus **out, const char *name_
     ARGCHK(out && (name_pool || n_bytes == 0) && n_names >= 0);
     auto *ll = new hgx_linear_locus();
     size_t p = 0;
-    ll->pool_off.push_back(0);
     for (int32_t a = 0; a < n_names; ++a) {
         const char *z = (const char *)memchr(name_pool + p, 0, n_bytes - p);
         if (!z) { delete ll; hgx_set_error("invalid argument: name pool holds fewer than %d names", n_names); return HGX_EINVAL; }
         const size_t len = (size_t)(z - (name_pool + p));
         ll->name.emplace_back(name_pool + p, len);
         ll->id.emplace(ll->name.back(), a);            // a repeated name keeps its first index, as a dict lookup would
-        ll->pool.insert(ll->pool.end(), name_pool + p, z);
-        ll->pool_off.push_back((uint32_t)ll->pool.size());
         p += len + 1;
     }
     std::vector<int32_t> idx(n_names);
@@ -708,7 +602,7 @@ extern "C" int hgx_linear_input_open(hgx_linear_input **out, const char *path, c
     in->has_regions = regions_or_null != nullptr;
     if (regions_or_null) in->regions = regions_or_null;
     in->al.file_order = true;
-    LCHK(hgx_read_alignment_lines(path, regions_or_null, 0, in->al, /*keep_binary=*/true));
+    RCHK(hgx_read_alignment_lines(path, regions_or_null, 0, in->al, /*keep_binary=*/true));
     in->base = in->al.raw;
     in->n_bytes = in->al.raw_bytes;
     in->binary = in->al.binary;
@@ -751,7 +645,7 @@ extern "C" int hgx_linear_type_file(hgx_linear **out, hgx_linear_locus *ll, cons
                                     const hgx_linear_opts *opts, void *stream) {
     ARGCHK(out && ll && path && opts);
     hgx_linear_input *in = nullptr;
-    LCHK(hgx_linear_input_open(&in, path, regions_or_null));
+    RCHK(hgx_linear_input_open(&in, path, regions_or_null));
     const int rc = lin_type(out, ll, *in, opts, stream);
     hgx_linear_input_close(in);
     return rc;

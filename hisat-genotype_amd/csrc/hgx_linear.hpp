@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "hgx.h"
+#include "hgx_records.hpp"
 
 // The names of a locus' alleles as the linear branch meets them in RNAME (ids = allele indices), their name order, and the device
 // hash of them (made on the first device-route call, freed with the handle).
@@ -14,11 +15,9 @@ struct hgx_linear_locus {
     std::vector<std::string> name;
     std::unordered_map<std::string, int32_t> id;
     std::vector<int32_t> rank;                   // position of name[a] among the sorted names (Python str order = byte order)
-    std::vector<char> pool;                      // names back to back
-    std::vector<uint32_t> pool_off;              // [n + 1]
     // device copies (hgx_linear.hip)
-    void *d_pool = nullptr, *d_off = nullptr, *d_slot = nullptr, *d_rank = nullptr;
-    uint32_t slot_mask = 0;
+    hgx_name_view d_names;
+    int32_t *d_rank = nullptr;
     int dev = -1;
 };
 
