@@ -168,7 +168,9 @@ int hgx_score_pairs(const hgx_index *ix,
  * dropped) are grouped by content; groups come out in FIRST-SEEN order (Python dict order)
  * with the summed weight.  Exact: every row is compared with its group's first row; rows that share a
  * 64-bit key with a different row are re-keyed and re-checked (HGX_ECOLLISION only if that fails 8 times,
- * or from the radix-sort form).  On any failure the constructors below hand out nothing: *out = NULL. */
+ * or from the radix-sort form).  On any failure the constructors below hand out nothing: *out = NULL.
+ * Caller's contract for row_hash_dev_or_null: equal masked rows carry equal keys, an all-zero row carries
+ * 0xFFFFFFFFFFFFFFFF and no other row does; the keys are ignored (recomputed from the masked rows) when and_mask is given. */
 typedef struct hgx_classes hgx_classes;   /* device-resident [n_classes][a_pad/64] + counts */
 
 int hgx_dedup_classes(hgx_classes **out,

@@ -283,6 +283,7 @@ def test_forged_hash_collision_is_detected(orc, n_rows):
     reports HGX_ECOLLISION; honest keys pass."""
     import os
     from hisatgenotype_amd import capi
+    from dedup_ref import dedup_ref
     a_pad = 1024
     w64 = a_pad // 64
     rng = np.random.RandomState(11)
@@ -305,6 +306,8 @@ def test_forged_hash_collision_is_detected(orc, n_rows):
             assert got.n_classes == want.n_classes == len(set(pick.tolist())) + 1
             for x, y in zip(got.to_host(), want.to_host()):
                 assert np.array_equal(x, y)
+            for x, y, z in zip(got.to_host(), want.to_host(), dedup_ref(forged)):       # ... and both what a Python dict gives
+                assert np.array_equal(x, z) and np.array_equal(y, z)
             # many collisions at once, weighted: every third row flips a bit of its own and keeps its (now shared) key
             many = rows.copy()
             flip = np.arange(0, n_rows, 3)
@@ -316,6 +319,10 @@ def test_forged_hash_collision_is_detected(orc, n_rows):
             assert got.n_classes == want.n_classes
             for x, y in zip(got.to_host(), want.to_host()):
                 assert np.array_equal(x, y)
+            ref = dedup_ref(many, wts.to_host())
+            assert got.n_classes == len(ref[1])
+            for x, y, z in zip(got.to_host(), want.to_host(), ref):
+                assert np.array_equal(x, z) and np.array_equal(y, z)
         finally:
             pass
 
