@@ -79,7 +79,7 @@ SYMBOLS = [
     "hgx_linear_locus_create", "hgx_linear_locus_destroy", "hgx_linear_type_sam", "hgx_linear_type_file", "hgx_linear_dims",
     "hgx_linear_counts", "hgx_linear_classes", "hgx_linear_extra_names", "hgx_linear_destroy",
     "hgx_linear_input_open", "hgx_linear_input_dims", "hgx_linear_type_input", "hgx_linear_input_close",
-    "hgx_extract_open", "hgx_extract_feed", "hgx_extract_file", "hgx_extract_take", "hgx_extract_stats", "hgx_extract_close",
+    "hgx_extract_open", "hgx_extract_feed", "hgx_extract_feed_bam", "hgx_extract_file", "hgx_extract_take", "hgx_extract_stats", "hgx_extract_close",
 ]
 
 _lib = None

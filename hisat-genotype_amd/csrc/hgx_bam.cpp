@@ -541,6 +541,20 @@ bool peek_is_bam(const unsigned char *data, const std::vector<hgx_bgzf_block> &b
 
 }   // namespace
 
+// The reader's pieces a BAM STREAM needs one at a time (read extraction, hgx_extract.hip: the file arrives in chunks): the header
+// parser (1 = complete, 0 = more bytes needed, -1 = no BAM), one BGZF block through zlib, and one record as the line `samtools view`
+// prints, appended to `line`.
+int hgx_bam_parse_header(const unsigned char *raw, size_t n, std::vector<std::string> &refs, size_t *body0) {
+    return parse_bam_header(raw, n, refs, body0);
+}
+bool hgx_bam_inflate_block(const unsigned char *data, const hgx_bgzf_block &b, unsigned char *dst) { return inflate_one(data, b, dst); }
+bool hgx_bam_record_line(const unsigned char *rec, size_t len, const std::vector<std::string> &refs, std::string &line) {
+    PString s;
+    if (!bam_record_text(rec, len, refs, s)) return false;
+    line.append(s.data(), s.size());
+    return true;
+}
+
 // What a deferred stream's owner needs to pull ONE region list out of it (hgx_alignment_parse_dev: a file opened once, a locus at a
 // time): the descriptor hgx_read_alignment_lines would have made had it been given these regions.  1 = not expressible (more than
 // one region): the caller reads the file the ordinary way for this locus.

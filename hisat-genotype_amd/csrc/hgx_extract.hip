@@ -20,6 +20,7 @@
 // its text twice (LDS in between).
 #include <algorithm>
 #include <cstdio>
+#include <functional>
 #include <memory>
 #include <vector>
 
@@ -27,6 +28,7 @@
 #include "hgx_internal.hpp"
 #include "hgx_extract.hpp"
 #include "hgx_records.hpp"
+#include "hgx_bam_walk.hpp"
 
 __device__ static inline bool ext_sp(char c) { return c == ' ' || (c >= '\t' && c <= '\r') || (c >= 0x1c && c <= 0x1f); }
 
@@ -128,6 +130,120 @@ __global__ void k_ext_records(const char *__restrict__ text, const uint32_t *__r
     R.loff[i] = l0; R.llen[i] = ln;
 }
 
+// BAM: one lane per record of the inflated stream (rec_off: behind its block_size word, rec_len: block_size).  It fills the arrays
+// k_ext_records fills, so everything behind it runs unchanged, and it declines whatever would make the line `samtools view`
+// prints for the record (hgx_bam.cpp: bam_record_text, the contract) split otherwise than the BAM fields lie: a blank, a control
+// blank or a byte >= 0x80 in QNAME, in a tag or in an A / Z / H value, a reference name of that kind (reftab -2), a quality whose
+// + 33 leaves ASCII, a QNAME that starts a header line, damaged aux data.  reftab: per refID the chromosome's index in the region
+// table or -1.  AS / XS / NH: every tag is walked by its type, the last occurrence wins, the integer types count.
+__global__ void k_ext_bam_records(const unsigned char *__restrict__ text, const uint32_t *__restrict__ rec_off, const uint32_t *__restrict__ rec_len,
+                                  long N, const int32_t *__restrict__ reftab, int n_ref, const uint32_t *__restrict__ creg,
+                                  const int32_t *__restrict__ rfam, const long long *__restrict__ rl, const long long *__restrict__ rr, int simulation,
+                                  ExtRec R, uint32_t *__restrict__ decline) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    const uint32_t o = rec_off[i], bs = rec_len[i];
+    const unsigned char *r = text + o;
+    // (the group kernel reads every record of a group: a declined record still gets defined fields)
+    R.flag[i] = 0x4; R.tags[i] = 0; R.fam[i] = -1; R.kh[i] = 0; R.qoff[i] = o + 32; R.qlen[i] = 0; R.klen[i] = 0;
+    R.soff[i] = R.loff[i] = o + 32; R.slen[i] = R.llen[i] = 0; R.as[i] = R.xs[i] = R.nh[i] = 0;
+    const int32_t rid = bam_i32(r), pos = bam_i32(r + 4), l_seq = bam_i32(r + 16), nrid = bam_i32(r + 20);
+    const uint32_t l_rn = r[8], n_cig = bam_u16(r + 12), flag = bam_u16(r + 14);
+    const size_t fixed = 32 + (size_t)l_rn + 4 * (size_t)n_cig + (l_seq > 0 ? (size_t)(l_seq + 1) / 2 + (size_t)l_seq : 0);
+    if (l_rn == 0 || l_seq < 0 || fixed > bs) { atomicOr(decline, 1u << HGX_EXT_DECLINE_RECORD); return; }
+    auto bad_text = [](uint32_t c) { return c >= 0x80u || ext_sp((char)c); };
+    uint32_t dec = 0;
+    const unsigned char *q = r + 32;
+    const uint32_t qn = l_rn - 1;
+    uint32_t kn = qn;
+    for (uint32_t k = 0; k < qn; ++k) {
+        const uint32_t c = q[k];
+        if (bad_text(c) || c == 0) dec |= 1u << HGX_EXT_DECLINE_RECORD;
+        if (simulation && c == '|' && kn == qn) kn = k;
+    }
+    if (qn && q[0] == '@') dec |= 1u << HGX_EXT_DECLINE_RECORD;
+    if (kn == 0) dec |= 1u << HGX_EXT_DECLINE_NAMES;
+    if (rid >= n_ref || (rid >= 0 && reftab[rid] == -2)) dec |= 1u << HGX_EXT_DECLINE_RECORD;
+    if (nrid >= 0 && nrid < n_ref && nrid != rid && reftab[nrid] == -2) dec |= 1u << HGX_EXT_DECLINE_RECORD;
+    const uint32_t so = 32 + l_rn + 4 * n_cig, lo = so + (uint32_t)(l_seq + 1) / 2;          // (within the record)
+    const bool no_qual = l_seq == 0 || r[lo] == 0xff;
+    if (!no_qual) {
+        uint32_t top = 0;
+        for (int32_t k = 0; k < l_seq; ++k) top = max(top, (uint32_t)r[lo + k]);
+        if (top + 33 >= 0x80u) dec |= 1u << HGX_EXT_DECLINE_RECORD;
+    }
+    uint32_t tags = 0;
+    int32_t v_as = 0, v_xs = 0, v_nh = 0;
+    size_t a = fixed;
+    while (a + 3 <= bs) {
+        const uint32_t t0 = r[a], t1 = r[a + 1], ty = r[a + 2];
+        a += 3;
+        if (bad_text(t0) || bad_text(t1)) dec |= 1u << HGX_EXT_DECLINE_RECORD;
+        const int which = (t0 == 'A' && t1 == 'S') ? 0 : (t0 == 'X' && t1 == 'S') ? 1 : (t0 == 'N' && t1 == 'H') ? 2 : -1;
+        size_t sz = 0;
+        bool broken = false, is_int = false;
+        switch (ty) {
+            case 'A': case 'c': case 'C': sz = 1; break;
+            case 's': case 'S': sz = 2; break;
+            case 'i': case 'I': case 'f': sz = 4; break;
+            case 'Z': case 'H': {
+                size_t e = a;
+                while (e < bs && r[e] != 0) { if (bad_text(r[e])) dec |= 1u << HGX_EXT_DECLINE_RECORD; ++e; }
+                broken = e >= bs;
+                sz = e - a + 1;
+            } break;
+            case 'B': {
+                if (a + 5 > bs) { broken = true; break; }
+                const uint32_t st = r[a];
+                const size_t w = (st == 'c' || st == 'C') ? 1 : (st == 's' || st == 'S') ? 2 : (st == 'i' || st == 'I' || st == 'f') ? 4 : 0;
+                broken = w == 0;
+                sz = 5 + w * (size_t)bam_u32(r + a + 1);
+            } break;
+            default: broken = true;
+        }
+        if (broken || a + sz > bs) { dec |= 1u << HGX_EXT_DECLINE_RECORD; a = bs; break; }
+        long long v = 0;
+        switch (ty) {
+            case 'A': if (bad_text(r[a])) dec |= 1u << HGX_EXT_DECLINE_RECORD; break;
+            case 'c': v = (int8_t)r[a]; is_int = true; break;
+            case 'C': v = r[a]; is_int = true; break;
+            case 's': v = (int16_t)bam_u16(r + a); is_int = true; break;
+            case 'S': v = bam_u16(r + a); is_int = true; break;
+            case 'i': v = bam_i32(r + a); is_int = true; break;
+            case 'I': v = bam_u32(r + a); is_int = true; break;
+            default: break;
+        }
+        if (which >= 0) {
+            // (the text kernel takes a sign and up to 2^31 - 1: the same range here, so that both decline the same streams)
+            if (!is_int || v > 0x7fffffffll || v < -0x7fffffffll) dec |= 1u << HGX_EXT_DECLINE_VALUE;
+            else if (which == 0) v_as = (int32_t)v;
+            else if (which == 1) v_xs = (int32_t)v;
+            else v_nh = (int32_t)v;
+            tags |= 1u << which;
+        }
+        a += sz;
+    }
+    if (a != bs) dec |= 1u << HGX_EXT_DECLINE_RECORD;
+    if (dec) { atomicOr(decline, dec); return; }
+    int32_t fam = -1;
+    if (!(flag & 0x4) && rid >= 0) {
+        const int32_t c = reftab[rid];
+        if (c >= 0) {
+            const long long p0 = pos;
+            for (uint32_t x = creg[c]; x < creg[c + 1]; ++x)
+                if (p0 >= rl[x] && p0 < rr[x]) { fam = rfam[x]; break; }
+        }
+    }
+    R.flag[i] = flag;
+    R.tags[i] = tags;
+    R.fam[i] = fam;
+    R.as[i] = v_as; R.xs[i] = v_xs; R.nh[i] = v_nh;
+    R.kh[i] = fnv1a((const char *)q, kn);
+    R.qoff[i] = o + 32; R.qlen[i] = qn; R.klen[i] = kn;
+    R.soff[i] = o + so; R.slen[i] = l_seq ? (uint32_t)l_seq : 1u;
+    R.loff[i] = o + lo; R.llen[i] = no_qual ? 1u : (uint32_t)l_seq;
+}
+
 // The loop body of process:1678-1713 for one group, in record order.
 __global__ void k_ext_groups(const uint32_t *__restrict__ gstart, long G, ExtRec R, int aligner, int paired,
                              unsigned long long *__restrict__ gbits, uint32_t *__restrict__ r1, uint32_t *__restrict__ r2,
@@ -211,6 +327,15 @@ __device__ static inline char ext_comp(char c) { return c == 'A' ? 'T' : c == 'C
 // span is read with 16-byte loads from its 16-byte-aligned start into LDS, the text is formed byte by byte in LDS, shifted by the
 // destination's offset within its dword, and leaves as whole dwords (the partial first and last dword as bytes: the neighbour
 // read's text shares them).  A read whose span or text does not fit in LDS is copied byte by byte.
+// BAM = true: `text` is the inflated stream; soff / loff are where the record's 4-bit bases and its binary qualities lie, slen /
+// llen the lengths of the text `samtools view` prints for them (1 for the '*' of an empty SEQ, or of qualities that start with 0xff);
+// l_seq is read from the record (qoff is its read_name: 32 bytes behind the record's start).  The staged span holds the packed
+// bases and the qualities; a base comes through the 16-entry table, high nibble first.
+__device__ static inline char ext_base(uint32_t code) {                 // "=ACMGRSVTWYHKDBN"[code], the table in two registers
+    const unsigned long long w = code < 8 ? 0x565352474d43413dull : 0x4e42444b48595754ull;
+    return (char)(w >> (8 * (code & 7)));
+}
+template <bool BAM>
 __global__ void __launch_bounds__(64) k_ext_emit(const char *__restrict__ text, const uint32_t *__restrict__ hg, long H,
                                                  const unsigned long long *__restrict__ gbits, int fam,
                                                  const uint32_t *__restrict__ gstart, const uint32_t *__restrict__ r1,
@@ -229,11 +354,14 @@ __global__ void __launch_bounds__(64) k_ext_emit(const char *__restrict__ text, 
     const char *name = text + R.qoff[first];
     const uint32_t nn = R.qlen[first], sn = R.slen[rec], ln = R.llen[rec];
     const uint32_t so = R.soff[rec], lo = R.loff[rec];
+    uint32_t l_seq = 0;                                                 // BAM: bases in the record (0: SEQ prints '*')
+    if (BAM) __builtin_memcpy(&l_seq, text + R.qoff[rec] - 16, 4);
+    const bool seq_star = BAM && l_seq == 0, qual_star = BAM && (l_seq == 0 || (uint8_t)text[lo] == 0xff);
     const bool rev = (R.flag[rec] & 0x10) != 0;
     char *dst = (mate ? out2 : out1) + (mate ? off2[h] : off1[h]);
     const uint32_t total = ext_read_bytes(nn, sn, ln, fastq);
     const uint32_t a0 = so & ~15u;
-    const uint32_t span = (fastq ? lo + ln : so + sn) - a0;
+    const uint32_t span = (BAM ? (fastq ? lo + l_seq : lo) : (fastq ? lo + ln : so + sn)) - a0;
     const uint32_t pad = (uint32_t)((uintptr_t)dst & 3u);
     const bool staged = span <= (uint32_t)EXT_SRC_MAX && pad + total <= (uint32_t)EXT_IMG_MAX && (!fastq || lo >= so);
     // where the pieces start in the text
@@ -250,11 +378,20 @@ __global__ void __launch_bounds__(64) k_ext_emit(const char *__restrict__ text, 
         if (k == 0) c = fastq ? '@' : '>';
         else if (k <= nn) c = name[k - 1];
         else if (k < p_seq) c = '\n';
-        else if (k < p_seq + sn) { const uint32_t x = k - p_seq; c = rev ? ext_comp(seq[sn - 1 - x]) : seq[x]; }
+        else if (k < p_seq + sn) {
+            const uint32_t x = k - p_seq, y = rev ? sn - 1 - x : x;
+            if (!BAM) c = seq[y];
+            else if (seq_star) c = '*';
+            else { const uint32_t b = (uint8_t)seq[y >> 1]; c = ext_base((y & 1) ? (b & 15u) : (b >> 4)); }
+            if (rev) c = ext_comp(c);
+        }
         else if (k < p_plus) c = '\n';
         else if (k == p_plus) c = '+';
         else if (k < p_qual) c = '\n';
-        else if (k < p_qual + ln) { const uint32_t x = k - p_qual; c = rev ? qual[ln - 1 - x] : qual[x]; }
+        else if (k < p_qual + ln) {
+            const uint32_t x = k - p_qual, y = rev ? ln - 1 - x : x;
+            c = !BAM ? qual[y] : qual_star ? '*' : (char)(qual[y] + 33);
+        }
         else c = '\n';
         if (staged) s_img[pad + k] = c; else dst[k] = c;
     }
@@ -271,7 +408,8 @@ __global__ void __launch_bounds__(64) k_ext_emit(const char *__restrict__ text, 
 }
 
 static void ext_free_table(hgx_extract &h) {
-    free_on_device(h.dev, {h.d_chrom.pool, h.d_chrom.off, h.d_chrom.slot, h.d_creg, h.d_rfam, h.d_rl, h.d_rr});
+    free_on_device(h.dev, {h.d_chrom.pool, h.d_chrom.off, h.d_chrom.slot, h.d_creg, h.d_rfam, h.d_rl, h.d_rr, h.d_reftab});
+    h.d_reftab = nullptr;
     h.d_chrom = hgx_name_view();
     h.d_creg = nullptr; h.d_rfam = nullptr; h.d_rl = h.d_rr = nullptr;
 }
@@ -295,34 +433,37 @@ static int ext_upload_table(hgx_extract &h) {
     return HGX_OK;
 }
 
-// the device route for one chunk; *declined != 0: nothing was appended, the host route takes the chunk
-static int ext_device(hgx_extract &h, const char *base, size_t n_bytes, const std::vector<uint32_t> &ls, const std::vector<uint32_t> &le,
-                      hipStream_t st, int *declined) {
-    *declined = 0;
-    const long N = (long)ls.size();
-    if (h.n_fam > 64) { *declined = HGX_EXT_DECLINE_FAMILIES; return HGX_OK; }
-    RCHK(ext_upload_table(h));
-    DevBufs m("extract route");
-    char *d_text, *d_scan;
-    uint32_t *d_ls, *d_le, *d_head, *d_gid, *d_dec, *d_tot;
+// the per-record and per-chunk arrays both record kernels fill and the group kernels read
+struct ExtWork {
+    char *d_scan;
+    uint32_t *d_head, *d_gid, *d_dec, *d_tot;
     unsigned long long *d_or;
     ExtRec R;
-    RCHK(m.get(d_text, n_bytes + 64));
-    RCHK(m.get(d_ls, N)); RCHK(m.get(d_le, N)); RCHK(m.get(d_head, N)); RCHK(m.get(d_gid, N));
+};
+static int ext_work_alloc(DevBufs &m, ExtWork &w, long N, hipStream_t st) {
+    ExtRec &R = w.R;
+    RCHK(m.get(w.d_head, N + 4)); RCHK(m.get(w.d_gid, N + 4));
     RCHK(m.get(R.flag, N)); RCHK(m.get(R.tags, N)); RCHK(m.get(R.qoff, N)); RCHK(m.get(R.qlen, N)); RCHK(m.get(R.klen, N));
     RCHK(m.get(R.soff, N)); RCHK(m.get(R.slen, N)); RCHK(m.get(R.loff, N)); RCHK(m.get(R.llen, N));
     RCHK(m.get(R.fam, N)); RCHK(m.get(R.as, N)); RCHK(m.get(R.xs, N)); RCHK(m.get(R.nh, N)); RCHK(m.get(R.kh, N));
-    RCHK(m.get(d_dec, 4)); RCHK(m.get(d_tot, 4 + 2 * 64)); RCHK(m.get(d_or, 2 + 64));
-    RCHK(m.get(d_scan, hgx_scan_u32_scratch_bytes(N)));
-    HIPCHK(hipMemcpyAsync(d_text, base, n_bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(d_text + n_bytes, 0, 64, st));
-    HIPCHK(hipMemcpyAsync(d_ls, ls.data(), (size_t)N * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_le, le.data(), (size_t)N * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(d_dec, 0, 16, st));
-    HIPCHK(hipMemsetAsync(d_or, 0, (2 + 64) * 8, st));
-    hipLaunchKernelGGL(k_ext_records, dim3(nblk(N, 256)), dim3(256), 0, st, d_text, d_ls, d_le, N, h.d_chrom, h.d_creg,
-                       h.d_rfam, h.d_rl, h.d_rr, h.simulation, R, d_dec);
-    HIPCHK(hipGetLastError());
+    RCHK(m.get(w.d_dec, 4)); RCHK(m.get(w.d_tot, 4 + 2 * 64)); RCHK(m.get(w.d_or, 2 + 64));
+    RCHK(m.get(w.d_scan, hgx_scan_u32_scratch_bytes(N)));
+    HIPCHK(hipMemsetAsync(w.d_dec, 0, 16, st));
+    HIPCHK(hipMemsetAsync(w.d_or, 0, (2 + 64) * 8, st));
+    return HGX_OK;
+}
+
+// Behind either record kernel: groups, hits, sizes and the text of the chunk's N records (d_text: the SAM text, or, BAM, the
+// inflated stream).  *declined != 0: nothing was appended.  keep_last (a BAM chunk that is not the stream's last): the last
+// group may go on in the next chunk and stays out -- *n_proc = its first record = the records this call took, *g_first = the
+// first record of the last group taken.  before_emit(n_proc, &code), if given, may still decline before anything is written.
+template <bool BAM>
+static int ext_groups_emit(hgx_extract &h, DevBufs &m, const char *d_text, ExtWork &w, long N, hipStream_t st, int *declined, bool keep_last,
+                           const std::function<int(uint32_t, int *)> &before_emit, uint32_t *n_proc, uint32_t *g_first) {
+    ExtRec &R = w.R;
+    char *d_scan = w.d_scan;
+    uint32_t *d_head = w.d_head, *d_gid = w.d_gid, *d_dec = w.d_dec, *d_tot = w.d_tot;
+    unsigned long long *d_or = w.d_or;
     hipLaunchKernelGGL(k_rec_heads<uint32_t>, dim3(nblk(N, 256)), dim3(256), 0, st, d_text, R.kh, R.qoff, R.klen, N, d_head);
     HIPCHK(hipGetLastError());
     RCHK(hgx_scan_u32_dev(d_head, d_gid, N, d_scan, d_tot, st));
@@ -333,12 +474,33 @@ static int ext_device(hgx_extract &h, const char *base, size_t n_bytes, const st
     if (h_dec) { *declined = first_decline(h_dec); return HGX_OK; }
     uint32_t *d_gstart, *d_r1, *d_r2, *d_ghit, *d_hpos;
     unsigned long long *d_gbits;
-    RCHK(m.get(d_gstart, (size_t)G + 1)); RCHK(m.get(d_r1, G)); RCHK(m.get(d_r2, G)); RCHK(m.get(d_ghit, G)); RCHK(m.get(d_hpos, G));
+    RCHK(m.get(d_gstart, (size_t)G + 1)); RCHK(m.get(d_r1, G + 4)); RCHK(m.get(d_r2, G)); RCHK(m.get(d_ghit, G + 4)); RCHK(m.get(d_hpos, G + 4));
     RCHK(m.get(d_gbits, G));
     hipLaunchKernelGGL(k_rec_gstart, dim3(nblk(N, 256)), dim3(256), 0, st, d_head, d_gid, N, d_gstart);
     HIPCHK(hipGetLastError());
     const uint32_t n32 = (uint32_t)N;
     HIPCHK(hipMemcpyAsync(d_gstart + G, &n32, 4, hipMemcpyHostToDevice, st));
+    if (keep_last) {
+        // the last set head flag is the first record of the last group: that group waits for the next chunk
+        if (G <= 1) { *n_proc = 0; *g_first = 0; return HGX_OK; }
+        uint32_t tail[2] = {0, 0};                                       // first records of the last group taken and of the one kept
+        HIPCHK(hipMemcpyAsync(tail, d_gstart + G - 2, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        *g_first = tail[0];
+        *n_proc = tail[1];
+        G -= 1;
+    } else if (n_proc) {
+        uint32_t first = 0;
+        HIPCHK(hipMemcpyAsync(&first, d_gstart + G - 1, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        *g_first = first;
+        *n_proc = n32;
+    }
+    if (before_emit) {
+        int code = 0;
+        RCHK(before_emit(*n_proc, &code));
+        if (code) { *declined = code; return HGX_OK; }
+    }
     hipLaunchKernelGGL(k_ext_groups, dim3(nblk(G, 256)), dim3(256), 0, st, d_gstart, (long)G, R, h.aligner, h.paired, d_gbits, d_r1, d_r2,
                        d_ghit, d_or, d_dec);
     HIPCHK(hipGetLastError());
@@ -350,7 +512,6 @@ static int ext_device(hgx_extract &h, const char *base, size_t n_bytes, const st
     HIPCHK(hipMemcpyAsync(&fam_or, d_or, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (h_dec) { *declined = first_decline(h_dec); return HGX_OK; }
-    h.up_bytes += (long long)n_bytes + 8ll * N;
     if (H == 0) { h.n_groups += G; return HGX_OK; }
     std::vector<int> fams;
     for (int f = 0; f < h.n_fam; ++f)
@@ -380,7 +541,7 @@ static int ext_device(hgx_extract &h, const char *base, size_t n_bytes, const st
     char *d_out;
     RCHK(m.get(d_out, part[2 * F] + 16));
     for (size_t k = 0; k < F; ++k) {
-        hipLaunchKernelGGL(k_ext_emit, dim3(2 * H), dim3(64), 0, st, d_text, d_hg, (long)H, d_gbits, fams[k], d_gstart, d_r1, d_r2, R, h.fastq,
+        hipLaunchKernelGGL(k_ext_emit<BAM>, dim3(2 * H), dim3(64), 0, st, d_text, d_hg, (long)H, d_gbits, fams[k], d_gstart, d_r1, d_r2, R, h.fastq,
                            d_off + (2 * k) * Hp, d_off + (2 * k + 1) * Hp, d_out + part[2 * k], h.paired ? d_out + part[2 * k + 1] : (char *)nullptr);
         HIPCHK(hipGetLastError());
     }
@@ -393,6 +554,33 @@ static int ext_device(hgx_extract &h, const char *base, size_t n_bytes, const st
         h.written[fams[k]] += (int64_t)cnt[1 + k];
     }
     h.n_groups += G;
+    return HGX_OK;
+}
+
+
+// the device route for one chunk of text; *declined != 0: nothing was appended, the host route takes the chunk
+static int ext_device(hgx_extract &h, const char *base, size_t n_bytes, const std::vector<uint32_t> &ls, const std::vector<uint32_t> &le,
+                      hipStream_t st, int *declined) {
+    *declined = 0;
+    const long N = (long)ls.size();
+    if (h.n_fam > 64) { *declined = HGX_EXT_DECLINE_FAMILIES; return HGX_OK; }
+    RCHK(ext_upload_table(h));
+    DevBufs m("extract route");
+    char *d_text;
+    uint32_t *d_ls, *d_le;
+    ExtWork w;
+    RCHK(m.get(d_text, n_bytes + 64));
+    RCHK(m.get(d_ls, N)); RCHK(m.get(d_le, N));
+    RCHK(ext_work_alloc(m, w, N, st));
+    HIPCHK(hipMemcpyAsync(d_text, base, n_bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_text + n_bytes, 0, 64, st));
+    HIPCHK(hipMemcpyAsync(d_ls, ls.data(), (size_t)N * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_le, le.data(), (size_t)N * 4, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_ext_records, dim3(nblk(N, 256)), dim3(256), 0, st, d_text, d_ls, d_le, N, h.d_chrom, h.d_creg,
+                       h.d_rfam, h.d_rl, h.d_rr, h.simulation, w.R, w.d_dec);
+    HIPCHK(hipGetLastError());
+    RCHK((ext_groups_emit<false>(h, m, d_text, w, N, st, declined, false, nullptr, nullptr, nullptr)));
+    if (!*declined) h.up_bytes += (long long)n_bytes + 8ll * N;
     return HGX_OK;
 }
 
@@ -470,6 +658,302 @@ static int ext_run(hgx_extract &h, bool last, hipStream_t st) {
     return rc;
 }
 
+
+// ---- a BAM stream (hgx_extract_feed_bam) ----------------------------------------------------------------------------------------
+// Deflated bytes go up in chunks and are inflated there (hgx_inflate.hip) behind the carry; the records are walked (hgx_bam_walk.hpp,
+// the open form) and decoded from their binary form (k_ext_bam_records); groups, hits and sizes are the text route's kernels, the
+// text is formed from the 4-bit bases and the binary qualities (k_ext_emit<true>).  Per record the device reads: its deflated
+// bytes once (inflate), 36 bytes of header per walk pass, the record once (k_ext_bam_records), and per written read its packed
+// span once.  Nothing of the inflated stream travels to the host unless the chunk declines.
+int hgx_bgzf_inflate_dev(const unsigned char *d_in, const hgx_bgzf_block *blocks, size_t n_blocks, unsigned char *d_out, hipStream_t st, int *bad,
+                         void *staging);
+
+static void ext_bam_drop_dev_carry(hgx_extract &h) {
+    if (h.d_carry) hgx_pool_free(h.d_carry);
+    h.d_carry = nullptr;
+    h.carry_dev = false;
+}
+
+// The header: the leading blocks through zlib until the reference list is complete.  `next` = the first block not consumed.
+static int ext_bam_header(hgx_extract &h, const std::vector<hgx_bgzf_block> &blocks, bool last, size_t &next) {
+    next = 0;
+    while (!h.have_hdr && next < blocks.size()) {
+        const hgx_bgzf_block &b = blocks[next++];
+        const size_t at = h.head.size();
+        h.head.resize(at + b.out_len);
+        if (!hgx_bam_inflate_block(h.comp.data(), b, h.head.data() + at)) {
+            hgx_set_error("corrupt BGZF block (inflate / CRC32 / ISIZE mismatch)");
+            return HGX_EPARSE;
+        }
+        size_t body0 = 0;
+        const int st = hgx_bam_parse_header(h.head.data(), h.head.size(), h.refs, &body0);
+        if (st < 0) { hgx_set_error("hgx_extract_feed_bam: the stream is no BAM (its inflated bytes do not start with BAM\\1)"); return HGX_EINVAL; }
+        if (st == 0) continue;
+        h.have_hdr = true;
+        // per refID: the chromosome of the handle's region table, from the host map (no name lookup per record on the device)
+        h.reftab.assign(h.refs.size(), -1);
+        for (size_t k = 0; k < h.refs.size(); ++k) {
+            const std::string &nm = h.refs[k];
+            bool plain = !nm.empty();
+            for (unsigned char c : nm) plain = plain && c < 0x80 && !(c == ' ' || (c >= '\t' && c <= '\r') || (c >= 0x1c && c <= 0x1f));
+            const auto it = h.chrom_id.find(nm);
+            h.reftab[k] = !plain ? -2 : it == h.chrom_id.end() ? -1 : it->second;
+        }
+        h.hcarry.assign(h.head.begin() + (ptrdiff_t)body0, h.head.end());           // the records behind the header in its block
+        h.carry_n = h.hcarry.size();
+        h.stream_pos = body0;
+        h.head.clear();
+        h.head.shrink_to_fit();
+    }
+    if (!h.have_hdr && last) { hgx_set_error(h.head.size() < 12 ? "truncated BAM header" : "truncated BAM reference list"); return HGX_EPARSE; }
+    return HGX_OK;
+}
+
+// The host route of a BAM chunk: the carry and the chunk's blocks (inflated here) as one stream, its complete records printed by
+// the reader's decoder, the text through hgx_extract_host.  Takes what the device declines and words every error.
+static int ext_bam_host(hgx_extract &h, const std::vector<hgx_bgzf_block> &blocks, size_t b0, size_t total_out, bool last, int code) {
+    if (h.carry_dev) {
+        h.hcarry.resize(h.carry_n);
+        if (h.carry_n) HIPCHK(hipMemcpy(h.hcarry.data(), (const char *)h.d_carry, h.carry_n, hipMemcpyDeviceToHost));
+        ext_bam_drop_dev_carry(h);
+    }
+    bool counted = false;
+    auto count = [&]() {                                         // the host route took (or refused) a chunk
+        if (counted) return;
+        counted = true;
+        ++h.chunks_host;
+        h.last_decline = code;
+        hgx_front_set_last(0, code, 0);
+    };
+    std::vector<unsigned char> s;
+    s.swap(h.hcarry);
+    const size_t cn = s.size(), n = cn + total_out;
+    s.resize(n);
+    const size_t out0 = b0 < blocks.size() ? blocks[b0].out_off : 0;
+    std::atomic<int> bad{0};
+    hgx_par_ranges(hgx_default_threads(), blocks.size() - b0, [&](int, size_t b, size_t e) {
+        for (size_t k = b0 + b; k < b0 + e; ++k)
+            if (!hgx_bam_inflate_block(h.comp.data(), blocks[k], s.data() + cn + (blocks[k].out_off - out0))) bad = 1;
+    });
+    if (bad) { count(); hgx_set_error("corrupt BGZF block (inflate / CRC32 / ISIZE mismatch)"); return HGX_EPARSE; }
+    struct Rec { size_t off; uint32_t len; };
+    std::vector<Rec> recs;
+    size_t q = 0;
+    auto rd32 = [&](size_t p) { return (uint32_t)s[p] | ((uint32_t)s[p + 1] << 8) | ((uint32_t)s[p + 2] << 16) | ((uint32_t)s[p + 3] << 24); };
+    while (q + 4 <= n) {
+        const uint32_t bs = rd32(q);
+        if (bs < 32) { count(); hgx_set_error("truncated BAM record at offset %zu", h.stream_pos + q); return HGX_EPARSE; }
+        if (q + 4 + (size_t)bs > n) break;
+        recs.push_back(Rec{q + 4, bs});
+        q += 4 + (size_t)bs;
+    }
+    if (last && q != n) { count(); hgx_set_error("truncated BAM record at offset %zu", h.stream_pos + q); return HGX_EPARSE; }
+    std::string txt;
+    std::vector<uint32_t> ls, le;
+    std::vector<size_t> rec_of;                                  // the record of every line (a QNAME that starts with '@' prints a header line: no record)
+    for (size_t i = 0; i < recs.size(); ++i) {
+        const size_t b = txt.size();
+        if (!hgx_bam_record_line(s.data() + recs[i].off, recs[i].len, h.refs, txt)) { count(); hgx_set_error("malformed BAM record"); return HGX_EPARSE; }
+        if (txt.size() > 0xFFFFFFF0ull) { hgx_set_error("BAM chunk too large"); return HGX_EPARSE; }
+        if (txt.size() == b || txt[b] != '@') { ls.push_back((uint32_t)b); le.push_back((uint32_t)txt.size()); rec_of.push_back(i); }
+        txt.push_back('\n');
+    }
+    size_t n_use = ls.size(), keep = q;
+    if (!last && n_use > 0) {
+        n_use = ext_last_group(h, txt.data(), ls, le, n_use);
+        keep = recs[rec_of[n_use]].off - 4;
+        // the stream's name test (process:1651-1659) looks at the second record before the first group is flushed: a first
+        // chunk of one record waits for the next one
+        if (h.chk_line && h.prev_name.empty() && n_use < 2) { n_use = 0; keep = 0; }
+    }
+    int rc = HGX_OK;
+    if (n_use > 0) {
+        count();
+        rc = hgx_extract_host(h, txt.data(), ls.data(), le.data(), n_use);
+    }
+    if (rc) return rc;
+    if (n - keep > EXT_MAX_BUF) { hgx_set_error("hgx_extract_feed_bam: one read's records span more than %zu bytes", EXT_MAX_BUF); return HGX_EINVAL; }
+    h.hcarry.assign(s.begin() + (ptrdiff_t)keep, s.end());
+    h.carry_n = h.hcarry.size();
+    h.stream_pos += keep;
+    return HGX_OK;
+}
+
+// The device route of a BAM chunk; *declined != 0: nothing was changed, the host route takes the chunk.
+static int ext_bam_device(hgx_extract &h, const std::vector<hgx_bgzf_block> &blocks, size_t b0, size_t used,
+                          size_t total_out, bool last, hipStream_t st, int *declined) {
+    *declined = 0;
+    if (h.n_fam > 64) { *declined = HGX_EXT_DECLINE_FAMILIES; return HGX_OK; }
+    // the gate before anything touches the device: a record takes at least 36 bytes of the stream, so fewer bytes than 36 per
+    // gate record cannot reach the gate (the exact count is known after the walk and gates again there)
+    const bool force = hgx_switch_has("front", "device");
+    if (!force && (h.carry_n + total_out) / 36 < (size_t)HGX_EXT_MIN_RECORDS) { *declined = HGX_EXT_DECLINE_SMALL; return HGX_OK; }
+    for (size_t k = b0; k < blocks.size(); ++k)
+        if (blocks[k].out_len > 65536) { *declined = HGX_EXT_DECLINE_INFLATE; return HGX_OK; }
+    RCHK(ext_upload_table(h));
+    if (!h.d_reftab && !upload_array(h.d_reftab, h.reftab.data(), h.reftab.size() * 4)) {
+        hgx_set_error("extract route: upload of the reference table failed: %s", hipGetErrorString(hipGetLastError()));
+        return HGX_EHIP;
+    }
+    const size_t cn = h.carry_n, n = cn + total_out;
+    if (n == 0) return HGX_OK;
+    // the stream lies behind `lead` bytes so that its inflated part starts on a 64-byte boundary and the aligned loads of the walk
+    // and of the emit kernel may reach below its first byte; 1 KB of zeros behind it
+    const size_t lead = 64 + ((64 - (cn & 63)) & 63), pad = 1024;
+    if (lead + n + pad >= (1ull << 32)) { *declined = HGX_EXT_DECLINE_SIZE; return HGX_OK; }
+    struct Hold { void *p; ~Hold() { if (p) hgx_pool_free(p); } } hold{hgx_pool_alloc(lead + n + pad)};
+    if (!hold.p) { hgx_set_error("extract route: device allocation of %zu bytes failed", lead + n + pad); return HGX_ENOMEM; }
+    char *d_text = (char *)hold.p;
+    DevBufs m("extract route");
+    long long up = 0;
+    HIPCHK(hipMemsetAsync(d_text, 0, lead, st));
+    HIPCHK(hipMemsetAsync(d_text + lead + n, 0, pad, st));
+    if (cn) {
+        if (h.carry_dev) HIPCHK(hipMemcpyAsync(d_text + lead, (const char *)h.d_carry, cn, hipMemcpyDeviceToDevice, st));
+        else { HIPCHK(hipMemcpyAsync(d_text + lead, h.hcarry.data(), cn, hipMemcpyHostToDevice, st)); up += (long long)cn; }
+    }
+    if (b0 < blocks.size()) {
+        const size_t c0 = blocks[b0].in_off, cb = used - c0, out0 = blocks[b0].out_off;     // (from the first block's deflate data on)
+        std::vector<hgx_bgzf_block> rel(blocks.begin() + (ptrdiff_t)b0, blocks.end());
+        for (hgx_bgzf_block &b : rel) { b.in_off -= c0; b.out_off -= out0; }
+        unsigned char *d_comp;
+        RCHK(m.get(d_comp, cb + 2048));
+        HIPCHK(hipMemcpyAsync(d_comp, h.comp.data() + c0, cb, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemsetAsync(d_comp + cb, 0, 2048, st));
+        int bad = 0;
+        RCHK(hgx_bgzf_inflate_dev(d_comp, rel.data(), rel.size(), (unsigned char *)d_text + lead + cn, st, &bad, nullptr));
+        if (bad) { *declined = HGX_EXT_DECLINE_INFLATE; return HGX_OK; }
+        up += (long long)cb + 20ll * (long long)rel.size();
+    }
+    // the record chain, from the known chain position (the stream's first byte)
+    const int W = (int)std::min<size_t>((size_t)1 << 20, n / 8192 + 1);
+    BamSeg seg{};
+    seg.base = (uint32_t)lead; seg.n = (uint32_t)n; seg.body0 = 0; seg.n_ref = (int32_t)h.refs.size(); seg.first_range = 0; seg.n_ranges = (uint32_t)W;
+    BamSeg *d_seg;
+    BamRange *d_rng;
+    BamCtl *d_ctl;
+    uint32_t *d_cnt, *d_base;
+    char *d_wscan;
+    RCHK(m.get(d_seg, 1)); RCHK(m.get(d_rng, W)); RCHK(m.get(d_ctl, 1)); RCHK(m.get(d_cnt, W + 4)); RCHK(m.get(d_base, W + 4));
+    RCHK(m.get(d_wscan, hgx_scan_u32_scratch_bytes(W)));
+    HIPCHK(hipMemsetAsync(d_ctl, 0, sizeof(BamCtl), st));
+    HIPCHK(hipMemcpyAsync(d_seg, &seg, sizeof seg, hipMemcpyHostToDevice, st));
+    const unsigned char *u_text = (const unsigned char *)d_text;
+    hipLaunchKernelGGL((k_bam_walk<0, true>), dim3(nblk(W, 64)), dim3(64), 0, st, u_text, d_seg, 1, W, d_rng, (const uint32_t *)nullptr,
+                       (uint32_t *)nullptr, (uint32_t *)nullptr, (uint16_t *)nullptr);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_bam_link_open, dim3(nblk(W, 256)), dim3(256), 0, st, u_text, d_rng, d_seg, 1, W, d_cnt, d_ctl);
+    HIPCHK(hipGetLastError());
+    RCHK(hgx_scan_u32_dev(d_cnt, d_base, W, d_wscan, d_ctl->tot, st));
+    BamCtl ctl;
+    HIPCHK(hipMemcpyAsync(&ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (ctl.decline) { *declined = HGX_EXT_DECLINE_CHAIN; return HGX_OK; }
+    const long N = (long)ctl.tot[0];
+    const size_t end = ctl.end;                                          // the first incomplete record (offset in the stream)
+    if (last && end != n) { hgx_set_error("truncated BAM record at offset %zu", h.stream_pos + end); return HGX_EPARSE; }
+    if (N > 0 && !force && N < HGX_EXT_MIN_RECORDS) { *declined = HGX_EXT_DECLINE_SMALL; return HGX_OK; }
+    uint32_t n_proc = 0, g_first = 0;
+    uint32_t *d_off = nullptr;
+    if (N > 0) {
+        uint32_t *d_len;
+        uint16_t *d_task;
+        ExtWork w;
+        RCHK(m.get(d_off, N)); RCHK(m.get(d_len, N)); RCHK(m.get(d_task, N + 8));
+        RCHK(ext_work_alloc(m, w, N, st));
+        hipLaunchKernelGGL((k_bam_walk<1, true>), dim3(nblk(W, 64)), dim3(64), 0, st, u_text, d_seg, 1, W, d_rng, (const uint32_t *)d_base, d_off, d_len, d_task);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(k_ext_bam_records, dim3(nblk(N, 256)), dim3(256), 0, st, u_text, d_off, d_len, N, h.d_reftab, (int)h.refs.size(), h.d_creg,
+                           h.d_rfam, h.d_rl, h.d_rr, h.simulation, w.R, w.d_dec);
+        HIPCHK(hipGetLastError());
+        // a record's name, copied back (the first two for the stream's name test, one per chunk for prev_name)
+        auto name_of = [&](uint32_t rec, std::string &name) -> int {
+            uint32_t off = 0;
+            unsigned char buf[32 + 256];
+            HIPCHK(hipMemcpyAsync(&off, d_off + rec, 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            HIPCHK(hipMemcpyAsync(buf, d_text + off, sizeof buf, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            name.assign((const char *)buf + 32, buf[8] ? (size_t)buf[8] - 1 : 0);
+            return HGX_OK;
+        };
+        auto chk = [&](uint32_t np, int *code) -> int {
+            if (!h.chk_line || np == 0) return HGX_OK;
+            std::string txt, nm;
+            std::vector<uint32_t> ls, le;
+            for (uint32_t k = 0; k < 2 && k < (uint32_t)N; ++k) {
+                RCHK(name_of(k, nm));
+                ls.push_back((uint32_t)txt.size());
+                txt += nm;
+                le.push_back((uint32_t)txt.size());
+                txt.push_back('\n');
+            }
+            if (!hgx_extract_chk(h, txt.data(), ls.data(), le.data(), (size_t)N)) *code = HGX_EXT_DECLINE_NAMES;
+            return HGX_OK;
+        };
+        RCHK((ext_groups_emit<true>(h, m, d_text, w, N, st, declined, !last, chk, &n_proc, &g_first)));
+        if (*declined) return HGX_OK;
+        if (n_proc > 0) {
+            RCHK(name_of(g_first, h.prev_name));
+            h.chk_line = false;
+            h.n_records += (int64_t)n_proc;
+            ++h.chunks_dev;
+        }
+    }
+    h.up_bytes += up;
+    hgx_front_set_last(2, 0, up);                                        // (also a chunk that only grew the carry)
+    // the carry: from the first record not taken on (with `last` the stream has ended on a record boundary: nothing)
+    size_t keep = n;
+    if (!last) {
+        keep = end;
+        if (n_proc < (uint32_t)N) {
+            uint32_t off = 0;
+            HIPCHK(hipMemcpyAsync(&off, d_off + n_proc, 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            keep = (size_t)off - 4 - lead;
+        }
+    }
+    const size_t new_n = n - keep;
+    if (new_n > EXT_MAX_BUF) { hgx_set_error("hgx_extract_feed_bam: one read's records span more than %zu bytes", EXT_MAX_BUF); return HGX_EINVAL; }
+    void *nc = nullptr;
+    if (new_n) {
+        nc = hgx_pool_alloc(new_n + 64);
+        if (!nc) { hgx_set_error("extract route: device allocation of %zu bytes failed", new_n + 64); return HGX_ENOMEM; }
+        const hipError_t e = hipMemcpyAsync(nc, d_text + lead + keep, new_n, hipMemcpyDeviceToDevice, st);
+        const hipError_t e2 = e == hipSuccess ? hipStreamSynchronize(st) : e;
+        if (e2 != hipSuccess) { hgx_pool_free(nc); hgx_set_error("extract route: %s", hipGetErrorString(e2)); return HGX_EHIP; }
+    }
+    ext_bam_drop_dev_carry(h);
+    h.hcarry.clear();
+    h.d_carry = nc;
+    h.carry_dev = nc != nullptr;
+    h.carry_n = new_n;
+    h.stream_pos += keep;
+    return HGX_OK;
+}
+
+// h.comp holds the undigested bytes and the new ones: run every complete block, keep the rest.
+static int ext_bam_run(hgx_extract &h, bool last, hipStream_t st) {
+    // the complete blocks at the head of h.comp (in_off within h.comp, out_off from 0); a partial one waits for the next feed
+    std::vector<hgx_bgzf_block> blocks;
+    size_t used = 0, b0 = 0;
+    RCHK(hgx_bgzf_scan_stream(h.comp.data(), h.comp.size(), last, h.comp_pos, blocks, nullptr, &used));
+    if (!h.have_hdr) RCHK(ext_bam_header(h, blocks, last, b0));
+    if (h.have_hdr && (b0 < blocks.size() || last)) {
+        size_t total_out = 0;
+        for (size_t k = b0; k < blocks.size(); ++k) total_out += blocks[k].out_len;
+        int declined = hgx_switch_has("front", "host") ? HGX_EXT_DECLINE_FORCED : 0;
+        if (!declined) {
+            const int rc = ext_bam_device(h, blocks, b0, used, total_out, last, st, &declined);
+            if (rc) { hgx_front_set_last(0, 0, 0); return rc; }
+        }
+        if (declined) RCHK(ext_bam_host(h, blocks, b0, total_out, last, declined));
+    }
+    h.comp.erase(h.comp.begin(), h.comp.begin() + (ptrdiff_t)used);
+    h.comp_pos += used;
+    return HGX_OK;
+}
+
 extern "C" int hgx_extract_open(hgx_extract **out, int32_t n_regions, const int32_t *family, const char *chrom_pool, size_t chrom_bytes,
                                 const int64_t *left, const int64_t *right, int32_t n_families, const hgx_extract_opts *opts) {
     ARGCHK(out && opts && n_regions >= 0 && n_families >= 0 && (n_regions == 0 || (family && chrom_pool && left && right)));
@@ -510,6 +994,8 @@ extern "C" int hgx_extract_feed(hgx_extract *h, const char *bytes, size_t n_byte
     ARGCHK(h && (bytes || n_bytes == 0));
     if (h->error_kind) { hgx_set_error("hgx_extract_feed: the stream has already raised"); return HGX_EPARSE; }
     if (h->finished) { hgx_set_error("hgx_extract_feed: the stream was closed by an earlier last feed"); return HGX_EINVAL; }
+    if (h->mode == 2) { hgx_set_error("hgx_extract_feed: the handle was fed BAM bytes (hgx_extract_feed_bam); a stream is text or BAM, not both"); return HGX_EINVAL; }
+    h->mode = 1;
     const size_t piece = hgx_test_switch("extract_piece") ? (size_t)atol(hgx_test_switch("extract_piece")) : ((size_t)256 << 20);
     size_t p = 0;
     do {
@@ -527,21 +1013,85 @@ extern "C" int hgx_extract_feed(hgx_extract *h, const char *bytes, size_t n_byte
     return HGX_OK;
 }
 
+
+constexpr size_t EXT_BAM_PIECE = (size_t)64 << 20;       // deflated bytes per chunk
+static size_t ext_bam_piece() {
+    const char *sw = hgx_test_switch("extract_bam_piece");
+    return std::max<size_t>(sw ? (size_t)atol(sw) : EXT_BAM_PIECE, 1);
+}
+
+extern "C" int hgx_extract_feed_bam(hgx_extract *h, const void *bgzf, size_t n_bytes, int32_t last, void *stream) {
+    ARGCHK(h && (bgzf || n_bytes == 0));
+    if (h->error_kind) { hgx_set_error("hgx_extract_feed_bam: the stream has already raised"); return HGX_EPARSE; }
+    if (h->finished) { hgx_set_error("hgx_extract_feed_bam: the stream was closed by an earlier last feed"); return HGX_EINVAL; }
+    if (h->mode == 1) { hgx_set_error("hgx_extract_feed_bam: the handle was fed text (hgx_extract_feed); a stream is text or BAM, not both"); return HGX_EINVAL; }
+    h->mode = 2;
+    const size_t piece = ext_bam_piece();
+    const unsigned char *bytes = (const unsigned char *)bgzf;
+    size_t p = 0;
+    do {
+        const size_t take = std::min(piece, n_bytes - p);
+        h->comp.insert(h->comp.end(), bytes + p, bytes + p + take);
+        p += take;
+        const bool fin = last && p == n_bytes;
+        RCHK(ext_bam_run(*h, fin, (hipStream_t)stream));
+        if (fin) h->finished = true;
+    } while (p < n_bytes);
+    return HGX_OK;
+}
+
+// true: the file's first BGZF block inflates to a BAM header's magic (a bgzipped SAM text, or anything else, goes the text way)
+static bool ext_file_is_bam(FILE *f) {
+    std::vector<unsigned char> d((size_t)1 << 16);
+    rewind(f);
+    const size_t n = fread(d.data(), 1, d.size(), f);
+    if (n < 18 || d[0] != 0x1f || d[1] != 0x8b || d[2] != 8 || !(d[3] & 4)) return false;
+    const size_t xlen = (size_t)d[10] | ((size_t)d[11] << 8);
+    size_t blen = 0;
+    for (size_t q = 12; q + 6 <= 12 + xlen && q + 6 <= n;) {
+        const size_t slen = (size_t)d[q + 2] | ((size_t)d[q + 3] << 8);
+        if (d[q] == 66 && d[q + 1] == 67 && slen == 2) blen = ((size_t)d[q + 4] | ((size_t)d[q + 5] << 8)) + 1;
+        q += 4 + slen;
+    }
+    if (!blen || blen > n || blen < 12 + xlen + 8) return false;
+    hgx_bgzf_block b;
+    b.in_off = 12 + xlen; b.in_len = blen - 12 - xlen - 8; b.out_off = 0;
+    b.crc = (uint32_t)d[blen - 8] | ((uint32_t)d[blen - 7] << 8) | ((uint32_t)d[blen - 6] << 16) | ((uint32_t)d[blen - 5] << 24);
+    b.out_len = (uint32_t)d[blen - 4] | ((uint32_t)d[blen - 3] << 8) | ((uint32_t)d[blen - 2] << 16) | ((uint32_t)d[blen - 1] << 24);
+    if (b.out_len < 4 || b.out_len > 65536) return false;
+    std::vector<unsigned char> out(b.out_len);
+    return hgx_bam_inflate_block(d.data(), b, out.data()) && memcmp(out.data(), "BAM\1", 4) == 0;
+}
+
 extern "C" int hgx_extract_file(hgx_extract *h, const char *path, void *stream) {
     ARGCHK(h && path);
     FILE *f = fopen(path, "rb");
     if (!f) { hgx_set_error("hgx_extract_file: cannot open %s", path); return HGX_EINVAL; }
     unsigned char magic[4] = {0, 0, 0, 0};
     const size_t got = fread(magic, 1, 4, f);
+    if (got >= 2 && magic[0] == 0x1f && magic[1] == 0x8b && ext_file_is_bam(f)) {
+        // BAM: the file's deflated bytes, block after block; the handle inflates them and reads the records in their binary form
+        rewind(f);
+        std::vector<unsigned char> blk(ext_bam_piece());
+        int rc = HGX_OK;
+        for (;;) {
+            const size_t n = fread(blk.data(), 1, blk.size(), f);
+            const bool fin = n < blk.size();
+            rc = hgx_extract_feed_bam(h, blk.data(), n, fin ? 1 : 0, stream);
+            if (rc || fin) break;
+        }
+        fclose(f);
+        return rc;
+    }
     if (got >= 2 && magic[0] == 0x1f && magic[1] == 0x8b) {
-        // BAM (BGZF): the existing reader inflates and walks the file in one piece, records in file order, as the text
-        // `samtools view` prints; that text is the stream
+        // any other BGZF / gzip file (a bgzipped SAM text): the reader inflates it in one piece; its lines, in file order, are
+        // the stream
         fclose(f);
         std::vector<char> text;
         size_t tot;
         RCHK(bam_as_sam_text(path, nullptr, EXT_MAX_BUF, text, tot));
         if (tot > EXT_MAX_BUF) {
-            hgx_set_error("hgx_extract_file: %s holds %zu bytes of records; a BAM is read in one piece of at most %zu (feed it as SAM text)",
+            hgx_set_error("hgx_extract_file: %s holds %zu bytes of records; a compressed text is read in one piece of at most %zu (feed it as SAM text)",
                           path, tot, EXT_MAX_BUF);
             return HGX_EINVAL;
         }
@@ -587,6 +1137,7 @@ extern "C" int hgx_extract_stats(const hgx_extract *h, int64_t *records, int64_t
 extern "C" int hgx_extract_close(hgx_extract *h) {
     if (!h) return HGX_OK;
     ext_free_table(*h);
+    ext_bam_drop_dev_carry(*h);
     delete h;
     return HGX_OK;
 }

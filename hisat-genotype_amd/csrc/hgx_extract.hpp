@@ -21,6 +21,8 @@ enum {
     HGX_EXT_DECLINE_FAMILIES = 8,   // more than 64 families
     HGX_EXT_DECLINE_NAMES = 9,      // the stream's first two records (chk_line), or an empty name before '|' in simulation mode
     HGX_EXT_DECLINE_SIZE = 10,      // a chunk's output beyond 32-bit offsets
+    HGX_EXT_DECLINE_INFLATE = 11,   // BAM: the device inflate gave a block a bad verdict (the host inflates the chunk and decides)
+    HGX_EXT_DECLINE_CHAIN = 12,     // BAM: the ranges of the record walk did not link up, or a block_size below 32
 };
 
 // hgx_extract_stats' error_kind: the exception the reference raises at that point
@@ -49,6 +51,22 @@ struct hgx_extract {
     int last_decline = 0;
     std::vector<int64_t> written;                                // pairs (reads) written per family
     std::vector<std::string> out, taken;                         // [n_fam * 2]: text not yet taken / the block handed out last
+    // a BAM stream (hgx_extract_feed_bam): deflated bytes in, the records read in their binary form
+    int mode = 0;                                                // 0 = nothing fed yet, 1 = text, 2 = BAM
+    std::vector<unsigned char> comp;                             // BGZF bytes not yet digested (at most one partial block stays)
+    size_t comp_pos = 0;                                         // file offset of comp[0]
+    bool have_hdr = false;
+    std::vector<unsigned char> head;                             // the leading block(s), inflated on the host until the header parses
+    std::vector<std::string> refs;                               // the header's reference names
+    std::vector<int32_t> reftab;                                 // [n_ref] chromosome index in `chrom`, -1 = none, -2 = a name text would split
+    // the carry: the inflated bytes from the first record of the last, possibly unfinished, group on.  After a device chunk it
+    // is a pool allocation of its own (copied out of the chunk's stream buffer), after a host chunk a vector; stream_pos = its
+    // offset in the inflated file
+    std::vector<unsigned char> hcarry;
+    void *d_carry = nullptr;
+    size_t carry_n = 0, stream_pos = 0;
+    bool carry_dev = false;
+    int32_t *d_reftab = nullptr;
     // device copies of the region table (hgx_extract.hip)
     hgx_name_view d_chrom;
     uint32_t *d_creg = nullptr;

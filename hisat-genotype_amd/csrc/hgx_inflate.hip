@@ -1121,28 +1121,40 @@ CrcOp make_crc_op() {
 
 }   // namespace
 
-// the BGZF blocks of `data` (host bytes; n bytes) as descriptors: HGX_OK, or the host reader's error for a malformed container
-int hgx_bgzf_scan(const unsigned char *data, size_t n, std::vector<hgx_bgzf_block> &blocks, size_t *total_out) {
+// the BGZF blocks of `data` (host bytes; n bytes) as descriptors: HGX_OK, or the host reader's error for a malformed container.
+// The stream form takes a piece of a file that arrives in chunks: `file_off` = where data[0] lies in the file (the errors' offsets),
+// `last` = the file ends with these bytes; otherwise a block that is not complete yet is left for the next call and *used = the
+// bytes the complete blocks take.
+int hgx_bgzf_scan_stream(const unsigned char *data, size_t n, bool last, size_t file_off, std::vector<hgx_bgzf_block> &blocks, size_t *total_out,
+                         size_t *used) {
     blocks.clear();
     size_t off = 0, total = 0;
     auto rd16 = [&](size_t p) { return (unsigned)data[p] | ((unsigned)data[p + 1] << 8); };
     auto rd32 = [&](size_t p) { return (uint32_t)data[p] | ((uint32_t)data[p + 1] << 8) | ((uint32_t)data[p + 2] << 16) | ((uint32_t)data[p + 3] << 24); };
     while (off < n) {
-        if (off + 18 > n || data[off] != 0x1f || data[off + 1] != 0x8b || data[off + 2] != 8 || !(data[off + 3] & 4)) {
-            hgx_set_error("not a BGZF block at offset %zu", off);
+        const size_t have = n - off;
+        const bool magic_bad = data[off] != 0x1f || (have > 1 && data[off + 1] != 0x8b) || (have > 2 && data[off + 2] != 8) || (have > 3 && !(data[off + 3] & 4));
+        if (magic_bad || (have < 18 && last)) {
+            hgx_set_error("not a BGZF block at offset %zu", file_off + off);
             return HGX_EPARSE;
         }
+        if (have < 18) break;
         const unsigned xlen = rd16(off + 10);
-        if (off + 12 + xlen > n) { hgx_set_error("truncated BGZF header at offset %zu", off); return HGX_EPARSE; }
+        if (off + 12 + xlen > n) {
+            if (!last) break;
+            hgx_set_error("truncated BGZF header at offset %zu", file_off + off);
+            return HGX_EPARSE;
+        }
         long bsize = -1;
         for (size_t p = off + 12; p + 4 <= off + 12 + xlen;) {
             const unsigned slen = rd16(p + 2);
             if (data[p] == 66 && data[p + 1] == 67 && slen == 2 && p + 6 <= off + 12 + xlen) bsize = (long)rd16(p + 4);
             p += 4 + slen;
         }
-        if (bsize < 0) { hgx_set_error("BGZF block without BC subfield at offset %zu", off); return HGX_EPARSE; }
+        if (bsize < 0) { hgx_set_error("BGZF block without BC subfield at offset %zu", file_off + off); return HGX_EPARSE; }
         const size_t blen = (size_t)bsize + 1;
-        if (off + blen > n || blen < 12 + xlen + 8) { hgx_set_error("truncated BGZF block at offset %zu", off); return HGX_EPARSE; }
+        if (off + blen > n && !last && blen >= 12 + xlen + 8) break;
+        if (off + blen > n || blen < 12 + xlen + 8) { hgx_set_error("truncated BGZF block at offset %zu", file_off + off); return HGX_EPARSE; }
         hgx_bgzf_block b;
         b.in_off = off + 12 + xlen;
         b.in_len = blen - 12 - xlen - 8;
@@ -1154,7 +1166,11 @@ int hgx_bgzf_scan(const unsigned char *data, size_t n, std::vector<hgx_bgzf_bloc
         off += blen;
     }
     if (total_out) *total_out = total;
+    if (used) *used = off;
     return HGX_OK;
+}
+int hgx_bgzf_scan(const unsigned char *data, size_t n, std::vector<hgx_bgzf_block> &blocks, size_t *total_out) {
+    return hgx_bgzf_scan_stream(data, n, true, 0, blocks, total_out, nullptr);
 }
 
 // The same on several host threads.  The blocks of a BGZF file form a chain (each BSIZE leads to the next header), and every hop of

@@ -172,6 +172,9 @@ struct hgx_line { char *p; uint32_t len, klen; uint64_t key; };     // klen = QN
 // BGZF container (hgx_inflate.hip: inflate on the device, one wavefront per block)
 struct hgx_bgzf_block { size_t in_off, in_len, out_off, out_len; uint32_t crc; };
 int hgx_bgzf_scan(const unsigned char *data, size_t n, std::vector<hgx_bgzf_block> &blocks, size_t *total_out);
+// (a piece of a file that arrives in chunks: errors worded with file offsets; unless `last`, a partial block at the end is left, *used = the complete ones' bytes)
+int hgx_bgzf_scan_stream(const unsigned char *data, size_t n, bool last, size_t file_off, std::vector<hgx_bgzf_block> &blocks, size_t *total_out,
+                         size_t *used);
 int hgx_bgzf_scan_par(const unsigned char *data, size_t n, std::vector<hgx_bgzf_block> &blocks, size_t *total_out, int n_threads);   // (the same, ranges on several threads)
 // a BAM whose record walk, region filter and name sort are left to the device front end (hgx_front.hip: k_bam_*): the reader stops
 // after the inflate and the header
@@ -225,6 +228,10 @@ struct hgx_align_lines {
     ~hgx_align_lines() { hgx_host_free(raw); }
 };
 int hgx_read_alignment_lines(const char *path, const char *regions, int n_threads, hgx_align_lines &out, bool keep_binary = false);
+// the reader's header parser, one-block inflate and record -> text decoder for a BAM that arrives in chunks (hgx_bam.cpp)
+int hgx_bam_parse_header(const unsigned char *raw, size_t n, std::vector<std::string> &refs, size_t *body0);
+bool hgx_bam_inflate_block(const unsigned char *data, const hgx_bgzf_block &b, unsigned char *dst);
+bool hgx_bam_record_line(const unsigned char *rec, size_t len, const std::vector<std::string> &refs, std::string &line);
 int hgx_deferred_for_regions(const char *regions, bool text, size_t body0, const std::vector<std::string> &refs, hgx_bam_deferred &d);
 
 // find-or-insert a piece given its word range and (MP,P) mask words

@@ -1,11 +1,12 @@
 """Read extraction: stage 1 of a real-data run (hisatgenotype_typing_process.extract_reads, process:1330-1784).
 
-The aligner's SAM stream over the whole genotype genome goes through the library's extraction handle (include/hgx.h "read
+The aligner's SAM stream over the whole genotype genome (or a BAM file of it, fed as deflated bytes) goes through the library's extraction handle (include/hgx.h "read
 extraction": record pass, grouping, family decision and FASTQ / FASTA text as gfx950 kernels, csrc/hgx_extract.hip); this module
 keeps the reference's file discovery, file names, "Files found: Omitted" rule and return value, starts the aligner with the
 reference's command line when no alignment file is given, and compresses the text it takes from the library on host threads."""
 import ctypes as C
 import glob
+import gzip
 import os
 import subprocess
 import sys
@@ -77,6 +78,11 @@ class Extractor:
     def feed(self, data, last=False):
         self._raise(capi.lib().hgx_extract_feed(self.h, C.c_char_p(data) if isinstance(data, bytes) else capi.ptr(data),
                                                 C.c_size_t(len(data)), C.c_int32(1 if last else 0), self.stream))
+
+    def feed_bam(self, data, last=False):
+        """The next bytes of a BAM file (its BGZF container), cut anywhere."""
+        self._raise(capi.lib().hgx_extract_feed_bam(self.h, C.c_char_p(data) if isinstance(data, bytes) else capi.ptr(data),
+                                                    C.c_size_t(len(data)), C.c_int32(1 if last else 0), self.stream))
 
     def feed_file(self, path):
         self._raise(capi.lib().hgx_extract_file(self.h, C.c_char_p(os.fsencode(path)), self.stream))
@@ -171,6 +177,18 @@ def aligner_command(aligner, base_filepath, fastq, paired, threads_aprocess, fq_
     else:
         cmd += ["-U", fq_fname]
     return cmd
+
+
+def is_bam(path):
+    """A BGZF file (magic 1f 8b) whose inflated bytes start with a BAM header's magic; a bgzipped SAM text is not."""
+    with open(path, "rb") as f:
+        if f.read(2) != b"\x1f\x8b":
+            return False
+    try:
+        with gzip.open(path, "rb") as g:
+            return g.read(4) == b"BAM\x01"
+    except (OSError, EOFError, zlib.error):
+        return True          # a damaged container: the BAM reader words the error
 
 
 def _out_names(out_dir, base, database, paired):
@@ -310,8 +328,21 @@ def extract_reads(base_fname, ix_dir, database_list, read_dir, out_dir, suffix, 
                 else:
                     path = alignment_fname
 
-                def source(ex, drain, path=path):
-                    ex.feed_file(path)
+                if is_bam(path):
+                    def source(ex, drain, path=path):
+                        # the file's deflated bytes block by block: what is ready is compressed and written while the file is read
+                        with open(path, "rb") as f:
+                            block = f.read(FEED_BYTES)
+                            while True:
+                                nxt = f.read(FEED_BYTES)
+                                ex.feed_bam(block, last=not nxt)
+                                drain()
+                                if not nxt:
+                                    break
+                                block = nxt
+                else:
+                    def source(ex, drain, path=path):
+                        ex.feed_file(path)
 
             ex = Extractor(regions, database_list, aligner, paired, simulation, fastq)
             files = [[open(n, "wb") for n in _out_names(out_dir, fq_fname_base, database, paired)] for database in database_list]

@@ -731,8 +731,21 @@ int hgx_linear_destroy(hgx_linear *r);
  * 32-bit parse does not, more than 64 families decline to the host route (csrc/hgx_extract_host.cpp) for that chunk, which gives
  * the same bytes or words the reference's error: HGX_EPARSE, with hgx_extract_stats' error_kind = 1 ValueError, 2 AssertionError,
  * 3 SystemExit(1), 4 IndexError, 5 TypeError; the text written before the error stays takeable.
- * hgx_extract_file (process:1468-1488, the aligner's stdout as a file): SAM text in 64 MB blocks through hgx_extract_feed, or a
- * BAM in one piece through the alignment reader (a worded error beyond 1 GB of records).
+ * hgx_extract_feed_bam: the same stream as a BAM file -- the next bytes of the BGZF container, cut anywhere (inside a block
+ * header, a block, the BAM header, a record); `last` != 0 ends it.  The handle keeps the undigested deflated bytes, inflates the
+ * header's block(s) on the host (reference names -> chromosomes of the region table, once), and per chunk of complete blocks
+ * sends the deflated bytes up, inflates them there behind the carried records, walks the record chain and reads FLAG, refID,
+ * POS, the read name, the 4-bit bases, the qualities and the AS / XS / NH tags (types c C s S i I; the last occurrence wins) from
+ * the binary records.  The rules above apply to the line `samtools view` prints for a record: output and errors are those of that
+ * text through hgx_extract_feed.  Whatever would make that line split otherwise than the fields lie (a blank or a byte >= 0x80
+ * in a name or a tag's value), AS / XS / NH of another type, damaged aux data, a block the device inflate refuses and a record
+ * chain that does not link up decline the chunk: the host inflates it, prints its records and runs the host route, which also
+ * words the reader's errors (corrupt BGZF block, truncated BAM record at offset ..., malformed BAM record).  The gate and the
+ * front switches are those of text; one read's records (the carry) may span 1 GB.  A handle takes text or BAM, not both:
+ * the other entry point returns HGX_EINVAL.  hgx_front_last's byte count of a device chunk: deflated bytes + block table.
+ * hgx_extract_file (process:1468-1488, the aligner's stdout as a file): SAM text in 64 MB blocks through hgx_extract_feed, a BAM
+ * of any size in 64 MB blocks of deflated bytes through hgx_extract_feed_bam (test switch extract_bam_piece=N: another block
+ * size); any other gzip file (a bgzipped SAM text) in one piece through the alignment reader, at most 1 GB of lines.
  * hgx_extract_take (write_read, process:1309-1322): the FASTQ / FASTA text of one family and mate (0 / 1) ready since the last
  * take; the pointer holds until the next take of the same family and mate, or the close.
  * hgx_extract_stats: records and groups read, pairs written per family, route (2 = every chunk on the device, 0 = a chunk on the
@@ -745,6 +758,7 @@ typedef struct hgx_extract hgx_extract;
 int hgx_extract_open(hgx_extract **out, int32_t n_regions, const int32_t *family, const char *chrom_pool, size_t chrom_bytes,
                      const int64_t *left, const int64_t *right, int32_t n_families, const hgx_extract_opts *opts);
 int hgx_extract_feed(hgx_extract *h, const char *bytes, size_t n_bytes, int32_t last, void *stream);
+int hgx_extract_feed_bam(hgx_extract *h, const void *bgzf, size_t n_bytes, int32_t last, void *stream);
 int hgx_extract_file(hgx_extract *h, const char *path, void *stream);
 int hgx_extract_take(hgx_extract *h, int32_t family, int32_t mate, const char **text, size_t *n_bytes);
 int hgx_extract_stats(const hgx_extract *h, int64_t *records, int64_t *groups, int64_t *written /* [n_families] */, int32_t *route,
