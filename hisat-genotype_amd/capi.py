@@ -79,6 +79,8 @@ SYMBOLS = [
     "hgx_linear_locus_create", "hgx_linear_locus_destroy", "hgx_linear_type_sam", "hgx_linear_type_file", "hgx_linear_dims",
     "hgx_linear_counts", "hgx_linear_classes", "hgx_linear_extra_names", "hgx_linear_destroy",
     "hgx_linear_input_open", "hgx_linear_input_dims", "hgx_linear_type_input", "hgx_linear_input_close",
+    "hgx_alignment_set_open", "hgx_alignment_set_dims", "hgx_alignment_set_info", "hgx_alignment_set_route", "hgx_alignment_set_routed",
+    "hgx_alignment_set_close", "hgx_many_create_set",
     "hgx_extract_open", "hgx_extract_feed", "hgx_extract_feed_bam", "hgx_extract_file", "hgx_extract_take", "hgx_extract_stats", "hgx_extract_close",
 ]
 

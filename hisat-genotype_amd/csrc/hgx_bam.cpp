@@ -1191,6 +1191,7 @@ int hgx_bgzf_tasks_read(std::vector<hgx_bgzf_task> &tasks, const char *const *pa
                     else if (!r.name.empty() && refs[i].size() == r.name.size() && memcmp(refs[i].data(), r.name.data(), r.name.size()) == 0) d.ref_action[i] = 2;
                 }
             }
+            T.refs = std::move(refs);
             T.ok = true;
             if (on_task) on_task((int)t);
         } catch (const std::exception &) {

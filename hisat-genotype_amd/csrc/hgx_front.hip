@@ -1292,15 +1292,17 @@ LineRef *line_refs(const char *raw, const hgx_line *lines, size_t n_lines, bool 
     return dst;
 }
 
-// the line table of unwalked BAM streams (resident at d_text: one per task, at `bases`), made on the device: (offset, length, task) of
-// the records the tasks' regions keep, task after task, in QNAME order inside a task (stable: file order among equal names) -- what
-// hgx_bam.cpp's walk + filter + sort_lines give per file
-int bam_lines_dev(const char *d_text, const std::vector<const hgx_bam_deferred *> &defs, const std::vector<size_t> &bases, const std::vector<size_t> &sizes,
-                  hipStream_t st, DevBuf &b_lines, uint32_t *n_lines, int *declined) {
+// The record table of unwalked BAM streams (resident at d_text: one per task, at `bases`): the chains walked in ranges, linked, and
+// (offset, length, task) of every record written in (task, file order).  The first half of bam_lines_dev, and what an
+// hgx_alignment_set keeps beside its inflated streams.
+struct BamTable {
+    DevBuf b_seg, b_act, b_ctl, b_off, b_len, b_task;
+    int n_seg = 0;
+    uint32_t n_rec = 0;
+};
+int bam_table_dev(const unsigned char *text, const std::vector<const hgx_bam_deferred *> &defs, const std::vector<size_t> &bases, const std::vector<size_t> &sizes,
+                  hipStream_t st, BamTable &T, int *declined, Lap &lap) {
     *declined = 0;
-    *n_lines = 0;
-    Lap lap(st);
-    const unsigned char *text = (const unsigned char *)d_text;
     const int n_seg = (int)defs.size();
     if (n_seg < 1 || n_seg > 65535) { *declined = HGX_FE_DECLINE_SIZE; return HGX_OK; }
     std::vector<BamSeg> segs((size_t)n_seg);
@@ -1330,19 +1332,19 @@ int bam_lines_dev(const char *d_text, const std::vector<const hgx_bam_deferred *
         w_at += G.n_ranges;
     }
     const int W = (int)w_at;
-    DevBuf b_seg, b_rng, b_base, b_cnt, b_tmpw, b_ctl, b_act, b_off, b_len, b_task, b_keep, b_pos, b_idx, b_idx2, b_key, b_key2, b_tmp;
+    DevBuf b_rng, b_base, b_cnt, b_tmpw;
     struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{st};
-    ALLOC(b_seg, (size_t)n_seg * sizeof(BamSeg));
+    ALLOC(T.b_seg, (size_t)n_seg * sizeof(BamSeg));
     ALLOC(b_rng, (size_t)W * sizeof(BamRange));
     ALLOC(b_base, (size_t)W * 4);
     ALLOC(b_cnt, (size_t)W * 4);
-    ALLOC(b_ctl, sizeof(BamCtl));
-    ALLOC(b_act, std::max<size_t>(acts.size(), 16));
-    HIPCHK(hipMemsetAsync(b_ctl.p, 0, sizeof(BamCtl), st));
-    HIPCHK(hipMemcpyAsync(b_seg.p, segs.data(), (size_t)n_seg * sizeof(BamSeg), hipMemcpyHostToDevice, st));
-    if (!acts.empty()) HIPCHK(hipMemcpyAsync(b_act.p, acts.data(), acts.size(), hipMemcpyHostToDevice, st));
-    BamCtl *ctl = b_ctl.as<BamCtl>();
-    const BamSeg *d_seg = b_seg.as<BamSeg>();
+    ALLOC(T.b_ctl, sizeof(BamCtl));
+    ALLOC(T.b_act, std::max<size_t>(acts.size(), 16));
+    HIPCHK(hipMemsetAsync(T.b_ctl.p, 0, sizeof(BamCtl), st));
+    HIPCHK(hipMemcpyAsync(T.b_seg.p, segs.data(), (size_t)n_seg * sizeof(BamSeg), hipMemcpyHostToDevice, st));
+    if (!acts.empty()) HIPCHK(hipMemcpyAsync(T.b_act.p, acts.data(), acts.size(), hipMemcpyHostToDevice, st));
+    BamCtl *ctl = T.b_ctl.as<BamCtl>();
+    const BamSeg *d_seg = T.b_seg.as<BamSeg>();
     k_bam_walk<0><<<nblk(W, 64), 64, 0, st>>>(text, d_seg, n_seg, W, b_rng.as<BamRange>(), nullptr, nullptr, nullptr, nullptr);
     k_bam_link<<<nblk(W, 256), 256, 0, st>>>(b_rng.as<BamRange>(), d_seg, n_seg, W, b_cnt.as<uint32_t>(), ctl);
     {
@@ -1362,19 +1364,99 @@ int bam_lines_dev(const char *d_text, const std::vector<const hgx_bam_deferred *
     if (h.decline) { *declined = h.decline; return HGX_OK; }
     const uint32_t n_rec = h.tot[0];
     if (n_rec >= (1u << 30)) { *declined = HGX_FE_DECLINE_SIZE; return HGX_OK; }
+    T.n_seg = n_seg;
+    T.n_rec = n_rec;
+    if (n_rec == 0) return HGX_OK;
+    ALLOC(T.b_off, (size_t)n_rec * 4); ALLOC(T.b_len, (size_t)n_rec * 4); ALLOC(T.b_task, (size_t)n_rec * 2 + 16);
+    k_bam_walk<1><<<nblk(W, 64), 64, 0, st>>>(text, d_seg, n_seg, W, b_rng.as<BamRange>(), b_base.as<uint32_t>(), T.b_off.as<uint32_t>(), T.b_len.as<uint32_t>(),
+                                             T.b_task.as<uint16_t>());
+    HIPCHK(hipGetLastError());
+    return HGX_OK;
+}
+
+// ... and its second half, on an index list: the n_kept records `idx` names (task after task, file order inside a task) brought into
+// QNAME order inside every task (stable: file order among equal names) and written as the line table.  `idx` is only read (an
+// hgx_alignment_set's lists serve many calls); `ctl` is a zeroed control block of the caller's.
+int bam_lines_of(const unsigned char *text, const uint32_t *rec_off, const uint32_t *rec_len, const uint16_t *rec_task, int n_seg, const uint32_t *idx,
+                 uint32_t n_kept, uint32_t max_klen, BamCtl *ctl, hipStream_t st, DevBuf &b_lines, Lap &lap) {
+    DevBuf b_idx_a, b_idx_b, b_key, b_key2, b_tmp;
+    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{st};     // (the last kernels read this function's buffers)
+    if (n_kept > 1) {
+        // an aligner writes its records grouped by read already: a stable sort would not move anything
+        DevBuf b_diff;
+        ALLOC(b_diff, sizeof(NameDiff));
+        HIPCHK(hipMemsetAsync(b_diff.p, 0, sizeof(NameDiff), st));
+        // names of one 8-byte chunk are sorted as they are (one sort either way); longer ones on their varying bits
+        const int n_chunks = (int)(max_klen + 7) / 8;
+        const bool packed = n_chunks >= 2 && n_chunks <= NAME_DIFF_CHUNKS && !hgx_switch_has("front", "name_chunks");
+        k_bam_sorted<<<nblk(n_kept, 256), 256, 0, st>>>(text, rec_off, rec_task, idx, n_kept, ctl, packed ? b_diff.as<unsigned long long>() : (unsigned long long *)nullptr);
+        NameDiff nd;
+        BamCtl h;
+        { const int rc_d = hgx_d2h(&h, ctl, sizeof(BamCtl), st); if (rc_d) { (void)hgx_sync(st); return rc_d; } }
+        { const int rc_d = hgx_d2h(&nd, b_diff.p, sizeof(NameDiff), st); if (rc_d) { (void)hgx_sync(st); return rc_d; } }
+        { const int rc_s = hgx_sync(st); if (rc_s) return rc_s; }
+        if (h.unsorted) {
+            size_t tmp_bytes = 0;
+            (void)hipcub::DeviceRadixSort::SortPairs((void *)nullptr, tmp_bytes, (unsigned long long *)nullptr, (unsigned long long *)nullptr, (uint32_t *)nullptr,
+                                                     (uint32_t *)nullptr, (int)n_kept, 0, 64, st);
+            ALLOC(b_tmp, std::max<size_t>(tmp_bytes, 256));
+            ALLOC(b_idx_a, (size_t)n_kept * 4); ALLOC(b_idx_b, (size_t)n_kept * 4); ALLOC(b_key, (size_t)n_kept * 8); ALLOC(b_key2, (size_t)n_kept * 8);
+            unsigned long long *key = b_key.as<unsigned long long>(), *key_alt = b_key2.as<unsigned long long>();
+            uint32_t *nxt = b_idx_a.as<uint32_t>();
+            auto took = [&]() { idx = nxt; nxt = nxt == b_idx_a.as<uint32_t>() ? b_idx_b.as<uint32_t>() : b_idx_a.as<uint32_t>(); };
+            int n_bits = 0;
+            for (int c = 0; c < std::min(n_chunks, NAME_DIFF_CHUNKS); ++c) n_bits += __builtin_popcountll(nd.m[c]);
+            if (packed) {
+                // the varying bits alone, 64 to a word, least significant word first; every pass stable
+                for (int word = 0; word < (n_bits + 63) / 64; ++word) {
+                    k_bam_name_key_packed<<<nblk(n_kept, 256), 256, 0, st>>>(text, rec_off, idx, n_kept, nd, n_chunks, n_bits, word, key);
+                    size_t b = tmp_bytes;
+                    HIPCHK(hipcub::DeviceRadixSort::SortPairs(b_tmp.p, b, key, key_alt, idx, nxt, (int)n_kept, 0, std::min(64, n_bits - 64 * word), st));
+                    took();
+                }
+            } else
+            for (int chunk = n_chunks - 1; chunk >= 0; --chunk) {      // (names beyond 256 bytes; test switch front=name_chunks) eight bytes at a time, least significant first
+                k_bam_name_key<<<nblk(n_kept, 256), 256, 0, st>>>(text, rec_off, idx, n_kept, (uint32_t)chunk, key);
+                size_t b = tmp_bytes;
+                HIPCHK(hipcub::DeviceRadixSort::SortPairs(b_tmp.p, b, key, key_alt, idx, nxt, (int)n_kept, 0, 64, st));
+                took();
+            }
+            if (n_seg > 1) {                                                           // ... and the tasks apart again, names in order inside
+                k_bam_task_key<<<nblk(n_kept, 256), 256, 0, st>>>(rec_task, idx, n_kept, key);
+                size_t b = tmp_bytes;
+                HIPCHK(hipcub::DeviceRadixSort::SortPairs(b_tmp.p, b, key, key_alt, idx, nxt, (int)n_kept, 0, 16, st));
+                took();
+            }
+        }
+        lap(h.unsorted ? "BAM name sort" : "BAM name order check");
+    }
+    if (n_kept) k_bam_lines<<<nblk(n_kept, 256), 256, 0, st>>>(rec_off, rec_len, rec_task, idx, n_kept, b_lines.as<LineRef>());
+    HIPCHK(hipGetLastError());
+    return HGX_OK;
+}
+
+// the line table of unwalked BAM streams, made on the device: (offset, length, task) of the records the tasks' regions keep, task
+// after task, in QNAME order inside a task (stable: file order among equal names) -- what hgx_bam.cpp's walk + filter + sort_lines
+// give per file
+int bam_lines_dev(const char *d_text, const std::vector<const hgx_bam_deferred *> &defs, const std::vector<size_t> &bases, const std::vector<size_t> &sizes,
+                  hipStream_t st, DevBuf &b_lines, uint32_t *n_lines, int *declined) {
+    *declined = 0;
+    *n_lines = 0;
+    Lap lap(st);
+    const unsigned char *text = (const unsigned char *)d_text;
+    BamTable T;
+    DevBuf b_keep, b_pos, b_idx, b_tmp;
+    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{st};
+    { const int rc_t = bam_table_dev(text, defs, bases, sizes, st, T, declined, lap); if (rc_t || *declined) return rc_t; }
+    const uint32_t n_rec = T.n_rec;
+    const int n_seg = T.n_seg;
+    BamCtl *ctl = T.b_ctl.as<BamCtl>();
     ALLOC(b_lines, std::max<size_t>(n_rec, 1) * sizeof(LineRef));
     if (n_rec == 0) return HGX_OK;
-    ALLOC(b_off, (size_t)n_rec * 4); ALLOC(b_len, (size_t)n_rec * 4); ALLOC(b_task, (size_t)n_rec * 2 + 16); ALLOC(b_keep, (size_t)n_rec * 4); ALLOC(b_pos, (size_t)n_rec * 4);
-    ALLOC(b_idx, (size_t)n_rec * 4); ALLOC(b_idx2, (size_t)n_rec * 4); ALLOC(b_key, (size_t)n_rec * 8); ALLOC(b_key2, (size_t)n_rec * 8);
-    size_t tb2 = 0;
-    (void)hipcub::DeviceRadixSort::SortPairs((void *)nullptr, tb2, (unsigned long long *)nullptr, (unsigned long long *)nullptr, (uint32_t *)nullptr,
-                                             (uint32_t *)nullptr, (int)n_rec, 0, 64, st);
-    const size_t tmp_bytes = std::max(tb2, fe_scan_scratch_bytes(n_rec));
-    ALLOC(b_tmp, std::max<size_t>(tmp_bytes, 256));
-    k_bam_walk<1><<<nblk(W, 64), 64, 0, st>>>(text, d_seg, n_seg, W, b_rng.as<BamRange>(), b_base.as<uint32_t>(), b_off.as<uint32_t>(), b_len.as<uint32_t>(),
-                                             b_task.as<uint16_t>());
-    k_bam_filter<<<nblk(n_rec, 256), 256, 0, st>>>(text, b_off.as<uint32_t>(), b_len.as<uint32_t>(), b_task.as<uint16_t>(), n_rec, d_seg, b_act.as<uint8_t>(),
-                                                   b_keep.as<uint32_t>(), ctl);
+    ALLOC(b_keep, (size_t)n_rec * 4); ALLOC(b_pos, (size_t)n_rec * 4); ALLOC(b_idx, (size_t)n_rec * 4);
+    ALLOC(b_tmp, std::max<size_t>(fe_scan_scratch_bytes(n_rec), 256));
+    k_bam_filter<<<nblk(n_rec, 256), 256, 0, st>>>(text, T.b_off.as<uint32_t>(), T.b_len.as<uint32_t>(), T.b_task.as<uint16_t>(), n_rec, T.b_seg.as<BamSeg>(),
+                                                   T.b_act.as<uint8_t>(), b_keep.as<uint32_t>(), ctl);
     {
         HIPCHK(hipMemsetAsync(b_tmp.p, 0, fe_scan_scratch_bytes(n_rec), st));
         FeScanArgs sa{};
@@ -1384,56 +1466,15 @@ int bam_lines_dev(const char *d_text, const std::vector<const hgx_bam_deferred *
         if (rcs) return rcs;
     }
     k_bam_compact<<<nblk(n_rec, 256), 256, 0, st>>>(b_keep.as<uint32_t>(), b_pos.as<uint32_t>(), n_rec, b_idx.as<uint32_t>(), ctl);
+    BamCtl h;
     { const int rc_d = hgx_d2h(&h, ctl, sizeof(BamCtl), st); if (rc_d) { (void)hgx_sync(st); return rc_d; } }
     { const int rc_s = hgx_sync(st); if (rc_s) return rc_s; }
     lap("BAM records + region filter");
     if (h.decline) { *declined = h.decline; return HGX_OK; }
     const uint32_t n_kept = h.n_kept;
-    uint32_t *idx = b_idx.as<uint32_t>(), *idx_alt = b_idx2.as<uint32_t>();
-    if (n_kept > 1) {
-        // an aligner writes its records grouped by read already: a stable sort would not move anything
-        DevBuf b_diff;
-        ALLOC(b_diff, sizeof(NameDiff));
-        HIPCHK(hipMemsetAsync(b_diff.p, 0, sizeof(NameDiff), st));
-        // names of one 8-byte chunk are sorted as they are (one sort either way); longer ones on their varying bits
-        const int n_chunks = (int)(h.max_klen + 7) / 8;
-        const bool packed = n_chunks >= 2 && n_chunks <= NAME_DIFF_CHUNKS && !hgx_switch_has("front", "name_chunks");
-        k_bam_sorted<<<nblk(n_kept, 256), 256, 0, st>>>(text, b_off.as<uint32_t>(), b_task.as<uint16_t>(), idx, n_kept, ctl,
-                                                        packed ? b_diff.as<unsigned long long>() : (unsigned long long *)nullptr);
-        NameDiff nd;
-        { const int rc_d = hgx_d2h(&h, ctl, sizeof(BamCtl), st); if (rc_d) { (void)hgx_sync(st); return rc_d; } }
-        { const int rc_d = hgx_d2h(&nd, b_diff.p, sizeof(NameDiff), st); if (rc_d) { (void)hgx_sync(st); return rc_d; } }
-        { const int rc_s = hgx_sync(st); if (rc_s) return rc_s; }
-        if (h.unsorted) {
-            unsigned long long *key = b_key.as<unsigned long long>(), *key_alt = b_key2.as<unsigned long long>();
-            int n_bits = 0;
-            for (int c = 0; c < std::min(n_chunks, NAME_DIFF_CHUNKS); ++c) n_bits += __builtin_popcountll(nd.m[c]);
-            if (packed) {
-                // the varying bits alone, 64 to a word, least significant word first; every pass stable
-                for (int word = 0; word < (n_bits + 63) / 64; ++word) {
-                    k_bam_name_key_packed<<<nblk(n_kept, 256), 256, 0, st>>>(text, b_off.as<uint32_t>(), idx, n_kept, nd, n_chunks, n_bits, word, key);
-                    size_t b = tmp_bytes;
-                    HIPCHK(hipcub::DeviceRadixSort::SortPairs(b_tmp.p, b, key, key_alt, idx, idx_alt, (int)n_kept, 0, std::min(64, n_bits - 64 * word), st));
-                    std::swap(idx, idx_alt);
-                }
-            } else
-            for (int chunk = n_chunks - 1; chunk >= 0; --chunk) {      // (names beyond 256 bytes; test switch front=name_chunks) eight bytes at a time, least significant first
-                k_bam_name_key<<<nblk(n_kept, 256), 256, 0, st>>>(text, b_off.as<uint32_t>(), idx, n_kept, (uint32_t)chunk, key);
-                size_t b = tmp_bytes;
-                HIPCHK(hipcub::DeviceRadixSort::SortPairs(b_tmp.p, b, key, key_alt, idx, idx_alt, (int)n_kept, 0, 64, st));
-                std::swap(idx, idx_alt);
-            }
-            if (n_seg > 1) {                                                           // ... and the tasks apart again, names in order inside
-                k_bam_task_key<<<nblk(n_kept, 256), 256, 0, st>>>(b_task.as<uint16_t>(), idx, n_kept, key);
-                size_t b = tmp_bytes;
-                HIPCHK(hipcub::DeviceRadixSort::SortPairs(b_tmp.p, b, key, key_alt, idx, idx_alt, (int)n_kept, 0, 16, st));
-                std::swap(idx, idx_alt);
-            }
-        }
-        lap(h.unsorted ? "BAM name sort" : "BAM name order check");
-    }
-    if (n_kept) k_bam_lines<<<nblk(n_kept, 256), 256, 0, st>>>(b_off.as<uint32_t>(), b_len.as<uint32_t>(), b_task.as<uint16_t>(), idx, n_kept, b_lines.as<LineRef>());
-    HIPCHK(hipGetLastError());
+    const int rc_l = bam_lines_of(text, T.b_off.as<uint32_t>(), T.b_len.as<uint32_t>(), T.b_task.as<uint16_t>(), n_seg, b_idx.as<uint32_t>(), n_kept, h.max_klen, ctl, st,
+                                  b_lines, lap);
+    if (rc_l) return rc_l;
     *n_lines = n_kept;
     return HGX_OK;
 }
@@ -2356,6 +2397,400 @@ extern "C" int hgx_alignment_parse_dev(hgx_dbatch **out, hgx_alignment *al, cons
         hgx_dbatch_destroy(made);
     }
     return hgx_parse_alignment_file_dev(out, loc, al->path.c_str(), regions, opts, stream);
+}
+
+// ---- many alignment files, many loci: the panel's rectangle (hisatgenotype:613-665 pools genotyping_locus over the samples; inside
+// each, typing() loops locus_list over that sample's ONE alignment file, typing_core.py:370, 436-468) ---------------------------------
+// An hgx_alignment_set is the samples' BAM files read ONCE: deflated bytes up as they are read, one inflate launch for all files'
+// blocks, one walk of all record chains; the inflated streams and the record table (offset, length, file) stay in HBM.
+// hgx_alignment_set_route sends every record to the loci that keep it in ONE pass (k_set_route: the record's refID, POS, FLAG and
+// CIGAR span read once, a 64-bit slot mask written) and partitions the record indices by slot (k_set_scatter), stable: per slot
+// the kept records in (file, file order) -- what k_bam_filter + k_bam_compact give that locus alone.  hgx_front_set_dev is a slot's
+// rest: name order (bam_lines_of), line table, records_run with one task per file.
+namespace {
+constexpr int SET_TILE = 1024;            // records per workgroup of the routing / partition kernels (one lane per record)
+constexpr int SET_MAX_LOCI = 64;          // bits of the slot mask
+struct SetFL { long long left0, right0; uint32_t act_off; int32_t n_ref; uint32_t filtered, pad; };      // per (file, locus): the region as that file's header resolves it
+struct SetCtl { int32_t decline; uint32_t total; uint32_t max_klen[SET_MAX_LOCI]; };
+
+// per-slot counts of one wavefront's masks: lane l leaves with slot l's count (ballot + popcount: no atomics)
+__device__ __forceinline__ uint32_t set_wave_counts(unsigned long long m, int n_loci, int lane) {
+    uint32_t mine = 0;
+    for (int l = 0; l < n_loci; ++l) {
+        const unsigned long long b = __ballot((int)((m >> l) & 1ull));
+        if (lane == l) mine = (uint32_t)__builtin_popcountll(b);
+    }
+    return mine;
+}
+__global__ void __launch_bounds__(SET_TILE) k_set_route(const unsigned char *__restrict__ text, const uint32_t *__restrict__ rec_off, const uint32_t *__restrict__ rec_len,
+                                                        const uint16_t *__restrict__ rec_task, uint32_t n_rec, const SetFL *__restrict__ fl,
+                                                        const uint8_t *__restrict__ act, int n_loci, uint32_t n_tiles, unsigned long long *__restrict__ mask,
+                                                        uint32_t *__restrict__ cnt /* [n_loci][n_tiles] */, SetCtl *ctl) {
+    __shared__ uint32_t s_cnt[SET_TILE / 64][64];
+    __shared__ uint32_t s_klen[SET_MAX_LOCI];
+    const uint32_t i = blockIdx.x * SET_TILE + threadIdx.x;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (threadIdx.x < SET_MAX_LOCI) s_klen[threadIdx.x] = 0u;
+    __syncthreads();
+    unsigned long long m = 0;
+    uint32_t klen = 0;
+    if (i < n_rec) {
+        const unsigned char *r = text + rec_off[i];
+        const uint32_t bs = rec_len[i], l_rn = r[8];
+        // the record's place on its reference, read once (k_bam_filter's arithmetic)
+        const int32_t rid = bam_i32(r), pos = bam_i32(r + 4);
+        const uint32_t n_cig = bam_u16(r + 12), flag = bam_u16(r + 14);
+        long long reflen = 0;
+        if (!(flag & 4) && 32 + (size_t)l_rn + 4 * (size_t)n_cig <= bs) {
+            const unsigned char *c = r + 32 + l_rn;
+            for (uint32_t x = 0; x < n_cig; ++x) {
+                const uint32_t v = bam_u32(c + 4 * x), op = v & 15;
+                if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) reflen += v >> 4;
+            }
+        }
+        const long long end0 = (long long)pos + (reflen > 0 ? reflen : 1) - 1;
+        const SetFL *F = fl + (size_t)rec_task[i] * (size_t)n_loci;
+        for (int l = 0; l < n_loci; ++l) {
+            const SetFL G = F[l];
+            uint32_t k = 1;
+            if (G.filtered) {
+                if (rid < 0 || rid >= G.n_ref) k = 0;
+                else {
+                    const uint8_t a = act[G.act_off + (uint32_t)rid];
+                    k = a == 1 ? 1u : (a == 2 ? ((end0 >= G.left0 && (long long)pos <= G.right0) ? 1u : 0u) : 0u);
+                }
+            }
+            m |= (unsigned long long)k << l;
+        }
+        if (m && (l_rn == 0 || 32 + (size_t)l_rn > bs || r[32 + l_rn - 1] != 0)) { atomicCAS(&ctl->decline, 0, HGX_FE_DECLINE_RECORD); m = 0; }   // "malformed BAM record": the host's to report
+        klen = l_rn - 1;
+        mask[i] = m;
+    }
+    for (int l = 0; l < n_loci; ++l)
+        if ((m >> l) & 1ull) atomicMax(&s_klen[l], klen);
+    s_cnt[wv][lane] = set_wave_counts(m, n_loci, lane);
+    __syncthreads();
+    if ((int)threadIdx.x < n_loci) {
+        uint32_t sum = 0;
+        for (int w = 0; w < SET_TILE / 64; ++w) sum += s_cnt[w][threadIdx.x];
+        cnt[(size_t)threadIdx.x * n_tiles + blockIdx.x] = sum;                                  // slot-major: one scan gives every slot's list its place
+        if (s_klen[threadIdx.x]) atomicMax(&ctl->max_klen[threadIdx.x], s_klen[threadIdx.x]);   // (a maximum: the same whatever the order)
+    }
+}
+// the stable multi-way partition: a record's place in slot l's list = the list's start + the slot's records in the tiles before
+// (the scan) + in this tile's wavefronts before + in the lanes before (ballot, prefix popcount)
+__global__ void __launch_bounds__(SET_TILE) k_set_scatter(const unsigned long long *__restrict__ mask, uint32_t n_rec, int n_loci, uint32_t n_tiles,
+                                                          const uint32_t *__restrict__ base /* [n_loci][n_tiles] */, uint32_t *__restrict__ idx) {
+    __shared__ uint32_t s_cnt[SET_TILE / 64][64];
+    __shared__ uint32_t s_base[SET_TILE / 64][64];
+    const uint32_t i = blockIdx.x * SET_TILE + threadIdx.x;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const unsigned long long m = i < n_rec ? mask[i] : 0ull;
+    s_cnt[wv][lane] = set_wave_counts(m, n_loci, lane);
+    __syncthreads();
+    {
+        uint32_t before = 0;
+        for (int w = 0; w < wv; ++w) before += s_cnt[w][lane];
+        s_base[wv][lane] = before;
+    }
+    __syncthreads();
+    const unsigned long long lanes_before = (1ull << lane) - 1ull;
+    for (int l = 0; l < n_loci; ++l) {
+        const bool mine = (m >> l) & 1ull;
+        const unsigned long long b = __ballot((int)mine);
+        if (mine) idx[base[(size_t)l * n_tiles + blockIdx.x] + s_base[wv][l] + (uint32_t)__builtin_popcountll(b & lanes_before)] = i;
+    }
+}
+__device__ __forceinline__ uint32_t set_lower_u16(const uint16_t *a, uint32_t n, uint32_t v) {
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) { const uint32_t mid = lo + (hi - lo) / 2; if ((uint32_t)a[mid] < v) lo = mid + 1; else hi = mid; }
+    return lo;
+}
+__device__ __forceinline__ uint32_t set_lower_u32(const uint32_t *a, uint32_t n, uint32_t v) {
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) { const uint32_t mid = lo + (hi - lo) / 2; if (a[mid] < v) lo = mid + 1; else hi = mid; }
+    return lo;
+}
+// kept[l][f]: the records of file f in slot l's list (the records are in file order, the lists ascending: four binary searches)
+__global__ void k_set_kept(const uint16_t *__restrict__ rec_task, uint32_t n_rec, const uint32_t *__restrict__ idx, const uint32_t *__restrict__ base, uint32_t n_tiles,
+                           int n_loci, int n_files, uint32_t total, uint32_t *__restrict__ kept) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (uint32_t)n_loci * (uint32_t)n_files) return;
+    const uint32_t l = t / (uint32_t)n_files, f = t % (uint32_t)n_files;
+    const uint32_t s0 = base[(size_t)l * n_tiles], s1 = (int)l + 1 < n_loci ? base[(size_t)(l + 1) * n_tiles] : total;
+    const uint32_t r0 = set_lower_u16(rec_task, n_rec, f), r1 = set_lower_u16(rec_task, n_rec, f + 1);
+    kept[t] = set_lower_u32(idx + s0, s1 - s0, r1) - set_lower_u32(idx + s0, s1 - s0, r0);
+}
+}   // namespace
+
+struct hgx_alignment_set {
+    std::vector<std::string> paths;
+    int dev = 0;
+    bool resident = false;
+    int n_files = 0;
+    DevBuf text;                                  // every file's inflated stream, each at a 64-byte aligned base
+    size_t ptotal = 0;
+    std::vector<size_t> body0;
+    std::vector<std::vector<std::string>> refs;   // per file: its header's reference names, in its own order
+    BamTable table;                               // (offset, length, file) of every record, in (file, file order)
+    long long bytes_up = 0, block_table_bytes = 0;
+    // after route
+    bool routed = false;
+    int n_loci = 0;
+    std::vector<std::string> regions;
+    std::vector<uint8_t> slot_host;               // a region list the kernels do not take (several entries): that slot goes per path
+    DevBuf idx;                                   // the slots' index lists, slot after slot
+    std::vector<uint32_t> slot_start, max_klen;   // [n_loci + 1], [n_loci]
+    std::vector<int64_t> kept;                    // [n_loci][n_files]
+    void drop_device() {
+        for (DevBuf *b : {&text, &table.b_seg, &table.b_act, &table.b_ctl, &table.b_off, &table.b_len, &table.b_task, &idx})
+            if (b->p) { hgx_pool_free(b->p); b->p = nullptr; }
+        table.n_rec = 0;
+    }
+};
+
+extern "C" int hgx_alignment_set_open(hgx_alignment_set **out, const char *const *paths, int32_t n_files, int32_t n_threads, void *stream) {
+    ARGCHK(out && n_files >= 0 && (n_files == 0 || paths));
+    for (int t = 0; t < n_files; ++t) ARGCHK(paths[t]);
+    *out = nullptr;
+    hipStream_t st = (hipStream_t)stream;
+    std::unique_ptr<hgx_alignment_set> S(new hgx_alignment_set());
+    S->n_files = n_files;
+    for (int t = 0; t < n_files; ++t) S->paths.push_back(paths[t]);
+    HIPCHK(hipGetDevice(&S->dev));
+    // (anything that keeps the set off the device leaves it to the per-path calls, which word the errors: *out is a set that is not resident)
+    if (n_files < 1 || n_files > 65535 || hgx_switch_has("front", "host") || hgx_switch_has("front", "host_inflate")) { *out = S.release(); return HGX_OK; }
+    std::vector<size_t> cbase((size_t)n_files + 1, 0), csize((size_t)n_files, 0);
+    for (int t = 0; t < n_files; ++t) {
+        struct stat sb;
+        if (stat(paths[t], &sb) != 0) { *out = S.release(); return HGX_OK; }
+        csize[t] = (size_t)sb.st_size;
+        cbase[(size_t)t + 1] = (cbase[t] + csize[t] + 63) & ~(size_t)63;
+    }
+    const size_t ctotal = cbase[(size_t)n_files];
+    // below the device front end's size gate (FE_MIN_DEFER_BYTES of stream; BGZF deflates ~1 : 4) the files are not even read here
+    if (ctotal >= (1ull << 32) - 4096 || (!hgx_switch_has("front", "device") && ctotal < FE_MIN_DEFER_BYTES / 16)) { *out = S.release(); return HGX_OK; }
+    Lap lap(st);
+    DevBuf b_comp;
+    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{st};
+    ALLOC(b_comp, ctotal + 4096);
+    const hgx_front_alloc mem{pinned_alloc, pinned_release};
+    std::vector<hgx_bgzf_task> bt;
+    std::atomic<bool> up_bad{false};
+    const int dev = S->dev;
+    auto on_bt = [&](int t) {
+        if (bt[t].n != csize[t] || hipSetDevice(dev) != hipSuccess ||
+            hipMemcpyAsync((char *)b_comp.p + cbase[t], bt[t].data, bt[t].n, hipMemcpyHostToDevice, st) != hipSuccess) up_bad = true;
+    };
+    struct FreeTasks { std::vector<hgx_bgzf_task> &v; hipStream_t s; ~FreeTasks() { (void)hipStreamSynchronize(s); for (auto &x : v) hgx_host_free(x.data); } } free_tasks{bt, st};
+    int rc = hgx_bgzf_tasks_read(bt, paths, nullptr, n_files, n_threads, &mem, on_bt);
+    if (rc) return rc;
+    lap("set: read (deflated; uploads issued)");
+    bool all_ok = !up_bad.load();
+    for (int t = 0; t < n_files && all_ok; ++t) all_ok = bt[t].ok;
+    if (!all_ok) { *out = S.release(); return HGX_OK; }                     // SAM text, a broken container, a header not understood
+    std::vector<size_t> pbase((size_t)n_files + 1, 0), psize((size_t)n_files, 0);
+    size_t n_blocks = 0;
+    for (int t = 0; t < n_files; ++t) {
+        psize[t] = bt[t].total;
+        pbase[(size_t)t + 1] = (pbase[t] + bt[t].total + 63) & ~(size_t)63;
+        n_blocks += bt[t].blocks.size();
+    }
+    const size_t ptotal = pbase[(size_t)n_files];
+    if (ptotal >= (1ull << 32) - 64 || (!hgx_switch_has("front", "device") && ptotal < FE_MIN_DEFER_BYTES)) { *out = S.release(); return HGX_OK; }
+    try {
+        std::vector<hgx_bgzf_block> all;
+        all.reserve(n_blocks);
+        for (int t = 0; t < n_files; ++t)
+            for (hgx_bgzf_block b : bt[t].blocks) { b.in_off += cbase[t]; b.out_off += pbase[t]; all.push_back(b); }
+        ALLOC(S->text, ptotal + 64);
+        HIPCHK(hipMemsetAsync((char *)b_comp.p + ctotal, 0, 4096, st));
+        int bad = 0;
+        rc = hgx_bgzf_inflate_dev(b_comp.as<unsigned char>(), all.data(), all.size(), S->text.as<unsigned char>(), st, &bad, nullptr);
+        if (rc) return rc;
+        lap("set: BGZF inflate (device)");
+        if (bad) { S->drop_device(); *out = S.release(); return HGX_OK; }
+        std::vector<const hgx_bam_deferred *> defs((size_t)n_files);
+        for (int t = 0; t < n_files; ++t) defs[t] = &bt[t].def;
+        pbase.resize((size_t)n_files);
+        int dec = 0;
+        rc = bam_table_dev(S->text.as<unsigned char>(), defs, pbase, psize, st, S->table, &dec, lap);
+        if (rc) return rc;
+        HIPCHK(hipStreamSynchronize(st));
+        if (dec) { S->drop_device(); *out = S.release(); return HGX_OK; }
+        for (int t = 0; t < n_files; ++t) {
+            S->bytes_up += (long long)bt[t].n;
+            S->body0.push_back(bt[t].def.body0);
+            S->refs.push_back(std::move(bt[t].refs));
+        }
+        S->block_table_bytes = (long long)(n_blocks * sizeof(hgx_bgzf_block));
+        S->bytes_up += S->block_table_bytes;
+        S->ptotal = ptotal;
+        S->resident = true;
+    } catch (const std::exception &e) {
+        hgx_set_error("hgx_alignment_set_open: %s", e.what());
+        return HGX_ENOMEM;
+    }
+    *out = S.release();
+    return HGX_OK;
+}
+
+extern "C" int hgx_alignment_set_close(hgx_alignment_set *s) { delete s; return HGX_OK; }
+
+extern "C" int hgx_alignment_set_dims(const hgx_alignment_set *s, int32_t *n_files, int32_t *resident, size_t *stream_bytes, long long *bytes_to_device,
+                                      int64_t *n_records) {
+    ARGCHK(s);
+    if (n_files) *n_files = s->n_files;
+    if (resident) *resident = s->resident ? 1 : 0;
+    if (stream_bytes) *stream_bytes = s->ptotal;
+    if (bytes_to_device) *bytes_to_device = s->bytes_up;
+    if (n_records) *n_records = s->resident ? (int64_t)s->table.n_rec : 0;
+    return HGX_OK;
+}
+
+extern "C" int hgx_alignment_set_info(const hgx_alignment_set *s, int32_t *route_tile, int32_t *max_loci, int64_t *block_table_bytes) {
+    if (route_tile) *route_tile = SET_TILE;
+    if (max_loci) *max_loci = SET_MAX_LOCI;
+    if (block_table_bytes) *block_table_bytes = s ? s->block_table_bytes : 0;
+    return HGX_OK;
+}
+
+extern "C" int hgx_alignment_set_route(hgx_alignment_set *s, const char *const *regions, int32_t n_loci, void *stream) {
+    ARGCHK(s && n_loci >= 0 && (n_loci == 0 || regions));
+    hipStream_t st = (hipStream_t)stream;
+    s->routed = false;
+    s->n_loci = n_loci;
+    s->regions.clear();
+    for (int l = 0; l < n_loci; ++l) s->regions.push_back(regions[l] ? regions[l] : "");
+    s->slot_host.assign((size_t)n_loci, 0);
+    s->kept.clear();
+    if (s->idx.p) { hgx_pool_free(s->idx.p); s->idx.p = nullptr; }
+    int dev = -1;
+    HIPCHK(hipGetDevice(&dev));
+    const uint32_t n_rec = s->table.n_rec;
+    // (more loci than the mask has bits, or lists that 32-bit positions do not hold: every slot goes per path)
+    if (!s->resident || dev != s->dev || n_loci < 1 || n_loci > SET_MAX_LOCI || (unsigned long long)n_rec * (unsigned long long)n_loci >= (1ull << 32) - 64) return HGX_OK;
+    const int n_files = s->n_files;
+    s->slot_start.assign((size_t)n_loci + 1, 0);
+    s->max_klen.assign((size_t)n_loci, 0);
+    s->kept.assign((size_t)n_loci * (size_t)n_files, 0);
+    // every region resolved against every file's own header
+    std::vector<SetFL> fl((size_t)n_files * (size_t)n_loci);
+    std::vector<uint8_t> acts;
+    for (int f = 0; f < n_files; ++f)
+        for (int l = 0; l < n_loci; ++l) {
+            hgx_bam_deferred def;
+            SetFL &G = fl[(size_t)f * n_loci + l];
+            G = SetFL{0, 0, 0u, 0, 1u, 0u};                                  // (filtered, no reference: keeps nothing)
+            if (hgx_deferred_for_regions(s->regions[l].c_str(), false, s->body0[f], s->refs[f], def) != 0) { s->slot_host[l] = 1; continue; }
+            G.left0 = (long long)def.left0; G.right0 = (long long)def.right0;
+            G.act_off = (uint32_t)acts.size(); G.n_ref = (int32_t)def.ref_action.size(); G.filtered = def.filtered ? 1u : 0u;
+            acts.insert(acts.end(), def.ref_action.begin(), def.ref_action.end());
+        }
+    if (n_rec == 0) { s->routed = true; return HGX_OK; }
+    Lap lap(st);
+    const uint32_t n_tiles = (n_rec + SET_TILE - 1) / SET_TILE;
+    const size_t n_cnt = (size_t)n_loci * n_tiles;
+    DevBuf b_fl, b_act, b_ctl, b_mask, b_cnt, b_base, b_tmp, b_kept;
+    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{st};
+    ALLOC(b_fl, fl.size() * sizeof(SetFL));
+    ALLOC(b_act, std::max<size_t>(acts.size(), 16));
+    ALLOC(b_ctl, sizeof(SetCtl));
+    ALLOC(b_mask, (size_t)n_rec * 8);
+    ALLOC(b_cnt, n_cnt * 4);
+    ALLOC(b_base, n_cnt * 4);
+    ALLOC(b_tmp, fe_scan_scratch_bytes((long)n_cnt));
+    ALLOC(b_kept, s->kept.size() * 4);
+    HIPCHK(hipMemsetAsync(b_ctl.p, 0, sizeof(SetCtl), st));
+    HIPCHK(hipMemsetAsync(b_tmp.p, 0, fe_scan_scratch_bytes((long)n_cnt), st));
+    HIPCHK(hipMemcpyAsync(b_fl.p, fl.data(), fl.size() * sizeof(SetFL), hipMemcpyHostToDevice, st));
+    if (!acts.empty()) HIPCHK(hipMemcpyAsync(b_act.p, acts.data(), acts.size(), hipMemcpyHostToDevice, st));
+    SetCtl *ctl = b_ctl.as<SetCtl>();
+    const BamTable &T = s->table;
+    k_set_route<<<n_tiles, SET_TILE, 0, st>>>(s->text.as<unsigned char>(), (const uint32_t *)T.b_off.p, (const uint32_t *)T.b_len.p, (const uint16_t *)T.b_task.p, n_rec,
+                                             b_fl.as<SetFL>(), b_act.as<uint8_t>(), n_loci, n_tiles, b_mask.as<unsigned long long>(), b_cnt.as<uint32_t>(), ctl);
+    {
+        FeScanArgs sa{};
+        sa.n_ch = 1;
+        sa.ch[0] = FeScanCh{b_cnt.p, b_base.as<uint32_t>(), 0, FSC_U32};
+        sa.totals = &ctl->total;
+        const int rcs = fe_scan(sa, (long)n_cnt, b_tmp.p, st);
+        if (rcs) return rcs;
+    }
+    SetCtl h;
+    HIPCHK(hipMemcpyAsync(&h, ctl, sizeof(SetCtl), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    lap("set: route (masks, counts, scan)");
+    if (h.decline) return HGX_OK;                                           // a malformed record some slot keeps: the per-path reader words it
+    ALLOC(s->idx, std::max<size_t>(h.total, 1) * 4);
+    k_set_scatter<<<n_tiles, SET_TILE, 0, st>>>(b_mask.as<unsigned long long>(), n_rec, n_loci, n_tiles, b_base.as<uint32_t>(), s->idx.as<uint32_t>());
+    const uint32_t n_lf = (uint32_t)n_loci * (uint32_t)n_files;
+    k_set_kept<<<nblk(n_lf, 256), 256, 0, st>>>((const uint16_t *)T.b_task.p, n_rec, s->idx.as<uint32_t>(), b_base.as<uint32_t>(), n_tiles, n_loci, n_files, h.total,
+                                                b_kept.as<uint32_t>());
+    HIPCHK(hipGetLastError());
+    std::vector<uint32_t> kept32(s->kept.size());
+    HIPCHK(hipMemcpyAsync(kept32.data(), b_kept.p, kept32.size() * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    lap("set: partition");
+    for (int l = 0; l < n_loci; ++l) {
+        uint32_t sum = 0;
+        for (int f = 0; f < n_files; ++f) { s->kept[(size_t)l * n_files + f] = kept32[(size_t)l * n_files + f]; sum += kept32[(size_t)l * n_files + f]; }
+        s->slot_start[(size_t)l + 1] = s->slot_start[l] + sum;
+        s->max_klen[l] = h.max_klen[l];
+    }
+    if (s->slot_start[(size_t)n_loci] != h.total) { hgx_set_error("hgx_alignment_set_route: the slots' lists do not add up"); return HGX_EHIP; }
+    s->routed = true;
+    return HGX_OK;
+}
+
+extern "C" int hgx_alignment_set_routed(const hgx_alignment_set *s, int64_t *n_kept) {
+    ARGCHK(s && n_kept);
+    if (!s->routed) { hgx_set_error("hgx_alignment_set_routed: the set is not routed on the device"); return HGX_EINVAL; }
+    std::copy(s->kept.begin(), s->kept.end(), n_kept);
+    return HGX_OK;
+}
+
+// what a slot's per-path call needs: hgx_many_create_files(paths, regions[slot] for every file)
+int hgx_alignment_set_paths(const hgx_alignment_set *s, int slot, std::vector<const char *> &paths, std::vector<const char *> &regions) {
+    ARGCHK(s && slot >= 0 && slot < s->n_loci);
+    paths.clear(); regions.clear();
+    for (const std::string &p : s->paths) { paths.push_back(p.c_str()); regions.push_back(s->regions[(size_t)slot].c_str()); }
+    return HGX_OK;
+}
+
+// one slot of a routed set through the record route, one task per file.  *declined != 0: nothing was made (the caller goes per path).
+int hgx_front_set_dev(hgx_dbatch **out, hgx_front_totals *tot, const hgx_locus *loc, const hgx_alignment_set *s, int slot, const hgx_parse_opts *opts,
+                      void *stream, int *declined) {
+    ARGCHK(out && tot && loc && s && opts && declined && slot >= 0 && slot < s->n_loci);
+    *out = nullptr;
+    *declined = 0;
+    hipStream_t st = (hipStream_t)stream;
+    int dev = -1;
+    HIPCHK(hipGetDevice(&dev));
+    if (!s->resident || !s->routed || s->slot_host[(size_t)slot] || dev != s->dev || hgx_switch_has("front", "host")) { *declined = -1; return HGX_OK; }
+    if (opts->keep_trace || opts->codis_choose_pairs || opts->interdist_exchange || opts->pileup_exchange || opts->pileup_exchange_dev) { *declined = HGX_FE_DECLINE_OPTS; return HGX_OK; }
+    const uint32_t n_kept = s->slot_start[(size_t)slot + 1] - s->slot_start[slot];
+    const BamTable &T = s->table;
+    const unsigned char *text = (const unsigned char *)s->text.p;
+    DevBuf b_lines, b_ctl;
+    hgx_dbatch *made = nullptr;
+    int rc, dec = 0;
+    {
+        struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{st};
+        Lap lap(st);
+        ALLOC(b_lines, std::max<size_t>(n_kept, 1) * sizeof(LineRef));
+        ALLOC(b_ctl, sizeof(BamCtl));
+        HIPCHK(hipMemsetAsync(b_ctl.p, 0, sizeof(BamCtl), st));
+        rc = bam_lines_of(text, (const uint32_t *)T.b_off.p, (const uint32_t *)T.b_len.p, (const uint16_t *)T.b_task.p, s->n_files,
+                          (const uint32_t *)s->idx.p + s->slot_start[slot], n_kept, s->max_klen[(size_t)slot], b_ctl.as<BamCtl>(), st, b_lines, lap);
+        if (!rc) rc = records_run(*const_cast<hgx_locus *>(loc), (const char *)text, s->ptotal, nullptr, n_kept, true, s->n_files, *opts, st, &made, tot, &dec,
+                                  b_lines.as<LineRef>());
+    }
+    if (rc) { hgx_dbatch_destroy(made); return rc; }
+    if (dec || !made) { hgx_dbatch_destroy(made); *declined = dec ? dec : HGX_FE_DECLINE_SIZE; return HGX_OK; }
+    g_last_route = 2; g_last_decline = 0; g_last_device = 1; g_last_bytes = 0; g_last_parts = 0;
+    *out = made;
+    return HGX_OK;
 }
 
 // MANY tasks of one locus (the samples of a panel) in ONE pass of the record route: the tasks' files are read side by side on the

@@ -376,6 +376,7 @@ struct hgx_bgzf_task {
     std::vector<hgx_bgzf_block> blocks;
     size_t total = 0;
     hgx_bam_deferred def;
+    std::vector<std::string> refs;       // the header's reference names, in the file's order
     bool ok = false;
 };
 int hgx_bgzf_tasks_read(std::vector<hgx_bgzf_task> &tasks, const char *const *paths, const char *const *regions, int n_tasks, int n_threads,
@@ -404,6 +405,11 @@ struct hgx_dbatch;
 // the device pass over them (hgx_front.hip): *declined != 0 -> nothing made, the caller goes task by task through the host stages
 int hgx_front_many_dev(hgx_dbatch **out, hgx_front_totals *tot, const hgx_locus *loc, const char *const *paths, const char *const *regions,
                        const char *const *sams, const size_t *sam_bytes, int n_tasks, const hgx_parse_opts *opts, void *stream, int *declined);
+// a slot of a routed hgx_alignment_set through the record route (hgx_front.hip), and the per-path call's arguments for a slot
+struct hgx_alignment_set;
+int hgx_front_set_dev(hgx_dbatch **out, hgx_front_totals *tot, const hgx_locus *loc, const hgx_alignment_set *s, int slot, const hgx_parse_opts *opts,
+                      void *stream, int *declined);
+int hgx_alignment_set_paths(const hgx_alignment_set *s, int slot, std::vector<const char *> &paths, std::vector<const char *> &regions);
 #ifdef HGX_LAB
 int hgx_front_emulate(hgx_batch **out, hgx_locus &L, const hgx_front_input &in, const hgx_parse_opts &opts, int *declined, int n_tasks = 1,
                       hgx_front_totals *many = nullptr);

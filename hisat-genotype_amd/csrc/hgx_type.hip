@@ -1137,6 +1137,28 @@ extern "C" int hgx_many_create(hgx_many **out, const hgx_locus *loc, const hgx_b
 }
 
 namespace {
+// a device batch of the many-task record route and its per-task totals -> hgx_many (takes `db` over)
+int many_adopt(hgx_many **out, const hgx_locus *loc, hgx_dbatch *db, const hgx_front_totals &tot, int32_t n_tasks, hipStream_t st) {
+    hgx_many *m = new hgx_many();
+    m->n_tasks = n_tasks; m->A = loc->A; m->a_pad = loc->a_pad;
+    m->db = db;
+    m->pair_base.assign((size_t)n_tasks + 1, 0);
+    for (int t = 0; t < n_tasks; ++t) {
+        m->pair_base[(size_t)t + 1] = m->pair_base[t] + (int32_t)tot.pairs[t];
+        m->n_reads.push_back((int32_t)tot.reads[t]);
+        m->n_pieces.push_back((int32_t)tot.pieces[t]);
+        m->n_refs.push_back((int64_t)tot.refs[t]);
+    }
+    if (m->pair_base[(size_t)n_tasks] != db->n_pairs) {
+        hgx_many_destroy(m);
+        hgx_set_error("device front end: the tasks' pair counts do not add up to the batch");
+        return HGX_EHIP;
+    }
+    const int rc = many_finish(m, loc, st);
+    if (rc) { hgx_many_destroy(m); return rc; }
+    *out = m;
+    return HGX_OK;
+}
 // alignment streams -> many-task batch: one pass of the device front end over all tasks, or -- where it declines (a record the
 // reference would raise on, options it leaves to the host, too little work) -- the host front end task by task, then the merge
 int many_from_streams(hgx_many **out, const hgx_locus *loc, const char *const *paths, const char *const *regions, const char *const *sams,
@@ -1149,27 +1171,7 @@ int many_from_streams(hgx_many **out, const hgx_locus *loc, const char *const *p
     int declined = 0;
     int rc = n_tasks > 0 ? hgx_front_many_dev(&db, &tot, loc, paths, regions, sams, sam_bytes, n_tasks, opts, stream, &declined) : HGX_OK;
     if (rc) return rc;
-    if (n_tasks > 0 && !declined && db) {
-        hgx_many *m = new hgx_many();
-        m->n_tasks = n_tasks; m->A = loc->A; m->a_pad = loc->a_pad;
-        m->db = db;
-        m->pair_base.assign((size_t)n_tasks + 1, 0);
-        for (int t = 0; t < n_tasks; ++t) {
-            m->pair_base[(size_t)t + 1] = m->pair_base[t] + (int32_t)tot.pairs[t];
-            m->n_reads.push_back((int32_t)tot.reads[t]);
-            m->n_pieces.push_back((int32_t)tot.pieces[t]);
-            m->n_refs.push_back((int64_t)tot.refs[t]);
-        }
-        if (m->pair_base[(size_t)n_tasks] != db->n_pairs) {
-            hgx_many_destroy(m);
-            hgx_set_error("device front end: the tasks' pair counts do not add up to the batch");
-            return HGX_EHIP;
-        }
-        rc = many_finish(m, loc, st);
-        if (rc) { hgx_many_destroy(m); return rc; }
-        *out = m;
-        return HGX_OK;
-    }
+    if (n_tasks > 0 && !declined && db) return many_adopt(out, loc, db, tot, n_tasks, st);
     // host front end, tasks side by side
     std::vector<hgx_batch *> bs((size_t)n_tasks, nullptr);
     std::vector<int> rcs((size_t)n_tasks, HGX_OK);
@@ -1196,6 +1198,24 @@ extern "C" int hgx_many_create_files(hgx_many **out, const hgx_locus *loc, const
     ARGCHK(out && loc && opts && n_tasks >= 0 && (n_tasks == 0 || paths));
     for (int t = 0; t < n_tasks; ++t) ARGCHK(paths[t]);
     return many_from_streams(out, loc, paths, regions, nullptr, nullptr, n_tasks, opts, stream);
+}
+
+// ... or from a slot of a routed hgx_alignment_set: the files were read, sent, inflated and walked once for all loci (hgx_front.hip);
+// a set that is not resident, or a slot the kernels decline, is exactly hgx_many_create_files(paths, regions[slot] for every file)
+extern "C" int hgx_many_create_set(hgx_many **out, const hgx_locus *loc, hgx_alignment_set *s, int32_t locus_slot, const hgx_parse_opts *opts, void *stream) {
+    ARGCHK(out && loc && s && opts);
+    *out = nullptr;
+    ARGCHK((int32_t)loc->name_rank.size() == loc->A && (int32_t)loc->allele_len.size() == loc->A);
+    std::vector<const char *> paths, regions;
+    int rc = hgx_alignment_set_paths(s, locus_slot, paths, regions);
+    if (rc) return rc;
+    hgx_dbatch *db = nullptr;
+    hgx_front_totals tot;
+    int declined = 0;
+    rc = hgx_front_set_dev(&db, &tot, loc, s, locus_slot, opts, stream, &declined);
+    if (rc) return rc;
+    if (!declined && db) return many_adopt(out, loc, db, tot, (int32_t)paths.size(), (hipStream_t)stream);
+    return many_from_streams(out, loc, paths.data(), regions.data(), nullptr, nullptr, (int32_t)paths.size(), opts, stream);
 }
 
 extern "C" int hgx_many_create_sams(hgx_many **out, const hgx_locus *loc, const char *const *sams, const size_t *n_bytes, int32_t n_tasks,

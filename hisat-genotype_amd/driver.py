@@ -164,10 +164,25 @@ def run_panel(tasks, index, base_fname, rank=0, world=1, weights=None, ix_dir=No
             by_gene.setdefault(task[1], []).append(task)
         parse_keys = ("num_editdist", "error_correction", "allow_discordant", "simulation", "base_locus")
         popts = {k: v for k, v in typing_opts.items() if k in parse_keys}
+        # the tasks of several genes naming the SAME alignment files, sample for sample (one BAM per sample holding every locus'
+        # records, typing_core.py:370): the files are read, sent, inflated and walked ONCE (engine.AlignmentSet) and every gene's
+        # batch comes out of the resident bytes -- the batch ManyBatch.from_files builds per gene, so the results are the same
+        aset, slot_of = None, {}
+        file_lists = [[sam for _, _, sam in group] for group in by_gene.values()]
+        if len(file_lists) > 1 and all(fl == file_lists[0] for fl in file_lists) and \
+                not any(isinstance(sam, (bytes, bytearray)) or "\t" in sam for sam in file_lists[0]):
+            set_regions = []
+            for gene in by_gene:
+                regions = typing_opts.get("regions", [packed[gene].ref_allele])
+                set_regions.append(regions if isinstance(regions, str) else "\n".join(regions))
+                slot_of[gene] = len(slot_of)
+            aset = engine.AlignmentSet(file_lists[0]).route(set_regions)
         for gene, group in by_gene.items():
             pl = packed[gene]
             is_text = [isinstance(sam, (bytes, bytearray)) or "\t" in sam for _, _, sam in group]
-            if all(is_text) or not any(is_text):
+            if aset is not None:
+                mb = engine.ManyBatch.from_set(pl, aset, slot_of[gene], **popts)
+            elif all(is_text) or not any(is_text):
                 # the samples of the locus through ONE pass of the device front end (hgx_many_create_sams / _files; where it
                 # declines, the library runs the host front end per task and merges: the same batch either way)
                 if all(is_text):
@@ -192,6 +207,8 @@ def run_panel(tasks, index, base_fname, rank=0, world=1, weights=None, ix_dir=No
             for t, ((sample_id, _, _), r) in enumerate(zip(group, res)):
                 r.n_pieces, r.n_refs = pieces[t], refs[t]
                 out[(sample_id, gene)] = r
+        if aset is not None:
+            aset.close()
         return out
     if inflight <= 1 or len(mine) <= 1:
         for task in mine:

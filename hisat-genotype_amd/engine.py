@@ -119,6 +119,62 @@ class Alignment:
             pass
 
 
+class AlignmentSet:
+    """The alignment files of MANY samples read ONCE (hgx_alignment_set_open): one BAM per sample, each holding the records of every
+    locus (hisatgenotype:613-665 pools the samples; typing_core.py:370, 436-468 loops the loci over each sample's one file).  The
+    files' deflated bytes go up once, one launch inflates them, the record chains are walked once; `route(regions)` sends every
+    record to the loci that keep it in one pass, and ManyBatch.from_set(pl, aset, slot) makes a locus' many-task batch (a task per
+    file) from the resident bytes -- the batch ManyBatch.from_files(pl, paths, [regions[slot]] * n_files) builds.  `resident` False
+    (a SAM-text member, a set below the front end's size gate, ...): every from_set is that from_files call."""
+
+    def __init__(self, paths, n_threads=0, stream=None):
+        self.paths = [str(p) for p in paths]
+        self.h = C.c_void_p()
+        self._stream = stream
+        n = len(self.paths)
+        p_arr = (C.c_char_p * max(n, 1))(*[p.encode() for p in self.paths])
+        capi.check(capi.lib().hgx_alignment_set_open(C.byref(self.h), p_arr, C.c_int32(n), C.c_int32(n_threads), stream))
+        nf, r, nb, up, nr = C.c_int32(), C.c_int32(), C.c_size_t(), C.c_longlong(), C.c_int64()
+        capi.check(capi.lib().hgx_alignment_set_dims(self.h, C.byref(nf), C.byref(r), C.byref(nb), C.byref(up), C.byref(nr)))
+        self.n_files, self.resident, self.stream_bytes, self.bytes_to_device, self.n_records = nf.value, bool(r.value), nb.value, up.value, nr.value
+        tile, ml, bt = C.c_int32(), C.c_int32(), C.c_int64()
+        capi.check(capi.lib().hgx_alignment_set_info(self.h, C.byref(tile), C.byref(ml), C.byref(bt)))
+        self.route_tile, self.max_loci, self.block_table_bytes = tile.value, ml.value, bt.value
+        self.regions, self.kept = None, None
+
+    def route(self, regions, stream=None):
+        """One samtools region string per locus slot.  `kept` = [n_loci][n_files] records each slot keeps of each file, or None where
+        the routing is left to the per-path calls (a set that is not resident, more than `max_loci` slots)."""
+        self.regions = [r if isinstance(r, str) else "\n".join(r) for r in regions]
+        n = len(self.regions)
+        r_arr = (C.c_char_p * max(n, 1))(*[r.encode() for r in self.regions])
+        capi.check(capi.lib().hgx_alignment_set_route(self.h, r_arr, C.c_int32(n), stream if stream is not None else self._stream))
+        self.kept = None
+        if self.resident and 1 <= n <= self.max_loci:
+            k = np.zeros((n, max(self.n_files, 1)), np.int64)
+            if capi.lib().hgx_alignment_set_routed(self.h, capi.ptr(k)) == 0:
+                self.kept = k[:, :self.n_files].tolist()
+        return self
+
+    def close(self):
+        if self.h:
+            capi.lib().hgx_alignment_set_close(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def stream_sets_info():
     """Stream placement of the current device (hgx_stream_sets_info): {'sets', 'queue_classes', 'probes', 'probe_ms', 'free_sets': [(em
     class, gene class)]}."""
@@ -235,6 +291,18 @@ class ManyBatch:
             r_arr = (C.c_char_p * max(n, 1))(*[(r.encode() if r else None) for r in regions])
         o = _parse_opts(locus, **opts)
         capi.check(capi.lib().hgx_many_create_files(C.byref(self.h), locus.h, p_arr, r_arr, C.c_int32(n), C.byref(o), stream))
+        self._dims()
+        return self
+
+    @classmethod
+    def from_set(cls, locus, aset, slot, stream=None, **opts):
+        """hgx_many_create_set: locus slot `slot` of a routed AlignmentSet, one task per file -- the files were read, sent, inflated
+        and walked once for all slots (`engine.front_last()` == (2, 0), no bytes sent); where the set is not resident or the kernels
+        decline the slot, exactly from_files(locus, aset.paths, [aset.regions[slot]] * n_files)."""
+        self = cls.__new__(cls)
+        self.h = C.c_void_p()
+        o = _parse_opts(locus, **opts)
+        capi.check(capi.lib().hgx_many_create_set(C.byref(self.h), locus.h, aset.h, C.c_int32(slot), C.byref(o), stream))
         self._dims()
         return self
 

@@ -369,6 +369,63 @@ def type_many_loci(pls, manies, remove_low=True, stream=None, light=False, em_fa
     return out
 
 
+def _many_from_set_side_by_side(pls, aset, slots, **parse_opts):
+    """ManyBatch.from_set for every (locus, slot), a thread and stream per locus (the set is read-only after route)."""
+    if len(pls) <= 1:
+        return [engine.ManyBatch.from_set(pl, aset, slot, **parse_opts) for pl, slot in zip(pls, slots)]
+    import threading
+    dev = capi.current_device()
+    manies, errs = [None] * len(pls), []
+
+    def work(i):
+        try:
+            capi.set_device(dev)
+            capi.set_stream_slot(("panel set", i))
+            st = capi.get_stream(2)
+            manies[i] = engine.ManyBatch.from_set(pls[i], aset, slots[i], stream=st, **parse_opts)
+            capi.sync(st)
+        except BaseException as e:      # noqa: BLE001 (re-raised on the calling thread)
+            errs.append(e)
+
+    ths = [threading.Thread(target=work, args=(i,)) for i in range(len(pls))]
+    for t in ths:
+        t.start()
+    for t in ths:
+        t.join()
+    if errs:
+        for m in manies:
+            if m is not None:
+                m.close()
+        raise errs[0]
+    return manies
+
+
+def type_panel_files(pls, paths, regions=None, remove_low=True, em_fast=None, **parse_opts):
+    """A panel from one alignment file per sample, each file holding every locus' records (hisatgenotype:613-665 x
+    typing_core.py:370, 436-468): ONE engine.AlignmentSet (the files read, sent, inflated and walked once), ONE route, the loci's
+    many-task batches made side by side, ONE type_many_loci.  `regions`: one samtools region per locus (default: its ref_allele).
+    Returns {(file_index, gene): LocusResult}, each identical to type_locus on that file and region."""
+    pls = list(pls)
+    regions = [pl.ref_allele for pl in pls] if regions is None else list(regions)
+    assert len(regions) == len(pls)
+    for pl in pls:
+        pl.index()                                  # (device index created before any worker needs it)
+    with engine.AlignmentSet(paths) as aset:
+        aset.route(regions)
+        manies = _many_from_set_side_by_side(pls, aset, list(range(len(pls))), **parse_opts)
+        try:
+            rows = type_many_loci(pls, manies, remove_low=remove_low, em_fast=em_fast)
+            out = {}
+            for pl, many, row in zip(pls, manies, rows):
+                for t, r in enumerate(row):
+                    r.n_pieces, r.n_refs = many.task_pieces[t], many.task_refs[t]
+                    out[(t, pl.gene)] = r
+        finally:
+            for m in manies:
+                m.close()
+    return out
+
+
 def report_lines(res, simulation=False, true_alleles=(), output_allele_counts=False, best_alleles=False):
     """Report body (core:1593, 1650-1677, 2076-2121)."""
     out = ["\t\t\t%d reads and %d pairs are aligned" % (res.num_reads, res.num_pairs)]

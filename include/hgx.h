@@ -537,6 +537,33 @@ int hgx_alignment_dims(const hgx_alignment *al, int32_t *resident, int32_t *is_t
 int hgx_alignment_parse_dev(hgx_dbatch **out, hgx_alignment *al, const hgx_locus *loc, const char *regions_or_null,
                             const hgx_parse_opts *opts, void *stream);
 int hgx_alignment_close(hgx_alignment *al);
+/* MANY alignment files, SEVERAL loci: the panel as its users have it.  The reference pools genotyping_locus over the samples
+ * (hisatgenotype:613-665), and inside each one typing() loops `locus_list` over that sample's ONE alignment file (typing_core.py:370,
+ * 436-468): a panel is one BAM per sample, each holding the records of every locus.  hgx_alignment_set_open reads the files side by
+ * side ONCE: the deflated bytes go up as they are read, one launch inflates every file's BGZF blocks into one device buffer (each
+ * file at a 64-byte aligned base), the record chains are walked once, and the record table (offset, length, file) stays in HBM beside
+ * the streams; every file's reference names stay on the host.  hgx_alignment_set_route takes up to 64 samtools region strings, one per
+ * locus slot, resolves each against every file's OWN header (the files may list the references in different orders) and sends every
+ * record to the slots that keep it in one pass -- a record may belong to several slots --, leaving per slot the kept records in
+ * (file, file order).  hgx_many_create_set is a slot's rest: name order per file, line table, the record route with one task per
+ * file -- the batch of hgx_many_create_files(paths, regions[slot] for every file), array for array; hgx_front_last reports route 2
+ * and 0 bytes for it (the bytes went up at open: hgx_alignment_set_dims).  The set is read-only after route: the slots may be made
+ * side by side from threads with streams of their own.
+ * NOT resident (hgx_alignment_set_dims): a SAM-text member, a set below the device front end's size gate, 4 GB or more of inflated
+ * stream, more than 65 535 files, a file that cannot be read or does not inflate / link up, the test switches front=host /
+ * host_inflate.  hgx_many_create_set is then exactly that hgx_many_create_files call -- as it is for more than 64 slots, for a slot
+ * whose region string lists several regions and for a slot the kernels decline -- and the per-path code words the errors.
+ * hgx_alignment_set_routed: n_kept[slot][file], the records each slot keeps of each file (HGX_EINVAL unless routed on the device).
+ * hgx_alignment_set_info: records per workgroup tile of the partition kernels, slots a route takes, bytes of the BGZF block tables
+ * that went up beside the files' bytes (`s` may be NULL for the constants). */
+typedef struct hgx_alignment_set hgx_alignment_set;
+int hgx_alignment_set_open(hgx_alignment_set **out, const char *const *paths, int32_t n_files, int32_t n_threads, void *stream);
+int hgx_alignment_set_dims(const hgx_alignment_set *s, int32_t *n_files, int32_t *resident, size_t *stream_bytes, long long *bytes_to_device,
+                           int64_t *n_records);
+int hgx_alignment_set_info(const hgx_alignment_set *s, int32_t *route_tile, int32_t *max_loci, int64_t *block_table_bytes);
+int hgx_alignment_set_route(hgx_alignment_set *s, const char *const *regions /* [n_loci], one samtools region each */, int32_t n_loci, void *stream);
+int hgx_alignment_set_routed(const hgx_alignment_set *s, int64_t *n_kept /* [n_loci][n_files] */);
+int hgx_alignment_set_close(hgx_alignment_set *s);
 /* a device batch back on the host (tests, tools): pieces, masks, refs, and the pileup tables if the kernels made them */
 int hgx_dbatch_to_host(const hgx_dbatch *d, hgx_batch **out);
 /* The same from class sets that already exist (intra-locus read sharding, 8e: every rank scores its share of the pairs, the
@@ -586,6 +613,8 @@ int hgx_many_create_files(hgx_many **out, const hgx_locus *loc, const char *cons
                           int32_t n_tasks, const hgx_parse_opts *opts, void *stream);
 int hgx_many_create_sams(hgx_many **out, const hgx_locus *loc, const char *const *sams, const size_t *n_bytes, int32_t n_tasks,
                          const hgx_parse_opts *opts, void *stream);
+/* ... or slot `locus_slot` of a routed hgx_alignment_set, one task per file of the set (see hgx_alignment_set_open) */
+int hgx_many_create_set(hgx_many **out, const hgx_locus *loc, hgx_alignment_set *s, int32_t locus_slot, const hgx_parse_opts *opts, void *stream);
 /* ... or ONE task from a batch that is already resident (hgx_parse_sam_dev / hgx_parse_alignment_file_dev / hgx_alignment_parse_dev):
  * the loci of one sample typed together by hgx_type_many_loci (typing_core.py:370).  The hgx_many takes `db` over on success. */
 int hgx_many_from_dbatch(hgx_many **out, const hgx_locus *loc, hgx_dbatch *db, void *stream);
