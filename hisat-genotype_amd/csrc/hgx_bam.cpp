@@ -468,6 +468,36 @@ inline bool region_hit(const Region &r, const char *rname, size_t rl, int64_t po
     return false;
 }
 
+// is a region list one the device front end takes?  (none, or 1 .. HGX_MAX_REGIONS entries)
+inline bool regions_defer(const std::vector<Region> &regs, bool filtered) {
+    return filtered ? (regs.size() >= 1 && regs.size() <= (size_t)HGX_MAX_REGIONS) : regs.empty();
+}
+// the region list as the deferred descriptor states it: for SAM text the strings and spans, for a BAM every region against the
+// file's own references
+void fill_deferred_regions(hgx_bam_deferred &d, const std::vector<Region> &regs, bool filtered, bool text, const std::vector<std::string> &refs) {
+    d.filtered = filtered;
+    d.more.clear();
+    if (!text) d.ref_action.assign(refs.size(), filtered ? 0 : 1);
+    if (!filtered) return;
+    d.more.resize(regs.size() - 1);
+    for (size_t g = 0; g < regs.size(); ++g) {
+        const Region &r = regs[g];
+        int64_t &l0 = g ? d.more[g - 1].left0 : d.left0, &r0 = g ? d.more[g - 1].right0 : d.right0;
+        l0 = r.left0; r0 = r.right0;
+        if (text) {
+            (g ? d.more[g - 1].region_whole : d.region_whole) = r.whole;
+            (g ? d.more[g - 1].region_name : d.region_name) = r.name;
+            continue;
+        }
+        std::vector<uint8_t> &act = g ? d.more[g - 1].ref_action : d.ref_action;
+        act.assign(refs.size(), 0);
+        for (size_t i = 0; i < refs.size(); ++i) {
+            if (refs[i].size() == r.whole.size() && memcmp(refs[i].data(), r.whole.data(), r.whole.size()) == 0) act[i] = 1;
+            else if (!r.name.empty() && refs[i].size() == r.name.size() && memcmp(refs[i].data(), r.name.data(), r.name.size()) == 0) act[i] = 2;
+        }
+    }
+}
+
 // reference bases consumed by a SAM CIGAR string (M D N = X); 0 for "*"
 inline int64_t cigar_text_reflen(const char *p, const char *e) {
     int64_t n = 0, tot = 0;
@@ -557,29 +587,16 @@ bool hgx_bam_record_line(const unsigned char *rec, size_t len, const std::vector
 
 // What a deferred stream's owner needs to pull ONE region list out of it (hgx_alignment_parse_dev: a file opened once, a locus at a
 // time): the descriptor hgx_read_alignment_lines would have made had it been given these regions.  1 = not expressible (more than
-// one region): the caller reads the file the ordinary way for this locus.
+// HGX_MAX_REGIONS regions): the caller reads the file the ordinary way for this locus.
 int hgx_deferred_for_regions(const char *regions, bool text, size_t body0, const std::vector<std::string> &refs, hgx_bam_deferred &d) {
     const std::vector<Region> regs = parse_regions(regions);
     const bool filtered = regions != nullptr && regions[0] != 0;
-    if (regs.size() > 1 || (filtered && regs.size() != 1)) return 1;
+    if (!regions_defer(regs, filtered)) return 1;
     d = hgx_bam_deferred();
     d.on = true;
     d.text = text;
     d.body0 = body0;
-    d.filtered = filtered;
-    if (text) {
-        if (filtered) { d.region_whole = regs[0].whole; d.region_name = regs[0].name; d.left0 = regs[0].left0; d.right0 = regs[0].right0; }
-        return 0;
-    }
-    d.ref_action.assign(refs.size(), filtered ? 0 : 1);
-    if (filtered) {
-        const Region &r = regs[0];
-        d.left0 = r.left0; d.right0 = r.right0;
-        for (size_t i = 0; i < refs.size(); ++i) {
-            if (refs[i].size() == r.whole.size() && memcmp(refs[i].data(), r.whole.data(), r.whole.size()) == 0) d.ref_action[i] = 1;
-            else if (!r.name.empty() && refs[i].size() == r.name.size() && memcmp(refs[i].data(), r.name.data(), r.name.size()) == 0) d.ref_action[i] = 2;
-        }
-    }
+    fill_deferred_regions(d, regs, filtered, text, refs);
     return 0;
 }
 
@@ -636,7 +653,7 @@ int hgx_read_alignment_lines(const char *path, const char *regions, int n_thread
         if (sb.st_size >= 4 && pread(fd, magic, 4, 0) != 4) { close(fd); hgx_set_error("short read on %s", path); return HGX_EINVAL; }
         const bool is_text = !(magic[0] == 0x1f && magic[1] == 0x8b) && memcmp(magic, "BAM\1", 4) != 0;
         // SAM text whose line table the caller makes itself (the device front end): any size from its gate on, not only big files
-        const bool text_defer_ok = out.defer_text && out.on_raw && keep_binary && regs.size() <= 1 && (!filtered || regs.size() == 1) &&
+        const bool text_defer_ok = out.defer_text && out.on_raw && keep_binary && regions_defer(regs, filtered) &&
                                    data.size() >= out.defer_min_bytes && data.size() < (1ull << 32) - 64;
         if (is_text && (data.size() > (8u << 20) || text_defer_ok)) {
             const int n_threads_file = n_threads;
@@ -713,8 +730,7 @@ int hgx_read_alignment_lines(const char *path, const char *regions, int n_thread
                 hgx_bam_deferred &d = out.deferred;
                 d.on = true;
                 d.text = true;
-                d.filtered = filtered;
-                if (filtered) { d.region_whole = regs[0].whole; d.region_name = regs[0].name; d.left0 = regs[0].left0; d.right0 = regs[0].right0; }
+                fill_deferred_regions(d, regs, filtered, true, {});
                 out.binary = false;
                 out.lines.clear();
                 hgx_host_free(out.raw);
@@ -746,8 +762,7 @@ int hgx_read_alignment_lines(const char *path, const char *regions, int n_thread
     }
     lap(text_scanned ? "read file + lines" : "read file");
     Bytes raw;
-    if (data.size() >= 2 && data[0] == 0x1f && data[1] == 0x8b && keep_binary && out.defer_walk && out.inflate_dev && regs.size() <= 1 &&
-        (!filtered || regs.size() == 1)) {
+    if (data.size() >= 2 && data[0] == 0x1f && data[1] == 0x8b && keep_binary && out.defer_walk && out.inflate_dev && regions_defer(regs, filtered)) {
         // The caller inflates, walks, filters and sorts on the device: the host hops through the container, inflates the block(s) that
         // hold the BAM header to learn the references and where the records begin, and hands the deflated bytes over.  Whatever
         // does not fit (not a BAM, a malformed container or header, a small stream, a block the kernel does not take) goes the
@@ -807,16 +822,7 @@ int hgx_read_alignment_lines(const char *path, const char *regions, int n_thread
                 d.on = true;
                 d.on_device = true;
                 d.body0 = body0;
-                d.filtered = filtered;
-                d.ref_action.assign(refs.size(), filtered ? 0 : 1);
-                if (filtered) {
-                    const Region &r = regs[0];
-                    d.left0 = r.left0; d.right0 = r.right0;
-                    for (size_t i = 0; i < refs.size(); ++i) {
-                        if (refs[i].size() == r.whole.size() && memcmp(refs[i].data(), r.whole.data(), r.whole.size()) == 0) d.ref_action[i] = 1;
-                        else if (!r.name.empty() && refs[i].size() == r.name.size() && memcmp(refs[i].data(), r.name.data(), r.name.size()) == 0) d.ref_action[i] = 2;
-                    }
-                }
+                fill_deferred_regions(d, regs, filtered, false, refs);
                 out.binary = true;
                 out.ref_names = refs;
                 out.lines.clear();
@@ -858,22 +864,13 @@ int hgx_read_alignment_lines(const char *path, const char *regions, int n_thread
             refs.emplace_back((const char *)&raw[p + 4], l_name - 1);
             p += 4 + l_name + 4;
         }
-        if (keep_binary && out.defer_walk && regs.size() <= 1 && (!filtered || regs.size() == 1) && n - p >= out.defer_min_bytes &&
+        if (keep_binary && out.defer_walk && regions_defer(regs, filtered) && n - p >= out.defer_min_bytes &&
             n < (1ull << 32) - 64 && refs.size() < 65536) {
             // the caller walks, filters and sorts the records itself (the device front end): hand the stream over as it is
             hgx_bam_deferred &d = out.deferred;
             d.on = true;
             d.body0 = p;
-            d.filtered = filtered;
-            d.ref_action.assign(refs.size(), filtered ? 0 : 1);
-            if (filtered) {
-                const Region &r = regs[0];
-                d.left0 = r.left0; d.right0 = r.right0;
-                for (size_t i = 0; i < refs.size(); ++i) {
-                    if (refs[i].size() == r.whole.size() && memcmp(refs[i].data(), r.whole.data(), r.whole.size()) == 0) d.ref_action[i] = 1;
-                    else if (!r.name.empty() && refs[i].size() == r.name.size() && memcmp(refs[i].data(), r.name.data(), r.name.size()) == 0) d.ref_action[i] = 2;
-                }
-            }
+            fill_deferred_regions(d, regs, filtered, false, refs);
             out.binary = true;
             out.ref_names = refs;
             lines.clear();
@@ -1167,7 +1164,7 @@ int hgx_bgzf_tasks_read(std::vector<hgx_bgzf_task> &tasks, const char *const *pa
             if (got_all != T.n || T.data[0] != 0x1f || T.data[1] != 0x8b) return;
             const std::vector<Region> regs = parse_regions(regions ? regions[t] : nullptr);
             const bool filtered = regions && regions[t] && regions[t][0] != 0;
-            if (regs.size() > 1 || (filtered && regs.size() != 1)) return;
+            if (!regions_defer(regs, filtered)) return;
             if (hgx_bgzf_scan(T.data, T.n, T.blocks, &T.total) != HGX_OK || T.total >= (1ull << 32) - 64) return;
             std::vector<unsigned char> head;
             std::vector<std::string> refs;
@@ -1181,16 +1178,7 @@ int hgx_bgzf_tasks_read(std::vector<hgx_bgzf_task> &tasks, const char *const *pa
             }
             if (st_h != 1 || body0 > T.total || refs.size() >= 65536) return;
             hgx_bam_deferred &d = T.def;
-            d.on = true; d.on_device = true; d.body0 = body0; d.filtered = filtered;
-            d.ref_action.assign(refs.size(), filtered ? 0 : 1);
-            if (filtered) {
-                const Region &r = regs[0];
-                d.left0 = r.left0; d.right0 = r.right0;
-                for (size_t i = 0; i < refs.size(); ++i) {
-                    if (refs[i].size() == r.whole.size() && memcmp(refs[i].data(), r.whole.data(), r.whole.size()) == 0) d.ref_action[i] = 1;
-                    else if (!r.name.empty() && refs[i].size() == r.name.size() && memcmp(refs[i].data(), r.name.data(), r.name.size()) == 0) d.ref_action[i] = 2;
-                }
-            }
+            d.on = true; d.on_device = true; d.body0 = body0; fill_deferred_regions(d, regs, filtered, false, refs);
             T.refs = std::move(refs);
             T.ok = true;
             if (on_task) on_task((int)t);

@@ -58,7 +58,11 @@ struct BamSeg {
     uint32_t filtered;
     long long left0, right0;
     uint32_t first_range, n_ranges;
+    // a region LIST (k_bam_filter): regions 1 .. n_regions - 1 -- region g's span at spans[span_off + g - 1], its references' actions at
+    // act_off + g * n_ref (region 0: left0 / right0 and act_off, as for one region)
+    uint32_t n_regions, span_off;
 };
+struct BamSpan { long long left0, right0; };
 __device__ __forceinline__ int bam_seg_of(const BamSeg *__restrict__ segs, int n_seg, uint32_t range) {
     int lo = 0, hi = n_seg - 1;
     while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (segs[mid].first_range <= range) lo = mid; else hi = mid - 1; }

@@ -779,10 +779,12 @@ __global__ void __launch_bounds__(256) k_fe_interdist_hist(const FeRec *__restri
 // is plausible and leads to three more plausible headers) and walks from there past its end; the guesses are then CHECKED -- a
 // range's walk must end exactly where the next one's begins -- and anything that does not link up declines the call.
 // (The walk and link kernels live in hgx_bam_walk.hpp: read extraction walks its chunks with them too.)
-// region filter (hgx_bam.cpp: reference span from the CIGAR, overlap with the one region) + the checks the host makes on a record
+// region filter (hgx_bam.cpp: reference span from the CIGAR, overlap with every region of the list) + the checks the host makes on a
+// record.  keep[i] = the record's region MASK (bit g: region g of its task's list keeps it; one region or none: 0 / 1) -- the header
+// and the CIGAR are read once, whatever the number of regions.
 __global__ void __launch_bounds__(256) k_bam_filter(const unsigned char *__restrict__ text, const uint32_t *__restrict__ rec_off, const uint32_t *__restrict__ rec_len,
                                                     const uint16_t *__restrict__ rec_task, uint32_t n_rec, const BamSeg *__restrict__ segs,
-                                                    const uint8_t *__restrict__ ref_action, uint32_t *__restrict__ keep, BamCtl *ctl) {
+                                                    const uint8_t *__restrict__ ref_action, const BamSpan *__restrict__ spans, uint32_t *__restrict__ keep, BamCtl *ctl) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_rec) return;
     const unsigned char *r = text + rec_off[i];
@@ -805,6 +807,11 @@ __global__ void __launch_bounds__(256) k_bam_filter(const unsigned char *__restr
             const long long end0 = (long long)pos + (reflen > 0 ? reflen : 1) - 1;
             const uint8_t act = ref_action[G.act_off + (uint32_t)rid];
             k = act == 1 ? 1u : (act == 2 ? ((end0 >= G.left0 && (long long)pos <= G.right0) ? 1u : 0u) : 0u);
+            for (uint32_t g = 1; g < G.n_regions; ++g) {
+                const uint8_t a = ref_action[G.act_off + g * (uint32_t)G.n_ref + (uint32_t)rid];
+                const BamSpan S = spans[G.span_off + g - 1];
+                if (a == 1 || (a == 2 && end0 >= S.left0 && (long long)pos <= S.right0)) k |= 1u << g;
+            }
         }
     }
     if (k && (l_rn == 0 || 32 + (size_t)l_rn > bs || r[32 + l_rn - 1] != 0)) { bam_decline(ctl, HGX_FE_DECLINE_RECORD); k = 0; }   // "malformed BAM record": the host's to report
@@ -816,6 +823,59 @@ __global__ void k_bam_compact(const uint32_t *__restrict__ keep, const uint32_t 
     if (i >= n_rec) return;
     if (keep[i]) idx[pos[i]] = i;
     if (i == n_rec - 1) ctl->n_kept = pos[i] + keep[i];
+}
+// ---- a region list: the stable multi-way partition of region masks (k_bam_filter, k_sam_line_info; the panel set's k_set_route) ---
+// One lane per record, PART_TILE records per workgroup.  part_wave_counts: per-slot counts of one wavefront's masks by ballot +
+// popcount (lane l leaves with slot l's count: no atomics).  k_part_counts stores a tile's counts slot-major, [n_slots][n_tiles], so
+// that ONE k_fe_scan gives every slot's list its start and every tile its place inside it; k_part_scatter adds the wavefronts
+// before (LDS) and the lanes before (prefix popcount of the ballot).  No atomic decides a position: the lists are slot after slot,
+// input order inside a slot, a record once per slot that keeps it.
+constexpr int PART_TILE = 1024;
+__device__ __forceinline__ uint32_t part_wave_counts(unsigned long long m, int n_slots, int lane) {
+    uint32_t mine = 0;
+    for (int l = 0; l < n_slots; ++l) {
+        const unsigned long long b = __ballot((int)((m >> l) & 1ull));
+        if (lane == l) mine = (uint32_t)__builtin_popcountll(b);
+    }
+    return mine;
+}
+template <class M>
+__global__ void __launch_bounds__(PART_TILE) k_part_counts(const M *__restrict__ mask, uint32_t n_rec, int n_slots, uint32_t n_tiles,
+                                                           uint32_t *__restrict__ cnt /* [n_slots][n_tiles] */) {
+    __shared__ uint32_t s_cnt[PART_TILE / 64][64];
+    const uint32_t i = blockIdx.x * PART_TILE + threadIdx.x;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const unsigned long long m = i < n_rec ? (unsigned long long)mask[i] : 0ull;
+    s_cnt[wv][lane] = part_wave_counts(m, n_slots, lane);
+    __syncthreads();
+    if ((int)threadIdx.x < n_slots) {
+        uint32_t sum = 0;
+        for (int w = 0; w < PART_TILE / 64; ++w) sum += s_cnt[w][threadIdx.x];
+        cnt[(size_t)threadIdx.x * n_tiles + blockIdx.x] = sum;
+    }
+}
+template <class M>
+__global__ void __launch_bounds__(PART_TILE) k_part_scatter(const M *__restrict__ mask, uint32_t n_rec, int n_slots, uint32_t n_tiles,
+                                                            const uint32_t *__restrict__ base /* [n_slots][n_tiles] */, uint32_t *__restrict__ idx) {
+    __shared__ uint32_t s_cnt[PART_TILE / 64][64];
+    __shared__ uint32_t s_base[PART_TILE / 64][64];
+    const uint32_t i = blockIdx.x * PART_TILE + threadIdx.x;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const unsigned long long m = i < n_rec ? (unsigned long long)mask[i] : 0ull;
+    s_cnt[wv][lane] = part_wave_counts(m, n_slots, lane);
+    __syncthreads();
+    {
+        uint32_t before = 0;
+        for (int w = 0; w < wv; ++w) before += s_cnt[w][lane];
+        s_base[wv][lane] = before;
+    }
+    __syncthreads();
+    const unsigned long long lanes_before = (1ull << lane) - 1ull;
+    for (int l = 0; l < n_slots; ++l) {
+        const bool mine = (m >> l) & 1ull;
+        const unsigned long long b = __ballot((int)mine);
+        if (mine) idx[base[(size_t)l * n_tiles + blockIdx.x] + s_base[wv][l] + (uint32_t)__builtin_popcountll(b & lanes_before)] = i;
+    }
 }
 // QNAME order as hgx_bam.cpp's line_less: bytes, a name that is a prefix of another first
 __device__ __forceinline__ int bam_name_cmp(const unsigned char *a, uint32_t la, const unsigned char *b, uint32_t lb) {
@@ -880,7 +940,10 @@ __global__ void __launch_bounds__(256) k_bam_sorted(const unsigned char *__restr
     const uint32_t la = (uint32_t)a[8] - 1, lb = (uint32_t)b[8] - 1;
     if (diff) name_diff_add(a + 32, la, b + 32, lb, valid, diff);          // (names of more than one 8-byte chunk: the sort will want it)
     if (!valid) return;
-    if (rec_task[idx[i - 1]] != rec_task[idx[i]]) return;                  // (records are in task order before the sort: only names inside a task matter)
+    // (one region per task: the records are in task order before the sort, only names inside a task matter; a region-major list of
+    // several tasks is not -- the sort's task key brings the tasks together again)
+    const uint32_t ta = rec_task[idx[i - 1]], tb = rec_task[idx[i]];
+    if (ta != tb) { if (ta > tb) ctl->unsorted = 1; return; }
     if (bam_name_cmp(b + 32, lb, a + 32, la) < 0) ctl->unsorted = 1;
 }
 __global__ void __launch_bounds__(256) k_bam_name_key_packed(const unsigned char *__restrict__ text, const uint32_t *__restrict__ rec_off, const uint32_t *__restrict__ idx,
@@ -1296,8 +1359,9 @@ LineRef *line_refs(const char *raw, const hgx_line *lines, size_t n_lines, bool 
 // (offset, length, task) of every record written in (task, file order).  The first half of bam_lines_dev, and what an
 // hgx_alignment_set keeps beside its inflated streams.
 struct BamTable {
-    DevBuf b_seg, b_act, b_ctl, b_off, b_len, b_task;
+    DevBuf b_seg, b_act, b_span, b_ctl, b_off, b_len, b_task;
     int n_seg = 0;
+    int max_regions = 0;                 // the longest region list among the tasks (0: nothing is filtered)
     uint32_t n_rec = 0;
 };
 int bam_table_dev(const unsigned char *text, const std::vector<const hgx_bam_deferred *> &defs, const std::vector<size_t> &bases, const std::vector<size_t> &sizes,
@@ -1307,8 +1371,10 @@ int bam_table_dev(const unsigned char *text, const std::vector<const hgx_bam_def
     if (n_seg < 1 || n_seg > 65535) { *declined = HGX_FE_DECLINE_SIZE; return HGX_OK; }
     std::vector<BamSeg> segs((size_t)n_seg);
     std::vector<uint8_t> acts;
+    std::vector<BamSpan> spans;
     size_t total_body = 0;
     for (int t = 0; t < n_seg; ++t) {
+        if (defs[t]->n_regions() > HGX_MAX_REGIONS) { *declined = HGX_FE_DECLINE_SIZE; return HGX_OK; }
         if (defs[t]->body0 > sizes[t] || bases[t] + sizes[t] >= (1ull << 32) - 64) { *declined = HGX_FE_DECLINE_SIZE; return HGX_OK; }
         total_body += sizes[t] - defs[t]->body0;
     }
@@ -1326,6 +1392,12 @@ int bam_table_dev(const unsigned char *text, const std::vector<const hgx_bam_def
         G.act_off = (uint32_t)acts.size();
         acts.insert(acts.end(), d.ref_action.begin(), d.ref_action.end());
         G.filtered = d.filtered ? 1u : 0u; G.left0 = (long long)d.left0; G.right0 = (long long)d.right0;
+        G.n_regions = (uint32_t)d.n_regions(); G.span_off = (uint32_t)spans.size();
+        for (int g = 1; g < d.n_regions(); ++g) {                               // (region-major rows: act_off + g * n_ref)
+            acts.insert(acts.end(), d.action_of(g).begin(), d.action_of(g).end());
+            spans.push_back(BamSpan{(long long)d.left_of(g), (long long)d.right_of(g)});
+        }
+        T.max_regions = std::max(T.max_regions, d.n_regions());
         const size_t body = sizes[t] - d.body0;
         G.first_range = w_at;
         G.n_ranges = (uint32_t)std::max<size_t>(1, total_body ? (W_all * body + total_body - 1) / total_body : 1);
@@ -1340,6 +1412,8 @@ int bam_table_dev(const unsigned char *text, const std::vector<const hgx_bam_def
     ALLOC(b_cnt, (size_t)W * 4);
     ALLOC(T.b_ctl, sizeof(BamCtl));
     ALLOC(T.b_act, std::max<size_t>(acts.size(), 16));
+    ALLOC(T.b_span, std::max<size_t>(spans.size(), 1) * sizeof(BamSpan));
+    if (!spans.empty()) HIPCHK(hipMemcpyAsync(T.b_span.p, spans.data(), spans.size() * sizeof(BamSpan), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(T.b_ctl.p, 0, sizeof(BamCtl), st));
     HIPCHK(hipMemcpyAsync(T.b_seg.p, segs.data(), (size_t)n_seg * sizeof(BamSeg), hipMemcpyHostToDevice, st));
     if (!acts.empty()) HIPCHK(hipMemcpyAsync(T.b_act.p, acts.data(), acts.size(), hipMemcpyHostToDevice, st));
@@ -1445,33 +1519,52 @@ int bam_lines_dev(const char *d_text, const std::vector<const hgx_bam_deferred *
     Lap lap(st);
     const unsigned char *text = (const unsigned char *)d_text;
     BamTable T;
-    DevBuf b_keep, b_pos, b_idx, b_tmp;
+    DevBuf b_keep, b_pos, b_idx, b_tmp, b_cnt;
     struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{st};
     { const int rc_t = bam_table_dev(text, defs, bases, sizes, st, T, declined, lap); if (rc_t || *declined) return rc_t; }
     const uint32_t n_rec = T.n_rec;
     const int n_seg = T.n_seg;
     BamCtl *ctl = T.b_ctl.as<BamCtl>();
-    ALLOC(b_lines, std::max<size_t>(n_rec, 1) * sizeof(LineRef));
-    if (n_rec == 0) return HGX_OK;
-    ALLOC(b_keep, (size_t)n_rec * 4); ALLOC(b_pos, (size_t)n_rec * 4); ALLOC(b_idx, (size_t)n_rec * 4);
-    ALLOC(b_tmp, std::max<size_t>(fe_scan_scratch_bytes(n_rec), 256));
+    // a region list: the kept list may be longer than the record table (a record once per region that keeps it)
+    const int n_reg = T.max_regions;
+    if (n_reg > 1 && (unsigned long long)n_rec * (unsigned long long)n_reg >= (1ull << 30)) { *declined = HGX_FE_DECLINE_SIZE; return HGX_OK; }
+    if (n_rec == 0) { ALLOC(b_lines, sizeof(LineRef)); return HGX_OK; }
+    const uint32_t n_tiles = (n_rec + PART_TILE - 1) / PART_TILE;
+    const size_t n_scan = n_reg > 1 ? (size_t)n_reg * n_tiles : (size_t)n_rec;
+    ALLOC(b_keep, (size_t)n_rec * 4); ALLOC(b_pos, n_scan * 4);
+    ALLOC(b_tmp, std::max<size_t>(fe_scan_scratch_bytes((long)n_scan), 256));
     k_bam_filter<<<nblk(n_rec, 256), 256, 0, st>>>(text, T.b_off.as<uint32_t>(), T.b_len.as<uint32_t>(), T.b_task.as<uint16_t>(), n_rec, T.b_seg.as<BamSeg>(),
-                                                   T.b_act.as<uint8_t>(), b_keep.as<uint32_t>(), ctl);
-    {
-        HIPCHK(hipMemsetAsync(b_tmp.p, 0, fe_scan_scratch_bytes(n_rec), st));
+                                                   T.b_act.as<uint8_t>(), T.b_span.as<BamSpan>(), b_keep.as<uint32_t>(), ctl);
+    HIPCHK(hipMemsetAsync(b_tmp.p, 0, fe_scan_scratch_bytes((long)n_scan), st));
+    if (n_reg > 1) {
+        // the stable partition by region: the list is region after region (all tasks' records of region 0, then of region 1, ...), file
+        // order inside; bam_lines_of's name sort and its stable task key make of it, per task, what the host reader's lists + sort give
+        ALLOC(b_cnt, n_scan * 4);
+        k_part_counts<uint32_t><<<n_tiles, PART_TILE, 0, st>>>(b_keep.as<uint32_t>(), n_rec, n_reg, n_tiles, b_cnt.as<uint32_t>());
+        FeScanArgs sa{};
+        sa.n_ch = 1;
+        sa.ch[0] = FeScanCh{b_cnt.p, b_pos.as<uint32_t>(), 0, FSC_U32};
+        sa.totals = &ctl->n_kept;
+        const int rcs = fe_scan(sa, (long)n_scan, b_tmp.p, st);
+        if (rcs) return rcs;
+        ALLOC(b_idx, (size_t)n_rec * (size_t)n_reg * 4);
+        k_part_scatter<uint32_t><<<n_tiles, PART_TILE, 0, st>>>(b_keep.as<uint32_t>(), n_rec, n_reg, n_tiles, b_pos.as<uint32_t>(), b_idx.as<uint32_t>());
+    } else {
+        ALLOC(b_idx, (size_t)n_rec * 4);
         FeScanArgs sa{};
         sa.n_ch = 1;
         sa.ch[0] = FeScanCh{b_keep.p, b_pos.as<uint32_t>(), 0, FSC_U32};
         const int rcs = fe_scan(sa, (long)n_rec, b_tmp.p, st);
         if (rcs) return rcs;
+        k_bam_compact<<<nblk(n_rec, 256), 256, 0, st>>>(b_keep.as<uint32_t>(), b_pos.as<uint32_t>(), n_rec, b_idx.as<uint32_t>(), ctl);
     }
-    k_bam_compact<<<nblk(n_rec, 256), 256, 0, st>>>(b_keep.as<uint32_t>(), b_pos.as<uint32_t>(), n_rec, b_idx.as<uint32_t>(), ctl);
     BamCtl h;
     { const int rc_d = hgx_d2h(&h, ctl, sizeof(BamCtl), st); if (rc_d) { (void)hgx_sync(st); return rc_d; } }
     { const int rc_s = hgx_sync(st); if (rc_s) return rc_s; }
     lap("BAM records + region filter");
     if (h.decline) { *declined = h.decline; return HGX_OK; }
     const uint32_t n_kept = h.n_kept;
+    ALLOC(b_lines, std::max<size_t>(n_kept, 1) * sizeof(LineRef));
     const int rc_l = bam_lines_of(text, T.b_off.as<uint32_t>(), T.b_len.as<uint32_t>(), T.b_task.as<uint16_t>(), n_seg, b_idx.as<uint32_t>(), n_kept, h.max_klen, ctl, st,
                                   b_lines, lap);
     if (rc_l) return rc_l;
@@ -1485,10 +1578,11 @@ int bam_lines_dev(const char *d_text, const std::vector<const hgx_bam_deferred *
 //   k_sam_nl<0/1>    newlines per 4 KB tile (a wavefront reads 1 KB per step, 16 bytes per lane, a SWAR zero-byte test per dword),
 //                    a scan of the tile counts, then the same walk again writing every line's start
 //   k_sam_line_info  a lane per line: '\r' stripped, blank and '@' lines dropped, the region test of `samtools view` on RNAME, POS and
-//                    the CIGAR's reference span (one region at most: hgx_bam_deferred), QNAME length
+//                    the CIGAR's reference span against every region of the list (hgx_bam_deferred; a region MASK), QNAME length
 //   scan + compact, k_sam_sorted (QNAME order check), LSD radix passes over 8-byte QNAME chunks where the text is not in name order
 //   (k_sam_name_key + hipcub sort, as for BAM), k_sam_lines -> FeLine
-struct SamRegion { int filtered, whole_len, name_len; long long left0, right0; char whole[96], name[96]; };
+struct SamRegion { int whole_len, name_len; long long left0, right0; char whole[96], name[96]; };
+struct SamRegions { int filtered, n; SamRegion r[HGX_MAX_REGIONS]; };       // (uploaded: the list is beyond what a launch's arguments should carry)
 constexpr int SAM_TILE = 4096;
 __device__ __forceinline__ uint32_t sam_nl_mask(uint32_t w) {          // bit 8 k + 7 set where byte k of w is '\n'
     const uint32_t x = w ^ 0x0A0A0A0Au;
@@ -1537,7 +1631,7 @@ __device__ __forceinline__ bool sam_bytes_eq(const unsigned char *a, const char 
     return true;
 }
 __global__ void __launch_bounds__(256) k_sam_line_info(const unsigned char *__restrict__ text, size_t n, const uint32_t *__restrict__ starts, uint32_t n_all,
-                                                       SamRegion R, uint32_t *__restrict__ keep, uint32_t *__restrict__ l_len, uint32_t *__restrict__ l_klen,
+                                                       const SamRegions *__restrict__ Rp, uint32_t *__restrict__ keep, uint32_t *__restrict__ l_len, uint32_t *__restrict__ l_klen,
                                                        BamCtl *ctl) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_all) return;
@@ -1546,13 +1640,14 @@ __global__ void __launch_bounds__(256) k_sam_line_info(const unsigned char *__re
     if (end < off) end = off;
     if (end > off && text[end - 1] == '\r') --end;
     const uint32_t len = end - off;
-    uint32_t k = 0, klen = 0;
+    uint32_t k = 0, klen = 0;                                                    // k: the line's region mask (nothing filtered: 0 / 1)
+    const int r_filtered = Rp->filtered, r_n = Rp->n;
     if (len && text[off] != '@') {
         // QNAME and, for the region test, FLAG / RNAME / POS / CIGAR (hgx_bam.cpp take_line)
         const unsigned char *p = text + off;
         uint32_t tab[6];
         int nf = 0;
-        const int want = R.filtered ? 6 : 1;
+        const int want = r_filtered ? 6 : 1;
         // the first `want` tabs, eight bytes per look (an exact zero-byte test of word ^ tabs gives their places)
         for (uint32_t q = 0; q < len && nf < want;) {
             if (q + 8 <= len) {
@@ -1568,7 +1663,7 @@ __global__ void __launch_bounds__(256) k_sam_line_info(const unsigned char *__re
             }
         }
         klen = nf ? tab[0] : len;
-        if (!R.filtered) k = 1;
+        if (!r_filtered) k = 1;
         else if (nf == 6) {
             long long flag = 0, pos = 0;
             bool fneg = false, pneg = false;
@@ -1598,8 +1693,11 @@ __global__ void __launch_bounds__(256) k_sam_line_info(const unsigned char *__re
             const long long end0 = pos0 + (reflen > 0 ? reflen : 1) - 1;
             const unsigned char *rn = p + tab[1] + 1;
             const int rl = (int)(tab[2] - tab[1] - 1);
-            if (rl == R.whole_len && sam_bytes_eq(rn, R.whole, rl)) k = 1;
-            else if (R.name_len > 0 && rl == R.name_len && sam_bytes_eq(rn, R.name, rl)) k = (end0 >= R.left0 && pos0 <= R.right0) ? 1u : 0u;
+            for (int g = 0; g < r_n; ++g) {
+                const SamRegion &R = Rp->r[g];
+                if (rl == R.whole_len && sam_bytes_eq(rn, R.whole, rl)) k |= 1u << g;
+                else if (R.name_len > 0 && rl == R.name_len && sam_bytes_eq(rn, R.name, rl)) k |= ((end0 >= R.left0 && pos0 <= R.right0) ? 1u : 0u) << g;
+            }
         }
     }
     keep[i] = k;
@@ -1614,6 +1712,15 @@ __global__ void k_sam_compact(const uint32_t *__restrict__ keep, const uint32_t 
     if (i >= n_all) return;
     if (keep[i]) { const uint32_t q = pos[i]; k_off[q] = starts[i]; k_len[q] = l_len[i]; k_klen[q] = l_klen[i]; idx[q] = q; }
     if (i == n_all - 1) ctl->n_kept = pos[i] + keep[i];
+}
+// ... and behind the partition of a region list (k_part_scatter: src[q] = the line at place q of the region-after-region list)
+__global__ void k_sam_gather(const uint32_t *__restrict__ src, uint32_t n_kept, const uint32_t *__restrict__ starts, const uint32_t *__restrict__ l_len,
+                             const uint32_t *__restrict__ l_klen, uint32_t *__restrict__ k_off, uint32_t *__restrict__ k_len, uint32_t *__restrict__ k_klen,
+                             uint32_t *__restrict__ idx) {
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n_kept) return;
+    const uint32_t i = src[q];
+    k_off[q] = starts[i]; k_len[q] = l_len[i]; k_klen[q] = l_klen[i]; idx[q] = q;
 }
 __global__ void __launch_bounds__(256) k_sam_sorted(const unsigned char *__restrict__ text, const uint32_t *__restrict__ k_off, const uint32_t *__restrict__ k_klen,
                                                     uint32_t n, BamCtl *ctl, unsigned long long *__restrict__ diff) {
@@ -1661,18 +1768,25 @@ int sam_lines_dev(const char *d_text, size_t n_bytes, const hgx_bam_deferred &de
     Lap lap(st);
     const unsigned char *text = (const unsigned char *)d_text;
     if (n_bytes >= (1ull << 32) - 64) { *declined = HGX_FE_DECLINE_SIZE; return HGX_OK; }
-    SamRegion R;
-    memset(&R, 0, sizeof(R));
-    R.filtered = def.filtered ? 1 : 0;
-    if (def.filtered) {
-        if (def.region_whole.size() >= sizeof(R.whole) || def.region_name.size() >= sizeof(R.name)) { *declined = HGX_FE_DECLINE_SIZE; return HGX_OK; }
-        R.whole_len = (int)def.region_whole.size(); memcpy(R.whole, def.region_whole.data(), def.region_whole.size());
-        R.name_len = (int)def.region_name.size(); memcpy(R.name, def.region_name.data(), def.region_name.size());
-        R.left0 = (long long)def.left0; R.right0 = (long long)def.right0;
+    SamRegions RS;
+    memset(&RS, 0, sizeof(RS));
+    RS.filtered = def.filtered ? 1 : 0;
+    RS.n = def.n_regions();
+    if (RS.n > HGX_MAX_REGIONS) { *declined = HGX_FE_DECLINE_SIZE; return HGX_OK; }
+    for (int g = 0; g < RS.n; ++g) {
+        SamRegion &R = RS.r[g];
+        const std::string &whole = def.whole_of(g), &name = def.name_of(g);
+        if (whole.size() >= sizeof(R.whole) || name.size() >= sizeof(R.name)) { *declined = HGX_FE_DECLINE_SIZE; return HGX_OK; }
+        R.whole_len = (int)whole.size(); memcpy(R.whole, whole.data(), whole.size());
+        R.name_len = (int)name.size(); memcpy(R.name, name.data(), name.size());
+        R.left0 = (long long)def.left_of(g); R.right0 = (long long)def.right_of(g);
     }
+    const int n_reg = RS.n;
     const uint32_t n_tiles = (uint32_t)((n_bytes + SAM_TILE - 1) / SAM_TILE);
-    DevBuf b_cnt, b_base, b_ctl, b_starts, b_keep, b_pos, b_len, b_klen, b_koff, b_klen2, b_klen3, b_idx, b_idx2, b_key, b_key2, b_tmp;
-    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{st};
+    DevBuf b_cnt, b_base, b_ctl, b_starts, b_keep, b_pos, b_len, b_klen, b_koff, b_klen2, b_klen3, b_idx, b_idx2, b_key, b_key2, b_tmp, b_reg, b_pcnt, b_src;
+    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{st};     // (the uploads below read this frame's RS)
+    ALLOC(b_reg, sizeof(SamRegions));
+    HIPCHK(hipMemcpyAsync(b_reg.p, &RS, sizeof(SamRegions), hipMemcpyHostToDevice, st));
     const size_t sc_t = fe_scan_scratch_bytes(std::max<uint32_t>(n_tiles, 1));
     ALLOC(b_cnt, std::max<size_t>(n_tiles, 1) * 4);
     ALLOC(b_base, std::max<size_t>(n_tiles, 1) * 4);
@@ -1701,27 +1815,47 @@ int sam_lines_dev(const char *d_text, size_t n_bytes, const hgx_bam_deferred &de
     const uint32_t n_all = n_nl + 1;
     lap("SAM newline scan");
     if (n_all >= (1u << 30)) { *declined = HGX_FE_DECLINE_SIZE; return HGX_OK; }
-    ALLOC(b_keep, (size_t)n_all * 4); ALLOC(b_pos, (size_t)n_all * 4); ALLOC(b_len, (size_t)n_all * 4); ALLOC(b_klen, (size_t)n_all * 4);
-    ALLOC(b_koff, (size_t)n_all * 4); ALLOC(b_klen2, (size_t)n_all * 4); ALLOC(b_klen3, (size_t)n_all * 4); ALLOC(b_idx, (size_t)n_all * 4);
+    // a region list: the kept list may be longer than the line table (a line once per region that keeps it)
+    if (n_reg > 1 && (unsigned long long)n_all * (unsigned long long)n_reg >= (1ull << 30)) { *declined = HGX_FE_DECLINE_SIZE; return HGX_OK; }
+    const size_t n_out = (size_t)n_all * (size_t)std::max(n_reg, 1);
+    const uint32_t p_tiles = (n_all + PART_TILE - 1) / PART_TILE;
+    const size_t n_scan = n_reg > 1 ? (size_t)n_reg * p_tiles : (size_t)n_all;
+    ALLOC(b_keep, (size_t)n_all * 4); ALLOC(b_pos, n_scan * 4); ALLOC(b_len, (size_t)n_all * 4); ALLOC(b_klen, (size_t)n_all * 4);
+    ALLOC(b_koff, n_out * 4); ALLOC(b_klen2, n_out * 4); ALLOC(b_klen3, n_out * 4); ALLOC(b_idx, n_out * 4);
     size_t tb2 = 0;
     (void)hipcub::DeviceRadixSort::SortPairs((void *)nullptr, tb2, (unsigned long long *)nullptr, (unsigned long long *)nullptr, (uint32_t *)nullptr,
-                                             (uint32_t *)nullptr, (int)n_all, 0, 64, st);
-    const size_t tmp_bytes = std::max(tb2, fe_scan_scratch_bytes(n_all));
+                                             (uint32_t *)nullptr, (int)n_out, 0, 64, st);
+    const size_t tmp_bytes = std::max(tb2, fe_scan_scratch_bytes((long)n_scan));
     ALLOC(b_tmp, std::max<size_t>(tmp_bytes, 256));
-    HIPCHK(hipMemsetAsync(b_tmp.p, 0, fe_scan_scratch_bytes(n_all), st));
-    k_sam_line_info<<<nblk(n_all, 256), 256, 0, st>>>(text, n_bytes, b_starts.as<uint32_t>(), n_all, R, b_keep.as<uint32_t>(), b_len.as<uint32_t>(),
+    HIPCHK(hipMemsetAsync(b_tmp.p, 0, fe_scan_scratch_bytes((long)n_scan), st));
+    k_sam_line_info<<<nblk(n_all, 256), 256, 0, st>>>(text, n_bytes, b_starts.as<uint32_t>(), n_all, b_reg.as<SamRegions>(), b_keep.as<uint32_t>(), b_len.as<uint32_t>(),
                                                       b_klen.as<uint32_t>(), ctl);
-    {
+    if (n_reg > 1) {
+        // the stable partition by region (k_part_*): region after region, file order inside; the name sort below is stable over it
+        ALLOC(b_pcnt, n_scan * 4); ALLOC(b_src, n_out * 4);
+        k_part_counts<uint32_t><<<p_tiles, PART_TILE, 0, st>>>(b_keep.as<uint32_t>(), n_all, n_reg, p_tiles, b_pcnt.as<uint32_t>());
+        FeScanArgs sa{};
+        sa.n_ch = 1;
+        sa.ch[0] = FeScanCh{b_pcnt.p, b_pos.as<uint32_t>(), 0, FSC_U32};
+        sa.totals = &ctl->n_kept;
+        const int rcs = fe_scan(sa, (long)n_scan, b_tmp.p, st);
+        if (rcs) return rcs;
+        k_part_scatter<uint32_t><<<p_tiles, PART_TILE, 0, st>>>(b_keep.as<uint32_t>(), n_all, n_reg, p_tiles, b_pos.as<uint32_t>(), b_src.as<uint32_t>());
+        { const int rc_d = hgx_d2h(&h, ctl, sizeof(BamCtl), st); if (rc_d) { (void)hgx_sync(st); return rc_d; } }
+        { const int rc_s = hgx_sync(st); if (rc_s) return rc_s; }
+        if (h.n_kept) k_sam_gather<<<nblk(h.n_kept, 256), 256, 0, st>>>(b_src.as<uint32_t>(), h.n_kept, b_starts.as<uint32_t>(), b_len.as<uint32_t>(), b_klen.as<uint32_t>(),
+                                                                       b_koff.as<uint32_t>(), b_klen2.as<uint32_t>(), b_klen3.as<uint32_t>(), b_idx.as<uint32_t>());
+    } else {
         FeScanArgs sa{};
         sa.n_ch = 1;
         sa.ch[0] = FeScanCh{b_keep.p, b_pos.as<uint32_t>(), 0, FSC_U32};
         const int rcs = fe_scan(sa, (long)n_all, b_tmp.p, st);
         if (rcs) return rcs;
+        k_sam_compact<<<nblk(n_all, 256), 256, 0, st>>>(b_keep.as<uint32_t>(), b_pos.as<uint32_t>(), b_starts.as<uint32_t>(), b_len.as<uint32_t>(), b_klen.as<uint32_t>(),
+                                                        n_all, b_koff.as<uint32_t>(), b_klen2.as<uint32_t>(), b_klen3.as<uint32_t>(), b_idx.as<uint32_t>(), ctl);
+        { const int rc_d = hgx_d2h(&h, ctl, sizeof(BamCtl), st); if (rc_d) { (void)hgx_sync(st); return rc_d; } }
+        { const int rc_s = hgx_sync(st); if (rc_s) return rc_s; }
     }
-    k_sam_compact<<<nblk(n_all, 256), 256, 0, st>>>(b_keep.as<uint32_t>(), b_pos.as<uint32_t>(), b_starts.as<uint32_t>(), b_len.as<uint32_t>(), b_klen.as<uint32_t>(),
-                                                    n_all, b_koff.as<uint32_t>(), b_klen2.as<uint32_t>(), b_klen3.as<uint32_t>(), b_idx.as<uint32_t>(), ctl);
-    { const int rc_d = hgx_d2h(&h, ctl, sizeof(BamCtl), st); if (rc_d) { (void)hgx_sync(st); return rc_d; } }
-    { const int rc_s = hgx_sync(st); if (rc_s) return rc_s; }
     lap("SAM lines + region filter");
     const uint32_t n_kept = h.n_kept;
     // QNAME is at most 254 characters (SAM specification 1.4; a BAM's l_read_name caps it at 255 with the NUL): a longer "name" is a
@@ -1947,6 +2081,8 @@ SideStreams g_side;
 int records_split(hgx_locus &L, const char *d_text, const char *raw, size_t raw_bytes, const hgx_bam_deferred &def, const std::vector<SamPhase> &phases,
                   const hgx_parse_opts &o, hipStream_t st, hgx_dbatch **out, int *declined, int *handled) {
     *handled = 0;
+    // (a region list: the parts' lists would join part-major, the reader's order is region-major -- the whole text at once, below)
+    if (def.n_regions() > 1) return HGX_OK;
     if (phases.size() < 2 || phases.back().end != raw_bytes || raw_bytes >= (1ull << 32) - 64) return HGX_OK;
     // The parts: everything before the last phase (whole lines), with many phases cut once more so that the part that waits for the
     // last byte is small -- [0, end of phase n-3) behind phase n-3's event, [.., end of phase n-2) behind phase n-2's, the rest behind
@@ -2408,20 +2544,11 @@ extern "C" int hgx_alignment_parse_dev(hgx_dbatch **out, hgx_alignment *al, cons
 // the kept records in (file, file order) -- what k_bam_filter + k_bam_compact give that locus alone.  hgx_front_set_dev is a slot's
 // rest: name order (bam_lines_of), line table, records_run with one task per file.
 namespace {
-constexpr int SET_TILE = 1024;            // records per workgroup of the routing / partition kernels (one lane per record)
-constexpr int SET_MAX_LOCI = 64;          // bits of the slot mask
+constexpr int SET_TILE = PART_TILE;       // records per workgroup of the routing / partition kernels (one lane per record)
+constexpr int SET_MAX_LOCI = 64;          // bits of the mask: (slot, region) pairs
 struct SetFL { long long left0, right0; uint32_t act_off; int32_t n_ref; uint32_t filtered, pad; };      // per (file, locus): the region as that file's header resolves it
 struct SetCtl { int32_t decline; uint32_t total; uint32_t max_klen[SET_MAX_LOCI]; };
 
-// per-slot counts of one wavefront's masks: lane l leaves with slot l's count (ballot + popcount: no atomics)
-__device__ __forceinline__ uint32_t set_wave_counts(unsigned long long m, int n_loci, int lane) {
-    uint32_t mine = 0;
-    for (int l = 0; l < n_loci; ++l) {
-        const unsigned long long b = __ballot((int)((m >> l) & 1ull));
-        if (lane == l) mine = (uint32_t)__builtin_popcountll(b);
-    }
-    return mine;
-}
 __global__ void __launch_bounds__(SET_TILE) k_set_route(const unsigned char *__restrict__ text, const uint32_t *__restrict__ rec_off, const uint32_t *__restrict__ rec_len,
                                                         const uint16_t *__restrict__ rec_task, uint32_t n_rec, const SetFL *__restrict__ fl,
                                                         const uint8_t *__restrict__ act, int n_loci, uint32_t n_tiles, unsigned long long *__restrict__ mask,
@@ -2468,37 +2595,13 @@ __global__ void __launch_bounds__(SET_TILE) k_set_route(const unsigned char *__r
     }
     for (int l = 0; l < n_loci; ++l)
         if ((m >> l) & 1ull) atomicMax(&s_klen[l], klen);
-    s_cnt[wv][lane] = set_wave_counts(m, n_loci, lane);
+    s_cnt[wv][lane] = part_wave_counts(m, n_loci, lane);
     __syncthreads();
     if ((int)threadIdx.x < n_loci) {
         uint32_t sum = 0;
         for (int w = 0; w < SET_TILE / 64; ++w) sum += s_cnt[w][threadIdx.x];
         cnt[(size_t)threadIdx.x * n_tiles + blockIdx.x] = sum;                                  // slot-major: one scan gives every slot's list its place
         if (s_klen[threadIdx.x]) atomicMax(&ctl->max_klen[threadIdx.x], s_klen[threadIdx.x]);   // (a maximum: the same whatever the order)
-    }
-}
-// the stable multi-way partition: a record's place in slot l's list = the list's start + the slot's records in the tiles before
-// (the scan) + in this tile's wavefronts before + in the lanes before (ballot, prefix popcount)
-__global__ void __launch_bounds__(SET_TILE) k_set_scatter(const unsigned long long *__restrict__ mask, uint32_t n_rec, int n_loci, uint32_t n_tiles,
-                                                          const uint32_t *__restrict__ base /* [n_loci][n_tiles] */, uint32_t *__restrict__ idx) {
-    __shared__ uint32_t s_cnt[SET_TILE / 64][64];
-    __shared__ uint32_t s_base[SET_TILE / 64][64];
-    const uint32_t i = blockIdx.x * SET_TILE + threadIdx.x;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const unsigned long long m = i < n_rec ? mask[i] : 0ull;
-    s_cnt[wv][lane] = set_wave_counts(m, n_loci, lane);
-    __syncthreads();
-    {
-        uint32_t before = 0;
-        for (int w = 0; w < wv; ++w) before += s_cnt[w][lane];
-        s_base[wv][lane] = before;
-    }
-    __syncthreads();
-    const unsigned long long lanes_before = (1ull << lane) - 1ull;
-    for (int l = 0; l < n_loci; ++l) {
-        const bool mine = (m >> l) & 1ull;
-        const unsigned long long b = __ballot((int)mine);
-        if (mine) idx[base[(size_t)l * n_tiles + blockIdx.x] + s_base[wv][l] + (uint32_t)__builtin_popcountll(b & lanes_before)] = i;
     }
 }
 __device__ __forceinline__ uint32_t set_lower_u16(const uint16_t *a, uint32_t n, uint32_t v) {
@@ -2538,7 +2641,7 @@ struct hgx_alignment_set {
     bool routed = false;
     int n_loci = 0;
     std::vector<std::string> regions;
-    std::vector<uint8_t> slot_host;               // a region list the kernels do not take (several entries): that slot goes per path
+    std::vector<uint8_t> slot_host;               // a region list the kernels do not take, or one the mask has no bits left for: that slot goes per path
     DevBuf idx;                                   // the slots' index lists, slot after slot
     std::vector<uint32_t> slot_start, max_klen;   // [n_loci + 1], [n_loci]
     std::vector<int64_t> kept;                    // [n_loci][n_files]
@@ -2668,29 +2771,47 @@ extern "C" int hgx_alignment_set_route(hgx_alignment_set *s, const char *const *
     int dev = -1;
     HIPCHK(hipGetDevice(&dev));
     const uint32_t n_rec = s->table.n_rec;
-    // (more loci than the mask has bits, or lists that 32-bit positions do not hold: every slot goes per path)
-    if (!s->resident || dev != s->dev || n_loci < 1 || n_loci > SET_MAX_LOCI || (unsigned long long)n_rec * (unsigned long long)n_loci >= (1ull << 32) - 64) return HGX_OK;
+    if (!s->resident || dev != s->dev || n_loci < 1 || n_loci > SET_MAX_LOCI) return HGX_OK;      // (more slots than the mask has bits: every slot goes per path)
     const int n_files = s->n_files;
+    // The mask's bits are (slot, region) PAIRS, slot-major: a slot's regions are neighbours, so its list -- region after region, (file,
+    // file order) inside a region -- is one contiguous piece of the partition's output.  Slots are given their bits in order while
+    // they fit; a slot whose list the kernels do not take (more than HGX_MAX_REGIONS entries) or whose pairs no longer fit goes per path.
+    std::vector<int> pair0((size_t)n_loci + 1, 0), n_reg((size_t)n_loci, 0);
+    std::vector<std::vector<hgx_bam_deferred>> defs((size_t)n_loci);               // [slot][file]
+    int n_pairs = 0;
+    for (int l = 0; l < n_loci; ++l) {
+        pair0[l] = n_pairs;
+        defs[l].resize((size_t)n_files);
+        bool ok = true;
+        for (int f = 0; f < n_files && ok; ++f) ok = hgx_deferred_for_regions(s->regions[l].c_str(), false, s->body0[f], s->refs[f], defs[l][f]) == 0;
+        const int want = ok ? std::max(1, defs[l][0].n_regions()) : 0;             // (nothing filtered: one pair that keeps everything)
+        if (!ok || n_pairs + want > SET_MAX_LOCI) { s->slot_host[l] = 1; continue; }
+        n_reg[l] = want;
+        n_pairs += want;
+    }
+    pair0[(size_t)n_loci] = n_pairs;
+    // (no slot on the device, or lists that 32-bit positions do not hold: every slot goes per path)
+    if (n_pairs < 1 || (unsigned long long)n_rec * (unsigned long long)n_pairs >= (1ull << 32) - 64) return HGX_OK;
     s->slot_start.assign((size_t)n_loci + 1, 0);
     s->max_klen.assign((size_t)n_loci, 0);
     s->kept.assign((size_t)n_loci * (size_t)n_files, 0);
     // every region resolved against every file's own header
-    std::vector<SetFL> fl((size_t)n_files * (size_t)n_loci);
+    std::vector<SetFL> fl((size_t)n_files * (size_t)n_pairs);
     std::vector<uint8_t> acts;
     for (int f = 0; f < n_files; ++f)
-        for (int l = 0; l < n_loci; ++l) {
-            hgx_bam_deferred def;
-            SetFL &G = fl[(size_t)f * n_loci + l];
-            G = SetFL{0, 0, 0u, 0, 1u, 0u};                                  // (filtered, no reference: keeps nothing)
-            if (hgx_deferred_for_regions(s->regions[l].c_str(), false, s->body0[f], s->refs[f], def) != 0) { s->slot_host[l] = 1; continue; }
-            G.left0 = (long long)def.left0; G.right0 = (long long)def.right0;
-            G.act_off = (uint32_t)acts.size(); G.n_ref = (int32_t)def.ref_action.size(); G.filtered = def.filtered ? 1u : 0u;
-            acts.insert(acts.end(), def.ref_action.begin(), def.ref_action.end());
-        }
+        for (int l = 0; l < n_loci; ++l)
+            for (int g = 0; g < n_reg[l]; ++g) {
+                const hgx_bam_deferred &def = defs[l][f];
+                SetFL &G = fl[(size_t)f * n_pairs + pair0[l] + g];
+                G.left0 = (long long)def.left_of(g); G.right0 = (long long)def.right_of(g);
+                G.act_off = (uint32_t)acts.size(); G.n_ref = (int32_t)def.action_of(g).size(); G.filtered = def.filtered ? 1u : 0u; G.pad = 0u;
+                acts.insert(acts.end(), def.action_of(g).begin(), def.action_of(g).end());
+            }
     if (n_rec == 0) { s->routed = true; return HGX_OK; }
     Lap lap(st);
     const uint32_t n_tiles = (n_rec + SET_TILE - 1) / SET_TILE;
-    const size_t n_cnt = (size_t)n_loci * n_tiles;
+    const size_t n_cnt = (size_t)n_pairs * n_tiles;
+    const size_t n_pf = (size_t)n_pairs * (size_t)n_files;
     DevBuf b_fl, b_act, b_ctl, b_mask, b_cnt, b_base, b_tmp, b_kept;
     struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{st};
     ALLOC(b_fl, fl.size() * sizeof(SetFL));
@@ -2700,7 +2821,7 @@ extern "C" int hgx_alignment_set_route(hgx_alignment_set *s, const char *const *
     ALLOC(b_cnt, n_cnt * 4);
     ALLOC(b_base, n_cnt * 4);
     ALLOC(b_tmp, fe_scan_scratch_bytes((long)n_cnt));
-    ALLOC(b_kept, s->kept.size() * 4);
+    ALLOC(b_kept, n_pf * 4);
     HIPCHK(hipMemsetAsync(b_ctl.p, 0, sizeof(SetCtl), st));
     HIPCHK(hipMemsetAsync(b_tmp.p, 0, fe_scan_scratch_bytes((long)n_cnt), st));
     HIPCHK(hipMemcpyAsync(b_fl.p, fl.data(), fl.size() * sizeof(SetFL), hipMemcpyHostToDevice, st));
@@ -2708,7 +2829,7 @@ extern "C" int hgx_alignment_set_route(hgx_alignment_set *s, const char *const *
     SetCtl *ctl = b_ctl.as<SetCtl>();
     const BamTable &T = s->table;
     k_set_route<<<n_tiles, SET_TILE, 0, st>>>(s->text.as<unsigned char>(), (const uint32_t *)T.b_off.p, (const uint32_t *)T.b_len.p, (const uint16_t *)T.b_task.p, n_rec,
-                                             b_fl.as<SetFL>(), b_act.as<uint8_t>(), n_loci, n_tiles, b_mask.as<unsigned long long>(), b_cnt.as<uint32_t>(), ctl);
+                                             b_fl.as<SetFL>(), b_act.as<uint8_t>(), n_pairs, n_tiles, b_mask.as<unsigned long long>(), b_cnt.as<uint32_t>(), ctl);
     {
         FeScanArgs sa{};
         sa.n_ch = 1;
@@ -2723,20 +2844,23 @@ extern "C" int hgx_alignment_set_route(hgx_alignment_set *s, const char *const *
     lap("set: route (masks, counts, scan)");
     if (h.decline) return HGX_OK;                                           // a malformed record some slot keeps: the per-path reader words it
     ALLOC(s->idx, std::max<size_t>(h.total, 1) * 4);
-    k_set_scatter<<<n_tiles, SET_TILE, 0, st>>>(b_mask.as<unsigned long long>(), n_rec, n_loci, n_tiles, b_base.as<uint32_t>(), s->idx.as<uint32_t>());
-    const uint32_t n_lf = (uint32_t)n_loci * (uint32_t)n_files;
-    k_set_kept<<<nblk(n_lf, 256), 256, 0, st>>>((const uint16_t *)T.b_task.p, n_rec, s->idx.as<uint32_t>(), b_base.as<uint32_t>(), n_tiles, n_loci, n_files, h.total,
-                                                b_kept.as<uint32_t>());
+    k_part_scatter<unsigned long long><<<n_tiles, SET_TILE, 0, st>>>(b_mask.as<unsigned long long>(), n_rec, n_pairs, n_tiles, b_base.as<uint32_t>(), s->idx.as<uint32_t>());
+    k_set_kept<<<nblk((uint32_t)n_pf, 256), 256, 0, st>>>((const uint16_t *)T.b_task.p, n_rec, s->idx.as<uint32_t>(), b_base.as<uint32_t>(), n_tiles, n_pairs, n_files, h.total,
+                                                          b_kept.as<uint32_t>());
     HIPCHK(hipGetLastError());
-    std::vector<uint32_t> kept32(s->kept.size());
+    std::vector<uint32_t> kept32(n_pf);
     HIPCHK(hipMemcpyAsync(kept32.data(), b_kept.p, kept32.size() * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     lap("set: partition");
+    // per (slot, file): the sum over the slot's regions; a slot's list: its pairs' lists, one after the other
     for (int l = 0; l < n_loci; ++l) {
         uint32_t sum = 0;
-        for (int f = 0; f < n_files; ++f) { s->kept[(size_t)l * n_files + f] = kept32[(size_t)l * n_files + f]; sum += kept32[(size_t)l * n_files + f]; }
+        for (int g = 0; g < n_reg[l]; ++g) {
+            const size_t pr = (size_t)(pair0[l] + g);
+            for (int f = 0; f < n_files; ++f) { s->kept[(size_t)l * n_files + f] += kept32[pr * n_files + f]; sum += kept32[pr * n_files + f]; }
+            s->max_klen[l] = std::max(s->max_klen[l], h.max_klen[pr]);
+        }
         s->slot_start[(size_t)l + 1] = s->slot_start[l] + sum;
-        s->max_klen[l] = h.max_klen[l];
     }
     if (s->slot_start[(size_t)n_loci] != h.total) { hgx_set_error("hgx_alignment_set_route: the slots' lists do not add up"); return HGX_EHIP; }
     s->routed = true;

@@ -177,12 +177,19 @@ int hgx_bgzf_scan_stream(const unsigned char *data, size_t n, bool last, size_t 
                          size_t *used);
 int hgx_bgzf_scan_par(const unsigned char *data, size_t n, std::vector<hgx_bgzf_block> &blocks, size_t *total_out, int n_threads);   // (the same, ranges on several threads)
 // a BAM whose record walk, region filter and name sort are left to the device front end (hgx_front.hip: k_bam_*): the reader stops
-// after the inflate and the header
+// after the inflate and the header.  A region LIST of up to HGX_MAX_REGIONS entries is expressible: the kernels give the records
+// region after region in the order given, file order inside a region, a record that overlaps several regions once per region
+// (`samtools view F r1 r2`, hgx_read_alignment_lines); region 0 lives in the scalar fields, the others in `more`.
+struct hgx_region_def {
+    std::vector<uint8_t> ref_action;     // [n_ref] as below, this region against the file's own header (BAM)
+    int64_t left0 = 0, right0 = 0;
+    std::string region_whole, region_name;      // (SAM text)
+};
 struct hgx_bam_deferred {
     bool on = false;
     bool on_device = false;              // the inflated stream exists only in the caller's device buffer (it inflated the blocks itself)
     size_t body0 = 0;                    // offset of the first record's block_size in the inflated stream
-    bool filtered = false;               // ONE region was given: per reference what it keeps
+    bool filtered = false;               // a region list was given: per reference what its FIRST region keeps
     std::vector<uint8_t> ref_action;     // [n_ref] 0 = drop, 1 = keep, 2 = keep where [pos0, end0] overlaps [left0, right0]
     int64_t left0 = 0, right0 = 0;
     // SAM TEXT left to the device (round 5): the line table -- newline scan, header / blank lines dropped, region filter on RNAME /
@@ -190,6 +197,13 @@ struct hgx_bam_deferred {
     // region_name (non-empty) the records overlapping [left0, right0] on it (a samtools region string reads both ways).
     bool text = false;
     std::string region_whole, region_name;
+    std::vector<hgx_region_def> more;    // regions 1 .. n - 1 of the list (empty: at most one region)
+    int n_regions() const { return filtered ? 1 + (int)more.size() : 0; }
+    const std::vector<uint8_t> &action_of(int g) const { return g == 0 ? ref_action : more[(size_t)g - 1].ref_action; }
+    int64_t left_of(int g) const { return g == 0 ? left0 : more[(size_t)g - 1].left0; }
+    int64_t right_of(int g) const { return g == 0 ? right0 : more[(size_t)g - 1].right0; }
+    const std::string &whole_of(int g) const { return g == 0 ? region_whole : more[(size_t)g - 1].region_whole; }
+    const std::string &name_of(int g) const { return g == 0 ? region_name : more[(size_t)g - 1].region_name; }
 };
 struct hgx_align_lines {
     char *raw = nullptr;                   // SAM text as read, or the inflated BAM stream (pooled block), or null
@@ -205,7 +219,7 @@ struct hgx_align_lines {
     // [begin, end) of the n_bytes at `raw` there
     std::function<void(const char *raw, size_t n_bytes, size_t begin, size_t end)> on_raw;
     // in: the caller can walk / filter / sort BAM records itself (the device front end) when the inflated stream has at least
-    // defer_min_bytes and at most one region was asked for; out: `deferred.on` -- `lines` is empty then
+    // defer_min_bytes and at most HGX_MAX_REGIONS regions were asked for; out: `deferred.on` -- `lines` is empty then
     bool defer_walk = false;
     // in: keep the records in file order (per region, regions one after the other), no name sort -- `samtools view <file> [region]`
     // without the `sort -k 1,1 -s` behind it, what the linear branch reads (typing_core.py:1597-1599)

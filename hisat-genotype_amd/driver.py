@@ -116,7 +116,8 @@ def genotyping_locus(base_fname, locus_list, genotype_genome, ix_dir, only_locus
     return test_passed
 
 
-def run_panel(tasks, index, base_fname, rank=0, world=1, weights=None, ix_dir=None, inflight=1, many=False, em_fast=False, **typing_opts):
+def run_panel(tasks, index, base_fname, rank=0, world=1, weights=None, ix_dir=None, inflight=1, many=False, em_fast=False,
+              genotype_genome=False, **typing_opts):
     """Type independent (sample_id, gene, sam_text_or_path) tasks; rank `rank` of `world` handles its share
     (deterministic greedy split, no communication).  `index` is the dict from indexio.load_index; with `ix_dir` the
     packed loci come through the binary cache next to the index files (indexio.packed_locus).  `inflight` > 1 types that many
@@ -126,6 +127,9 @@ def run_panel(tasks, index, base_fname, rank=0, world=1, weights=None, ix_dir=No
     task -- the many-samples form, /root/reference/hisatgenotype:613-665); results are identical to the one-by-one form
     (`em_fast` False: the reference's order of floating-point operations; None: hgx_type_many's default, table-lookup arithmetic --
     ~3x faster per panel, abundances within 1e-8).
+    `genotype_genome`: the files are aligned to a genotype genome (typing_core.py:436-444) -- every gene is viewed through the PAIR
+    `chr:left-right` + its backbone and re-based to its locus (index["refGene_loci"]); a region list goes through the device front
+    end like one region.
     Returns {(sample_id, gene): LocusResult} for this rank's tasks."""
     import threading
     from . import capi
@@ -144,6 +148,13 @@ def run_panel(tasks, index, base_fname, rank=0, world=1, weights=None, ix_dir=No
         packed[gene].index()                     # device index created once, before any worker needs it
     out = {}
 
+    def gene_opts(gene):
+        # the view of this gene's records: its backbone (core:443-444), in genotype-genome mode the locus span on the chromosome too
+        if not genotype_genome:
+            return {"regions": typing_opts.get("regions", [packed[gene].ref_allele])}
+        _, chr_, left, right = index["refGene_loci"][gene][:4]
+        return {"regions": ["%s:%d-%d" % (chr_, left + 1, right + 1), packed[gene].ref_allele], "base_locus": left}
+
     from . import engine
     heavy = engine.Gate() if inflight > 1 else None          # one bandwidth-bound front (scoring, exon dedup) at a time
 
@@ -154,7 +165,7 @@ def run_panel(tasks, index, base_fname, rank=0, world=1, weights=None, ix_dir=No
         # a SAM / BAM path: read, grouped and decoded inside libhgx
         # (the view is restricted to the gene's backbone, as the reference's `samtools view F ref_allele` does, core:443-444)
         opts = dict(typing_opts)
-        opts.setdefault("regions", [packed[gene].ref_allele])
+        opts.update(gene_opts(gene))
         return (sample_id, gene), type_locus(packed[gene], None, alignment_file=sam, stream=stream, gate=heavy, **opts)
 
     if many:
@@ -173,12 +184,14 @@ def run_panel(tasks, index, base_fname, rank=0, world=1, weights=None, ix_dir=No
                 not any(isinstance(sam, (bytes, bytearray)) or "\t" in sam for sam in file_lists[0]):
             set_regions = []
             for gene in by_gene:
-                regions = typing_opts.get("regions", [packed[gene].ref_allele])
+                regions = gene_opts(gene)["regions"]
                 set_regions.append(regions if isinstance(regions, str) else "\n".join(regions))
                 slot_of[gene] = len(slot_of)
             aset = engine.AlignmentSet(file_lists[0]).route(set_regions)
         for gene, group in by_gene.items():
             pl = packed[gene]
+            gopts = gene_opts(gene)
+            popts = {k: v for k, v in dict(typing_opts, **gopts).items() if k in parse_keys}
             is_text = [isinstance(sam, (bytes, bytearray)) or "\t" in sam for _, _, sam in group]
             if aset is not None:
                 mb = engine.ManyBatch.from_set(pl, aset, slot_of[gene], **popts)
@@ -188,7 +201,7 @@ def run_panel(tasks, index, base_fname, rank=0, world=1, weights=None, ix_dir=No
                 if all(is_text):
                     mb = engine.ManyBatch.from_sams(pl, [sam for _, _, sam in group], **popts)
                 else:
-                    regions = typing_opts.get("regions", [pl.ref_allele])
+                    regions = gopts["regions"]
                     regions = regions if isinstance(regions, str) else "\n".join(regions)
                     mb = engine.ManyBatch.from_files(pl, [sam for _, _, sam in group], regions=[regions] * len(group), **popts)
             else:
@@ -197,7 +210,7 @@ def run_panel(tasks, index, base_fname, rank=0, world=1, weights=None, ix_dir=No
                     if text:
                         batches.append(pl.parse_sam(sam, **popts))
                     else:
-                        batches.append(pl.parse_alignment_file(sam, typing_opts.get("regions", [pl.ref_allele]), **popts))
+                        batches.append(pl.parse_alignment_file(sam, gopts["regions"], **popts))
                 mb = engine.ManyBatch(pl, batches)
             try:
                 res = type_many(pl, mb, remove_low=typing_opts.get("remove_low_abundance_alleles", True), em_fast=em_fast)

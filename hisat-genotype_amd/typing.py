@@ -403,7 +403,8 @@ def _many_from_set_side_by_side(pls, aset, slots, **parse_opts):
 def type_panel_files(pls, paths, regions=None, remove_low=True, em_fast=None, **parse_opts):
     """A panel from one alignment file per sample, each file holding every locus' records (hisatgenotype:613-665 x
     typing_core.py:370, 436-468): ONE engine.AlignmentSet (the files read, sent, inflated and walked once), ONE route, the loci's
-    many-task batches made side by side, ONE type_many_loci.  `regions`: one samtools region per locus (default: its ref_allele).
+    many-task batches made side by side, ONE type_many_loci.  `regions`: per locus one samtools region string or a LIST of them (default:
+    its ref_allele; genotype-genome mode: ["chr:left-right", ref_allele] with base_locus=left) -- up to 8 regions stay on the device.
     Returns {(file_index, gene): LocusResult}, each identical to type_locus on that file and region."""
     pls = list(pls)
     regions = [pl.ref_allele for pl in pls] if regions is None else list(regions)

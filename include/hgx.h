@@ -422,6 +422,9 @@ int hgx_parse_sam(hgx_batch **out, const hgx_locus *loc, const char *sam, size_t
  * alignment never reach this locus' decode.
  * *text_out is a library-owned (pooled), NUL-terminated buffer of *n_bytes_out bytes (every record ends
  * in '\n'), ready for hgx_parse_sam; release it with hgx_free_text (not free()).  n_threads <= 0: the host's hardware threads, capped at twice the container's cgroup CPU quota if it has one (HGX_THREADS overrides). */
+/* the longest region list the DEVICE front end takes (hgx_parse_alignment_file_dev, hgx_type_file, hgx_alignment_parse_dev,
+ * hgx_many_create_files, a slot of hgx_alignment_set_route); a longer list is read, filtered and sorted by the host reader */
+#define HGX_MAX_REGIONS 8
 int hgx_read_alignments(const char *path, const char *regions_or_null, int32_t n_threads, char **text_out, size_t *n_bytes_out);
 int hgx_free_text(char *text);
 /* hgx_read_alignments + hgx_parse_sam in one call: the reader's buffer is tokenised in place (no copy, no trip through the
@@ -511,7 +514,7 @@ int hgx_type_file(hgx_typing **out, const hgx_locus *loc, const hgx_index *ix, c
  * the same batch either way, and hgx_front_last says which way the calling thread's last call went (route: 2 = record route,
  * 1 = key route, 0 = host stages; decline_code: see HGX_FE_DECLINE_* / FE_E_* in csrc/hgx_internal.hpp,
  * csrc/hgx_front_core.hpp).  hgx_type_file goes through hgx_parse_alignment_file_dev.
- * A BAM file (with at most one region) does not even get inflated on the host: the host reads it, hops through the BGZF container
+ * A BAM file (with a list of at most HGX_MAX_REGIONS regions) does not even get inflated on the host: the host reads it, hops through the BGZF container
  * and inflates the block(s) holding the BAM header; the deflated bytes go up, and BGZF inflate (csrc/hgx_inflate.hip), the record
  * chain walk, the region filter (samtools' overlap rule, typing_core.py:438-444) and the stable sort by read name
  * (`sort -k 1,1 -s`, typing_core.py:436-468) run as kernels in front of the record route.  A block that fails CRC-32 / ISIZE, a
@@ -528,7 +531,7 @@ int hgx_front_last_parts(int32_t *parts);
  * leaves its bytes in HBM: the SAM text, or the BAM stream inflated on the device; hgx_alignment_parse_dev is the per-locus rest --
  * region filter, name order and the record route of hgx_parse_alignment_file_dev as kernels over those resident bytes (read-only: the
  * loci of a panel may be parsed side by side from threads with streams of their own).  The batch is the one
- * hgx_parse_alignment_file_dev(path, regions) builds; a locus the kernels decline, a region list with several entries, a file below
+ * hgx_parse_alignment_file_dev(path, regions) builds; a locus the kernels decline, a region list of more than HGX_MAX_REGIONS entries, a file below
  * the device front end's size gate or beyond 4 GB of stream go through exactly that call on the path (hgx_front_last tells).
  * hgx_alignment_dims: resident = the bytes are in HBM (0: every locus takes the per-path call). */
 typedef struct hgx_alignment hgx_alignment;
@@ -552,7 +555,9 @@ int hgx_alignment_close(hgx_alignment *al);
  * NOT resident (hgx_alignment_set_dims): a SAM-text member, a set below the device front end's size gate, 4 GB or more of inflated
  * stream, more than 65 535 files, a file that cannot be read or does not inflate / link up, the test switches front=host /
  * host_inflate.  hgx_many_create_set is then exactly that hgx_many_create_files call -- as it is for more than 64 slots, for a slot
- * whose region string lists several regions and for a slot the kernels decline -- and the per-path code words the errors.
+ * whose region string lists more than HGX_MAX_REGIONS regions or whose (slot, region) pairs no longer fit the 64-bit mask (a slot's
+ * string may list several regions: the mask's bits are then (slot, region) pairs, given to the slots in order) and for a slot the
+ * kernels decline -- and the per-path code words the errors.
  * hgx_alignment_set_routed: n_kept[slot][file], the records each slot keeps of each file (HGX_EINVAL unless routed on the device).
  * hgx_alignment_set_info: records per workgroup tile of the partition kernels, slots a route takes, bytes of the BGZF block tables
  * that went up beside the files' bytes (`s` may be NULL for the constants). */
@@ -561,7 +566,7 @@ int hgx_alignment_set_open(hgx_alignment_set **out, const char *const *paths, in
 int hgx_alignment_set_dims(const hgx_alignment_set *s, int32_t *n_files, int32_t *resident, size_t *stream_bytes, long long *bytes_to_device,
                            int64_t *n_records);
 int hgx_alignment_set_info(const hgx_alignment_set *s, int32_t *route_tile, int32_t *max_loci, int64_t *block_table_bytes);
-int hgx_alignment_set_route(hgx_alignment_set *s, const char *const *regions /* [n_loci], one samtools region each */, int32_t n_loci, void *stream);
+int hgx_alignment_set_route(hgx_alignment_set *s, const char *const *regions /* [n_loci], a samtools region list each ('\n' between regions) */, int32_t n_loci, void *stream);
 int hgx_alignment_set_routed(const hgx_alignment_set *s, int64_t *n_kept /* [n_loci][n_files] */);
 int hgx_alignment_set_close(hgx_alignment_set *s);
 /* a device batch back on the host (tests, tools): pieces, masks, refs, and the pileup tables if the kernels made them */
