@@ -271,3 +271,12 @@ def write_bam_native(path, sam_text, refs, sort_by_coordinate=False, n_threads=0
     lens = np.array([ln for _, ln in refs] or [0], np.int32)
     capi.check(capi.lib().hgx_write_bam(path.encode(), data, C.c_size_t(len(data)), names, capi.ptr(lens), C.c_int32(len(refs)),
                                         C.c_int32(int(bool(sort_by_coordinate))), C.c_int32(n_threads)))
+
+
+def index_bam(path, out=None, n_threads=0):
+    """Write the index of a coordinate-sorted BAM (`samtools index`; hgx_bam_index_build): `out` or <path>.bai.  With an index beside
+    it, a region read of a large BAM touches only the blocks that hold the region (typing() builds none on its own)."""
+    import ctypes as C
+    from . import capi
+    capi.check(capi.lib().hgx_bam_index_build(path.encode(), out.encode() if out else None, C.c_int32(n_threads)))
+    return out or path + ".bai"

@@ -81,6 +81,7 @@ SYMBOLS = [
     "hgx_linear_input_open", "hgx_linear_input_dims", "hgx_linear_type_input", "hgx_linear_input_close",
     "hgx_alignment_set_open", "hgx_alignment_set_dims", "hgx_alignment_set_info", "hgx_alignment_set_route", "hgx_alignment_set_routed",
     "hgx_alignment_set_close", "hgx_many_create_set",
+    "hgx_bam_index_build", "hgx_bam_index_last", "hgx_bam_splice",
     "hgx_extract_open", "hgx_extract_feed", "hgx_extract_feed_bam", "hgx_extract_file", "hgx_extract_take", "hgx_extract_stats", "hgx_extract_close",
 ]
 

@@ -569,7 +569,293 @@ bool peek_is_bam(const unsigned char *data, const std::vector<hgx_bgzf_block> &b
     return false;
 }
 
+// ---- a region list through the file's index (hgx_bai.cpp) ----------------------------------------------------------
+// `samtools view file chr:left-right` touches the few BGZF blocks the .bai names.  So does this: the BAM header from the file's first
+// blocks, the segments the index plans for the region list, only their blocks read and inflated, and `raw` = the header's bytes up to
+// the first record followed by every segment's bytes from its first record to its end -- a well-formed inflated BAM stream that
+// holds every record the regions keep (and some they do not: the region filter behind it is the one every stream goes through).
+// The index is never trusted: each segment's record chain must start at its first byte and land exactly on its end, or the call
+// drops the index and reads the whole file, which words any error.
+struct BaiReport { int32_t used = 0, why = HGX_BAI_NONE; int64_t bytes = 0; int32_t n_seg = 0; int64_t n_blocks = 0; };
+thread_local BaiReport g_bai_last;
+
+bool pread_all(int fd, unsigned char *dst, size_t n, size_t at) {
+    size_t got_all = 0;
+    while (got_all < n) {
+        const ssize_t got = pread(fd, dst + got_all, n - got_all, (off_t)(at + got_all));
+        if (got <= 0) return false;
+        got_all += (size_t)got;
+    }
+    return true;
+}
+
+// length of the BGZF block whose header lies at `off` (its first bytes only are read); 0 = not told by the usual 18-byte header
+size_t bgzf_block_len_at(int fd, size_t off, size_t file_size) {
+    unsigned char h[18];
+    if (off + 18 > file_size || !pread_all(fd, h, 18, off)) return 0;
+    if (h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || !(h[3] & 4) || rd16(h + 10) < 6 || h[12] != 66 || h[13] != 67 || rd16(h + 14) != 2) return 0;
+    return (size_t)rd16(h + 16) + 1;
+}
+
+// the BAM header out of a growing prefix of the file (16 KB, x4 up to 64 MB); `head` = the inflated bytes it was parsed from
+bool bai_read_header(int fd, size_t file_size, std::vector<unsigned char> &head, std::vector<std::string> &refs, size_t *body0, size_t *bytes_read) {
+    std::vector<unsigned char> pre;
+    std::vector<hgx_bgzf_block> blocks;
+    for (size_t want = 16u << 10;; want *= 4) {
+        const size_t n = std::min(want, file_size);
+        pre.resize(n);
+        if (!pread_all(fd, pre.data(), n, 0)) return false;
+        *bytes_read += n;                                     // (a prefix that grows is read again from the file's first byte)
+        size_t total = 0, used = 0;
+        if (hgx_bgzf_scan_stream(pre.data(), n, n == file_size, 0, blocks, &total, &used) != HGX_OK) return false;
+        head.clear();
+        int st = 0;
+        for (size_t k = 0; k < blocks.size() && st == 0; ++k) {
+            if (blocks[k].out_len > 65536 || head.size() > (64u << 20)) return false;
+            const size_t at = head.size();
+            head.resize(at + blocks[k].out_len);
+            if (!inflate_one(pre.data(), blocks[k], head.data() + at)) return false;
+            st = parse_bam_header(head.data(), head.size(), refs, body0);
+        }
+        if (st == 1) return true;
+        if (st < 0 || n == file_size || want >= (64u << 20)) return false;
+    }
+}
+
+// 0 = the index was not used (g_bai_last says why), 1 = `raw` is the stream, 2 = the stream lies in the caller's device buffer
+// (`dev` given: out.splice_dev took the selected blocks; `dev`'s deferred descriptor is filled)
+int read_through_index(const char *path, const std::vector<Region> &regs, bool filtered, int n_threads, Bytes &raw, hgx_align_lines *dev) {
+    BaiReport &rep = g_bai_last;
+    rep = BaiReport();
+    const char *sw = hgx_test_switch("bai");
+    if (sw && strcmp(sw, "off") == 0) { rep.why = HGX_BAI_OFF; return 0; }
+    const bool force = sw && strcmp(sw, "force") == 0;
+    if (!filtered) { rep.why = HGX_BAI_NO_REGIONS; return 0; }
+    const int fd = open(path, O_RDONLY);
+    if (fd < 0) return 0;                                        // (the ordinary path words the error)
+    struct Closer { int fd; ~Closer() { close(fd); } } closer{fd};
+    struct stat sb;
+    unsigned char magic[2] = {0, 0};
+    if (fstat(fd, &sb) != 0 || sb.st_size < 28 || !pread_all(fd, magic, 2, 0) || magic[0] != 0x1f || magic[1] != 0x8b) { rep.why = HGX_BAI_NOT_BGZF; return 0; }
+    const size_t file_size = (size_t)sb.st_size;
+    if (!force && file_size < HGX_BAI_MIN_BYTES) { rep.why = HGX_BAI_SMALL; return 0; }
+    hgx_bai_index ix;
+    const int lr = hgx_bai_load(path, ix);
+    if (lr) { rep.why = lr == 1 ? HGX_BAI_NONE : HGX_BAI_UNUSABLE; return 0; }
+    std::vector<unsigned char> head;
+    std::vector<std::string> refs;
+    size_t body0 = 0, head_read = 0;
+    if (!bai_read_header(fd, file_size, head, refs, &body0, &head_read)) { rep.why = HGX_BAI_NOT_BGZF; return 0; }
+    if (refs.size() != ix.refs.size()) { rep.why = HGX_BAI_UNUSABLE; return 0; }
+    // ---- plan ------------------------------------------------------------------------------------------------------------
+    std::vector<hgx_bai_chunk> chunks, segs;
+    if (!regs.empty()) {
+        hgx_bam_deferred d;
+        fill_deferred_regions(d, regs, true, false, refs);
+        for (int g = 0; g < d.n_regions(); ++g) {
+            const std::vector<uint8_t> &act = d.action_of(g);
+            const int64_t l0 = d.left_of(g), r0 = d.right_of(g);
+            for (size_t i = 0; i < act.size(); ++i) {
+                bool ok = true;
+                if (act[i] == 1) ok = hgx_bai_query(ix, (int32_t)i, 0, (int64_t)1 << 29, chunks);
+                else if (act[i] == 2) ok = r0 >= l0 && hgx_bai_query(ix, (int32_t)i, l0, r0 == INT64_MAX ? ((int64_t)1 << 29) : r0 + 1, chunks);
+                if (!ok) { rep.why = HGX_BAI_UNUSABLE; return 0; }         // (positions the binning scheme does not reach; an inverted span)
+            }
+        }
+    }
+    hgx_bai_plan(chunks, segs);
+    // ---- read the segments' byte ranges and hop their block headers -----------------------------------------------------------
+    struct SegIO {
+        size_t file_beg = 0, len = 0, comp_at = 0;          // the byte range read, and where it lies in `comp`
+        std::vector<hgx_bgzf_block> blocks;                 // the selected blocks (offsets within the range; out_off within the segment)
+        size_t lo = 0, hi = 0;                              // [first record, end) in the segment's inflated bytes
+        size_t dense_at = 0;                                // ... and where they go in `raw`
+    };
+    std::vector<SegIO> io(segs.size());
+    size_t comp_total = 0;
+    if (!hgx_bai_plan_fits(segs, file_size)) { rep.why = HGX_BAI_INFLATE; return 0; }
+    for (size_t s = 0; s < segs.size(); ++s) {
+        const uint64_t fb = segs[s].beg >> 16, fe = segs[s].end >> 16;
+        const unsigned ue = (unsigned)(segs[s].end & 0xffff);
+        io[s].file_beg = (size_t)fb;
+        // the end block is read whole: its length from its header, or -- an extra field laid out another way -- the 64 KB a block may take
+        const size_t end_len = ue ? bgzf_block_len_at(fd, (size_t)fe, file_size) : 0;
+        io[s].len = (size_t)((ue ? std::min<uint64_t>(file_size, fe + (end_len ? end_len : 65536)) : fe) - fb);
+        io[s].comp_at = comp_total;
+        comp_total += (io[s].len + 63) & ~(size_t)63;
+    }
+    Bytes comp;
+    comp.alloc(comp_total + 1);
+    {
+        std::vector<int> bad((size_t)n_threads, 0);
+        for (size_t s = 0; s < segs.size(); ++s)
+            par_for(io[s].len > (8u << 20) ? n_threads : 1, io[s].len, [&](int t, size_t b, size_t e) {
+                if (e > b && !pread_all(fd, comp.data() + io[s].comp_at + b, e - b, io[s].file_beg + b)) bad[(size_t)t] = 1;
+            });
+        for (int v : bad) if (v) { rep.why = HGX_BAI_INFLATE; return 0; }
+    }
+    size_t dense_total = body0, n_blocks = 0, bytes_read = head_read;
+    for (size_t s = 0; s < segs.size(); ++s) {
+        SegIO &S = io[s];
+        const size_t want_end = (size_t)((segs[s].end >> 16) - (segs[s].beg >> 16));     // the end block's header, within the range
+        const unsigned ub = (unsigned)(segs[s].beg & 0xffff), ue = (unsigned)(segs[s].end & 0xffff);
+        size_t total = 0, used = 0;
+        if (hgx_bgzf_scan_stream(comp.data() + S.comp_at, S.len, S.file_beg + S.len == file_size, S.file_beg, S.blocks, &total, &used) != HGX_OK) { rep.why = HGX_BAI_INFLATE; return 0; }
+        size_t hdr = 0, keep = 0, stage = 0;
+        bool linked = false;
+        for (; keep < S.blocks.size(); ++keep) {                  // the block table must link up: a header exactly where the segment ends
+            if (hdr == want_end) { linked = true; if (ue) ++keep; break; }
+            if (hdr > want_end) break;
+            hdr = S.blocks[keep].in_off + S.blocks[keep].in_len + 8;
+        }
+        if (!linked && !ue && keep == S.blocks.size() && hdr == want_end) linked = true;
+        if (!linked || keep == 0 || keep > S.blocks.size()) { rep.why = HGX_BAI_INFLATE; return 0; }
+        S.blocks.resize(keep);
+        for (hgx_bgzf_block &b : S.blocks) {
+            if (b.out_len > 65536) { rep.why = HGX_BAI_INFLATE; return 0; }
+            b.out_off = stage;
+            stage += b.out_len;
+        }
+        S.lo = ub;
+        S.hi = ue ? stage - S.blocks.back().out_len + ue : stage;
+        if ((ue && ue > S.blocks.back().out_len) || S.lo > S.hi || S.hi > stage) { rep.why = HGX_BAI_CHAIN; return 0; }
+        S.dense_at = dense_total;
+        dense_total += S.hi - S.lo;
+        n_blocks += S.blocks.size();
+        bytes_read += S.len;
+    }
+    // ---- the device route: the selected blocks go up as they are; inflate and splice are the caller's kernels ----------------------------
+    if (dev && dev->splice_dev && dense_total - body0 >= std::max<size_t>(dev->defer_min_bytes, 1) && refs.size() < 65536) {
+        std::vector<hgx_bgzf_block> all;
+        std::vector<std::pair<uint64_t, uint64_t>> parts;
+        all.reserve(n_blocks);
+        size_t staged = 0;
+        for (const SegIO &S : io) {
+            for (hgx_bgzf_block b : S.blocks) { b.in_off += S.comp_at; b.out_off += staged; all.push_back(b); }
+            parts.emplace_back((uint64_t)(staged + S.lo), (uint64_t)(S.hi - S.lo));
+            staged += S.blocks.back().out_off + S.blocks.back().out_len;
+        }
+        if (dev->splice_dev(comp.data(), comp_total, all, staged, parts, dense_total - body0) == 0) {
+            hgx_bam_deferred &d = dev->deferred;
+            d = hgx_bam_deferred();
+            d.on = true;
+            d.on_device = true;
+            d.body0 = 0;                                           // (the spliced stream holds records only)
+            fill_deferred_regions(d, regs, true, false, refs);
+            dev->binary = true;
+            dev->ref_names = refs;
+            dev->lines.clear();
+            hgx_host_free(dev->raw);
+            dev->raw = nullptr;
+            dev->raw_bytes = dense_total - body0;
+            rep.used = 1;
+            rep.why = HGX_BAI_USED;
+            rep.bytes = (int64_t)bytes_read;
+            rep.n_seg = (int32_t)segs.size();
+            rep.n_blocks = (int64_t)n_blocks;
+            return 2;
+        }
+    }
+    // ---- inflate the selected blocks straight to their place; a segment's edge blocks through a buffer ----------------------------
+    raw.alloc(dense_total + 1);
+    raw.n = dense_total;
+    memcpy(raw.data(), head.data(), body0);
+    {
+        struct Job { uint32_t seg, blk; };
+        std::vector<Job> jobs;
+        jobs.reserve(n_blocks);
+        for (size_t s = 0; s < segs.size(); ++s)
+            for (size_t k = 0; k < io[s].blocks.size(); ++k) jobs.push_back(Job{(uint32_t)s, (uint32_t)k});
+        const FastInflate *fi = fast_inflate();
+        std::vector<int> bad((size_t)n_threads, 0);
+        par_for(jobs.size() >= 64 ? n_threads : 1, jobs.size(), [&](int t, size_t j0, size_t j1) {
+            void *dec = fi ? fi->alloc() : nullptr;
+            std::vector<unsigned char> tmp;
+            for (size_t j = j0; j < j1 && !bad[(size_t)t]; ++j) {
+                const SegIO &S = io[jobs[j].seg];
+                const hgx_bgzf_block &b = S.blocks[jobs[j].blk];
+                const size_t a = std::max(b.out_off, S.lo), z = std::min(b.out_off + b.out_len, S.hi);
+                if (a >= z) continue;
+                const bool whole = a == b.out_off && z == b.out_off + b.out_len;
+                if (!whole) tmp.resize(65536);
+                unsigned char *dst = whole ? raw.data() + S.dense_at + (a - S.lo) : tmp.data();
+                const unsigned char *src = comp.data() + S.comp_at;
+                bool ok;
+                if (dec) {
+                    size_t got = 0;
+                    ok = fi->decompress(dec, src + b.in_off, b.in_len, dst, b.out_len, &got) == 0 && got == b.out_len && fi->crc32(0, dst, b.out_len) == b.crc;
+                } else ok = inflate_one(src, b, dst);
+                if (!ok) { bad[(size_t)t] = 1; break; }
+                if (!whole) memcpy(raw.data() + S.dense_at + (a - S.lo), tmp.data() + (a - b.out_off), z - a);
+            }
+            if (dec) fi->release(dec);
+        });
+        for (int v : bad) if (v) { raw.release(); rep.why = HGX_BAI_INFLATE; return 0; }
+    }
+    // ---- the guard: every segment is a whole number of records ------------------------------------------------------------------
+    {
+        std::vector<int> bad(segs.size() + 1, 0);
+        const int32_t n_ref = (int32_t)refs.size();
+        par_for(n_threads, segs.size(), [&](int, size_t s0, size_t s1) {
+            for (size_t s = s0; s < s1; ++s) {
+                size_t q = io[s].dense_at;
+                const size_t end = q + (io[s].hi - io[s].lo);
+                while (q < end) {
+                    if (q + 36 > end) break;
+                    const uint32_t bs = rd32(&raw[q]);
+                    const unsigned char *r = &raw[q + 4];
+                    const int32_t rid = rdi32(r);
+                    if (bs < 32 || q + 4 + (size_t)bs > end || rid < -1 || rid >= n_ref || r[8] == 0 || 32 + (size_t)r[8] + 4 * (size_t)rd16(r + 12) > bs) break;
+                    q += 4 + (size_t)bs;
+                }
+                if (q != end) bad[s] = 1;
+            }
+        });
+        for (int v : bad) if (v) { raw.release(); rep.why = HGX_BAI_CHAIN; return 0; }
+    }
+    rep.used = 1;
+    rep.why = HGX_BAI_USED;
+    rep.bytes = (int64_t)bytes_read;
+    rep.n_seg = (int32_t)segs.size();
+    rep.n_blocks = (int64_t)n_blocks;
+    return 1;
+}
+
 }   // namespace
+
+bool hgx_bam_has_index(const char *path) {
+    BaiReport &rep = g_bai_last;
+    rep = BaiReport();
+    const char *sw = hgx_test_switch("bai");
+    if (sw && strcmp(sw, "off") == 0) { rep.why = HGX_BAI_OFF; return false; }
+    const int fd = open(path, O_RDONLY);
+    if (fd < 0) return false;
+    struct Closer { int fd; ~Closer() { close(fd); } } closer{fd};
+    struct stat sb;
+    unsigned char magic[2] = {0, 0};
+    if (fstat(fd, &sb) != 0 || sb.st_size < 28 || !pread_all(fd, magic, 2, 0) || magic[0] != 0x1f || magic[1] != 0x8b) { rep.why = HGX_BAI_NOT_BGZF; return false; }
+    hgx_bai_index ix;
+    const int lr = hgx_bai_load(path, ix);
+    if (lr) { rep.why = lr == 1 ? HGX_BAI_NONE : HGX_BAI_UNUSABLE; return false; }
+    std::vector<unsigned char> head;
+    std::vector<std::string> refs;
+    size_t body0 = 0, head_read = 0;
+    if (!bai_read_header(fd, (size_t)sb.st_size, head, refs, &body0, &head_read)) { rep.why = HGX_BAI_NOT_BGZF; return false; }
+    if (refs.size() != ix.refs.size()) { rep.why = HGX_BAI_UNUSABLE; return false; }
+    rep.used = 1;
+    rep.why = HGX_BAI_USED;
+    rep.bytes = (int64_t)head_read;
+    return true;
+}
+
+extern "C" int hgx_bam_index_last(int32_t *used, int32_t *why_not, int64_t *file_bytes_read, int32_t *n_segments, int64_t *n_blocks) {
+    if (used) *used = g_bai_last.used;
+    if (why_not) *why_not = g_bai_last.why;
+    if (file_bytes_read) *file_bytes_read = g_bai_last.bytes;
+    if (n_segments) *n_segments = g_bai_last.n_seg;
+    if (n_blocks) *n_blocks = g_bai_last.n_blocks;
+    return HGX_OK;
+}
 
 // The reader's pieces a BAM STREAM needs one at a time (read extraction, hgx_extract.hip: the file arrives in chunks): the header
 // parser (1 = complete, 0 = more bytes needed, -1 = no BAM), one BGZF block through zlib, and one record as the line `samtools view`
@@ -640,8 +926,16 @@ int hgx_read_alignment_lines(const char *path, const char *regions, int n_thread
     bool on_raw_done = false;
     int text_nt = 0;
     bool text_scanned = false, text_defer = false;
+    // a region list on a BGZF file with a usable index beside it: only the blocks the index names are read; `raw_ix` is
+    // then the inflated stream everything below the inflate works on, and the file is not read here
+    Bytes raw_ix;
+    const bool dev_ok = keep_binary && out.defer_walk && out.splice_dev && regions_defer(regs, filtered);
+    const int ix_rc = read_through_index(path, regs, filtered, n_threads, raw_ix, dev_ok ? &out : nullptr);
+    const bool via_index = ix_rc != 0;
+    if (via_index) lap("index: header + segments");
+    if (ix_rc == 2) return HGX_OK;                                   // (inflate, splice, walk, filter, sort: the device)
     Bytes data;
-    {
+    if (!via_index) {
         const int fd = open(path, O_RDONLY);
         if (fd < 0) { hgx_set_error("cannot open %s", path); return HGX_EINVAL; }
         struct stat sb;
@@ -760,8 +1054,9 @@ int hgx_read_alignment_lines(const char *path, const char *regions, int n_thread
             for (int v : bad) if (v) { hgx_set_error("short read on %s", path); return HGX_EINVAL; }
         }
     }
-    lap(text_scanned ? "read file + lines" : "read file");
+    if (!via_index) lap(text_scanned ? "read file + lines" : "read file");
     Bytes raw;
+    if (via_index) raw.swap(raw_ix);
     if (data.size() >= 2 && data[0] == 0x1f && data[1] == 0x8b && keep_binary && out.defer_walk && out.inflate_dev && regions_defer(regs, filtered)) {
         // The caller inflates, walks, filters and sorts on the device: the host hops through the container, inflates the block(s) that
         // hold the BAM header to learn the references and where the records begin, and hands the deflated bytes over.  Whatever
@@ -844,7 +1139,7 @@ int hgx_read_alignment_lines(const char *path, const char *regions, int n_thread
         if (out.comp_sync) out.comp_sync();                    // (an upload of these bytes begun by comp_early may still be reading them: on
         if (rc) return rc;                                     //  EVERY way out of here that gives `data` back)
         data.release();
-    } else raw.swap(data);
+    } else if (!via_index) raw.swap(data);
     lap("inflate");
     if (out.on_raw && !on_raw_done) out.on_raw((const char *)raw.data(), raw.size(), 0, raw.size());       // (the device front end's upload starts here)
     LineVec &lines = out.lines;
@@ -865,7 +1160,7 @@ int hgx_read_alignment_lines(const char *path, const char *regions, int n_thread
             p += 4 + l_name + 4;
         }
         if (keep_binary && out.defer_walk && regions_defer(regs, filtered) && n - p >= out.defer_min_bytes &&
-            n < (1ull << 32) - 64 && refs.size() < 65536) {
+            n < (1ull << 32) - 64 && refs.size() < 65536 && !(via_index && n == p)) {      // (an index that names no block: nothing to walk)
             // the caller walks, filters and sorts the records itself (the device front end): hand the stream over as it is
             hgx_bam_deferred &d = out.deferred;
             d.on = true;
@@ -1140,10 +1435,52 @@ int hgx_bgzf_tasks_read(std::vector<hgx_bgzf_task> &tasks, const char *const *pa
     tasks.resize((size_t)n_tasks);
     if (n_threads <= 0) n_threads = hgx_default_threads();
     n_threads = std::max(1, std::min(n_threads, 512));
+    std::vector<BaiReport> bai_used((size_t)n_tasks);              // what each task's reader (a pool thread) did with its file's index
     hgx_par_tasks(std::min(n_threads, std::max(n_tasks, 1)), (size_t)n_tasks, [&](int, size_t t) {
         hgx_bgzf_task &T = tasks[t];
         try {
             if (!paths[t]) return;
+            {
+                // a region list the file's index answers: the task is the blocks the index names, not the file (read_through_index hands
+                // them to splice_dev: kept here as they are, for the pass's one inflate launch and the task's splice)
+                const std::vector<Region> regs_ix = parse_regions(regions ? regions[t] : nullptr);
+                const bool filtered_ix = regions && regions[t] && regions[t][0] != 0;
+                if (regions_defer(regs_ix, filtered_ix) && filtered_ix) {
+                    hgx_align_lines tmp;
+                    tmp.defer_walk = true;
+                    tmp.splice_dev = [&](const unsigned char *comp, size_t n, const std::vector<hgx_bgzf_block> &blocks, size_t staged,
+                                         const std::vector<std::pair<uint64_t, uint64_t>> &parts, size_t total) -> int {
+                        if (staged >= (1ull << 32) - 64 || total >= (1ull << 32) - 64) return 1;
+                        {
+                            std::unique_ptr<hgx_big_alloc_scope> pinned;
+                            if (mem && mem->alloc) pinned.reset(new hgx_big_alloc_scope(*mem, 64u << 10));
+                            T.data = (unsigned char *)hgx_host_alloc(n + 1);
+                        }
+                        memcpy(T.data, comp, n);
+                        T.n = n;
+                        T.blocks = blocks;
+                        T.staged = staged;
+                        T.parts = parts;
+                        T.total = total;
+                        return 0;
+                    };
+                    Bytes unused;
+                    const int ix_rc = read_through_index(paths[t], regs_ix, true, 1, unused, &tmp);
+                    bai_used[t] = g_bai_last;
+                    if (ix_rc == 2) {
+                        T.indexed = true;
+                        T.def = tmp.deferred;
+                        T.refs = tmp.ref_names;
+                        T.ok = true;
+                        if (on_task) on_task((int)t);
+                        return;
+                    }
+                    hgx_host_free(T.data);
+                    T.data = nullptr;
+                    T.n = 0;
+                    T.blocks.clear();
+                }
+            }
             const int fd = open(paths[t], O_RDONLY);
             if (fd < 0) return;
             struct stat sb;
@@ -1186,6 +1523,14 @@ int hgx_bgzf_tasks_read(std::vector<hgx_bgzf_task> &tasks, const char *const *pa
             T.ok = false;
         }
     });
+    // hgx_bam_index_last on the calling thread: the pass as a whole -- used = the tasks that went through their index, the rest summed
+    BaiReport sum;
+    sum.why = HGX_BAI_NONE;
+    for (const BaiReport &r : bai_used) {
+        if (r.used) { sum.used += 1; sum.why = HGX_BAI_USED; sum.bytes += r.bytes; sum.n_seg += r.n_seg; sum.n_blocks += r.n_blocks; }
+        else if (!sum.used && r.why != HGX_BAI_NONE) sum.why = r.why;
+    }
+    g_bai_last = sum;
     return HGX_OK;
 }
 

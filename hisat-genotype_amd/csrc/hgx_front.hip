@@ -39,6 +39,8 @@
 int hgx_bgzf_inflate_dev(const unsigned char *d_in, const hgx_bgzf_block *blocks, size_t n_blocks, unsigned char *d_out, hipStream_t st, int *bad,
                          void *staging);
 size_t hgx_bgzf_inflate_staging_bytes(size_t n_blocks);
+int hgx_bam_splice_dev(const unsigned char *d_src, size_t src_bytes, const uint64_t *seg_off, const uint64_t *seg_len, size_t n_seg, unsigned char *d_dst,
+                       size_t dst_off, hipStream_t st, size_t *total_out);
 
 namespace {
 
@@ -2312,6 +2314,34 @@ int parse_dev(hgx_dbatch **out, hipStream_t st, const hgx_parse_opts *opts_in, P
                 g_last_bytes += (long long)n;
                 return 0;
             };
+            // a region list the file's index answers (hgx_bam.cpp read_through_index): only the blocks the index names come up; they are
+            // inflated into a staging buffer and k_bam_splice packs every segment's [first record, end) into the dense stream the walk reads
+            hook.splice_dev = [&](const unsigned char *comp, size_t n, const std::vector<hgx_bgzf_block> &blocks, size_t staged,
+                                  const std::vector<std::pair<uint64_t, uint64_t>> &segs, size_t total) -> int {
+                if (up_failed || total >= (1ull << 32) - 64 || staged >= (1ull << 32) - 64 || n >= (1ull << 32) - 4096) return 1;
+                if (!text_room(total + 64)) return 1;
+                DevBuf b_stage;                                  // (declared first: given back after the stream has drained)
+                struct DrainC { hipStream_t s; ~DrainC() { (void)hipStreamSynchronize(s); } } drain_c{st};
+                if (b_comp.p) { (void)hipStreamSynchronize(st); hgx_pool_free(b_comp.p); b_comp.p = nullptr; }
+                comp_from = nullptr;
+                if (b_comp.alloc(n + 2048) || b_stage.alloc(staged + 64)) return 1;
+                if (hipMemcpyAsync(b_comp.p, comp, n, hipMemcpyHostToDevice, st) != hipSuccess) return 1;
+                if (hipMemsetAsync((char *)b_comp.p + n, 0, 2048, st) != hipSuccess) return 1;
+                if (hipMemsetAsync((char *)b_stage.p + staged, 0, 64, st) != hipSuccess) return 1;
+                int bad = 0;
+                void *stg = pinned_alloc(hgx_bgzf_inflate_staging_bytes(blocks.size()));
+                struct Unstage { void *p; ~Unstage() { pinned_release(p); } } unstage{stg};
+                if (hgx_bgzf_inflate_dev(b_comp.as<unsigned char>(), blocks.data(), blocks.size(), b_stage.as<unsigned char>(), st, &bad, stg) != HGX_OK || bad) return 1;
+                std::vector<uint64_t> off(segs.size()), len(segs.size());
+                for (size_t k = 0; k < segs.size(); ++k) { off[k] = segs[k].first; len[k] = segs[k].second; }
+                size_t made = 0;
+                if (hgx_bam_splice_dev(b_stage.as<unsigned char>(), staged, off.data(), len.data(), segs.size(), b_text.as<unsigned char>(), 0, st, &made) != HGX_OK ||
+                    made != total) return 1;
+                up_raw = nullptr;
+                up_bytes = total;
+                g_last_bytes += (long long)n;
+                return 0;
+            };
         }
         hook.records = [&](hgx_locus &L, const char *raw, size_t raw_bytes, const hgx_line *lines, size_t n, bool binary, const hgx_parse_opts &o,
                            int *declined, const hgx_bam_deferred *def) {
@@ -2408,6 +2438,17 @@ extern "C" int hgx_alignment_open(hgx_alignment **out, const char *path, int32_t
     A->path = path;
     HIPCHK(hipGetDevice(&A->dev));
     if (hgx_switch_has("front", "host")) { *out = A.release(); return HGX_OK; }          // (every locus through the host stages)
+    {
+        // A BGZF file of 4 GB or more with a usable index beside it is not read at all: its stream would not be resident
+        // (4 GB of stream is the limit of the kernels' 32-bit offsets, and a BAM does not inflate to less than it deflates to unless its
+        // writer stored incompressible blocks), and the per-path call reads a locus' blocks through the index.  Either way the batches are
+        // the same: the rule only chooses the cheaper way.  Test switch bai=force: any size.
+        struct stat sb_ix;
+        if (stat(path, &sb_ix) == 0 && (hgx_switch_has("bai", "force") || (unsigned long long)sb_ix.st_size >= (4ull << 30)) && hgx_bam_has_index(path)) {
+            *out = A.release();
+            return HGX_OK;
+        }
+    }
     if (!hgx_switch_has("front", "device")) {
         // below the device front end's size gate (FE_MIN_BYTES of stream; BGZF deflates ~1 : 4) the file is not even read here: the
         // per-locus call on the path decides
@@ -2948,11 +2989,15 @@ int hgx_front_many_dev(hgx_dbatch **out, hgx_front_totals *tot, const hgx_locus 
     if (paths && !hgx_switch_has("front", "host_inflate")) {
         std::vector<size_t> cbase((size_t)n_tasks + 1, 0), csize((size_t)n_tasks, 0);
         bool stat_ok = true;
+        size_t files_total = 0;                      // (what hgx_front_last reports for files sent whole: their sizes, 64-byte aligned)
         for (int t = 0; t < n_tasks; ++t) {
             struct stat sb;
             if (!paths[t] || stat(paths[t], &sb) != 0) { stat_ok = false; break; }
-            csize[t] = (size_t)sb.st_size;
+            // (a task that goes through its file's index sends the blocks the index names, each segment's range padded to 64 bytes: segments
+            // lie at least 64 KB of file apart, so the padding stays below a 1024th of the file)
+            csize[t] = (size_t)sb.st_size + (size_t)sb.st_size / 1024 + 128;
             cbase[(size_t)t + 1] = (cbase[t] + csize[t] + 63) & ~(size_t)63;
+            files_total += ((size_t)sb.st_size + 63) & ~(size_t)63;
         }
         const size_t ctotal = cbase[(size_t)n_tasks];
         if (stat_ok && ctotal < (1ull << 32) - 4096) {
@@ -2964,7 +3009,7 @@ int hgx_front_many_dev(hgx_dbatch **out, hgx_front_totals *tot, const hgx_locus 
             std::vector<hgx_bgzf_task> bt;
             std::atomic<bool> up_bad{false};
             auto on_bt = [&](int t) {
-                if (bt[t].n != csize[t] || hipSetDevice(dev) != hipSuccess ||
+                if (bt[t].n > csize[t] || hipSetDevice(dev) != hipSuccess ||
                     hipMemcpyAsync((char *)b_comp.p + cbase[t], bt[t].data, bt[t].n, hipMemcpyHostToDevice, st) != hipSuccess) up_bad = true;
             };
             struct FreeTasks { std::vector<hgx_bgzf_task> &v; hipStream_t s; ~FreeTasks() { (void)hipStreamSynchronize(s); for (auto &x : v) hgx_host_free(x.data); } } free_tasks{bt, st};
@@ -2973,24 +3018,56 @@ int hgx_front_many_dev(hgx_dbatch **out, hgx_front_totals *tot, const hgx_locus 
             lap("read (deflated; uploads issued)");
             bool all_ok = !up_bad.load();
             for (int t = 0; t < n_tasks && all_ok; ++t) all_ok = bt[t].ok;
-            std::vector<size_t> pbase((size_t)n_tasks + 1, 0), psize((size_t)n_tasks, 0);
-            size_t n_blocks = 0;
+            // A task that went through its file's index (bt[t].indexed) sent only the blocks the index names: they are
+            // inflated into a staging buffer (the task's part at a 64-byte aligned base) and k_bam_splice writes the task's dense stream --
+            // every segment's [first record, end) -- at the task's 64-byte aligned base of the text buffer.  The other tasks' blocks are
+            // inflated straight to their place, as before.
+            std::vector<size_t> pbase((size_t)n_tasks + 1, 0), psize((size_t)n_tasks, 0), sbase((size_t)n_tasks + 1, 0);
+            size_t n_blocks = 0, sent = 0;
+            bool any_indexed = false;
             for (int t = 0; t < n_tasks && all_ok; ++t) {
                 psize[t] = bt[t].total;
                 pbase[(size_t)t + 1] = (pbase[t] + bt[t].total + 63) & ~(size_t)63;
+                sbase[(size_t)t + 1] = bt[t].indexed ? (sbase[t] + bt[t].staged + 63) & ~(size_t)63 : sbase[t];
                 n_blocks += bt[t].blocks.size();
+                sent += bt[t].n;
+                any_indexed = any_indexed || bt[t].indexed;
             }
-            const size_t ptotal = pbase[(size_t)n_tasks];
-            if (all_ok && ptotal < (1ull << 32) - 64 && (hgx_switch_has("front", "device") || ptotal >= FE_MIN_DEFER_BYTES)) {
-                std::vector<hgx_bgzf_block> all;
+            const size_t ptotal = pbase[(size_t)n_tasks], stotal = sbase[(size_t)n_tasks];
+            if (all_ok && ptotal < (1ull << 32) - 64 && stotal < (1ull << 32) - 64 && (hgx_switch_has("front", "device") || ptotal >= FE_MIN_DEFER_BYTES)) {
+                std::vector<hgx_bgzf_block> all, staged_blocks;
                 all.reserve(n_blocks);
                 for (int t = 0; t < n_tasks; ++t)
-                    for (hgx_bgzf_block b : bt[t].blocks) { b.in_off += cbase[t]; b.out_off += pbase[t]; all.push_back(b); }
+                    for (hgx_bgzf_block b : bt[t].blocks) {
+                        b.in_off += cbase[t];
+                        b.out_off += bt[t].indexed ? sbase[t] : pbase[t];
+                        (bt[t].indexed ? staged_blocks : all).push_back(b);
+                    }
+                DevBuf b_stage;
                 ALLOC(b_text2, ptotal + 64);
+                if (any_indexed) {
+                    ALLOC(b_stage, stotal + 64);
+                    HIPCHK(hipMemsetAsync((char *)b_stage.p + stotal, 0, 64, st));
+                }
                 HIPCHK(hipMemsetAsync((char *)b_comp.p + ctotal, 0, 4096, st));
-                int bad = 0;
+                int bad = 0, bad_staged = 0;
                 rcb = hgx_bgzf_inflate_dev(b_comp.as<unsigned char>(), all.data(), all.size(), b_text2.as<unsigned char>(), st, &bad, nullptr);
                 if (rcb) return rcb;
+                if (any_indexed) {
+                    rcb = hgx_bgzf_inflate_dev(b_comp.as<unsigned char>(), staged_blocks.data(), staged_blocks.size(), b_stage.as<unsigned char>(), st, &bad_staged, nullptr);
+                    if (rcb) return rcb;
+                    bad += bad_staged;
+                    for (int t = 0; t < n_tasks && !bad; ++t) {
+                        if (!bt[t].indexed) continue;
+                        std::vector<uint64_t> off(bt[t].parts.size()), len(bt[t].parts.size());
+                        for (size_t k = 0; k < off.size(); ++k) { off[k] = bt[t].parts[k].first + sbase[t]; len[k] = bt[t].parts[k].second; }
+                        size_t made = 0;
+                        rcb = hgx_bam_splice_dev(b_stage.as<unsigned char>(), stotal, off.data(), len.data(), off.size(), b_text2.as<unsigned char>(), pbase[t], st, &made);
+                        if (rcb) return rcb;
+                        if (made != bt[t].total) bad = 1;
+                    }
+                    (void)hipStreamSynchronize(st);                  // (b_stage is given back when this block ends)
+                }
                 lap("BGZF inflate (device)");
                 if (!bad) {
                     std::vector<const hgx_bam_deferred *> defs((size_t)n_tasks);
@@ -3008,7 +3085,7 @@ int hgx_front_many_dev(hgx_dbatch **out, hgx_front_totals *tot, const hgx_locus 
                         lap("device stages");
                         if (rcb) { hgx_dbatch_destroy(made); return rcb; }
                         if (!dec && made) {
-                            g_last_bytes += (long long)ctotal;
+                            g_last_bytes += (long long)(any_indexed ? sent : files_total);
                             g_last_route = 2; g_last_device = 1;
                             *out = made;
                             return HGX_OK;

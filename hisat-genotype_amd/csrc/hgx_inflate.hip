@@ -1346,6 +1346,120 @@ int hgx_bgzf_inflate_dev(const unsigned char *d_in, const hgx_bgzf_block *blocks
     return HGX_OK;
 }
 
+// ---- k_bam_splice: the selected segments of an inflated staging buffer as one dense stream -----------------------------------------
+// A region read through the file's index (hgx_bai.cpp) inflates only the blocks the index names; a segment's records begin somewhere
+// inside its first block and end somewhere inside its last.  The record walk wants ONE stream of whole records: segment after
+// segment, each from its first record to its end.  The kernel is destination-centric: a lane owns 16 aligned destination bytes, finds
+// the segment its first byte belongs to by binary search in the prefix sums of the segment lengths (in LDS up to SPL_LDS_SEGS
+// segments, in global memory beyond), and where all 16 bytes come from that segment loads the five aligned source dwords that cover
+// them and shifts them into place (v_alignbyte): one 16-byte store per lane, no two lanes write the same dword.  The bytes at a
+// segment's edge and at the stream's two ends go one by one.  It is a copy: a workgroup takes 64 KB of destination.
+namespace {
+constexpr int SPL_LDS_SEGS = 2048;             // prefix entries (+ 1) a workgroup keeps in LDS: 8 KB
+constexpr int SPL_WG_UNITS = 4096;             // 16-byte units per workgroup
+template <bool LDS>
+__global__ void __launch_bounds__(256) k_bam_splice(const unsigned char *__restrict__ src, const uint32_t *__restrict__ pre, const uint32_t *__restrict__ soff, int n_seg,
+                                                    unsigned char *__restrict__ dst, unsigned long long dst_off, unsigned long long total) {
+    __shared__ uint32_t s_pre[LDS ? SPL_LDS_SEGS + 1 : 1];
+    if (LDS) {
+        for (int i = threadIdx.x; i <= n_seg; i += 256) s_pre[i] = pre[i];
+        __syncthreads();
+    }
+    const uint32_t *P = LDS ? s_pre : pre;                     // P[0] = 0 ... P[n_seg] = total
+    const unsigned long long u0 = dst_off >> 4, n_units = ((dst_off + total + 15) >> 4) - u0;
+    for (int k = 0; k < SPL_WG_UNITS / 256; ++k) {
+        const unsigned long long u = (unsigned long long)blockIdx.x * SPL_WG_UNITS + (unsigned)k * 256u + threadIdx.x;
+        if (u >= n_units) return;
+        const unsigned long long D = (u0 + u) << 4;
+        const unsigned long long a = D > dst_off ? D : dst_off, b = D + 16 < dst_off + total ? D + 16 : dst_off + total;
+        uint32_t x = (uint32_t)(a - dst_off);                  // offset in the stream: P[lo] <= x < P[hi] throughout
+        int lo = 0, hi = n_seg;
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (P[mid] <= x) lo = mid; else hi = mid;
+        }
+        int s = lo;                                            // (the last segment that begins at or before x: never an empty one)
+        if (b - a == 16 && (unsigned long long)x + 16 <= P[s + 1]) {
+            const unsigned long long S = (unsigned long long)soff[s] + (x - P[s]);
+            const uint32_t *w = reinterpret_cast<const uint32_t *>(src + (S & ~3ull));
+            const uint32_t sh = (uint32_t)(S & 3);
+            const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = sh ? w[4] : 0u;
+            uint4 o;
+            o.x = __builtin_amdgcn_alignbyte(w1, w0, sh);
+            o.y = __builtin_amdgcn_alignbyte(w2, w1, sh);
+            o.z = __builtin_amdgcn_alignbyte(w3, w2, sh);
+            o.w = __builtin_amdgcn_alignbyte(w4, w3, sh);
+            *reinterpret_cast<uint4 *>(dst + D) = o;
+        } else {
+            for (unsigned long long d = a; d < b; ++d, ++x) {
+                while (x >= P[s + 1]) ++s;                     // (x < total = P[n_seg]: s stays below n_seg)
+                dst[d] = src[(unsigned long long)soff[s] + (x - P[s])];
+            }
+        }
+    }
+}
+}   // namespace
+
+// d_dst[dst_off ...) = the bytes [seg_off[s], seg_off[s] + seg_len[s]) of d_src, segment after segment; *total = their sum.  d_src is
+// readable 4 bytes beyond its last segment byte and both buffers are 16-byte aligned (device allocations are).  Offsets and the sum stay
+// below 4 GB (the streams the front end takes do).  Returns after the stream has drained.
+int hgx_bam_splice_dev(const unsigned char *d_src, size_t src_bytes, const uint64_t *seg_off, const uint64_t *seg_len, size_t n_seg, unsigned char *d_dst,
+                       size_t dst_off, hipStream_t st, size_t *total_out) {
+    ARGCHK(total_out && (n_seg == 0 || (d_src && seg_off && seg_len && d_dst)) && n_seg < (1u << 30) && src_bytes < (1ull << 32));
+    ARGCHK(((uintptr_t)d_src & 15) == 0 && ((uintptr_t)d_dst & 15) == 0);
+    std::vector<uint32_t> h(2 * n_seg + 1);
+    uint64_t total = 0;
+    for (size_t s = 0; s < n_seg; ++s) {
+        if (seg_off[s] > src_bytes || seg_len[s] > src_bytes - seg_off[s] || total + seg_len[s] >= (1ull << 32) - 64) {
+            hgx_set_error("splice segment %zu does not fit (offset %llu, length %llu of %zu bytes)", s, (unsigned long long)seg_off[s], (unsigned long long)seg_len[s], src_bytes);
+            return HGX_EINVAL;
+        }
+        h[s] = (uint32_t)total;
+        h[n_seg + 1 + s] = (uint32_t)seg_off[s];
+        total += seg_len[s];
+    }
+    h[n_seg] = (uint32_t)total;
+    *total_out = (size_t)total;
+    if (total == 0) return HGX_OK;
+    DevBuf b_tab;
+    ALLOC(b_tab, h.size() * 4);
+    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{st};
+    HIPCHK(hipMemcpyAsync(b_tab.p, h.data(), h.size() * 4, hipMemcpyHostToDevice, st));
+    const uint32_t *pre = b_tab.as<uint32_t>(), *soff = pre + n_seg + 1;
+    const uint64_t n_units = ((dst_off + total + 15) >> 4) - (dst_off >> 4);
+    const unsigned grid = (unsigned)((n_units + SPL_WG_UNITS - 1) / SPL_WG_UNITS);
+    if (n_seg <= (size_t)SPL_LDS_SEGS) k_bam_splice<true><<<grid, 256, 0, st>>>(d_src, pre, soff, (int)n_seg, d_dst, dst_off, total);
+    else k_bam_splice<false><<<grid, 256, 0, st>>>(d_src, pre, soff, (int)n_seg, d_dst, dst_off, total);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    return HGX_OK;
+}
+
+// test entry (hgx.h): host -> device -> host
+extern "C" int hgx_bam_splice(const void *src, size_t src_bytes, const uint64_t *seg_off, const uint64_t *seg_len, int32_t n_seg, void *out, size_t dst_bytes,
+                              size_t dst_off, void *stream) {
+    ARGCHK(n_seg >= 0 && (src || src_bytes == 0) && (out || dst_bytes == 0) && (n_seg == 0 || (seg_off && seg_len)) && dst_off <= dst_bytes);
+    hipStream_t st = (hipStream_t)stream;
+    uint64_t total = 0;
+    for (int32_t s = 0; s < n_seg; ++s) {
+        if (seg_len[s] > dst_bytes - dst_off - total) { hgx_set_error("output buffer too small for the spliced segments"); return HGX_EINVAL; }
+        total += seg_len[s];
+    }
+    DevBuf b_src, b_dst;
+    ALLOC(b_src, src_bytes + 64);
+    ALLOC(b_dst, dst_bytes + 64);
+    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{st};
+    if (src_bytes) HIPCHK(hipMemcpyAsync(b_src.p, src, src_bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync((char *)b_src.p + src_bytes, 0, 64, st));
+    if (dst_bytes) HIPCHK(hipMemcpyAsync(b_dst.p, out, dst_bytes, hipMemcpyHostToDevice, st));
+    size_t made = 0;
+    const int rc = hgx_bam_splice_dev(b_src.as<unsigned char>(), src_bytes, seg_off, seg_len, (size_t)n_seg, b_dst.as<unsigned char>(), dst_off, st, &made);
+    if (rc) return rc;
+    if (dst_bytes) HIPCHK(hipMemcpyAsync(out, b_dst.p, dst_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return HGX_OK;
+}
+
 // test / tool entry (hgx.h): a whole BGZF file in host memory -> its payload in host memory, inflated on the device
 extern "C" int hgx_bgzf_inflate(const void *bgzf, size_t n_bytes, void *out, size_t out_cap, size_t *n_out, int32_t *bad_blocks, void *stream) {
     ARGCHK(bgzf && n_out && bad_blocks && (out || out_cap == 0));

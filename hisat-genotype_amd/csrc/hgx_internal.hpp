@@ -231,6 +231,13 @@ struct hgx_align_lines {
     // block table once the BAM header (inflated on the host) says the stream qualifies; returns 0 when the payload now lies in
     // the caller's device buffer (deferred.on_device: `raw` stays NULL, raw_bytes = the payload's size), else the host inflates
     std::function<int(const unsigned char *data, size_t n, const std::vector<hgx_bgzf_block> &blocks, size_t total)> inflate_dev;
+    // in, with defer_walk and a region list the file's index answers: the caller inflates the SELECTED blocks and packs
+    // the segments into the dense stream itself.  comp = the blocks the index names, each segment's byte range at a 64-byte aligned
+    // offset (n bytes); blocks = their table (in_off into comp, out_off into a staging stream of `staged` bytes); segs = (offset in the
+    // staging stream, length) of every segment's [first record, end); total = the lengths' sum.  Returns 0 when the dense stream -- records
+    // from byte 0 on, no header: deferred.body0 = 0 -- lies in the caller's device buffer (deferred.on_device), else the host inflates.
+    std::function<int(const unsigned char *comp, size_t n, const std::vector<hgx_bgzf_block> &blocks, size_t staged,
+                      const std::vector<std::pair<uint64_t, uint64_t>> &segs, size_t total)> splice_dev;
     // in, optional: called with the file's bytes as soon as they are read and look like BGZF -- the caller may start sending them
     // while the host still hops through the container and inflates the header (inflate_dev then finds them on their way)
     std::function<void(const unsigned char *data, size_t n)> comp_early;
@@ -247,6 +254,31 @@ int hgx_bam_parse_header(const unsigned char *raw, size_t n, std::vector<std::st
 bool hgx_bam_inflate_block(const unsigned char *data, const hgx_bgzf_block &b, unsigned char *dst);
 bool hgx_bam_record_line(const unsigned char *rec, size_t len, const std::vector<std::string> &refs, std::string &line);
 int hgx_deferred_for_regions(const char *regions, bool text, size_t body0, const std::vector<std::string> &refs, hgx_bam_deferred &d);
+
+// ---- BAM index (hgx_bai.cpp; the reader's use of it: hgx_bam.cpp) -------------------------------------------------------------------
+struct hgx_bai_chunk { uint64_t beg, end; };         // virtual offsets: (block's file offset << 16) | offset in its payload
+struct hgx_bai_index {
+    struct Bin { uint32_t bin, n_chunk; size_t chunk0; };
+    struct Ref { size_t bin0 = 0, n_bin = 0, intv0 = 0, n_intv = 0; };
+    std::vector<Ref> refs;
+    std::vector<Bin> bins;
+    std::vector<hgx_bai_chunk> chunks;
+    std::vector<uint64_t> ioffset;
+    int64_t n_no_coor = -1;                          // -1: the file ends without it
+};
+#define HGX_BAI_MERGE_GAP 65536ull                   // hgx_bai_plan: chunks this many bytes of file apart (block start to block start) are read as one
+#define HGX_BAI_MIN_BYTES ((size_t)32 << 20)         // a smaller file is read whole: planning would not pay (not measured: DESIGN.md 5.12)
+// hgx_bam_index_last's why_not
+enum { HGX_BAI_USED = 0, HGX_BAI_NONE = 1, HGX_BAI_UNUSABLE = 2, HGX_BAI_SMALL = 3, HGX_BAI_NO_REGIONS = 4, HGX_BAI_CHAIN = 5, HGX_BAI_INFLATE = 6,
+       HGX_BAI_OFF = 7, HGX_BAI_NOT_BGZF = 8 };
+bool hgx_bai_parse(const unsigned char *p, size_t n, hgx_bai_index &ix);                  // false: unusable
+int hgx_bai_load(const char *bam_path, hgx_bai_index &ix);                                // 0 usable, 1 none beside the file, 2 unusable
+bool hgx_bai_query(const hgx_bai_index &ix, int32_t ref, int64_t beg0, int64_t end0, std::vector<hgx_bai_chunk> &out);
+void hgx_bai_plan(std::vector<hgx_bai_chunk> &chunks, std::vector<hgx_bai_chunk> &segments);
+bool hgx_bai_plan_fits(const std::vector<hgx_bai_chunk> &segments, uint64_t file_size);
+// does `path` (a BGZF file) have a usable index beside it whose reference count is its header's?  Reads the header's blocks only and
+// reports through hgx_bam_index_last (hgx_alignment_open: such a file need not be read to be opened)
+bool hgx_bam_has_index(const char *path);
 
 // find-or-insert a piece given its word range and (MP,P) mask words
 uint32_t hgx_intern_masks(hgx_batch &b, uint16_t lo, uint16_t nw, const uint32_t *m);
@@ -373,6 +405,8 @@ struct hgx_front_hook {
     bool defer_text = false;           // ... and SAM text without a line table
     size_t defer_min_bytes = 0;
     std::function<int(const unsigned char *data, size_t n, const std::vector<hgx_bgzf_block> &blocks, size_t total)> inflate_dev;   // ... and deflated ones
+    std::function<int(const unsigned char *comp, size_t n, const std::vector<hgx_bgzf_block> &blocks, size_t staged,
+                      const std::vector<std::pair<uint64_t, uint64_t>> &segs, size_t total)> splice_dev;                         // ... and the blocks an index names
     std::function<void(const unsigned char *data, size_t n)> comp_early;             // (the deflated bytes, before the container is looked at)
     std::function<void()> comp_sync;                                                 // (... and the wait for that copy, before the bytes are released)
     std::function<void(const char *raw, size_t n_bytes, size_t begin, size_t end)> on_raw;
@@ -392,6 +426,13 @@ struct hgx_bgzf_task {
     hgx_bam_deferred def;
     std::vector<std::string> refs;       // the header's reference names, in the file's order
     bool ok = false;
+    // the task's region list went through its file's index: data = ONLY the blocks the index names (each segment's
+    // byte range at a 64-byte aligned offset), blocks[].out_off = offsets in a staging stream of `staged` bytes, parts = (offset in the
+    // staging stream, length) of every segment's [first record, end), total = the lengths' sum = the dense stream k_bam_splice makes
+    // (records from byte 0: def.body0 = 0)
+    bool indexed = false;
+    size_t staged = 0;
+    std::vector<std::pair<uint64_t, uint64_t>> parts;
 };
 int hgx_bgzf_tasks_read(std::vector<hgx_bgzf_task> &tasks, const char *const *paths, const char *const *regions, int n_tasks, int n_threads,
                         const hgx_front_alloc *mem, const std::function<void(int)> &on_task);

@@ -1836,7 +1836,7 @@ int hgx_parse_alignment_file_hook(hgx_batch **out, const hgx_locus *Lc, const ch
             al.on_raw = hook->on_raw;
             al.defer_walk = hook->defer_walk;
             al.defer_min_bytes = hook->defer_min_bytes;
-            if (al.defer_walk) { al.inflate_dev = hook->inflate_dev; al.comp_early = hook->comp_early; al.comp_sync = hook->comp_sync; }
+            if (al.defer_walk) { al.inflate_dev = hook->inflate_dev; al.splice_dev = hook->splice_dev; al.comp_early = hook->comp_early; al.comp_sync = hook->comp_sync; }
             al.defer_text = al.defer_walk && hook->defer_text;
         }
         int rc = hgx_read_alignment_lines(path, regions, opts->n_threads, al, /*keep_binary=*/true);

@@ -208,6 +208,31 @@ def front_last_bytes():
     return n.value
 
 
+BAI_WHY = {0: "used", 1: "none", 2: "unusable", 3: "small", 4: "no regions", 5: "chain", 6: "inflate", 7: "off", 8: "not bgzf"}
+
+
+def bam_index_last():
+    """What the calling thread's last alignment read did with the file's index (hgx_bam_index_last): {'used', 'n_used' (1; after a
+    many-task pass the tasks that went through their index, the other figures summed over them), 'why_not' (a BAI_WHY word),
+    'file_bytes_read', 'n_segments', 'n_blocks'}."""
+    used, why, n_seg, nb, nblk = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int64(0), C.c_int64(0)
+    capi.check(capi.lib().hgx_bam_index_last(C.byref(used), C.byref(why), C.byref(nb), C.byref(n_seg), C.byref(nblk)))
+    return {"used": bool(used.value), "n_used": used.value, "why_not": BAI_WHY.get(why.value, str(why.value)), "file_bytes_read": nb.value, "n_segments": n_seg.value,
+            "n_blocks": nblk.value}
+
+
+def bam_splice(src, segments, dst, dst_off=0, stream=None):
+    """Test entry of k_bam_splice (hgx_bam_splice): the bytes src[off : off + len] of every (off, len) in `segments`, one after the
+    other, written into the uint8 array `dst` from byte `dst_off` on -- on the device; every other byte of `dst` comes back as it was."""
+    src = np.ascontiguousarray(src, np.uint8)
+    assert dst.dtype == np.uint8 and dst.flags["C_CONTIGUOUS"]
+    off = np.array([s[0] for s in segments] or [0], np.uint64)
+    ln = np.array([s[1] for s in segments] or [0], np.uint64)
+    capi.check(capi.lib().hgx_bam_splice(capi.ptr(src), C.c_size_t(src.size), capi.ptr(off), capi.ptr(ln), C.c_int32(len(segments)), capi.ptr(dst),
+                                         C.c_size_t(dst.size), C.c_size_t(dst_off), stream))
+    return dst
+
+
 def em_last_order(n_alleles):
     """Insertion order of the dict the last em() / em_ordered() of this thread returned (position per allele, -1 outside), or None
     when that EM did not run on the reference-order kernel (hgx_em_last_order)."""

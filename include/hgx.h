@@ -499,7 +499,8 @@ int hgx_type_batch(hgx_typing **out, const hgx_locus *loc, const hgx_index *ix, 
 int hgx_type_file(hgx_typing **out, const hgx_locus *loc, const hgx_index *ix, const char *path, const char *regions_or_null,
                   const hgx_parse_opts *parse_opts, const hgx_type_opts *opts, void *stream);
 /* ---- the front end on the device (rows 8a-1 .. 8a-5 as kernels, csrc/hgx_front.hip) ----------------------------------------
- * RECORD route (tried first): the host only reads the file -- and, for BAM, inflates it, walks the record chain and name-sorts it;
+ * RECORD route (tried first): the host only reads the file (with a region list and an index beside a BAM: the blocks the index names,
+ * see hgx_bam_index_last) -- and, for BAM, inflates it, walks the record chain and name-sorts it;
  * the SAM text / inflated stream goes to the GPU while that happens, and the record fields (typing_core.py:800-841), the record
  * filters (typing_core.py:815-872) and the grouping of the records by decode key run as kernels, one lane per record.
  * KEY route (when the record route declines: a line with blanks, a float-typed NM tag, ...): the host tokenises, filters and groups;
@@ -514,7 +515,7 @@ int hgx_type_file(hgx_typing **out, const hgx_locus *loc, const hgx_index *ix, c
  * the same batch either way, and hgx_front_last says which way the calling thread's last call went (route: 2 = record route,
  * 1 = key route, 0 = host stages; decline_code: see HGX_FE_DECLINE_* / FE_E_* in csrc/hgx_internal.hpp,
  * csrc/hgx_front_core.hpp).  hgx_type_file goes through hgx_parse_alignment_file_dev.
- * A BAM file (with a list of at most HGX_MAX_REGIONS regions) does not even get inflated on the host: the host reads it, hops through the BGZF container
+ * A BAM file (with a list of at most HGX_MAX_REGIONS regions) that is read whole does not even get inflated on the host: the host reads it, hops through the BGZF container
  * and inflates the block(s) holding the BAM header; the deflated bytes go up, and BGZF inflate (csrc/hgx_inflate.hip), the record
  * chain walk, the region filter (samtools' overlap rule, typing_core.py:438-444) and the stable sort by read name
  * (`sort -k 1,1 -s`, typing_core.py:436-468) run as kernels in front of the record route.  A block that fails CRC-32 / ISIZE, a
@@ -533,6 +534,8 @@ int hgx_front_last_parts(int32_t *parts);
  * loci of a panel may be parsed side by side from threads with streams of their own).  The batch is the one
  * hgx_parse_alignment_file_dev(path, regions) builds; a locus the kernels decline, a region list of more than HGX_MAX_REGIONS entries, a file below
  * the device front end's size gate or beyond 4 GB of stream go through exactly that call on the path (hgx_front_last tells).
+ * A BGZF file of 4 GB or more with a usable index beside it is not read at open (its stream could not be resident): it opens as not
+ * resident, and every locus takes the per-path call, which reads the locus' blocks through the index.
  * hgx_alignment_dims: resident = the bytes are in HBM (0: every locus takes the per-path call). */
 typedef struct hgx_alignment hgx_alignment;
 int hgx_alignment_open(hgx_alignment **out, const char *path, int32_t n_threads, void *stream);
@@ -612,6 +615,8 @@ int hgx_many_create(hgx_many **out, const hgx_locus *loc, const hgx_batch *const
  * buffer, every record carries its task: keys, read ids and pairs never cross tasks, each task has its own pileup for the error
  * correction, the piece table is shared).  The batch is the one hgx_many_create makes of hgx_parse_alignment_file's per-task
  * batches, array for array; where the device front end declines (hgx_front_last) exactly that is done instead.
+ * A task whose region list its file's index answers (hgx_bam_index_last) sends only the blocks the index names; they are inflated and
+ * spliced into the task's stream on the device.  A task without an index is sent whole, as ever.
  * The reference's call site: one hisatgenotype_locus process per sample through the pool (/root/reference/hisatgenotype:613-665),
  * each reading its own alignment file (typing_core.py:826-897).                                                               */
 int hgx_many_create_files(hgx_many **out, const hgx_locus *loc, const char *const *paths, const char *const *regions /* or NULL */,
@@ -645,6 +650,33 @@ int hgx_bgzf_inflate(const void *bgzf, size_t n_bytes, void *out, size_t out_cap
  * of the device inflate: each range finds a block start and the ranges must link up, csrc/hgx_inflate.hip hgx_bgzf_scan_par).
  * *n_blocks = blocks of the file (-1: not a BGZF container), *same = 1 iff both walks gave the same verdict and descriptors.   */
 int hgx_bgzf_scan_compare(const void *bgzf, size_t n_bytes, int32_t n_threads, int64_t *n_blocks, int32_t *same);
+
+/* ---- BAM regions through the file's index (.bai, SAM specification section 5.2; csrc/hgx_bai.cpp) ------------------
+ * The reference runs `samtools index` and `samtools view file chr:left-right` (typing_core.py:433-444): samtools touches only the BGZF
+ * blocks the index names.  With a region list, a BGZF file of at least 32 MB and a usable index beside it (<path>.bai, or <path minus
+ * .bam>.bai) the readers of this library do the same: the BAM header from the file's first blocks, then only the blocks the index
+ * plans for the regions are read and inflated, and the record walk, the region filter and the name sort run on that short stream --
+ * the result is byte for byte the one of the full read.  The index is never trusted: every segment it names must be a whole chain of
+ * records, or the call drops the index and reads the file as before (a stale index costs time, never a wrong answer); an index that
+ * is truncated or malformed counts as no index.  Nothing builds an index on its own.
+ * hgx_bam_index_build writes one, as `samtools index` does for a coordinate-sorted BAM: one streaming pass on the host, memory bounded
+ * by a piece of the file and one reference's index; out_path NULL = <path>.bai.  The file appears under its name only when complete.
+ * HGX_EINVAL / HGX_EPARSE with a message that names the offset, and no file, for: records out of coordinate order, a placed record
+ * behind an unplaced one, a reference longer than 2^29, a damaged block or record.
+ * hgx_bam_index_last: what the calling thread's last read did.  used = 1: the index answered the call (after hgx_many_create_files:
+ * the number of tasks whose index answered, the other figures summed over them); file_bytes_read = bytes of the
+ * alignment file read (header prefix + segments), n_segments / n_blocks = byte ranges read and BGZF blocks inflated.  used = 0:
+ * why_not = 1 no index beside the file, 2 unusable (malformed, another reference count, positions beyond 2^29), 3 file below the
+ * size gate, 4 no regions, 5 a segment that is not a chain of records, 6 a block that does not inflate / a block table that does not
+ * link up / a short read, 7 switched off (test switch bai=off), 8 not a BGZF-compressed BAM.
+ * hgx_bam_splice (test entry; host -> device -> host like hgx_bgzf_inflate): the kernel that packs the selected segments of an
+ * inflated staging buffer into the dense stream the record walk expects (k_bam_splice): out = src[off[0] .. off[0] + len[0]) followed
+ * by src[off[1] ..) and so on, written at byte `dst_off` of a buffer of dst_bytes bytes whose other bytes come back as they were
+ * sent (`out` is read and written: dst_bytes bytes). */
+int hgx_bam_index_build(const char *path, const char *out_path_or_null, int32_t n_threads);
+int hgx_bam_index_last(int32_t *used, int32_t *why_not, int64_t *file_bytes_read, int32_t *n_segments, int64_t *n_blocks);
+int hgx_bam_splice(const void *src, size_t src_bytes, const uint64_t *seg_off, const uint64_t *seg_len, int32_t n_seg, void *out, size_t dst_bytes,
+                   size_t dst_off, void *stream);
 
 /* Kernel timing for roofline reports.  hgx_em_set_timing(1) makes hgx_em time a sample of its table-lookup mat-vec launches
  * (every 4th ungated rows pass and the cols pass after it), hgx_em_set_timing(2) every plain rows / cols pass, with events
