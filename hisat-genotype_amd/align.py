@@ -1,0 +1,101 @@
+"""The "hgx" aligner: reads that belong to a locus family, aligned to the backbones in `Genes` through the known
+variants in `Vars` -- end to end, at most `max_edits` unknown mismatches, known variants free -- and written as SAM text in the
+dialect the front end consumes (NM, MD, Zs, NH, YT as simulate._truth_record renders them).
+
+It is NOT HISAT2 and its output is not compared with HISAT2's anywhere: no whole-genome index, no novel indels, no soft clips, no
+secondary records, mates placed independently.  The rules are stated in plain Python in tests/align_ref.py; the kernels
+(csrc/hgx_align.hip) and the host route (csrc/hgx_align_host.cpp) run one shared core (csrc/hgx_align_core.hpp).
+"""
+import ctypes as C
+
+from . import capi
+
+_TYPES = {"insertion": capi.VAR_INSERTION, "single": capi.VAR_SINGLE, "deletion": capi.VAR_DELETION}
+ROUTES = {"auto": 0, "host": 1, "device": 2}
+
+
+class AlignOpts(C.Structure):
+    _fields_ = [("max_edits", C.c_int32), ("max_fragment", C.c_int32), ("fastq", C.c_int32), ("route", C.c_int32)]
+
+
+class AlignIndex:
+    """The loci of `Genes` (in its order) with their variants in `Var_list` order, ready for align()."""
+
+    def __init__(self, Genes, Vars, Var_list, refGenes):
+        names, bbs, off, vtype, vpos, vdata, vid = [], [], [0], [], [], [], []
+        for g in Genes:
+            names.append(refGenes[g].encode())
+            bbs.append(Genes[g][refGenes[g]].encode())
+            gv = Vars.get(g, {})
+            for _, v in Var_list.get(g, []):
+                t, p, d = gv[v][:3]
+                vtype.append(_TYPES[t])
+                vpos.append(int(p))
+                vdata.append(str(d).encode())
+                vid.append(v.encode())
+            off.append(len(vtype))
+        n = len(vtype)
+        self.n_loci = len(names)
+        self.h = C.c_void_p()
+        capi.check(capi.lib().hgx_align_index_create(
+            C.byref(self.h), C.c_int32(self.n_loci), (C.c_char_p * len(names))(*names), (C.c_char_p * len(bbs))(*bbs),
+            (C.c_int32 * len(off))(*off), (C.c_int32 * max(n, 1))(*vtype), (C.c_int32 * max(n, 1))(*vpos),
+            (C.c_char_p * max(n, 1))(*vdata), (C.c_char_p * max(n, 1))(*vid)))
+
+    def align(self, reads, max_edits=2, max_fragment=1000, fastq=None, route="auto"):
+        """SAM text (bytes) for `reads` = one or two FASTA / FASTQ[.gz] paths (str) or in-memory texts (bytes)."""
+        assert len(reads) in (1, 2)
+        opts = AlignOpts(int(max_edits), int(max_fragment), -1 if fastq is None else int(bool(fastq)), ROUTES[route])
+        out_p, n = C.c_void_p(), C.c_size_t(0)
+        if all(isinstance(r, str) for r in reads):
+            paths = (C.c_char_p * len(reads))(*[r.encode() for r in reads])
+            rc = capi.lib().hgx_align_reads(self.h, C.c_int32(len(reads)), paths, None, None, C.byref(opts), C.byref(out_p), C.byref(n))
+        else:
+            bufs = [bytes(r) for r in reads]
+            texts = (C.c_char_p * len(bufs))(*bufs)
+            sizes = (C.c_size_t * len(bufs))(*[len(b) for b in bufs])
+            rc = capi.lib().hgx_align_reads(self.h, C.c_int32(len(bufs)), None, texts, sizes, C.byref(opts), C.byref(out_p), C.byref(n))
+        capi.check(rc)
+        try:
+            return C.string_at(out_p.value, n.value)
+        finally:
+            capi.lib().hgx_free_text(out_p)
+
+    def close(self):
+        if self.h:
+            capi.lib().hgx_align_index_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def align_last():
+    """dict(route, reads, aligned, pairs_concordant, decline) of the calling thread's last align(): route 2 = the kernels, 0 = the
+    host route (decline says why: HGX_ALN_DECLINE_* of csrc/hgx_align_core.hpp)."""
+    route, dec = C.c_int32(0), C.c_int32(0)
+    reads, aligned, conc = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    capi.check(capi.lib().hgx_align_last(C.byref(route), C.byref(reads), C.byref(aligned), C.byref(conc), C.byref(dec)))
+    return dict(route=route.value, reads=reads.value, aligned=aligned.value, pairs_concordant=conc.value, decline=dec.value)
+
+
+DECLINE_GATE, DECLINE_READ_LEN, DECLINE_ANCHORS, DECLINE_STACK, DECLINE_VARS, DECLINE_STEPS, DECLINE_SWITCH = 1, 2, 3, 4, 5, 6, 7
+
+_INDEX_CACHE = []          # [(Genes, Vars, Var_list, refGenes, AlignIndex)]: typing() runs once per sample on the same dicts
+
+
+def cached_index(Genes, Vars, Var_list, refGenes):
+    """The index of these dicts, found again by the IDENTITY of the four dict objects only (the packed-locus cache also keeps a
+    content key; this one does not): dicts edited in place after the first call return the index of their old content, and dicts
+    re-read from the index files (every genotyping_locus call) miss, so the index is built and uploaded again -- 3 ms for a
+    six-locus panel.  Callers that edit their dicts build an AlignIndex themselves."""
+    for g, v, vl, rg, ix in _INDEX_CACHE:
+        if g is Genes and v is Vars and vl is Var_list and rg is refGenes:
+            return ix
+    ix = AlignIndex(Genes, Vars, Var_list, refGenes)
+    _INDEX_CACHE.append((Genes, Vars, Var_list, refGenes, ix))
+    del _INDEX_CACHE[:-4]
+    return ix

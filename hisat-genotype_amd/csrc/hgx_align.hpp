@@ -1,0 +1,41 @@
+// hgx_align.hpp -- what the two routes of the "hgx" aligner share besides the core: the index and the read table.
+#pragma once
+#include <cstdint>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "hgx.h"
+#include "hgx_align_core.hpp"
+
+#define HGX_ALN_HOST_VARS (3 * HGX_ALN_MAX_READ + 8)     // no alignment of a read the core takes has more variants
+#define HGX_ALN_HOST_STEPS (1L << 24)                   // read bases walked per side of one anchor, with the memo: a read beyond it is left unaligned
+
+struct hgx_align_index {
+    std::vector<char> bb, pool;
+    std::vector<int32_t> bb_off, hpos, vpos, vlen, vdata, vid_off, vid_len, name_off, name_len;
+    std::vector<uint32_t> hkey;
+    std::vector<uint8_t> vtype;
+    std::vector<int32_t> sgl_off, sgl, dls_off, dls, dle_off, dle, ins_off, ins;
+    std::string header;                   // the @SQ lines
+    hgx_aln_view hv{};                    // over the vectors above
+    std::mutex mu;                        // the device copy is made on first use (hgx_align.hip)
+    int dev_ready = -1;                   // device it lives on
+    void *d_block = nullptr;
+    hgx_aln_view dv{};
+};
+
+// the reads of one call, mates interleaved (2k, 2k + 1) when paired; `text` holds names, upper-case bases and qualities
+struct hgx_aln_reads {
+    std::vector<char> text;
+    std::vector<int64_t> name_off, seq_off, qual_off;      // qual_off < 0: no qualities (FASTA)
+    std::vector<int32_t> name_len, len;
+    int paired = 0;
+    size_t n() const { return len.size(); }
+};
+
+// the kernels' route: the records of `reads` appended to `body`, per-read flags (1 aligned, 2 concordant).  *decline != 0: nothing
+// was appended and the host route finishes the call.
+int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_align_opts *opts, std::string &body,
+                     int64_t *aligned, int64_t *concordant, int *decline);
+void hgx_align_device_free(hgx_align_index *ix);

@@ -1,0 +1,525 @@
+// hgx_align_core.hpp -- the "hgx" aligner's per-anchor and per-read logic, compiled into the kernels
+// (hgx_align.hip) and into the host route (hgx_align_host.cpp).  The rules are stated in plain Python in tests/align_ref.py.
+//
+// An alignment of an oriented read at a locus = a start pos0 + an ordered list of known variants.  The walk of
+// simulate._truth_record consumes the read with them: at state (r, p), r > 0, at most one known insertion and one known deletion
+// that start at p are taken (the insertion first, so that both sit at their database position), then read base r sits on backbone
+// base p -- a match, a known single (free; the first in Var_list order whose data is the base) or one unknown edit.
+// The search is a depth-first enumeration of the indel choices left
+// and right of a 16-base anchor, cut where a side's edits exceed the budget or its cost exceeds the best found; the first three
+// components of the order are sums over the two sides, so each side is minimised on its own.  Scratch is of fixed size (MAXSTK
+// pending choices, MAXV variants, max_steps read bases walked): reaching a limit returns a decline code before anything is written.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define HGX_ALN_HD __host__ __device__
+#else
+#define HGX_ALN_HD
+#endif
+
+#define HGX_ALN_K 16
+#define HGX_ALN_STRIDE 4
+#define HGX_ALN_MAX_READ 1024          // the longest read the core takes (either route)
+#define HGX_ALN_DEV_MAX_READ 256       // the longest read the kernels take
+#define HGX_ALN_DEV_ANCHORS 128        // anchor slots per read on the device (a 256-base read has 61 seed offsets: two placements fit)
+#define HGX_ALN_DEV_STK 32             // pending indel choices per side on the device
+#define HGX_ALN_DEV_VARS 32            // variants per alignment on the device
+#define HGX_ALN_DEV_STEPS 200000       // read bases walked per side on the device
+
+// decline codes (hgx_align_last)
+#define HGX_ALN_DECLINE_NONE 0
+#define HGX_ALN_DECLINE_GATE 1         // fewer reads than the gate
+#define HGX_ALN_DECLINE_READ_LEN 2
+#define HGX_ALN_DECLINE_ANCHORS 3
+#define HGX_ALN_DECLINE_STACK 4
+#define HGX_ALN_DECLINE_VARS 5
+#define HGX_ALN_DECLINE_STEPS 6
+#define HGX_ALN_DECLINE_SWITCH 7       // front=host
+
+#define HGX_ALN_INS 0
+#define HGX_ALN_SGL 1
+#define HGX_ALN_DEL 2
+
+// the index as flat arrays (host or device memory); positions are GLOBAL: locus g covers [bb_off[g], bb_off[g + 1]) of `bb`, and a
+// variant's global index orders it as (locus, Var_list index)
+struct hgx_aln_view {
+    const char *bb;
+    const int32_t *bb_off;
+    int32_t n_loci, n_pos;
+    const uint32_t *hkey;              // open-addressing table of the 16-mer codes: hpos < 0 = empty; equal codes sit in one probe run
+    const int32_t *hpos;
+    uint32_t hmask;
+    const uint8_t *vtype;
+    const int32_t *vpos, *vlen;        // vlen: deleted bases / inserted bases / 1
+    const int32_t *vdata;              // single: the base; insertion: offset of its bases in `pool`
+    const int32_t *vid_off, *vid_len;  // the variant's id in `pool`
+    const int32_t *name_off, *name_len;   // per locus: its reference name in `pool`
+    const char *pool;
+    // per-position CSR tables [n_pos + 1]: singles at p, deletions starting at p, deletions ending at p (first base behind them), insertions at p
+    const int32_t *sgl_off, *sgl, *dls_off, *dls, *dle_off, *dle, *ins_off, *ins;
+};
+
+struct hgx_aln_read {
+    const char *seq;                   // upper case, as given
+    int32_t L, strand;
+    HGX_ALN_HD char at(int r) const {
+        if (!strand) return seq[r];
+        const char c = seq[L - 1 - r];
+        return c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'T' ? 'A' : c;
+    }
+};
+
+HGX_ALN_HD inline int hgx_aln_code2(char c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : -1; }
+HGX_ALN_HD inline uint32_t hgx_aln_hash(uint32_t code) { return (code * 0x9E3779B1u) ^ (code >> 15); }
+HGX_ALN_HD inline int hgx_aln_n_offsets(int L) {        // 0, 4, 8, ... <= L - 16, plus L - 16
+    if (L < HGX_ALN_K) return 0;
+    const int last = L - HGX_ALN_K;
+    return last / HGX_ALN_STRIDE + 1 + (last % HGX_ALN_STRIDE != 0);
+}
+HGX_ALN_HD inline int hgx_aln_offset(int L, int k) {
+    const int last = L - HGX_ALN_K;
+    return k * HGX_ALN_STRIDE <= last ? k * HGX_ALN_STRIDE : last;
+}
+// the 16-mer code of the oriented read at offset o, false if it holds a non-ACGT base
+HGX_ALN_HD inline bool hgx_aln_seed_code(const hgx_aln_read &R, int o, uint32_t *code) {
+    uint32_t c = 0;
+    for (int k = 0; k < HGX_ALN_K; ++k) {
+        const int b = hgx_aln_code2(R.at(o + k));
+        if (b < 0) return false;
+        c = (c << 2) | (uint32_t)b;
+    }
+    *code = c;
+    return true;
+}
+HGX_ALN_HD inline int hgx_aln_locus_of(const hgx_aln_view &V, int32_t P) {
+    int g = 0;
+    while (g + 1 < V.n_loci && V.bb_off[g + 1] <= P) ++g;
+    return g;
+}
+
+// read base r on backbone base P: 0 = match, 1 = unknown edit, 2 = the known single *v
+HGX_ALN_HD inline int hgx_aln_base(const hgx_aln_view &V, const hgx_aln_read &R, int r, int32_t P, int32_t *v) {
+    const char c = R.at(r);
+    if (c == V.bb[P]) return 0;
+    if (hgx_aln_code2(c) >= 0)
+        for (int32_t k = V.sgl_off[P]; k < V.sgl_off[P + 1]; ++k)
+            if ((char)V.vdata[V.sgl[k]] == c) { *v = V.sgl[k]; return 2; }
+    return 1;
+}
+// bases the insertion v consumes at read base r (cut by the read's right end), or -1 if they differ
+HGX_ALN_HD inline int hgx_aln_ins_fits(const hgx_aln_view &V, const hgx_aln_read &R, int32_t v, int r) {
+    const char *d = V.pool + V.vdata[v];
+    int n = V.vlen[v];
+    if (n > R.L - r) n = R.L - r;
+    for (int k = 0; k < n; ++k)
+        if (R.at(r + k) != d[k]) return -1;
+    return n;
+}
+
+template <int MAXV> struct hgx_aln_side {
+    int32_t found, nm, nind, nl, pos;          // pos: pos0 (left side) or the backbone end (right side), global
+    int32_t vl[MAXV];                          // in walk order
+};
+template <int MAXV> struct hgx_aln_res {
+    int32_t ok, nm, nind, nvar, locus, strand, pos0, end;      // pos0 / end global
+    int32_t vl[MAXV];
+};
+struct hgx_aln_frame { int32_t r, P, nm, nind, nl, k; };
+
+// MEMO: what a route remembers about the states a side's search has reached through a known indel.  dominated(side, r, P, cost, list)
+// == true cuts the path: an earlier path reached the same state (side 0: (r, P) before its events; side 1: base r on P) with a
+// smaller cost, or the same cost and a list that sorts first -- every way to finish from here is then a way to finish from there
+// with a smaller total, so nothing the order could pick is lost.  Without a memo (the kernels: fixed scratch) the enumeration grows
+// with the number of COMBINATIONS of known indels that lead to one state (a tandem repeat with many known unit deletions and
+// insertions) and ends at max_steps; with one (the host route) a state is finished once per improvement of its arrival.
+struct hgx_aln_no_memo {
+    HGX_ALN_HD void reset() {}
+    HGX_ALN_HD bool dominated(int, int, int32_t, int, int, int, const int32_t *) { return false; }
+};
+
+HGX_ALN_HD inline int hgx_aln_cmp3(int a0, int a1, int a2, int b0, int b1, int b2) {
+    return a0 != b0 ? (a0 < b0 ? -1 : 1) : a1 != b1 ? (a1 < b1 ? -1 : 1) : a2 != b2 ? (a2 < b2 ? -1 : 1) : 0;
+}
+
+// every way to finish from state (r0, P0), r0 > 0, inside the locus [lo, hi): the smallest by (NM, indels, variants, list)
+template <int MAXSTK, int MAXV, class MEMO>
+HGX_ALN_HD int hgx_aln_right(const hgx_aln_view &V, const hgx_aln_read &R, int32_t hi, int r0, int32_t P0, int max_nm, long max_steps,
+                             hgx_aln_frame *stk, int32_t *cur, hgx_aln_side<MAXV> &best, MEMO &memo) {
+    int sp = 0;
+    long steps = 0;
+    best.found = 0;
+    int r = r0, nm = 0, nind = 0, nl = 0, k = 0;
+    int32_t P = P0;
+    for (;;) {
+        bool dead = false, done = false;
+        int32_t end = P;
+        if (r == R.L) done = true;
+        else if (P >= hi) dead = true;
+        else {
+            if (++steps > max_steps) return HGX_ALN_DECLINE_STEPS;
+            const int nd = V.dls_off[P + 1] - V.dls_off[P], ni = V.ins_off[P + 1] - V.ins_off[P];
+            const int nopt = 1 + nd + ni + nd * ni;
+            if (k + 1 < nopt) {
+                if (sp == MAXSTK) return HGX_ALN_DECLINE_STACK;
+                stk[sp++] = hgx_aln_frame{r, P, nm, nind, nl, k + 1};
+            }
+            int32_t dv = -1, iv = -1;
+            if (k == 0) {
+            } else if (k <= nd) dv = V.dls[V.dls_off[P] + k - 1];
+            else if (k <= nd + ni) iv = V.ins[V.ins_off[P] + k - 1 - nd];
+            else {
+                const int idx = k - 1 - nd - ni;
+                dv = V.dls[V.dls_off[P] + idx / ni];
+                iv = V.ins[V.ins_off[P] + idx % ni];
+            }
+            int rr = r;
+            int32_t PP = P;
+            for (int step = 0; step < 2 && !dead; ++step) {
+                const bool take_del = step == 1;
+                const int32_t v = take_del ? dv : iv;
+                if (v < 0) continue;
+                if (nl == MAXV) return HGX_ALN_DECLINE_VARS;
+                cur[nl++] = v;
+                ++nind;
+                if (take_del) PP += V.vlen[v];
+                else {
+                    const int n = hgx_aln_ins_fits(V, R, v, rr);
+                    if (n < 0) dead = true;
+                    else rr += n;
+                }
+            }
+            if (!dead) {
+                if (rr >= R.L) { done = true; end = PP; }
+                else if (PP >= hi) dead = true;
+                else {
+                    int32_t sv = -1;
+                    const int c = hgx_aln_base(V, R, rr, PP, &sv);
+                    if (c == 1) { if (++nm > max_nm) dead = true; }
+                    else if (c == 2) {
+                        if (nl == MAXV) return HGX_ALN_DECLINE_VARS;
+                        cur[nl++] = sv;
+                    }
+                    r = rr + 1;
+                    P = PP + 1;
+                    k = 0;
+                    if (!dead && best.found && hgx_aln_cmp3(nm, nind, nl, best.nm, best.nind, best.nl) > 0) dead = true;
+                    if (!dead && nind > 0 && r < R.L && memo.dominated(0, r, P, nm, nind, nl, cur)) dead = true;
+                }
+            }
+        }
+        if (done) {
+            int c = best.found ? hgx_aln_cmp3(nm, nind, nl, best.nm, best.nind, best.nl) : -1;
+            for (int i = 0; c == 0 && i < nl; ++i) c = cur[i] != best.vl[i] ? (cur[i] < best.vl[i] ? -1 : 1) : 0;
+            if (c < 0) {
+                best.found = 1; best.nm = nm; best.nind = nind; best.nl = nl; best.pos = end;
+                for (int i = 0; i < nl; ++i) best.vl[i] = cur[i];
+            }
+        }
+        if (dead || done) {
+            if (sp == 0) break;
+            const hgx_aln_frame f = stk[--sp];
+            r = f.r; P = f.P; nm = f.nm; nind = f.nind; nl = f.nl; k = f.k;
+        }
+    }
+    return 0;
+}
+
+// every way to have arrived at "read base r0 sits on backbone base Q0" inside the locus [lo, hi): the smallest by
+// (NM, indels, variants, pos0, list).  `cur` holds the list backwards.
+template <int MAXSTK, int MAXV, class MEMO>
+HGX_ALN_HD int hgx_aln_left(const hgx_aln_view &V, const hgx_aln_read &R, int32_t lo, int r0, int32_t Q0, int max_nm, long max_steps,
+                            hgx_aln_frame *stk, int32_t *cur, hgx_aln_side<MAXV> &best, MEMO &memo) {
+    int sp = 0;
+    long steps = 0;
+    best.found = 0;
+    int r = r0, nm = 0, nind = 0, nl = 0, k = 0;
+    int32_t Q = Q0;
+    for (;;) {
+        bool dead = false, done = false;
+        if (r == 0) done = true;
+        else {
+            if (++steps > max_steps) return HGX_ALN_DECLINE_STEPS;
+            const int nde = V.dle_off[Q + 1] - V.dle_off[Q], niq = V.ins_off[Q + 1] - V.ins_off[Q];
+            int nopt = 1 + nde + niq;
+            for (int j = 0; j < nde; ++j) {
+                const int32_t p1 = V.vpos[V.dle[V.dle_off[Q] + j]];
+                nopt += V.ins_off[p1 + 1] - V.ins_off[p1];
+            }
+            if (k + 1 < nopt) {
+                if (sp == MAXSTK) return HGX_ALN_DECLINE_STACK;
+                stk[sp++] = hgx_aln_frame{r, Q, nm, nind, nl, k + 1};
+            }
+            int32_t dv = -1, iv = -1;
+            if (k == 0) {
+            } else if (k <= nde) dv = V.dle[V.dle_off[Q] + k - 1];
+            else if (k <= nde + niq) iv = V.ins[V.ins_off[Q] + k - 1 - nde];
+            else {
+                int idx = k - 1 - nde - niq;
+                for (int j = 0; j < nde; ++j) {
+                    const int32_t d = V.dle[V.dle_off[Q] + j], p1 = V.vpos[d];
+                    const int cnt = V.ins_off[p1 + 1] - V.ins_off[p1];
+                    if (idx < cnt) { dv = d; iv = V.ins[V.ins_off[p1] + idx]; break; }
+                    idx -= cnt;
+                }
+            }
+            int r1 = r;
+            int32_t P1 = dv >= 0 ? V.vpos[dv] : Q;
+            if (iv >= 0) {
+                const int n = V.vlen[iv];
+                if (r - n < 1 || hgx_aln_ins_fits(V, R, iv, r - n) != n) dead = true;
+                else r1 = r - n;
+            }
+            if (!dead) {
+                // backwards: the later event of the pair, the deletion, first
+                for (int step = 0; step < 2; ++step) {
+                    const bool take_del = step == 0;
+                    const int32_t v = take_del ? dv : iv;
+                    if (v < 0) continue;
+                    if (nl == MAXV) return HGX_ALN_DECLINE_VARS;
+                    cur[nl++] = v;
+                    ++nind;
+                }
+                if (P1 - 1 < lo) dead = true;
+                else {
+                    int32_t sv = -1;
+                    const int c = hgx_aln_base(V, R, r1 - 1, P1 - 1, &sv);
+                    if (c == 1) { if (++nm > max_nm) dead = true; }
+                    else if (c == 2) {
+                        if (nl == MAXV) return HGX_ALN_DECLINE_VARS;
+                        cur[nl++] = sv;
+                    }
+                    r = r1 - 1;
+                    Q = P1 - 1;
+                    k = 0;
+                    if (!dead && best.found && hgx_aln_cmp3(nm, nind, nl, best.nm, best.nind, best.nl) > 0) dead = true;
+                    if (!dead && nind > 0 && r > 0 && memo.dominated(1, r, Q, nm, nind, nl, cur)) dead = true;
+                }
+            }
+        }
+        if (done) {
+            int c = best.found ? hgx_aln_cmp3(nm, nind, nl, best.nm, best.nind, best.nl) : -1;
+            if (c == 0 && Q != best.pos) c = Q < best.pos ? -1 : 1;
+            for (int i = 0; c == 0 && i < nl; ++i) {
+                const int32_t a = cur[nl - 1 - i];
+                c = a != best.vl[i] ? (a < best.vl[i] ? -1 : 1) : 0;
+            }
+            if (c < 0) {
+                best.found = 1; best.nm = nm; best.nind = nind; best.nl = nl; best.pos = Q;
+                for (int i = 0; i < nl; ++i) best.vl[i] = cur[nl - 1 - i];
+            }
+        }
+        if (dead || done) {
+            if (sp == 0) break;
+            const hgx_aln_frame f = stk[--sp];
+            r = f.r; Q = f.P; nm = f.nm; nind = f.nind; nl = f.nl; k = f.k;
+        }
+    }
+    return 0;
+}
+
+// canon(a) of the anchor (read offset o, global backbone position b) of strand R.strand: res.ok = 0 if no alignment is admissible
+// through it.  `side` is scratch for one side's best.
+template <int MAXSTK, int MAXV, class MEMO>
+HGX_ALN_HD int hgx_aln_canon(const hgx_aln_view &V, const hgx_aln_read &R, int o, int32_t b, int max_edits, long max_steps,
+                             hgx_aln_frame *stk, int32_t *cur, hgx_aln_side<MAXV> &side, hgx_aln_res<MAXV> &res, MEMO &memo) {
+    const int g = hgx_aln_locus_of(V, b);
+    const int32_t lo = V.bb_off[g], hi = V.bb_off[g + 1];
+    res.ok = 0;
+    memo.reset();
+    int rc = hgx_aln_left<MAXSTK, MAXV>(V, R, lo, o, b, max_edits, max_steps, stk, cur, side, memo);
+    if (rc) return rc;
+    if (!side.found) return 0;
+    memo.reset();
+    res.nm = side.nm; res.nind = side.nind; res.nvar = side.nl; res.pos0 = side.pos;
+    for (int i = 0; i < side.nl; ++i) res.vl[i] = side.vl[i];
+    rc = hgx_aln_right<MAXSTK, MAXV>(V, R, hi, o + HGX_ALN_K, b + HGX_ALN_K, max_edits - res.nm, max_steps, stk, cur, side, memo);
+    if (rc) return rc;
+    if (!side.found) return 0;
+    if (res.nvar + side.nl > MAXV) return HGX_ALN_DECLINE_VARS;
+    for (int i = 0; i < side.nl; ++i) res.vl[res.nvar + i] = side.vl[i];
+    res.nm += side.nm; res.nind += side.nind; res.nvar += side.nl; res.end = side.pos;
+    res.locus = g; res.strand = R.strand; res.ok = 1;
+    return 0;
+}
+
+template <int MAXV> HGX_ALN_HD int hgx_aln_res_cmp(const hgx_aln_res<MAXV> &a, const hgx_aln_res<MAXV> &b) {
+    int c = hgx_aln_cmp3(a.nm, a.nind, a.nvar, b.nm, b.nind, b.nvar);
+    if (c) return c;
+    c = hgx_aln_cmp3(a.locus, a.strand, a.pos0, b.locus, b.strand, b.pos0);
+    for (int i = 0; c == 0 && i < a.nvar; ++i) c = a.vl[i] != b.vl[i] ? (a.vl[i] < b.vl[i] ? -1 : 1) : 0;
+    return c;
+}
+
+// the read's alignment among the canon(a) of its anchors: index of the smallest (-1: unaligned) and NH, the number of placements
+// of those with the smallest NM
+template <int MAXV> HGX_ALN_HD int hgx_aln_pick(const hgx_aln_res<MAXV> *res, int n, int *nh_out) {
+    int best = -1;
+    for (int i = 0; i < n; ++i)
+        if (res[i].ok && (best < 0 || hgx_aln_res_cmp(res[i], res[best]) < 0)) best = i;
+    *nh_out = 0;
+    if (best < 0) return -1;
+    const int nm = res[best].nm;
+    // walk those with NM == nm in (locus, strand, pos0, slot) order
+    int nh = 0, last = -1, cur_g = -1, cur_s = -1;
+    int32_t cur_end = 0;
+    for (;;) {
+        int nxt = -1;
+        for (int i = 0; i < n; ++i) {
+            if (!res[i].ok || res[i].nm != nm) continue;
+            if (last >= 0) {
+                const int c = hgx_aln_cmp3(res[i].locus, res[i].strand, res[i].pos0, res[last].locus, res[last].strand, res[last].pos0);
+                if (c < 0 || (c == 0 && i <= last)) continue;
+            }
+            if (nxt >= 0) {
+                const int c = hgx_aln_cmp3(res[i].locus, res[i].strand, res[i].pos0, res[nxt].locus, res[nxt].strand, res[nxt].pos0);
+                if (c > 0 || (c == 0 && i > nxt)) continue;
+            }
+            nxt = i;
+        }
+        if (nxt < 0) break;
+        if (res[nxt].locus != cur_g || res[nxt].strand != cur_s || res[nxt].pos0 >= cur_end) {
+            ++nh;
+            cur_g = res[nxt].locus; cur_s = res[nxt].strand; cur_end = res[nxt].end;
+        } else if (res[nxt].end > cur_end) cur_end = res[nxt].end;
+        last = nxt;
+    }
+    *nh_out = nh;
+    return best;
+}
+
+// ---- the SAM record ----------------------------------------------------------------------------------------------------------------
+struct hgx_aln_out {                       // p == nullptr: count only
+    char *p;
+    int64_t n;
+    HGX_ALN_HD void ch(char c) { if (p) p[n] = c; ++n; }
+    HGX_ALN_HD void str(const char *s, int len) { for (int i = 0; i < len; ++i) ch(s[i]); }
+    HGX_ALN_HD void num(int64_t v) {
+        char t[24];
+        int k = 0;
+        if (v < 0) { ch('-'); v = -v; }
+        do { t[k++] = (char)('0' + v % 10); v /= 10; } while (v);
+        while (k) ch(t[--k]);
+    }
+};
+
+// one of CIGAR (what = 0), MD (1), Zs (2) of the walk, as simulate._truth_record renders them; returns the number of Zs items
+HGX_ALN_HD inline int hgx_aln_walk_text(const hgx_aln_view &V, const hgx_aln_read &R, int32_t pos0, const int32_t *vl, int nvar, int what,
+                                        hgx_aln_out &out) {
+    int r = 0, vi = 0, md_run = 0, gap = 0, n_zs = 0, run = 0;
+    char op = 0;
+    int32_t P = pos0;
+    auto cigar = [&](char o, int n) {
+        if (op == o) run += n;
+        else {
+            if (op && what == 0) { out.num(run); out.ch(op); }
+            op = o; run = n;
+        }
+    };
+    auto zs = [&](char kind, int32_t v) {
+        if (what == 2) {
+            if (n_zs) out.ch(',');
+            out.num(gap); out.ch('|'); out.ch(kind); out.ch('|');
+            out.str(V.pool + V.vid_off[v], V.vid_len[v]);
+        }
+        ++n_zs;
+    };
+    while (r < R.L) {
+        if (r > 0) {
+            const int32_t at = P;
+            while (vi < nvar && V.vtype[vl[vi]] != HGX_ALN_SGL && V.vpos[vl[vi]] == at) {
+                const int32_t v = vl[vi++];
+                if (V.vtype[v] == HGX_ALN_DEL) {
+                    const int n = V.vlen[v];
+                    if (what == 1) { out.num(md_run); out.ch('^'); out.str(V.bb + P, n); }
+                    md_run = 0;
+                    cigar('D', n);
+                    zs('D', v);
+                    gap = 0;
+                    P += n;
+                } else {
+                    int n = V.vlen[v];
+                    if (n > R.L - r) n = R.L - r;
+                    zs('I', v);
+                    gap = n;
+                    cigar('I', n);
+                    r += n;
+                }
+            }
+        }
+        if (r >= R.L) break;
+        if (R.at(r) == V.bb[P]) { ++md_run; ++gap; }
+        else {
+            if (what == 1) { out.num(md_run); out.ch(V.bb[P]); }
+            md_run = 0;
+            if (vi < nvar && V.vtype[vl[vi]] == HGX_ALN_SGL && V.vpos[vl[vi]] == P) { zs('S', vl[vi++]); gap = 0; }
+            else ++gap;
+        }
+        cigar('M', 1);
+        ++r;
+        ++P;
+    }
+    if (what == 0 && op) { out.num(run); out.ch(op); }
+    if (what == 1) out.num(md_run);
+    return n_zs;
+}
+
+// FLAG / RNEXT / PNEXT / YT of a record: `mate` = the other mate's alignment (nullptr: single-end; ok == 0: unaligned)
+template <int MAXV>
+HGX_ALN_HD bool hgx_aln_concordant(const hgx_aln_res<MAXV> &a, const hgx_aln_res<MAXV> &b, int max_fragment) {
+    if (!a.ok || !b.ok || a.locus != b.locus || a.strand == b.strand) return false;
+    const hgx_aln_res<MAXV> &plus = a.strand == 0 ? a : b, &minus = a.strand == 0 ? b : a;
+    if (plus.pos0 > minus.pos0) return false;
+    const int32_t left = a.pos0 < b.pos0 ? a.pos0 : b.pos0, right = a.end > b.end ? a.end : b.end;
+    return right - left <= max_fragment;
+}
+
+// the whole line (with its '\n'); `name` / `qual` as the file has them (qual == nullptr: 'I' x L)
+template <int MAXV>
+HGX_ALN_HD void hgx_aln_line(const hgx_aln_view &V, const char *name, int name_len, const char *seq, const char *qual, int L,
+                             const hgx_aln_res<MAXV> &a, int nh, const hgx_aln_res<MAXV> *mate, int mate_no, int max_fragment,
+                             hgx_aln_out &out) {
+    const hgx_aln_read R{seq, L, a.strand};
+    const int32_t lo = V.bb_off[a.locus];
+    int flag = a.strand ? 16 : 0;
+    const char *yt = "UU";
+    int rnext = 0;                          // 0 '*', 1 '=', 2 the mate's locus
+    int64_t pnext = 0;
+    if (mate) {
+        flag |= 1 | (mate_no == 0 ? 0x40 : 0x80);
+        if (!mate->ok) { flag |= 8; rnext = 1; pnext = a.pos0 - lo + 1; yt = "UP"; }
+        else {
+            if (mate->strand) flag |= 0x20;
+            rnext = mate->locus == a.locus ? 1 : 2;
+            pnext = mate->pos0 - V.bb_off[mate->locus] + 1;
+            if (hgx_aln_concordant(a, *mate, max_fragment)) { flag |= 2; yt = "CP"; }
+            else yt = "DP";
+        }
+    }
+    out.str(name, name_len); out.ch('\t');
+    out.num(flag); out.ch('\t');
+    out.str(V.pool + V.name_off[a.locus], V.name_len[a.locus]); out.ch('\t');
+    out.num(a.pos0 - lo + 1); out.ch('\t');
+    out.num(nh == 1 ? 60 : 1); out.ch('\t');
+    hgx_aln_walk_text(V, R, a.pos0, a.vl, a.nvar, 0, out); out.ch('\t');
+    if (rnext == 0) out.ch('*');
+    else if (rnext == 1) out.ch('=');
+    else out.str(V.pool + V.name_off[mate->locus], V.name_len[mate->locus]);
+    out.ch('\t');
+    out.num(pnext); out.ch('\t');
+    out.ch('0'); out.ch('\t');
+    for (int r = 0; r < L; ++r) out.ch(R.at(r));
+    out.ch('\t');
+    for (int r = 0; r < L; ++r) out.ch(qual ? qual[a.strand ? L - 1 - r : r] : 'I');
+    out.str("\tNM:i:", 6); out.num(a.nm);
+    out.str("\tMD:Z:", 6);
+    hgx_aln_walk_text(V, R, a.pos0, a.vl, a.nvar, 1, out);
+    hgx_aln_out count{nullptr, 0};
+    if (hgx_aln_walk_text(V, R, a.pos0, a.vl, a.nvar, 2, count)) {
+        out.str("\tZs:Z:", 6);
+        hgx_aln_walk_text(V, R, a.pos0, a.vl, a.nvar, 2, out);
+    }
+    out.str("\tNH:i:", 6); out.num(nh);
+    out.str("\tYT:Z:", 6); out.str(yt, 2);
+    out.ch('\n');
+}

@@ -1,0 +1,436 @@
+// hgx_align_host.cpp -- the "hgx" aligner's C-ABI, index, read files and HOST route.  The host route runs the
+// same core as the kernels (hgx_align_core.hpp) with scratch large enough for every read the core takes: it is their checker
+// and what finishes a call they decline.  Plain C++: this unit is also compiled on its own, with a main(), for the sanitizers.
+#include <zlib.h>
+
+#include <algorithm>
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+#include <stdexcept>
+#include <unordered_map>
+
+#include "hgx_align.hpp"
+
+extern "C" void hgx_set_error(const char *fmt, ...);
+extern "C" const char *hgx_test_switch(const char *name);
+void *hgx_host_alloc(size_t bytes);
+
+namespace {
+thread_local int g_route = 0, g_decline = 0;
+thread_local int64_t g_reads = 0, g_aligned = 0, g_conc = 0;
+
+template <class T> void csr(const std::vector<std::pair<int32_t, int32_t>> &items, int32_t n_pos, std::vector<T> &off, std::vector<T> &list) {
+    off.assign((size_t)n_pos + 1, 0);
+    for (auto &it : items) off[(size_t)it.first + 1]++;
+    for (int32_t p = 0; p < n_pos; ++p) off[(size_t)p + 1] += off[p];
+    list.resize(items.size());
+    std::vector<T> fill(off.begin(), off.end() - 1);
+    for (auto &it : items) list[(size_t)fill[it.first]++] = it.second;          // items arrive in variant order: kept per position
+}
+
+int add_pool(std::vector<char> &pool, const char *s, size_t n) {
+    const int off = (int)pool.size();
+    pool.insert(pool.end(), s, s + n);
+    return off;
+}
+
+// ---- read files ------------------------------------------------------------------------------------------------------------------
+int slurp(const char *path, std::string &out) {
+    gzFile f = gzopen(path, "rb");                     // plain files pass through unchanged
+    if (!f) { hgx_set_error("hgx_align_reads: cannot open %s", path); return HGX_EINVAL; }
+    char buf[1 << 16];
+    int n;
+    while ((n = gzread(f, buf, sizeof buf)) > 0) out.append(buf, (size_t)n);
+    gzclose(f);
+    if (n < 0) { hgx_set_error("hgx_align_reads: %s is damaged", path); return HGX_EPARSE; }
+    return HGX_OK;
+}
+int inflate_text(const char *p, size_t n, std::string &out) {
+    if (n < 2 || (unsigned char)p[0] != 0x1f || (unsigned char)p[1] != 0x8b) { out.assign(p, n); return HGX_OK; }
+    z_stream z;
+    memset(&z, 0, sizeof z);
+    if (inflateInit2(&z, 15 + 32) != Z_OK) return HGX_ENOMEM;
+    z.next_in = (Bytef *)p;
+    z.avail_in = (uInt)n;
+    char buf[1 << 16];
+    int rc = Z_OK;
+    while (rc != Z_STREAM_END) {
+        z.next_out = (Bytef *)buf;
+        z.avail_out = sizeof buf;
+        rc = inflate(&z, Z_NO_FLUSH);
+        if (rc != Z_OK && rc != Z_STREAM_END) { inflateEnd(&z); hgx_set_error("hgx_align_reads: damaged gzip text"); return HGX_EPARSE; }
+        out.append(buf, sizeof buf - z.avail_out);
+        if (rc == Z_STREAM_END && z.avail_in > 0) { if (inflateReset(&z) != Z_OK) break; rc = Z_OK; }      // the next member
+    }
+    inflateEnd(&z);
+    return HGX_OK;
+}
+
+struct Rec { size_t name, name_len, seq, seq_len; long qual; };          // offsets into the parsed text; qual < 0: none
+
+// records of one FASTA / FASTQ text; multi-line FASTA bases are joined into `joined`
+int parse_reads(const std::string &t, int fastq, std::vector<Rec> &recs, std::string &joined, std::vector<char> &from_joined) {
+    size_t k = 0;
+    const size_t n = t.size();
+    auto line = [&](size_t &b, size_t &e) {            // next line [b, e) without its end, false at the end of the text
+        if (k >= n) return false;
+        b = k;
+        const char *nl = (const char *)memchr(t.data() + k, '\n', n - k);
+        e = nl ? (size_t)(nl - t.data()) : n;
+        k = e + 1;
+        if (e > b && t[e - 1] == '\r') --e;
+        return true;
+    };
+    if (fastq < 0) fastq = n > 0 && t[0] == '@';
+    size_t b, e;
+    bool have = line(b, e);
+    while (have) {
+        if (e == b) { have = line(b, e); continue; }
+        if (t[b] != (fastq ? '@' : '>')) { hgx_set_error("hgx_align_reads: neither FASTA nor FASTQ at byte %zu", b); return HGX_EPARSE; }
+        Rec r{};
+        r.name = b + 1;
+        size_t q = b + 1;
+        while (q < e && t[q] != ' ' && t[q] != '\t') ++q;
+        r.name_len = q - r.name;
+        if (fastq) {
+            size_t sb, se, pb, pe, qb, qe;
+            if (!line(sb, se) || !line(pb, pe) || !line(qb, qe) || qe - qb != se - sb) {
+                hgx_set_error("hgx_align_reads: truncated FASTQ record at byte %zu", b);
+                return HGX_EPARSE;
+            }
+            r.seq = sb; r.seq_len = se - sb; r.qual = (long)qb;
+            from_joined.push_back(0);
+            have = line(b, e);
+        } else {
+            size_t sb = 0, se = 0;
+            int n_lines = 0;
+            r.qual = -1;
+            while ((have = line(b, e)) && !(e > b && t[b] == '>')) {
+                if (n_lines == 0) { sb = b; se = e; }
+                else {
+                    if (n_lines == 1) { r.seq = joined.size(); joined.append(t, sb, se - sb); }
+                    joined.append(t, b, e - b);
+                }
+                ++n_lines;
+            }
+            if (n_lines <= 1) { r.seq = sb; r.seq_len = se - sb; from_joined.push_back(0); }
+            else { r.seq_len = joined.size() - r.seq; from_joined.push_back(1); }
+        }
+        recs.push_back(r);
+    }
+    return HGX_OK;
+}
+
+int load_reads(int n_inputs, const char *const *paths, const char *const *texts, const size_t *text_bytes, int fastq, hgx_aln_reads &out) {
+    std::vector<std::string> text(n_inputs), joined(n_inputs);
+    std::vector<std::vector<Rec>> recs(n_inputs);
+    std::vector<std::vector<char>> fj(n_inputs);
+    for (int i = 0; i < n_inputs; ++i) {
+        int rc;
+        if (paths) rc = slurp(paths[i], text[i]);
+        else rc = inflate_text(texts[i], text_bytes[i], text[i]);
+        if (rc) return rc;
+        if ((rc = parse_reads(text[i], fastq, recs[i], joined[i], fj[i]))) return rc;
+    }
+    if (n_inputs == 2 && recs[0].size() != recs[1].size()) {
+        hgx_set_error("hgx_align_reads: %zu reads in the first file, %zu in the second", recs[0].size(), recs[1].size());
+        return HGX_EPARSE;
+    }
+    out.paired = n_inputs == 2;
+    for (size_t k = 0; k < recs[0].size(); ++k)
+        for (int i = 0; i < n_inputs; ++i) {
+            const Rec &r = recs[i][k];
+            if (r.seq_len > HGX_ALN_MAX_READ) {
+                hgx_set_error("hgx_align_reads: a read of %zu bases (the aligner takes up to %d)", r.seq_len, HGX_ALN_MAX_READ);
+                return HGX_EINVAL;
+            }
+            out.name_off.push_back((int64_t)out.text.size());
+            out.name_len.push_back((int32_t)r.name_len);
+            out.text.insert(out.text.end(), text[i].data() + r.name, text[i].data() + r.name + r.name_len);
+            out.seq_off.push_back((int64_t)out.text.size());
+            out.len.push_back((int32_t)r.seq_len);
+            const char *s = (fj[i][k] ? joined[i].data() : text[i].data()) + r.seq;
+            for (size_t j = 0; j < r.seq_len; ++j) out.text.push_back((char)toupper((unsigned char)s[j]));
+            if (r.qual >= 0) {
+                out.qual_off.push_back((int64_t)out.text.size());
+                out.text.insert(out.text.end(), text[i].data() + r.qual, text[i].data() + r.qual + r.seq_len);
+            } else out.qual_off.push_back(-1);
+        }
+    return HGX_OK;
+}
+
+// ---- the host route ----------------------------------------------------------------------------------------------------------------
+typedef hgx_aln_res<HGX_ALN_HOST_VARS> HostRes;
+
+// the host route's MEMO (hgx_align_core.hpp): the best arrival at every state reached through a known indel, per side of one anchor
+struct HostMemo {
+    struct Arrival { int nm, nind, nl; std::vector<int32_t> list; };
+    std::unordered_map<uint64_t, Arrival> seen[2];
+    void reset() { seen[0].clear(); seen[1].clear(); }
+    bool dominated(int side, int r, int32_t P, int nm, int nind, int nl, const int32_t *cur) {
+        const uint64_t key = ((uint64_t)(uint32_t)r << 32) | (uint32_t)P;
+        auto it = seen[side].find(key);
+        if (it != seen[side].end()) {
+            const Arrival &a = it->second;
+            int c = hgx_aln_cmp3(nm, nind, nl, a.nm, a.nind, a.nl);
+            // equal costs: equal lengths.  Side 0 lists are in walk order; side 1 lists are held backwards, and the part behind this
+            // state is the TAIL of the alignment's list, so they are compared from their last element down
+            for (int i = 0; c == 0 && i < nl; ++i) {
+                const int32_t x = side ? cur[nl - 1 - i] : cur[i], y = side ? a.list[(size_t)(nl - 1 - i)] : a.list[(size_t)i];
+                c = x != y ? (x < y ? -1 : 1) : 0;
+            }
+            if (c >= 0) return true;
+        }
+        seen[side][key] = Arrival{nm, nind, nl, std::vector<int32_t>(cur, cur + nl)};
+        return false;
+    }
+};
+
+struct HostScratch {
+    std::vector<hgx_aln_frame> stk;
+    std::vector<int32_t> cur;
+    std::unique_ptr<hgx_aln_side<HGX_ALN_HOST_VARS>> side{new hgx_aln_side<HGX_ALN_HOST_VARS>};
+    std::vector<HostRes> res;
+    HostMemo memo;
+    HostScratch() : stk(HGX_ALN_HOST_VARS), cur(HGX_ALN_HOST_VARS) {}
+};
+
+int align_one(const hgx_aln_view &V, const char *seq, int L, int max_edits, HostScratch &S, HostRes &best, int *nh, int *gave_up) {
+    S.res.clear();
+    for (int strand = 0; strand < 2; ++strand) {
+        const hgx_aln_read R{seq, L, strand};
+        const int n_off = hgx_aln_n_offsets(L);
+        for (int k = 0; k < n_off; ++k) {
+            const int o = hgx_aln_offset(L, k);
+            uint32_t code;
+            if (!hgx_aln_seed_code(R, o, &code)) continue;
+            for (uint32_t h = hgx_aln_hash(code) & V.hmask; V.hpos[h] >= 0; h = (h + 1) & V.hmask) {
+                if (V.hkey[h] != code) continue;
+                S.res.emplace_back();
+                const int rc = hgx_aln_canon<HGX_ALN_HOST_VARS, HGX_ALN_HOST_VARS>(V, R, o, V.hpos[h], max_edits, HGX_ALN_HOST_STEPS,
+                                                                                  S.stk.data(), S.cur.data(), *S.side, S.res.back(), S.memo);
+                if (rc) {                     // beyond the host route's own limits: this read is left unaligned, the call goes on
+                    S.res.clear();
+                    best.ok = 0;
+                    *nh = 0;
+                    *gave_up = rc;
+                    return HGX_OK;
+                }
+                if (!S.res.back().ok) S.res.pop_back();
+            }
+        }
+    }
+    const int b = hgx_aln_pick(S.res.data(), (int)S.res.size(), nh);
+    best.ok = 0;
+    if (b >= 0) best = S.res[(size_t)b];
+    return HGX_OK;
+}
+
+int host_route(const hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_align_opts *o, std::string &body, int64_t *aligned,
+               int64_t *conc, int *gave_up) {
+    const hgx_aln_view &V = ix->hv;
+    HostScratch S;
+    const int per = reads.paired ? 2 : 1;
+    std::vector<HostRes> best(per);
+    int nh[2] = {0, 0};
+    std::vector<char> line;
+    for (size_t k = 0; k < reads.n(); k += per) {
+        for (int m = 0; m < per; ++m) {
+            const int rc = align_one(V, reads.text.data() + reads.seq_off[k + m], reads.len[k + m], o->max_edits, S, best[m], &nh[m], gave_up);
+            if (rc) return rc;
+        }
+        if (per == 2 && hgx_aln_concordant(best[0], best[1], o->max_fragment)) ++*conc;
+        for (int m = 0; m < per; ++m) {
+            if (!best[m].ok) continue;
+            ++*aligned;
+            const size_t i = k + m;
+            const char *qual = reads.qual_off[i] >= 0 ? reads.text.data() + reads.qual_off[i] : nullptr;
+            const HostRes *mate = per == 2 ? &best[1 - m] : nullptr;
+            hgx_aln_out cnt{nullptr, 0};
+            hgx_aln_line(V, reads.text.data() + reads.name_off[i], reads.name_len[i], reads.text.data() + reads.seq_off[i], qual,
+                         reads.len[i], best[m], nh[m], mate, m, o->max_fragment, cnt);
+            line.resize((size_t)cnt.n);
+            hgx_aln_out w{line.data(), 0};
+            hgx_aln_line(V, reads.text.data() + reads.name_off[i], reads.name_len[i], reads.text.data() + reads.seq_off[i], qual,
+                         reads.len[i], best[m], nh[m], mate, m, o->max_fragment, w);
+            body.append(line.data(), line.size());
+        }
+    }
+    return HGX_OK;
+}
+}      // namespace
+
+#ifdef HGX_ALIGN_STANDALONE
+// the stand-alone build (tools/align_host_main.cpp) has no kernels and none of the library around it
+extern "C" void hgx_set_error(const char *fmt, ...) { va_list ap; va_start(ap, fmt); vfprintf(stderr, fmt, ap); va_end(ap); fputc('\n', stderr); }
+extern "C" const char *hgx_test_switch(const char *) { return "host"; }
+void *hgx_host_alloc(size_t bytes) { return malloc(bytes); }
+int hgx_align_device(hgx_align_index *, const hgx_aln_reads &, const hgx_align_opts *, std::string &, int64_t *, int64_t *, int *decline) {
+    *decline = HGX_ALN_DECLINE_SWITCH;
+    return HGX_OK;
+}
+void hgx_align_device_free(hgx_align_index *) {}
+#endif
+
+extern "C" int hgx_align_index_create(hgx_align_index **out, int32_t n_loci, const char *const *names, const char *const *backbones,
+                                      const int32_t *var_off, const int32_t *var_type, const int32_t *var_pos,
+                                      const char *const *var_data, const char *const *var_id) {
+    if (!out || n_loci < 1 || !names || !backbones || !var_off) {
+        hgx_set_error("invalid argument: hgx_align_index_create");
+        return HGX_EINVAL;
+    }
+    *out = nullptr;
+    try {
+        std::unique_ptr<hgx_align_index> ix(new hgx_align_index);
+        ix->bb_off.push_back(0);
+        for (int g = 0; g < n_loci; ++g) {
+            const size_t n = strlen(backbones[g]);
+            for (size_t k = 0; k < n; ++k) ix->bb.push_back((char)toupper((unsigned char)backbones[g][k]));
+            ix->bb_off.push_back((int32_t)ix->bb.size());
+            ix->name_off.push_back(add_pool(ix->pool, names[g], strlen(names[g])));
+            ix->name_len.push_back((int32_t)strlen(names[g]));
+            ix->header += "@SQ\tSN:" + std::string(names[g]) + "\tLN:" + std::to_string(n) + "\n";
+        }
+        const int32_t n_pos = (int32_t)ix->bb.size();
+        std::vector<std::pair<int32_t, int32_t>> sgl, dls, dle, ins;
+        const int32_t n_vars = var_off[n_loci];
+        for (int g = 0; g < n_loci; ++g) {
+            const int32_t lo = ix->bb_off[g], hi = ix->bb_off[g + 1];
+            for (int32_t v = var_off[g]; v < var_off[g + 1]; ++v) {
+                const int32_t P = lo + var_pos[v];
+                ix->vtype.push_back((uint8_t)var_type[v]);
+                ix->vpos.push_back(P);
+                ix->vid_off.push_back(add_pool(ix->pool, var_id[v], strlen(var_id[v])));
+                ix->vid_len.push_back((int32_t)strlen(var_id[v]));
+                const bool inside = var_pos[v] >= 0 && P < hi;      // a variant off the backbone can never be walked
+                if (var_type[v] == HGX_ALN_SGL) {
+                    ix->vlen.push_back(1);
+                    ix->vdata.push_back(toupper((unsigned char)var_data[v][0]));
+                    if (inside) sgl.emplace_back(P, v);
+                } else if (var_type[v] == HGX_ALN_DEL) {
+                    const int32_t n = atoi(var_data[v]);
+                    ix->vlen.push_back(n);
+                    ix->vdata.push_back(0);
+                    if (inside && n > 0 && P + n < hi) { dls.emplace_back(P, v); dle.emplace_back(P + n, v); }
+                } else if (var_type[v] == HGX_ALN_INS) {
+                    const size_t n = strlen(var_data[v]);
+                    ix->vlen.push_back((int32_t)n);
+                    const int off = (int)ix->pool.size();
+                    for (size_t k = 0; k < n; ++k) ix->pool.push_back((char)toupper((unsigned char)var_data[v][k]));
+                    ix->vdata.push_back(off);
+                    if (inside && n > 0) ins.emplace_back(P, v);
+                } else {
+                    hgx_set_error("hgx_align_index_create: variant type %d", var_type[v]);
+                    return HGX_EINVAL;
+                }
+            }
+        }
+        (void)n_vars;
+        csr(sgl, n_pos, ix->sgl_off, ix->sgl);
+        csr(dls, n_pos, ix->dls_off, ix->dls);
+        csr(dle, n_pos, ix->dle_off, ix->dle);
+        csr(ins, n_pos, ix->ins_off, ix->ins);
+        // the 16-mers of every backbone (windows with a non-ACGT base are not indexed)
+        std::vector<std::pair<uint32_t, int32_t>> kmers;
+        for (int g = 0; g < n_loci; ++g) {
+            const hgx_aln_read R{ix->bb.data() + ix->bb_off[g], ix->bb_off[g + 1] - ix->bb_off[g], 0};
+            for (int p = 0; p + HGX_ALN_K <= R.L; ++p) {
+                uint32_t code;
+                if (hgx_aln_seed_code(R, p, &code)) kmers.emplace_back(code, ix->bb_off[g] + p);
+            }
+        }
+        uint32_t cap = 16;
+        while (cap < 2 * kmers.size() + 1) cap <<= 1;
+        ix->hkey.assign(cap, 0);
+        ix->hpos.assign(cap, -1);
+        for (auto &km : kmers) {
+            uint32_t h = hgx_aln_hash(km.first) & (cap - 1);
+            while (ix->hpos[h] >= 0) h = (h + 1) & (cap - 1);
+            ix->hkey[h] = km.first;
+            ix->hpos[h] = km.second;
+        }
+        hgx_aln_view &V = ix->hv;
+        V.bb = ix->bb.data(); V.bb_off = ix->bb_off.data(); V.n_loci = n_loci; V.n_pos = n_pos;
+        V.hkey = ix->hkey.data(); V.hpos = ix->hpos.data(); V.hmask = cap - 1;
+        V.vtype = ix->vtype.data(); V.vpos = ix->vpos.data(); V.vlen = ix->vlen.data(); V.vdata = ix->vdata.data();
+        V.vid_off = ix->vid_off.data(); V.vid_len = ix->vid_len.data();
+        V.name_off = ix->name_off.data(); V.name_len = ix->name_len.data(); V.pool = ix->pool.data();
+        V.sgl_off = ix->sgl_off.data(); V.sgl = ix->sgl.data(); V.dls_off = ix->dls_off.data(); V.dls = ix->dls.data();
+        V.dle_off = ix->dle_off.data(); V.dle = ix->dle.data(); V.ins_off = ix->ins_off.data(); V.ins = ix->ins.data();
+        *out = ix.release();
+        return HGX_OK;
+    } catch (const std::exception &e) {
+        hgx_set_error("hgx_align_index_create: %s", e.what());
+        return HGX_ENOMEM;
+    }
+}
+
+extern "C" int hgx_align_index_free(hgx_align_index *ix) {
+    if (ix) {
+        hgx_align_device_free(ix);
+        delete ix;
+    }
+    return HGX_OK;
+}
+
+extern "C" int hgx_align_reads(hgx_align_index *ix, int32_t n_inputs, const char *const *paths, const char *const *texts,
+                               const size_t *text_bytes, const hgx_align_opts *opts, char **sam_out, size_t *n_bytes_out) {
+    if (!ix || (n_inputs != 1 && n_inputs != 2) || (!paths && !(texts && text_bytes)) || !opts || !sam_out || !n_bytes_out ||
+        opts->max_edits < 0 || opts->route < 0 || opts->route > 2) {
+        hgx_set_error("invalid argument: hgx_align_reads");
+        return HGX_EINVAL;
+    }
+    *sam_out = nullptr;
+    *n_bytes_out = 0;
+    g_route = 0; g_decline = 0; g_reads = g_aligned = g_conc = 0;
+    try {
+        hgx_aln_reads reads;
+        int rc = load_reads(n_inputs, paths, texts, text_bytes, opts->fastq, reads);
+        if (rc) return rc;
+        g_reads = (int64_t)reads.n();
+        std::string body;
+        int64_t aligned = 0, conc = 0;
+        int decline = 0;
+        const char *sw = hgx_test_switch("front");
+        if (opts->route == 1 || (opts->route == 0 && sw && !strcmp(sw, "host"))) decline = HGX_ALN_DECLINE_SWITCH;
+        else if (opts->route == 0 && !(sw && !strcmp(sw, "device")) && reads.n() < 1000) decline = HGX_ALN_DECLINE_GATE;
+        if (!decline && reads.n() > 0) {
+            if ((rc = hgx_align_device(ix, reads, opts, body, &aligned, &conc, &decline))) return rc;
+        }
+        if (decline) {
+            body.clear();
+            aligned = conc = 0;
+            int gave_up = 0;
+            if ((rc = host_route(ix, reads, opts, body, &aligned, &conc, &gave_up))) return rc;
+            if (gave_up) fprintf(stderr, "[hgx_align_reads] a read's search passed the host route's limits (code %d): left unaligned\n", gave_up);
+        }
+        g_route = decline ? 0 : 2;
+        g_decline = decline;
+        g_aligned = aligned;
+        g_conc = conc;
+        const size_t total = ix->header.size() + body.size();
+        char *out = (char *)hgx_host_alloc(total + 1);
+        if (!out) { hgx_set_error("hgx_align_reads: out of memory"); return HGX_ENOMEM; }
+        memcpy(out, ix->header.data(), ix->header.size());
+        memcpy(out + ix->header.size(), body.data(), body.size());
+        out[total] = 0;
+        *sam_out = out;
+        *n_bytes_out = total;
+        return HGX_OK;
+    } catch (const std::exception &e) {
+        hgx_set_error("hgx_align_reads: %s", e.what());
+        return HGX_ENOMEM;
+    }
+}
+
+extern "C" int hgx_align_last(int32_t *route, int64_t *reads, int64_t *aligned, int64_t *pairs_concordant, int32_t *decline_code) {
+    if (route) *route = g_route;
+    if (reads) *reads = g_reads;
+    if (aligned) *aligned = g_aligned;
+    if (pairs_concordant) *pairs_concordant = g_conc;
+    if (decline_code) *decline_code = g_decline;
+    return HGX_OK;
+}

@@ -653,3 +653,6 @@ def em_set_backend(backend):
     """0 = auto (table lookup), 1 = EXEC-masked FP64 VALU mat-vec, 3 = table-lookup mat-vec (256 subset sums per 8 columns in
     LDS); 2 = int8 MFMA mat-vec (128-bit fixed point), lab build only (capi.use_lab())."""
     capi.check(capi.lib().hgx_em_set_backend(C.c_int(backend)))
+
+
+from .align import AlignIndex, align_last          # noqa: E402,F401  (the "hgx" aligner, DESIGN.md 5.13)

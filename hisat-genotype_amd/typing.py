@@ -745,7 +745,8 @@ def typing(simulation, full_path_base_fname, locus_list, genotype_genome, partia
                 alignment_fname = "%s_output.bam" % base_fname if simulation else "%s.bam" % core_fid
                 gegenome = genotype_genome if genotype_genome != "" else full_path_base_fname + "." + index_type
                 simulate.align_reads(aligner, simulation, gegenome, index_type, base_fname, read_fname, fastq, threads,
-                                     alignment_fname, verbose, truth=(Genes, Vars, refGenes))
+                                     alignment_fname, verbose, truth=(Genes, Vars, refGenes), var_list=Var_list,
+                                     max_edits=num_editdist)
             # The reference's loop `for test_Gene_names in locus_list` (core:370) runs `samtools view F ref_allele | sort` per locus:
             # here the file is read ONCE (engine.Alignment: its bytes stay in HBM) and the loci -- independent of each other in the
             # reference too: every per-locus structure is rebuilt -- are typed side by side, one host thread and stream per locus;

@@ -831,6 +831,35 @@ int hgx_extract_stats(const hgx_extract *h, int64_t *records, int64_t *groups, i
                       int32_t *decline, int32_t *error_kind, int64_t *chunks_device, int64_t *chunks_host);
 int hgx_extract_close(hgx_extract *h);
 
+/* ---- the "hgx" aligner: reads of a locus family -> SAM text in the front end's dialect ------------------------------
+ * Stands in for typing_common.align_reads (common:985-1056) for reads already known to belong to the loci: end to end, at most
+ * max_edits unknown mismatches, known variants free; no whole-genome index, no novel indels, no soft clips, no secondary records,
+ * mates placed independently.  NOT HISAT2 and not compared with its output: the rules are those of tests/align_ref.py.
+ * index_create (the `hisat2 -x <index>` argument of common:1013-1023: what the reads are aligned to): n_loci loci in the caller's
+ * order, names[g] = the backbone's reference name, backbones[g] its bases; the variants of locus g are
+ * var_off[g] .. var_off[g + 1] in Var_list order with var_type (0 insertion, 1 single, 2 deletion), var_pos (0-based backbone
+ * position), var_data (the base / the deleted length in decimal / the inserted bases) and var_id.
+ * align_reads (the aligner run of common:1024-1051, without the samtools pipe: the caller stores the text): one or two inputs
+ * (mate files) of FASTA or FASTQ, plain or gzip -- paths[i], or where paths is NULL the in-memory texts[i] of text_bytes[i] bytes.
+ * opts.fastq: 1 FASTQ, 0 FASTA, < 0 look at the first byte.  opts.route: 0 = the kernels from 1 000 reads on (test switch
+ * front=device / front=host forces either), 1 = host route, 2 = kernels.  Where the kernels decline (a read longer than 256 bases,
+ * more than 128 anchors of one read, more pending indel choices or variants than their scratch holds) the host route gives the
+ * bytes; a read longer than 1 024 bases is HGX_EINVAL on either route.  *sam_out: header (@SQ per locus) + records in input order,
+ * mate 1 before mate 2, unaligned reads left out; release with hgx_free_text.
+ * align_last (as hgx_front_last): the calling thread's last hgx_align_reads -- route taken (2 kernels, 0 host), reads, reads
+ * aligned, concordant pairs, decline code (HGX_ALN_DECLINE_* of csrc/hgx_align_core.hpp).                                        */
+typedef struct hgx_align_opts {
+    int32_t max_edits, max_fragment, fastq, route;
+} hgx_align_opts;
+typedef struct hgx_align_index hgx_align_index;
+int hgx_align_index_create(hgx_align_index **out, int32_t n_loci, const char *const *names, const char *const *backbones,
+                           const int32_t *var_off, const int32_t *var_type, const int32_t *var_pos, const char *const *var_data,
+                           const char *const *var_id);
+int hgx_align_index_free(hgx_align_index *ix);
+int hgx_align_reads(hgx_align_index *ix, int32_t n_inputs, const char *const *paths, const char *const *texts,
+                    const size_t *text_bytes, const hgx_align_opts *opts, char **sam_out, size_t *n_bytes_out);
+int hgx_align_last(int32_t *route, int64_t *reads, int64_t *aligned, int64_t *pairs_concordant, int32_t *decline_code);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,53 @@
+// align_host_main.cpp -- the host route of the "hgx" aligner as a stand-alone program, for sanitizer builds:
+//   g++ -std=c++17 -g -O1 -fsanitize=address,undefined -DHGX_ALIGN_STANDALONE -I include -I hisat-genotype_amd/csrc \
+//       hisat-genotype_amd/csrc/hgx_align_host.cpp tools/align_host_main.cpp -lz -o align_host_main
+//   align_host_main <index file> <max_edits> <reads> [<mate reads>]  > out.sam
+// The index file is text: "<n_loci>", then per locus "<name> <backbone> <n_vars>" followed by one "<type 0|1|2> <pos> <data> <id>"
+// line per variant in Var_list order.  Nothing of the GPU library is linked.
+#include <cstdio>
+#include <cstdlib>
+#include <fstream>
+#include <iostream>
+#include <string>
+#include <vector>
+
+#include "hgx.h"
+
+int main(int argc, char **argv) {
+    if (argc < 4 || argc > 5) { fprintf(stderr, "usage: %s index max_edits reads [mate reads]\n", argv[0]); return 2; }
+    std::ifstream in(argv[1]);
+    int n_loci = 0;
+    in >> n_loci;
+    std::vector<std::string> names(n_loci), bbs(n_loci), data, ids;
+    std::vector<int32_t> off{0}, type, pos;
+    for (int g = 0; g < n_loci; ++g) {
+        int nv = 0;
+        in >> names[g] >> bbs[g] >> nv;
+        for (int v = 0; v < nv; ++v) {
+            int t, p;
+            std::string d, id;
+            in >> t >> p >> d >> id;
+            type.push_back(t); pos.push_back(p); data.push_back(d); ids.push_back(id);
+        }
+        off.push_back((int32_t)type.size());
+    }
+    if (!in) { fprintf(stderr, "bad index file\n"); return 2; }
+    std::vector<const char *> c_names, c_bbs, c_data, c_ids;
+    for (auto &s : names) c_names.push_back(s.c_str());
+    for (auto &s : bbs) c_bbs.push_back(s.c_str());
+    for (auto &s : data) c_data.push_back(s.c_str());
+    for (auto &s : ids) c_ids.push_back(s.c_str());
+    c_data.push_back(nullptr); c_ids.push_back(nullptr); type.push_back(0); pos.push_back(0);
+    hgx_align_index *ix = nullptr;
+    if (hgx_align_index_create(&ix, n_loci, c_names.data(), c_bbs.data(), off.data(), type.data(), pos.data(), c_data.data(), c_ids.data()))
+        return 1;
+    hgx_align_opts o{atoi(argv[2]), 1000, -1, 1};
+    const char *paths[2] = {argv[3], argc == 5 ? argv[4] : nullptr};
+    char *sam = nullptr;
+    size_t n = 0;
+    const int rc = hgx_align_reads(ix, argc - 3, paths, nullptr, nullptr, &o, &sam, &n);
+    if (rc == 0) fwrite(sam, 1, n, stdout);
+    free(sam);
+    hgx_align_index_free(ix);
+    return rc ? 1 : 0;
+}
