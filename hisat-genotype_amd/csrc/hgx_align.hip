@@ -9,12 +9,30 @@
 //   k_aln_emit     a lane per read, twice: record sizes, (exclusive scan,) then the SAM lines at their offsets; the pair's flags are
 //                  read off the mate's pick
 // Every write is bounds-checked by construction: slots < HGX_ALN_DEV_ANCHORS, a record's bytes = the size the same code counted.
+//
+// opts.search != 0 adds a second tier, the search over STATES (hgx_align_states.hpp), for the reads of a chunk that are MARKED: in
+// "states" a read that passes the anchor slots, or an anchor of which reaches the stack or step limit (k_aln_extend marks instead
+// of raising the decline word); in "states_all" every read with an anchor (k_aln_extend does not run).  Per chunk with a mark:
+//   k_aln_seed_marked   a lane per (marked read, strand, seed offset), twice: hits counted, (exclusive scan,) the anchors written
+//                       at their offsets -- the read's FULL list, capped only in total (ST_ANCHOR_CAP: HGX_ALN_DECLINE_ANCHORS)
+//   k_aln_task_info     a lane per (marked read, strand, locus): its anchors' count and the hull of their diagonals.  The host
+//                       turns the non-empty ones into tasks: the window (wider than HGX_ALN_STATES_MAX_WINDOW: DECLINE_WINDOW),
+//                       the offset of the task's two tables in the scratch, batches that fit ST_CELL_BUDGET cells
+//   k_aln_states        a workgroup per task: lanes across the window's columns, rows in sequence (right row L - t and left row t
+//                       in step t, one barrier per step); then every anchor's canon by two lookups, the task's best and placements
+//   k_aln_states_pick   a lane per marked read: its tasks' bests combined (hgx_st_combine) into the read's first res slot,
+//                       best[i], nh[i]; k_aln_pick leaves marked reads alone
+// Tables live in HBM / L2 (16 B per cell): a row reads the rows within the longest known insertion + 1 of it, and the lists are
+// read back from any row, so an LDS ring would not spare the table.  Every index into the scratch is bounded by
+// the numbers the host sized it with: the task's window, read length and cell offset.
 #include "hgx_common.hpp"
 #include "hgx_align.hpp"
 
 namespace {
 typedef hgx_aln_res<HGX_ALN_DEV_VARS> DevRes;
 constexpr int CHUNK = 8192;           // reads per chunk (an even number: mates stay together)
+constexpr long ST_ANCHOR_CAP = (long)CHUNK * HGX_ALN_DEV_ANCHORS;      // anchors of a chunk's marked reads, in total
+constexpr size_t ST_CELL_BUDGET = (size_t)1 << 26;                     // table cells of the tasks in flight (1 GiB)
 
 struct DevReads {
     const char *text;
@@ -41,15 +59,20 @@ k_aln_seed(hgx_aln_view V, DevReads rd, long first, int nc, int n_off_max, int32
     }
 }
 
-__global__ void __launch_bounds__(64)
+// MARK (search "states"): a read past the anchor slots, or an anchor at the stack or step limit, marks its read for the second tier
+// instead of raising the decline word; decline[2] counts the reads marked.  MARK = false is the kernel as it was.
+template <bool MARK> __global__ void __launch_bounds__(64)
 k_aln_extend(hgx_aln_view V, DevReads rd, long first, int nc, int max_edits, const int32_t *cnt, const int2 *anch, DevRes *res,
-             int *decline) {
+             int *decline, int32_t *mark) {
     const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= (long)nc * HGX_ALN_DEV_ANCHORS) return;
     const int i = (int)(gid / HGX_ALN_DEV_ANCHORS), slot = (int)(gid % HGX_ALN_DEV_ANCHORS);
     const int n = cnt[i];
     if (n > HGX_ALN_DEV_ANCHORS) {
-        if (slot == 0) atomicMax(decline, HGX_ALN_DECLINE_ANCHORS);
+        if (slot == 0) {
+            if constexpr (MARK) { if (atomicExch(&mark[i], 1) == 0) atomicAdd(decline + 2, 1); }
+            else atomicMax(decline, HGX_ALN_DECLINE_ANCHORS);
+        }
         return;
     }
     if (slot >= n) return;
@@ -61,13 +84,18 @@ k_aln_extend(hgx_aln_view V, DevReads rd, long first, int nc, int max_edits, con
     const hgx_aln_read R{rd.text + rd.seq_off[first + i], rd.len[first + i], a.x >> 16};
     const int rc = hgx_aln_canon<HGX_ALN_DEV_STK, HGX_ALN_DEV_VARS>(V, R, a.x & 0xffff, a.y, max_edits, HGX_ALN_DEV_STEPS, stk, cur, side,
                                                                    res[gid], memo);
-    if (rc) { res[gid].ok = 0; atomicMax(decline, rc); }
+    if (rc) {
+        res[gid].ok = 0;
+        if (MARK && (rc == HGX_ALN_DECLINE_STACK || rc == HGX_ALN_DECLINE_STEPS)) { if (atomicExch(&mark[i], 1) == 0) atomicAdd(decline + 2, 1); }
+        else atomicMax(decline, rc);
+    }
 }
 
 __global__ void __launch_bounds__(64)
-k_aln_pick(int nc, const int32_t *cnt, const DevRes *res, int32_t *best, int32_t *nh) {
+k_aln_pick(int nc, const int32_t *cnt, const DevRes *res, int32_t *best, int32_t *nh, const int32_t *mark) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nc) return;
+    if (mark && mark[i]) return;                   // k_aln_states_pick's
     const int n = cnt[i] < HGX_ALN_DEV_ANCHORS ? cnt[i] : HGX_ALN_DEV_ANCHORS;
     int h = 0;
     best[i] = hgx_aln_pick(res + (long)i * HGX_ALN_DEV_ANCHORS, n, &h);
@@ -100,6 +128,268 @@ k_aln_emit(hgx_aln_view V, DevReads rd, long first, int nc, int max_fragment, co
         sizes[i] = (uint32_t)w.n;
         flags[i] = 1 | ((rd.paired && !(i & 1) && hgx_aln_concordant(a, *mate, max_fragment)) ? 2 : 0);
     }
+}
+
+
+// ---- the second tier: the search over states (hgx_align_states.hpp) ------------------------------------------------------------
+struct StInfo { int32_t n, dmin, dmax, a0, a1; };                  // of one (marked read, strand, locus): anchors [a0, a1) are the (read, strand)'s
+struct StTask {
+    int32_t i, strand, locus, a0, a1, wlo, whi;                    // i: the read's index in the chunk
+    uint64_t cell_off;                                             // of its right table in the batch's scratch; the left one follows
+};
+
+// search "states_all": every read with an anchor
+__global__ void __launch_bounds__(256) k_aln_mark_all(int nc, const int32_t *cnt, int32_t *mark, int *misc) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nc || cnt[i] <= 0) return;
+    mark[i] = 1;
+    atomicAdd(misc + 2, 1);
+}
+
+// off == nullptr: n_hits[gid]; else the anchors at off[gid] + 0, 1, ... (below cap)
+__global__ void __launch_bounds__(256)
+k_aln_seed_marked(hgx_aln_view V, DevReads rd, long first, const int32_t *marked, int n_marked, int n_off_max, uint32_t *n_hits,
+                  const uint32_t *off, hgx_st_anchor *anch, long cap) {
+    const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (long)n_marked * 2 * n_off_max) return;
+    const int k = (int)(gid % n_off_max), strand = (int)((gid / n_off_max) & 1), i = marked[gid / (2L * n_off_max)];
+    const int L = rd.len[first + i];
+    uint32_t n = 0;
+    if (k < hgx_aln_n_offsets(L)) {
+        const hgx_aln_read R{rd.text + rd.seq_off[first + i], L, strand};
+        const int o = hgx_aln_offset(L, k);
+        uint32_t code;
+        if (hgx_aln_seed_code(R, o, &code))
+            for (uint32_t h = hgx_aln_hash(code) & V.hmask; V.hpos[h] >= 0; h = (h + 1) & V.hmask) {
+                if (V.hkey[h] != code) continue;
+                if (off && (long)off[gid] + n < cap) anch[off[gid] + n] = hgx_st_anchor{o | (strand << 16), V.hpos[h]};
+                ++n;
+            }
+    }
+    if (!off) n_hits[gid] = n;
+}
+
+__global__ void __launch_bounds__(256)
+k_aln_task_info(hgx_aln_view V, int n_marked, int n_off_max, const uint32_t *off, uint32_t total, const hgx_st_anchor *anch, StInfo *info) {
+    const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (long)n_marked * 2 * V.n_loci) return;
+    const int g = (int)(gid % V.n_loci);
+    const long ms = gid / V.n_loci;                                // marked read * 2 + strand
+    const uint32_t a0 = off[ms * n_off_max], a1 = ms + 1 < (long)n_marked * 2 ? off[(ms + 1) * n_off_max] : total;
+    const int32_t lo = V.bb_off[g], hi = V.bb_off[g + 1];
+    StInfo t{0, INT32_MAX, INT32_MIN, (int32_t)a0, (int32_t)a1};
+    for (uint32_t a = a0; a < a1; ++a) {
+        const hgx_st_anchor x = anch[a];
+        if (x.y < lo || x.y >= hi) continue;
+        const int32_t d = x.y - (x.x & 0xffff);
+        ++t.n;
+        t.dmin = d < t.dmin ? d : t.dmin;
+        t.dmax = d > t.dmax ? d : t.dmax;
+    }
+    info[gid] = t;
+}
+
+__device__ inline unsigned long long st_key(const int4 c, int32_t lo) {      // (NM, indels, variants, pos0) of a stored cost, in order
+    return ((unsigned long long)c.x << 54) | ((unsigned long long)(c.w >> 16) << 42) | ((unsigned long long)(c.w & 0xffff) << 30) |
+           (unsigned long long)(c.y - lo);
+}
+
+// acost[a] = (NM or -1, pos0, end, indels << 16 | variants) of anchor a, written by the one task whose locus holds it
+__global__ void __launch_bounds__(256)
+k_aln_states(hgx_aln_view V, DevReads rd, long first, int max_edits, const StTask *tasks, const hgx_st_anchor *anch, int4 *acost,
+             hgx_st_cell *scratch, DevRes *tres, int32_t *tnh, int *decline) {
+    __shared__ unsigned long long s_key;
+    __shared__ int s_flag, s_nh;
+    const StTask tk = tasks[blockIdx.x];
+    const int tid = threadIdx.x, L = rd.len[first + tk.i];
+    hgx_st_task T;
+    T.R = hgx_aln_read{rd.text + rd.seq_off[first + tk.i], L, tk.strand};
+    T.lo = V.bb_off[tk.locus]; T.hi = V.bb_off[tk.locus + 1];
+    T.wlo = tk.wlo; T.whi = tk.whi;
+    T.stride = tk.whi - tk.wlo + 1;
+    T.max_edits = max_edits < L ? max_edits : L;
+    T.right = scratch + tk.cell_off;
+    T.left = T.right + hgx_st_table_cells(L, tk.whi - tk.wlo);
+    if (tid == 0) { s_key = ~0ull; s_flag = 0; s_nh = 0; }
+    const int W = tk.whi - tk.wlo;
+    for (int t = 0; t < L; ++t) {
+        for (int col = tid; col <= W; col += blockDim.x) {
+            hgx_st_right_cell(V, T, L - t, tk.wlo + col);
+            if (col < W) hgx_st_left_cell(V, T, t, tk.wlo + col);
+        }
+        __threadfence_block();
+        __syncthreads();
+    }
+    // every anchor's canon: two lookups
+    for (int a = tk.a0 + tid; a < tk.a1; a += blockDim.x) {
+        const hgx_st_anchor x = anch[a];
+        if (x.y < T.lo || x.y >= T.hi) continue;
+        hgx_st_cost c;
+        const int rc = hgx_st_canon_cost(T, x.x & 0xffff, x.y, &c);
+        int4 v = make_int4(-1, 0, 0, 0);
+        if (rc == HGX_ST_POISONED) atomicMax(&s_flag, HGX_ALN_DECLINE_WINDOW);
+        else if (rc) {
+            v = make_int4(c.nm, c.pos0, c.end, (c.nind << 16) | c.nvar);
+            atomicMin(&s_key, st_key(v, T.lo));
+        }
+        acost[a] = v;
+    }
+    __threadfence_block();
+    __syncthreads();
+    DevRes &res = tres[blockIdx.x];
+    if (tid == 0) {
+        res.ok = 0;
+        int32_t tmp[HGX_ALN_DEV_VARS];
+        for (int a = tk.a0; a < tk.a1 && !s_flag && s_key != ~0ull; ++a) {
+            const hgx_st_anchor x = anch[a];
+            if (x.y < T.lo || x.y >= T.hi) continue;
+            const int4 c = acost[a];
+            if (c.x < 0 || st_key(c, T.lo) != s_key) continue;
+            const int nvar = c.w & 0xffff;
+            if (nvar > HGX_ALN_DEV_VARS) { s_flag = HGX_ALN_DECLINE_VARS; break; }
+            if (!res.ok) {
+                hgx_st_canon_list(V, T, x.x & 0xffff, x.y, res.vl);
+                res.ok = 1; res.nm = c.x; res.nind = c.w >> 16; res.nvar = nvar; res.locus = tk.locus; res.strand = tk.strand;
+                res.pos0 = c.y; res.end = c.z;
+            } else if (nvar > 0) {
+                hgx_st_canon_list(V, T, x.x & 0xffff, x.y, tmp);
+                int cmp = 0;
+                for (int j = 0; cmp == 0 && j < nvar; ++j) cmp = tmp[j] != res.vl[j] ? (tmp[j] < res.vl[j] ? -1 : 1) : 0;
+                if (cmp < 0) {
+                    for (int j = 0; j < nvar; ++j) res.vl[j] = tmp[j];
+                    res.end = c.z;
+                }
+            }
+        }
+        if (s_flag) { res.ok = 0; atomicMax(decline, s_flag); }
+    }
+    __syncthreads();
+    if (s_flag || s_key == ~0ull) {
+        if (tid == 0) tnh[blockIdx.x] = 0;
+        return;
+    }
+    // placements of the anchors with the task's smallest NM: anchor a starts one iff no anchor before it in (pos0, a) order ends behind a's pos0
+    const int nm = (int)(s_key >> 54);
+    for (int a = tk.a0 + tid; a < tk.a1; a += blockDim.x) {
+        const hgx_st_anchor x = anch[a];
+        if (x.y < T.lo || x.y >= T.hi) continue;
+        const int4 c = acost[a];
+        if (c.x != nm) continue;
+        int start = 1;
+        for (int b = tk.a0; b < tk.a1 && start; ++b) {
+            const hgx_st_anchor y = anch[b];
+            if (b == a || y.y < T.lo || y.y >= T.hi) continue;
+            const int4 d = acost[b];
+            if (d.x != nm) continue;
+            if ((d.y < c.y || (d.y == c.y && b < a)) && d.z > c.y) start = 0;
+        }
+        if (start) atomicAdd(&s_nh, 1);
+    }
+    __syncthreads();
+    if (tid == 0) tnh[blockIdx.x] = s_nh;
+}
+
+// t_first[m] .. t_first[m + 1]: the tasks of marked read m
+__global__ void __launch_bounds__(64)
+k_aln_states_pick(int n_marked, const int32_t *marked, const int32_t *t_first, const DevRes *tres, const int32_t *tnh, DevRes *res,
+                  int32_t *best, int32_t *nh) {
+    const int m = blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= n_marked) return;
+    const int i = marked[m], t0 = t_first[m], n = t_first[m + 1] - t0;
+    int h = 0;
+    const int b = hgx_st_combine(tres + t0, tnh + t0, n, &h);
+    if (b >= 0) res[(long)i * HGX_ALN_DEV_ANCHORS] = tres[t0 + b];
+    best[i] = b >= 0 ? 0 : -1;
+    nh[i] = h;
+}
+
+// the second tier of one chunk: *decline != 0: the call goes to the host route
+int states_tier(hgx_align_index *ix, const hgx_aln_reads &reads, const DevReads &rd, const hgx_align_opts *opts, long first, int nc,
+                int n_off_max, const int32_t *d_mark, DevRes *d_res, int32_t *d_best, int32_t *d_nh, int *d_decline,
+                uint32_t *d_total, hipStream_t st, int *decline) {
+    const hgx_aln_view &V = ix->dv;
+    std::vector<int32_t> mark(nc), marked;
+    HIPCHK(hipMemcpy(mark.data(), d_mark, (size_t)nc * 4, hipMemcpyDeviceToHost));
+    for (int i = 0; i < nc; ++i)
+        if (mark[i]) marked.push_back(i);
+    const int nm = (int)marked.size();
+    if (!nm) return HGX_OK;
+    const long n_lanes = (long)nm * 2 * n_off_max;
+    DevBuf d_marked, d_hits, d_off, d_scan2, d_anch;
+    ALLOC(d_marked, (size_t)nm * 4);
+    ALLOC(d_hits, (size_t)n_lanes * 4); ALLOC(d_off, (size_t)n_lanes * 4);
+    ALLOC(d_scan2, hgx_scan_u32_scratch_bytes(n_lanes) + 16);
+    HIPCHK(hipMemcpy(d_marked.p, marked.data(), (size_t)nm * 4, hipMemcpyHostToDevice));
+    k_aln_seed_marked<<<nblk(n_lanes, 256), 256, 0, st>>>(V, rd, first, d_marked.as<int32_t>(), nm, n_off_max, d_hits.as<uint32_t>(), nullptr,
+                                                         nullptr, 0);
+    HIPCHK(hipGetLastError());
+    int rc = hgx_scan_u32_dev(d_hits.as<uint32_t>(), d_off.as<uint32_t>(), n_lanes, d_scan2.p, d_total, st);
+    if (rc) return rc;
+    uint32_t total = 0;
+    HIPCHK(hipMemcpy(&total, d_total, 4, hipMemcpyDeviceToHost));
+    if ((long)total > ST_ANCHOR_CAP) { *decline = HGX_ALN_DECLINE_ANCHORS; return HGX_OK; }
+    ALLOC(d_anch, (size_t)std::max<uint32_t>(total, 1) * sizeof(hgx_st_anchor));
+    k_aln_seed_marked<<<nblk(n_lanes, 256), 256, 0, st>>>(V, rd, first, d_marked.as<int32_t>(), nm, n_off_max, nullptr, d_off.as<uint32_t>(),
+                                                         d_anch.as<hgx_st_anchor>(), (long)total);
+    const long n_info = (long)nm * 2 * V.n_loci;
+    DevBuf d_info;
+    ALLOC(d_info, (size_t)n_info * sizeof(StInfo));
+    k_aln_task_info<<<nblk(n_info, 256), 256, 0, st>>>(V, nm, n_off_max, d_off.as<uint32_t>(), total, d_anch.as<hgx_st_anchor>(),
+                                                      d_info.as<StInfo>());
+    HIPCHK(hipGetLastError());
+    std::vector<StInfo> info((size_t)n_info);
+    HIPCHK(hipMemcpy(info.data(), d_info.p, (size_t)n_info * sizeof(StInfo), hipMemcpyDeviceToHost));
+    // the tasks, in (marked read, strand, locus) order; batches whose tables fit the budget
+    std::vector<StTask> tasks;
+    std::vector<int32_t> t_first(1, 0), batch_first(1, 0);
+    size_t in_batch = 0, largest = 0;
+    int64_t cells = 0;
+    for (int m = 0; m < nm; ++m) {
+        const int L = reads.len[first + marked[m]];
+        for (int sg = 0; sg < 2 * V.n_loci; ++sg) {
+            const StInfo &t = info[(size_t)m * 2 * V.n_loci + sg];
+            if (t.n <= 0) continue;
+            const int g = sg % V.n_loci;
+            const int32_t lo = ix->bb_off[g], hi = ix->bb_off[g + 1];
+            StTask k{marked[m], sg / V.n_loci, g, t.a0, t.a1, 0, 0, 0};
+            hgx_st_window(lo, hi, t.dmin, t.dmax, L, HGX_ALN_STATES_MARGIN, &k.wlo, &k.whi);
+            if (k.whi - k.wlo > HGX_ALN_STATES_MAX_WINDOW || hi - lo >= (1 << 30)) { *decline = HGX_ALN_DECLINE_WINDOW; return HGX_OK; }
+            const size_t need = 2 * hgx_st_table_cells(L, k.whi - k.wlo);
+            if (in_batch && in_batch + need > ST_CELL_BUDGET) { batch_first.push_back((int32_t)tasks.size()); in_batch = 0; }
+            k.cell_off = in_batch;
+            in_batch += need;
+            largest = std::max(largest, in_batch);
+            cells += 2 * (int64_t)L * (k.whi - k.wlo);
+            tasks.push_back(k);
+        }
+        t_first.push_back((int32_t)tasks.size());
+    }
+    batch_first.push_back((int32_t)tasks.size());
+    const size_t nt = tasks.size();
+    DevBuf d_tasks, d_tf, d_tres, d_tnh, d_acost, d_cells;
+    ALLOC(d_tasks, std::max<size_t>(nt, 1) * sizeof(StTask));
+    ALLOC(d_tf, t_first.size() * 4);
+    ALLOC(d_tres, std::max<size_t>(nt, 1) * sizeof(DevRes));
+    ALLOC(d_tnh, std::max<size_t>(nt, 1) * 4);
+    ALLOC(d_acost, (size_t)std::max<uint32_t>(total, 1) * sizeof(int4));
+    ALLOC(d_cells, std::max<size_t>(largest, 1) * sizeof(hgx_st_cell));
+    HIPCHK(hipMemcpy(d_tasks.p, tasks.data(), nt * sizeof(StTask), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_tf.p, t_first.data(), t_first.size() * 4, hipMemcpyHostToDevice));
+    for (size_t b = 0; b + 1 < batch_first.size(); ++b) {
+        const int t0 = batch_first[b], n = batch_first[b + 1] - t0;
+        if (n <= 0) continue;
+        k_aln_states<<<n, 256, 0, st>>>(V, rd, first, opts->max_edits, d_tasks.as<StTask>() + t0, d_anch.as<hgx_st_anchor>(), d_acost.as<int4>(),
+                                        d_cells.as<hgx_st_cell>(), d_tres.as<DevRes>() + t0, d_tnh.as<int32_t>() + t0, d_decline);
+        HIPCHK(hipGetLastError());
+    }
+    k_aln_states_pick<<<nblk(nm, 64), 64, 0, st>>>(nm, d_marked.as<int32_t>(), d_tf.as<int32_t>(), d_tres.as<DevRes>(), d_tnh.as<int32_t>(), d_res,
+                                                   d_best, d_nh);
+    HIPCHK(hipGetLastError());
+    int dec = 0;
+    HIPCHK(hipMemcpy(&dec, d_decline, 4, hipMemcpyDeviceToHost));      // (also: the tier is finished before its buffers go back to the pool)
+    if (dec) { *decline = dec; return HGX_OK; }
+    hgx_align_states_count(nm, (int64_t)total, cells);
+    return HGX_OK;
 }
 
 template <class T> size_t put(std::vector<char> &blk, const std::vector<T> &v) {
@@ -171,14 +461,17 @@ int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
     const DevReads rd{d_text.as<char>(), d_no.as<int64_t>(), d_so.as<int64_t>(), d_qo.as<int64_t>(), d_nl.as<int32_t>(), d_len.as<int32_t>(),
                       reads.paired};
     const int cmax = (int)std::min<long>(n, CHUNK);
-    DevBuf d_cnt, d_anch, d_res, d_best, d_nh, d_sizes, d_off, d_flags, d_scan, d_misc;
+    DevBuf d_cnt, d_anch, d_res, d_best, d_nh, d_sizes, d_off, d_flags, d_scan, d_misc, d_mark;
+    const int search = opts->search;
+    if (search) ALLOC(d_mark, (size_t)cmax * 4);
+    int32_t *mark = search ? d_mark.as<int32_t>() : nullptr;
     ALLOC(d_cnt, (size_t)cmax * 4);
     ALLOC(d_anch, (size_t)cmax * HGX_ALN_DEV_ANCHORS * sizeof(int2));
     ALLOC(d_res, (size_t)cmax * HGX_ALN_DEV_ANCHORS * sizeof(DevRes));
     ALLOC(d_best, (size_t)cmax * 4); ALLOC(d_nh, (size_t)cmax * 4); ALLOC(d_sizes, (size_t)cmax * 4); ALLOC(d_off, (size_t)cmax * 4);
     ALLOC(d_flags, (size_t)cmax * 4);
     ALLOC(d_scan, hgx_scan_u32_scratch_bytes(cmax) + 16);
-    ALLOC(d_misc, 16);                       // [0] decline code, [1] total bytes
+    ALLOC(d_misc, 16);                       // [0] decline code, [1] total bytes, [2] reads marked for the second tier
     int *d_decline = d_misc.as<int>();
     uint32_t *d_total = d_misc.as<uint32_t>() + 1;
     std::vector<int32_t> flags(cmax);
@@ -187,14 +480,26 @@ int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
         const int nc = (int)std::min<long>(CHUNK, n - first);
         HIPCHK(hipMemsetAsync(d_cnt.p, 0, (size_t)nc * 4, st));
         HIPCHK(hipMemsetAsync(d_misc.p, 0, 16, st));
+        if (search) HIPCHK(hipMemsetAsync(d_mark.p, 0, (size_t)nc * 4, st));
         const long n_seed = (long)nc * 2 * n_off_max;
         if (n_seed > 0)
             k_aln_seed<<<nblk(n_seed, 256), 256, 0, st>>>(ix->dv, rd, first, nc, n_off_max, d_cnt.as<int32_t>(), d_anch.as<int2>());
-        k_aln_extend<<<nblk((long)nc * HGX_ALN_DEV_ANCHORS, 64), 64, 0, st>>>(ix->dv, rd, first, nc, opts->max_edits, d_cnt.as<int32_t>(),
-                                                                               d_anch.as<int2>(), d_res.as<DevRes>(), d_decline);
+        if (search == 2) k_aln_mark_all<<<nblk(nc, 256), 256, 0, st>>>(nc, d_cnt.as<int32_t>(), mark, d_decline);
+        else if (search == 1)
+            k_aln_extend<true><<<nblk((long)nc * HGX_ALN_DEV_ANCHORS, 64), 64, 0, st>>>(ix->dv, rd, first, nc, opts->max_edits, d_cnt.as<int32_t>(),
+                                                                                         d_anch.as<int2>(), d_res.as<DevRes>(), d_decline, mark);
+        else
+            k_aln_extend<false><<<nblk((long)nc * HGX_ALN_DEV_ANCHORS, 64), 64, 0, st>>>(ix->dv, rd, first, nc, opts->max_edits, d_cnt.as<int32_t>(),
+                                                                                          d_anch.as<int2>(), d_res.as<DevRes>(), d_decline, nullptr);
         HIPCHK(hipGetLastError());
-        int dec = 0;
-        HIPCHK(hipMemcpy(&dec, d_decline, 4, hipMemcpyDeviceToHost));
+        int misc[4] = {0, 0, 0, 0};
+        HIPCHK(hipMemcpy(misc, d_misc.p, search ? 16 : 4, hipMemcpyDeviceToHost));
+        int dec = misc[0];
+        if (!dec && search && misc[2] > 0) {
+            rc = states_tier(ix, reads, rd, opts, first, nc, n_off_max, mark, d_res.as<DevRes>(), d_best.as<int32_t>(), d_nh.as<int32_t>(),
+                             d_decline, d_total, st, &dec);
+            if (rc) return rc;
+        }
         if (dec) {                               // (a later chunk: what the earlier ones appended is taken back)
             body.resize(body0);
             *aligned = aligned0;
@@ -202,7 +507,7 @@ int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
             *decline = dec;
             return HGX_OK;
         }
-        k_aln_pick<<<nblk(nc, 64), 64, 0, st>>>(nc, d_cnt.as<int32_t>(), d_res.as<DevRes>(), d_best.as<int32_t>(), d_nh.as<int32_t>());
+        k_aln_pick<<<nblk(nc, 64), 64, 0, st>>>(nc, d_cnt.as<int32_t>(), d_res.as<DevRes>(), d_best.as<int32_t>(), d_nh.as<int32_t>(), mark);
         k_aln_emit<<<nblk(nc, 64), 64, 0, st>>>(ix->dv, rd, first, nc, opts->max_fragment, d_res.as<DevRes>(), d_best.as<int32_t>(),
                                                 d_nh.as<int32_t>(), d_sizes.as<uint32_t>(), d_flags.as<int32_t>(), nullptr, nullptr);
         HIPCHK(hipGetLastError());

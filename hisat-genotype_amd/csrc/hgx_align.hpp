@@ -7,6 +7,7 @@
 
 #include "hgx.h"
 #include "hgx_align_core.hpp"
+#include "hgx_align_states.hpp"
 
 #define HGX_ALN_HOST_VARS (3 * HGX_ALN_MAX_READ + 8)     // no alignment of a read the core takes has more variants
 #define HGX_ALN_HOST_STEPS (1L << 24)                   // read bases walked per side of one anchor, with the memo: a read beyond it is left unaligned
@@ -39,3 +40,6 @@ struct hgx_aln_reads {
 int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_align_opts *opts, std::string &body,
                      int64_t *aligned, int64_t *concordant, int *decline);
 void hgx_align_device_free(hgx_align_index *ix);
+
+// what the states form took in the calling thread's current call (hgx_align_last_states): added to by either route
+void hgx_align_states_count(int64_t reads, int64_t anchors, int64_t cells);

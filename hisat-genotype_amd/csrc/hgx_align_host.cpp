@@ -4,6 +4,7 @@
 #include <zlib.h>
 
 #include <algorithm>
+#include <climits>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -21,6 +22,7 @@ void *hgx_host_alloc(size_t bytes);
 namespace {
 thread_local int g_route = 0, g_decline = 0;
 thread_local int64_t g_reads = 0, g_aligned = 0, g_conc = 0;
+thread_local int64_t g_st_reads = 0, g_st_anchors = 0, g_st_cells = 0;
 
 template <class T> void csr(const std::vector<std::pair<int32_t, int32_t>> &items, int32_t n_pos, std::vector<T> &off, std::vector<T> &list) {
     off.assign((size_t)n_pos + 1, 0);
@@ -229,17 +231,102 @@ int align_one(const hgx_aln_view &V, const char *seq, int L, int max_edits, Host
     return HGX_OK;
 }
 
+// ---- the host route's states form (hgx_align_states.hpp): the same cells as the kernels, in loops --------------------------------
+struct StatesScratch {
+    struct A { int32_t strand, locus; hgx_st_anchor a; };
+    std::vector<A> all;
+    std::vector<hgx_st_anchor> anch;
+    std::vector<hgx_st_cell> right, left;
+    std::vector<HostRes> res;
+    std::vector<int32_t> nh, tmp;
+    StatesScratch() : tmp(HGX_ALN_HOST_VARS) {}
+};
+
+int align_one_states(const hgx_aln_view &V, const char *seq, int L, int max_edits, StatesScratch &S, HostRes &best, int *nh, int *gave_up) {
+    S.all.clear();
+    S.res.clear();
+    S.nh.clear();
+    best.ok = 0;
+    *nh = 0;
+    for (int strand = 0; strand < 2; ++strand) {
+        const hgx_aln_read R{seq, L, strand};
+        const int n_off = hgx_aln_n_offsets(L);
+        for (int k = 0; k < n_off; ++k) {
+            const int o = hgx_aln_offset(L, k);
+            uint32_t code;
+            if (!hgx_aln_seed_code(R, o, &code)) continue;
+            for (uint32_t h = hgx_aln_hash(code) & V.hmask; V.hpos[h] >= 0; h = (h + 1) & V.hmask)
+                if (V.hkey[h] == code) S.all.push_back({strand, hgx_aln_locus_of(V, V.hpos[h]), {o | (strand << 16), V.hpos[h]}});
+        }
+    }
+    if (S.all.empty()) return HGX_OK;
+    std::stable_sort(S.all.begin(), S.all.end(), [](const StatesScratch::A &a, const StatesScratch::A &b) {
+        return a.strand != b.strand ? a.strand < b.strand : a.locus < b.locus;
+    });
+    int64_t cells = 0;
+    for (size_t first = 0; first < S.all.size();) {
+        size_t last = first;
+        int32_t dmin = INT32_MAX, dmax = INT32_MIN;
+        S.anch.clear();
+        for (; last < S.all.size() && S.all[last].strand == S.all[first].strand && S.all[last].locus == S.all[first].locus; ++last) {
+            const int32_t d = S.all[last].a.y - (S.all[last].a.x & 0xffff);
+            dmin = std::min(dmin, d);
+            dmax = std::max(dmax, d);
+            S.anch.push_back(S.all[last].a);
+        }
+        hgx_st_task T{};
+        T.R = hgx_aln_read{seq, L, S.all[first].strand};
+        T.lo = V.bb_off[S.all[first].locus];
+        T.hi = V.bb_off[S.all[first].locus + 1];
+        T.max_edits = std::min(max_edits, L);
+        S.res.emplace_back();
+        S.nh.push_back(0);
+        // the kernels decline a window they cannot take; here it is widened until nothing leaves it (the whole locus at the latest)
+        for (int32_t margin = HGX_ALN_STATES_MARGIN;; margin = margin > (1 << 28) ? margin : margin * 4) {
+            hgx_st_window(T.lo, T.hi, dmin, dmax, L, margin, &T.wlo, &T.whi);
+            T.stride = T.whi - T.wlo + 1;
+            const size_t n_cells = hgx_st_table_cells(L, T.whi - T.wlo);
+            S.right.resize(n_cells);
+            S.left.resize(n_cells);
+            T.right = S.right.data();
+            T.left = S.left.data();
+            for (int r = L; r >= 1; --r)
+                for (int32_t p = T.wlo; p <= T.whi; ++p) hgx_st_right_cell(V, T, r, p);
+            for (int r = 0; r < L; ++r)
+                for (int32_t q = T.wlo; q < T.whi; ++q) hgx_st_left_cell(V, T, r, q);
+            cells += 2 * (int64_t)L * (T.whi - T.wlo);
+            const int rc = hgx_st_reduce(V, T, S.all[first].locus, S.anch.data(), (int)S.anch.size(), S.res.back(), S.tmp.data(), &S.nh.back());
+            if (rc == HGX_ALN_DECLINE_WINDOW && (T.wlo > T.lo || T.whi < T.hi)) continue;
+            if (rc) {
+                best.ok = 0;
+                *nh = 0;
+                *gave_up = rc;
+                return HGX_OK;
+            }
+            break;
+        }
+        first = last;
+    }
+    hgx_align_states_count(1, (int64_t)S.all.size(), cells);
+    const int b = hgx_st_combine(S.res.data(), S.nh.data(), (int)S.res.size(), nh);
+    if (b >= 0) best = S.res[(size_t)b];
+    return HGX_OK;
+}
+
 int host_route(const hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_align_opts *o, std::string &body, int64_t *aligned,
                int64_t *conc, int *gave_up) {
     const hgx_aln_view &V = ix->hv;
     HostScratch S;
+    StatesScratch SS;
     const int per = reads.paired ? 2 : 1;
     std::vector<HostRes> best(per);
     int nh[2] = {0, 0};
     std::vector<char> line;
     for (size_t k = 0; k < reads.n(); k += per) {
         for (int m = 0; m < per; ++m) {
-            const int rc = align_one(V, reads.text.data() + reads.seq_off[k + m], reads.len[k + m], o->max_edits, S, best[m], &nh[m], gave_up);
+            const char *seq = reads.text.data() + reads.seq_off[k + m];
+            const int rc = o->search ? align_one_states(V, seq, reads.len[k + m], o->max_edits, SS, best[m], &nh[m], gave_up)
+                                     : align_one(V, seq, reads.len[k + m], o->max_edits, S, best[m], &nh[m], gave_up);
             if (rc) return rc;
         }
         if (per == 2 && hgx_aln_concordant(best[0], best[1], o->max_fragment)) ++*conc;
@@ -262,6 +349,12 @@ int host_route(const hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
     return HGX_OK;
 }
 }      // namespace
+
+void hgx_align_states_count(int64_t reads, int64_t anchors, int64_t cells) {
+    g_st_reads += reads;
+    g_st_anchors += anchors;
+    g_st_cells += cells;
+}
 
 #ifdef HGX_ALIGN_STANDALONE
 // the stand-alone build (tools/align_host_main.cpp) has no kernels and none of the library around it
@@ -379,13 +472,14 @@ extern "C" int hgx_align_index_free(hgx_align_index *ix) {
 extern "C" int hgx_align_reads(hgx_align_index *ix, int32_t n_inputs, const char *const *paths, const char *const *texts,
                                const size_t *text_bytes, const hgx_align_opts *opts, char **sam_out, size_t *n_bytes_out) {
     if (!ix || (n_inputs != 1 && n_inputs != 2) || (!paths && !(texts && text_bytes)) || !opts || !sam_out || !n_bytes_out ||
-        opts->max_edits < 0 || opts->route < 0 || opts->route > 2) {
+        opts->max_edits < 0 || opts->route < 0 || opts->route > 2 || opts->search < 0 || opts->search > 2) {
         hgx_set_error("invalid argument: hgx_align_reads");
         return HGX_EINVAL;
     }
     *sam_out = nullptr;
     *n_bytes_out = 0;
     g_route = 0; g_decline = 0; g_reads = g_aligned = g_conc = 0;
+    g_st_reads = g_st_anchors = g_st_cells = 0;
     try {
         hgx_aln_reads reads;
         int rc = load_reads(n_inputs, paths, texts, text_bytes, opts->fastq, reads);
@@ -403,6 +497,7 @@ extern "C" int hgx_align_reads(hgx_align_index *ix, int32_t n_inputs, const char
         if (decline) {
             body.clear();
             aligned = conc = 0;
+            g_st_reads = g_st_anchors = g_st_cells = 0;          // what the kernels took before they declined is not this call's answer
             int gave_up = 0;
             if ((rc = host_route(ix, reads, opts, body, &aligned, &conc, &gave_up))) return rc;
             if (gave_up) fprintf(stderr, "[hgx_align_reads] a read's search passed the host route's limits (code %d): left unaligned\n", gave_up);
@@ -432,5 +527,12 @@ extern "C" int hgx_align_last(int32_t *route, int64_t *reads, int64_t *aligned, 
     if (aligned) *aligned = g_aligned;
     if (pairs_concordant) *pairs_concordant = g_conc;
     if (decline_code) *decline_code = g_decline;
+    return HGX_OK;
+}
+
+extern "C" int hgx_align_last_states(int64_t *reads, int64_t *anchors, int64_t *cells) {
+    if (reads) *reads = g_st_reads;
+    if (anchors) *anchors = g_st_anchors;
+    if (cells) *cells = g_st_cells;
     return HGX_OK;
 }

@@ -847,9 +847,19 @@ int hgx_extract_close(hgx_extract *h);
  * bytes; a read longer than 1 024 bases is HGX_EINVAL on either route.  *sam_out: header (@SQ per locus) + records in input order,
  * mate 1 before mate 2, unaligned reads left out; release with hgx_free_text.
  * align_last (as hgx_front_last): the calling thread's last hgx_align_reads -- route taken (2 kernels, 0 host), reads, reads
- * aligned, concordant pairs, decline code (HGX_ALN_DECLINE_* of csrc/hgx_align_core.hpp).                                        */
+ * aligned, concordant pairs, decline code (HGX_ALN_DECLINE_* of csrc/hgx_align_core.hpp and hgx_align_states.hpp).
+ * opts.search: how a read's alignments are searched.  0 "ways" = a depth-first enumeration of the ways through the known indels
+ * per anchor (exponential in a tandem repeat with many known unit indels: the kernels stop at a step limit and the call declines).
+ * 1 "states" = the same, but on the host route every read -- and on the kernels' route a read that passes the anchor slots, the
+ * stack or the step limit -- is searched over (read base, backbone position) STATES instead: two tables per (oriented read,
+ * locus), one best entry per state, polynomial.  2 "states_all" = every read with an anchor goes through the tables (the test
+ * and timing form).  The bytes are the same in all three.  The kernels decline a states search whose window of backbone
+ * positions is wider than 8 192 or has an option that leaves it (HGX_ALN_DECLINE_WINDOW); the host route widens the window.
+ * Any other value is HGX_EINVAL.  align_last_states: reads, anchors and table cells the states form took in the calling
+ * thread's last call, on the route that gave the bytes.                                                                         */
 typedef struct hgx_align_opts {
     int32_t max_edits, max_fragment, fastq, route;
+    int32_t search;            /* 0 ways (the default), 1 states, 2 states_all */
 } hgx_align_opts;
 typedef struct hgx_align_index hgx_align_index;
 int hgx_align_index_create(hgx_align_index **out, int32_t n_loci, const char *const *names, const char *const *backbones,
@@ -859,6 +869,7 @@ int hgx_align_index_free(hgx_align_index *ix);
 int hgx_align_reads(hgx_align_index *ix, int32_t n_inputs, const char *const *paths, const char *const *texts,
                     const size_t *text_bytes, const hgx_align_opts *opts, char **sam_out, size_t *n_bytes_out);
 int hgx_align_last(int32_t *route, int64_t *reads, int64_t *aligned, int64_t *pairs_concordant, int32_t *decline_code);
+int hgx_align_last_states(int64_t *reads, int64_t *anchors, int64_t *cells);
 
 #ifdef __cplusplus
 }

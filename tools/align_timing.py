@@ -1,14 +1,24 @@
-"""Time the "hgx" aligner's device route against its host route: reads/s of AlignIndex.align on simulated
-100-base pairs of a synth HLA-like locus, upload and copy back included, at a few read counts round the route gate.
+"""Time the "hgx" aligner's device route against its host route: reads/s of AlignIndex.align, upload and copy
+back included, at a few read counts.
 
-    python tools/align_timing.py [--err 0.5] [--reps 5] [--sizes 250,500,1000,2000,4000,16000,64000]
+    python tools/align_timing.py [--workload synth|tandem] [--search ways|states|states_all] [--err 0.5] [--reps 5]
+                                 [--sizes 250,500,1000,2000,4000,16000,64000] [--tandem-indels 12] [--no-host]
 
-Prints one line per size (best of --reps after one warm-up call) and the break-even size if the sweep brackets it.  A tool,
-not a test.
+--workload synth   simulated 100-base pairs of a synth HLA-like locus, at read counts round the route gate
+--workload tandem  150-base single reads across a GATA x 40 repeat with --tandem-indels known unit deletions and as many known
+                   unit insertions (two alleles: the backbone's, and one with three units fewer).  Reads inside the plain repeat
+                   pass the kernels' anchor slots: with --search ways the call goes to the host route (default --sizes 64).
+--search           the search form of the device-route call (hgx_align_opts.search).  The host route is timed with "ways" and,
+                   when --search is not "ways", with "states" as well.
+
+Prints one line per size and configuration: the median and the range of --reps calls after one warm-up call, the route the call
+took and its decline code, what the states form took.  With --workload synth it also prints the break-even size of device
+against host "ways" if the sweep brackets it.  A tool, not a test.
 """
 import argparse
 import os
 import random
+import statistics
 import sys
 import tempfile
 import time
@@ -39,38 +49,84 @@ def reads_of(err_percent, n_pairs):
     return d, texts
 
 
+def tandem_reads(n_indels, n_reads, units=40, flank=300, read_len=150, stride=11):
+    """(reference dicts, [one FASTA text]): a locus flank + GATA x units + flank with n_indels known 4-base deletions and n_indels
+    known GATA insertions inside the repeat, 8 bases apart; reads cut every `stride` bases from the backbone and from an allele
+    with three units fewer, one substitution in every third read, cycled to n_reads."""
+    rng = random.Random(7)
+    seq = lambda n: "".join(rng.choice("ACGT") for _ in range(n))          # noqa: E731
+    bb = seq(flank) + "GATA" * units + seq(flank)
+    Vars, Var_list = {}, []
+    for j in range(min(n_indels, units // 2)):
+        for t, p, data in (("deletion", flank + 4 + 8 * j, "4"), ("insertion", flank + 8 + 8 * j, "GATA")):
+            vid = "hv%d" % len(Var_list)
+            Vars[vid] = [t, p, data]
+            Var_list.append([p, vid])
+    short = bb[:flank + 4] + bb[flank + 16:]
+    pool = []
+    for allele in (bb, short):
+        for k, start in enumerate(range(0, len(allele) - read_len + 1, stride)):
+            r = list(allele[start:start + read_len])
+            if k % 3 == 0:
+                r[20] = "ACGT"[("ACGT".index(r[20]) + 1) % 4]
+            pool.append("".join(r))
+    rng.shuffle(pool)
+    text = "".join(">t%d\n%s\n" % (k, pool[k % len(pool)]) for k in range(n_reads)).encode()
+    return dict(Genes={"T": {"T*BACKBONE": bb}}, Vars={"T": Vars}, Var_list={"T": Var_list}, refGenes={"T": "T*BACKBONE"}), [text]
+
+
+def timed(ix, texts, reps, **kw):
+    out = ix.align(texts, **kw)                                       # warm-up
+    last = align.align_last()
+    ts = []
+    for _ in range(reps):
+        t = time.perf_counter()
+        ix.align(texts, **kw)
+        ts.append(time.perf_counter() - t)
+    return out, last, ts
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--workload", choices=("synth", "tandem"), default="synth")
+    ap.add_argument("--search", choices=sorted(align.SEARCHES), default="ways")
     ap.add_argument("--err", type=float, default=0.5)
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--sizes", default="250,500,1000,2000,4000,16000,64000")
+    ap.add_argument("--sizes", default=None)
+    ap.add_argument("--tandem-indels", type=int, default=12)
+    ap.add_argument("--no-host", action="store_true", help="time the device-route call only")
     args = ap.parse_args()
+    sizes = args.sizes or ("250,500,1000,2000,4000,16000,64000" if args.workload == "synth" else "64")
     capi.set_device(0)
+    search = {} if args.search == "ways" else {"search": args.search}
+    configs = [("device " + args.search, dict(route="device", **search))]
+    if not args.no_host:
+        configs.append(("host ways", dict(route="host")))
+        if search:
+            configs.append(("host states", dict(route="host", search="states")))
     rows = []
-    for n in [int(x) for x in args.sizes.split(",")]:
-        d, texts = reads_of(args.err, n // 2)
+    for n in [int(x) for x in sizes.split(",")]:
+        d, texts = reads_of(args.err, n // 2) if args.workload == "synth" else tandem_reads(args.tandem_indels, n)
         ix = align.AlignIndex(d["Genes"], d["Vars"], d["Var_list"], d["refGenes"])
-        out, best = {}, {}
-        for route in ("device", "host"):
-            out[route] = ix.align(texts, route=route)
-            last = align.align_last()
-            assert last["route"] == (2 if route == "device" else 0), last
-            ts = []
-            for _ in range(args.reps):
-                t = time.perf_counter()
-                ix.align(texts, route=route)
-                ts.append(time.perf_counter() - t)
-            best[route] = min(ts)
-        assert out["device"] == out["host"]
-        rows.append((n, best["device"], best["host"]))
-        print("%7d reads  device %9.3f ms %10.0f reads/s   host %9.3f ms %10.0f reads/s   aligned %d" % (
-            n, best["device"] * 1e3, n / best["device"], best["host"] * 1e3, n / best["host"], last["aligned"]), flush=True)
+        outs, med = [], {}
+        for name, kw in configs:
+            out, last, ts = timed(ix, texts, args.reps, **kw)
+            outs.append(out)
+            med[name] = statistics.median(ts)
+            print("%7d reads  %-18s median %10.3f ms  range %10.3f .. %10.3f ms  %10.0f reads/s   route %d decline %d aligned %d  "
+                  "states: reads %d anchors %d cells %d" % (
+                      n, name, med[name] * 1e3, min(ts) * 1e3, max(ts) * 1e3, n / med[name], last["route"], last["decline"],
+                      last["aligned"], last["states_reads"], last["states_anchors"], last["states_cells"]),
+                  flush=True)
+        assert all(o == outs[0] for o in outs)
+        rows.append((n, med[configs[0][0]], med.get("host ways")))
         ix.close()
-    for (n0, d0, h0), (n1, d1, h1) in zip(rows, rows[1:]):
-        if d0 > h0 and d1 <= h1:
-            print("break-even between %d and %d reads" % (n0, n1))
-    if rows and rows[0][1] <= rows[0][2]:
-        print("the device route is already ahead at %d reads" % rows[0][0])
+    if args.workload == "synth" and not args.no_host:
+        for (n0, d0, h0), (n1, d1, h1) in zip(rows, rows[1:]):
+            if d0 > h0 and d1 <= h1:
+                print("break-even between %d and %d reads" % (n0, n1))
+        if rows and rows[0][1] <= rows[0][2]:
+            print("the device route is already ahead at %d reads" % rows[0][0])
 
 
 if __name__ == "__main__":
