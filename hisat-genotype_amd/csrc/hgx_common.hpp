@@ -126,6 +126,12 @@ struct DevBuf {
         }                                                              \
     } while (0)
 
+// a function that queues work on `s` over buffers of its own frame: whatever way it returns, the stream has run dry before they go
+struct Drain {
+    hipStream_t s;
+    ~Drain() { (void)hipStreamSynchronize(s); }
+};
+
 // a consumer of class set `c` about to queue work on `st`: order it behind the kernels that are still filling the set
 static inline void hgx_classes_order_after(const hgx_classes *c, hipStream_t st) {
     if (c && c->ready && st != c->made_on) (void)hipStreamWaitEvent(st, c->ready, 0);

@@ -1300,7 +1300,7 @@ int hgx_bgzf_inflate_dev(const unsigned char *d_in, const hgx_bgzf_block *blocks
     DevBuf b_desc, b_verdict;
     ALLOC(b_desc, n_blocks * sizeof(BlockDesc));
     ALLOC(b_verdict, n_blocks * 4);
-    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{st};
+    Drain drain{st};
     HIPCHK(hipMemcpyAsync(b_desc.p, h, n_blocks * sizeof(BlockDesc), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(b_verdict.p, 0xFF, n_blocks * 4, st));
     static const CrcOp op = make_crc_op();
@@ -1423,7 +1423,7 @@ int hgx_bam_splice_dev(const unsigned char *d_src, size_t src_bytes, const uint6
     if (total == 0) return HGX_OK;
     DevBuf b_tab;
     ALLOC(b_tab, h.size() * 4);
-    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{st};
+    Drain drain{st};
     HIPCHK(hipMemcpyAsync(b_tab.p, h.data(), h.size() * 4, hipMemcpyHostToDevice, st));
     const uint32_t *pre = b_tab.as<uint32_t>(), *soff = pre + n_seg + 1;
     const uint64_t n_units = ((dst_off + total + 15) >> 4) - (dst_off >> 4);
@@ -1448,7 +1448,7 @@ extern "C" int hgx_bam_splice(const void *src, size_t src_bytes, const uint64_t 
     DevBuf b_src, b_dst;
     ALLOC(b_src, src_bytes + 64);
     ALLOC(b_dst, dst_bytes + 64);
-    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{st};
+    Drain drain{st};
     if (src_bytes) HIPCHK(hipMemcpyAsync(b_src.p, src, src_bytes, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync((char *)b_src.p + src_bytes, 0, 64, st));
     if (dst_bytes) HIPCHK(hipMemcpyAsync(b_dst.p, out, dst_bytes, hipMemcpyHostToDevice, st));
@@ -1474,7 +1474,7 @@ extern "C" int hgx_bgzf_inflate(const void *bgzf, size_t n_bytes, void *out, siz
     DevBuf b_in, b_out;
     ALLOC(b_in, n_bytes + 2048);
     ALLOC(b_out, std::max<size_t>(total, 16));
-    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{st};
+    Drain drain{st};
     HIPCHK(hipMemcpyAsync(b_in.p, bgzf, n_bytes, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync((char *)b_in.p + n_bytes, 0, 2048, st));
     int bad = 0;

@@ -140,7 +140,7 @@ extern "C" int hgx_classes_merge_gathered(hgx_classes **out, const void *dev_rec
     DevBuf b_rows, b_w;
     // declared after the buffers = destroyed before them: an error return behind a queued copy drains the stream before the
     // buffers go back to the pool
-    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{st};
+    Drain drain{st};
     ALLOC(b_rows, (size_t)std::max<int64_t>(total, 1) * w64 * 8);
     ALLOC(b_w, (size_t)std::max<int64_t>(total, 1) * 8);
     int64_t at = 0;
@@ -180,7 +180,7 @@ extern "C" int hgx_classes_allgather(hgx_classes **out, const hgx_classes *mine,
     for (int32_t c : sizes) cap = std::max(cap, c);
     const size_t pitch = (size_t)(w64 + 1) * 8;
     DevBuf b_send, b_recv;
-    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{st};
+    Drain drain{st};
     ALLOC(b_send, (size_t)cap * pitch);
     ALLOC(b_recv, (size_t)world * cap * pitch);
     { int rc_ = hgx_classes_pack_rows(mine, a_pad, cap, b_send.p, stream); if (rc_) return rc_; }

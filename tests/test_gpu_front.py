@@ -269,7 +269,7 @@ def test_sam_text_lines_filtered_and_sorted_on_the_device(tmp_path):
 
 
 def test_bam_records_walked_filtered_and_sorted_on_the_device(tmp_path):
-    """hgx_bam.cpp leaves a BAM's record walk, region filter and name sort to the device (k_bam_*): same batch as the host reader's
+    """hgx_bam.cpp leaves a BAM's record walk, region filter and name sort to the device (k_bam_*, name_order): same batch as the host reader's
     own walk / filter / stable name sort on -- a coordinate-sorted BAM with reads on a decoy reference, with a span region (overlap
     rule from the CIGAR), without regions, with read names that are prefixes of each other and longer than one 8-byte sort chunk,
     with a 40 kb record (longer than a walk range: the range without a record start is passed over), and a name-grouped BAM
