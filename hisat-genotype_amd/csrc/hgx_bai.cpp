@@ -108,14 +108,9 @@ int hgx_bai_load(const char *bam_path, hgx_bai_index &ix) {
         struct stat sb;
         if (fstat(fd, &sb) != 0 || sb.st_size < 0 || !S_ISREG(sb.st_mode)) { close(fd); return 2; }
         std::vector<unsigned char> bytes((size_t)sb.st_size);
-        size_t got_all = 0;
-        while (got_all < bytes.size()) {
-            const ssize_t got = pread(fd, bytes.data() + got_all, bytes.size() - got_all, (off_t)got_all);
-            if (got <= 0) break;
-            got_all += (size_t)got;
-        }
+        const bool got_all = hgx_pread_all(fd, bytes.data(), bytes.size(), 0);
         close(fd);
-        if (got_all != bytes.size()) return 2;
+        if (!got_all) return 2;
         return hgx_bai_parse(bytes.data(), bytes.size(), ix) ? 0 : 2;
     }
     return 1;
@@ -272,12 +267,8 @@ extern "C" int hgx_bam_index_build(const char *path, const char *out_path, int32
             if (!last) {
                 const size_t want = std::min(piece, file_size - file_pos), at = comp.size();
                 comp.resize(at + want);
-                size_t got_all = 0;
-                while (got_all < want) {
-                    const ssize_t got = pread(fd, comp.data() + at + got_all, want - got_all, (off_t)(file_pos + got_all));
-                    if (got <= 0) { hgx_set_error("short read on %s at offset %zu", path, file_pos + got_all); return fail(HGX_EINVAL); }
-                    got_all += (size_t)got;
-                }
+                size_t got = 0;
+                if (!hgx_pread_all(fd, comp.data() + at, want, file_pos, &got)) { hgx_set_error("short read on %s at offset %zu", path, file_pos + got); return fail(HGX_EINVAL); }
                 file_pos += want;
             }
             const bool at_end = file_pos >= file_size;
@@ -363,7 +354,6 @@ extern "C" int hgx_bam_index_build(const char *path, const char *out_path, int32
                 const unsigned char *r = &text[q + 4];
                 const uint64_t v = voffset(text_at + q);
                 const int32_t rid = (int32_t)ld32(r), pos = (int32_t)ld32(r + 4);
-                const uint32_t l_rn = r[8], n_cig = (uint32_t)r[12] | ((uint32_t)r[13] << 8), flag = (uint32_t)r[14] | ((uint32_t)r[15] << 8);
                 if (rid >= n_ref) { hgx_set_error("record with reference %d of %d at virtual offset %llu", rid, n_ref, (unsigned long long)v); return fail(HGX_EPARSE); }
                 if (rid < 0 || pos < 0) {
                     close_run(v);
@@ -375,15 +365,7 @@ extern "C" int hgx_bam_index_build(const char *path, const char *out_path, int32
                         hgx_set_error("records out of coordinate order at virtual offset %llu (reference %d, position %d)", (unsigned long long)v, rid, pos + 1);
                         return fail(HGX_EINVAL);
                     }
-                    int64_t span = 0;
-                    if (!(flag & 4) && 32 + (size_t)l_rn + 4 * (size_t)n_cig <= bs) {
-                        const unsigned char *c = r + 32 + l_rn;
-                        for (uint32_t k = 0; k < n_cig; ++k) {
-                            const uint32_t w = ld32(c + 4 * k), op = w & 15;
-                            if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) span += w >> 4;
-                        }
-                    }
-                    const int64_t end = (int64_t)pos + std::max<int64_t>(span, 1);
+                    const int64_t end = (int64_t)pos + std::max<int64_t>(hgx_bam_cigar_reflen(r, bs), 1);
                     if (end > BAI_MAX_POS) { hgx_set_error("record beyond position 2^29 at virtual offset %llu: a .bai cannot index it", (unsigned long long)v); return fail(HGX_EINVAL); }
                     const uint32_t bin = (uint32_t)bai_reg2bin(pos, end);
                     if (rid != cur_ref) { close_run(v); flush_to(rid); last_pos = -1; }

@@ -10,6 +10,8 @@
 #include <unordered_map>
 #include <vector>
 
+#include <unistd.h>
+
 #include "hgx.h"
 
 extern "C" void hgx_set_error(const char *fmt, ...);
@@ -148,6 +150,18 @@ struct hgx_batch {
 // piece "left-ids-right" -> index of the distinct piece in the batch (creates it if new). < 0 on error.
 int64_t hgx_intern_piece(hgx_batch &b, const hgx_locus &loc, int32_t left, int32_t right, const int32_t *ids, int32_t n_ids);
 
+// n bytes of a file from offset `at` on (pread until they are in); false = the file ended or failed first, *got (optional) = the bytes read
+inline bool hgx_pread_all(int fd, void *dst, size_t n, size_t at, size_t *got = nullptr) {
+    size_t have = 0;
+    while (have < n) {
+        const ssize_t k = pread(fd, (char *)dst + have, n - have, (off_t)(at + have));
+        if (k <= 0) break;
+        have += (size_t)k;
+    }
+    if (got) *got = have;
+    return have == n;
+}
+
 // Persistent host worker pool (hgx_host.cpp): body(worker) runs on `n` threads (worker 0 = the caller) and the call returns when
 // all are done.  The helpers below cut [0, n_items) into contiguous ranges / hand out task indices dynamically.
 void hgx_run_workers(int n, const std::function<void(int)> &body);
@@ -169,8 +183,19 @@ inline void hgx_par_tasks(int n_threads, size_t n_tasks, F fn) {           // fn
 // The alignment reader's internal result (hgx_bam.cpp -> hgx_sam.cpp): the records as a line table, stable-sorted by QNAME, over
 // buffers this object owns.  p[len] is a byte the parser may overwrite (the line's terminator).
 struct hgx_line { char *p; uint32_t len, klen; uint64_t key; };     // klen = QNAME length, key = its first 8 bytes, big endian
-// BGZF container (hgx_inflate.hip: inflate on the device, one wavefront per block)
+// BGZF container (hgx_bgzf.cpp: the host's walk through it; hgx_inflate.hip: inflate on the device, one wavefront per block)
 struct hgx_bgzf_block { size_t in_off, in_len, out_off, out_len; uint32_t crc; };
+// The container's one block-header reader (hgx_bgzf.cpp): the block whose header lies at data + off (off < n), as far as the n bytes
+// tell.  HGX_BGZF_BLOCK: the block lies whole in them -- *b = its payload's place, crc and size (out_off 0).  *blen (optional) = the
+// block's length by its BC subfield, 0 where the bytes present do not show one.
+enum { HGX_BGZF_BLOCK = 0,
+       HGX_BGZF_NOT,             // no gzip magic with an extra field
+       HGX_BGZF_SHORT,           // fewer than the 18 bytes a header takes (the magic holds as far as it goes)
+       HGX_BGZF_CUT_HEADER,      // the extra field runs past the n bytes
+       HGX_BGZF_NO_BC,           // an extra field without a BC subfield
+       HGX_BGZF_BAD_LEN,         // a block length that does not hold header and trailer
+       HGX_BGZF_CUT_BLOCK };     // the block runs past the n bytes
+int hgx_bgzf_block_at(const unsigned char *data, size_t n, size_t off, hgx_bgzf_block *b, size_t *blen);
 int hgx_bgzf_scan(const unsigned char *data, size_t n, std::vector<hgx_bgzf_block> &blocks, size_t *total_out);
 // (a piece of a file that arrives in chunks: errors worded with file offsets; unless `last`, a partial block at the end is left, *used = the complete ones' bytes)
 int hgx_bgzf_scan_stream(const unsigned char *data, size_t n, bool last, size_t file_off, std::vector<hgx_bgzf_block> &blocks, size_t *total_out,
@@ -253,6 +278,18 @@ int hgx_read_alignment_lines(const char *path, const char *regions, int n_thread
 int hgx_bam_parse_header(const unsigned char *raw, size_t n, std::vector<std::string> &refs, size_t *body0);
 bool hgx_bam_inflate_block(const unsigned char *data, const hgx_bgzf_block &b, unsigned char *dst);
 bool hgx_bam_record_line(const unsigned char *rec, size_t len, const std::vector<std::string> &refs, std::string &line);
+// reference bases the binary CIGAR of a BAM record consumes (M D N = X; r = the record behind its block_size bs): 0 for an unmapped
+// record or a CIGAR that does not fit the record (bam_endpos then counts one base)
+inline int64_t hgx_bam_cigar_reflen(const unsigned char *r, uint32_t bs) {
+    const size_t l_rn = r[8], n_cig = (size_t)r[12] | ((size_t)r[13] << 8);
+    if ((r[14] & 4) || 32 + l_rn + 4 * n_cig > bs) return 0;
+    int64_t tot = 0;
+    for (const unsigned char *c = r + 32 + l_rn, *e = c + 4 * n_cig; c < e; c += 4) {
+        const uint32_t op = c[0] & 15;
+        if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) tot += (int64_t)(((uint32_t)c[0] >> 4) | ((uint32_t)c[1] << 4) | ((uint32_t)c[2] << 12) | ((uint32_t)c[3] << 20));
+    }
+    return tot;
+}
 int hgx_deferred_for_regions(const char *regions, bool text, size_t body0, const std::vector<std::string> &refs, hgx_bam_deferred &d);
 
 // ---- BAM index (hgx_bai.cpp; the reader's use of it: hgx_bam.cpp) -------------------------------------------------------------------
