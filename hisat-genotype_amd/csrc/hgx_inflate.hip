@@ -304,6 +304,9 @@ __global__ void __launch_bounds__(64) k_bgzf_inflate(const unsigned char *__rest
                 const uint32_t len = bits_take(b, 16), nlen = bits_take(b, 16);
                 if ((len ^ 0xFFFFu) != nlen) { err = INF_BAD_STORED; break; }
                 if (wpos + len > B.out_len) { err = INF_OVERRUN; break; }
+                // (the bytes lie inside the member: without this the footer and the next member's bytes went out as payload, and only the
+                // CRC-32 -- which whoever wrote those bytes chooses -- stood against it.  4 * taken - cnt / 8 bytes from `base` are used.)
+                if (4u * b.taken - (uint32_t)(b.cnt >> 3) + len > (uint32_t)((uintptr_t)(in + B.in_off) & 3) + B.in_len) { err = INF_INPUT_END; break; }
                 for (uint32_t i = 0; i < len; ++i) {
                     bits_refill(b, lane);
                     const uint32_t v = bits_take(b, 8);
@@ -462,7 +465,9 @@ __global__ void __launch_bounds__(64) k_bgzf_inflate(const unsigned char *__rest
                 }
                 if (wpos - fpos >= (uint32_t)FLUSH) { __builtin_amdgcn_wave_barrier(); flush(FLUSH); }
             }
-            if (!err && b.taken > b.n_dwords + 2) err = INF_INPUT_END;        // (the reader runs at most two dwords ahead of what it used)
+            // (32 * taken - cnt bits from `base` are used: to the bit, as the lane-parallel form has it -- a block that ended inside the
+            // member's footer passed the looser "two dwords ahead" this line had)
+            if (!err && 32u * b.taken - (uint32_t)b.cnt > 8u * ((uint32_t)((uintptr_t)(in + B.in_off) & 3) + B.in_len)) err = INF_INPUT_END;
         }
         __builtin_amdgcn_wave_barrier();
         if (!err) {
@@ -1128,8 +1133,9 @@ CrcOp make_crc_op() {
 // stream has drained -- the deflated file was still landing -- and only then stages it: the kernel started 0.4 ms after the file's
 // last byte (tools/bam_gap_timeline.py).
 size_t hgx_bgzf_inflate_staging_bytes(size_t n_blocks) { return n_blocks * (sizeof(BlockDesc) + 4) + 64; }
-int hgx_bgzf_inflate_dev(const unsigned char *d_in, const hgx_bgzf_block *blocks, size_t n_blocks, unsigned char *d_out, hipStream_t st, int *bad,
-                         void *staging) {
+// (`verdicts`, optional: room for n_blocks values -- every block's INF_* verdict, for hgx_bgzf_inflate_verdicts)
+static int inflate_dev(const unsigned char *d_in, const hgx_bgzf_block *blocks, size_t n_blocks, unsigned char *d_out, hipStream_t st, int *bad,
+                       void *staging, uint32_t *verdicts) {
     ARGCHK(bad && (n_blocks == 0 || (d_in && blocks && d_out)));
     *bad = 0;
     if (n_blocks == 0) return HGX_OK;
@@ -1190,7 +1196,12 @@ int hgx_bgzf_inflate_dev(const unsigned char *d_in, const hgx_bgzf_block *blocks
     int n_bad = 0;
     for (size_t i = 0; i < n_blocks; ++i) n_bad += v[i] != 0 ? 1 : 0;
     *bad = n_bad;
+    if (verdicts) memcpy(verdicts, v, n_blocks * 4);
     return HGX_OK;
+}
+int hgx_bgzf_inflate_dev(const unsigned char *d_in, const hgx_bgzf_block *blocks, size_t n_blocks, unsigned char *d_out, hipStream_t st, int *bad,
+                         void *staging) {
+    return inflate_dev(d_in, blocks, n_blocks, d_out, st, bad, staging, nullptr);
 }
 
 // ---- k_bam_splice: the selected segments of an inflated staging buffer as one dense stream -----------------------------------------
@@ -1307,28 +1318,43 @@ extern "C" int hgx_bam_splice(const void *src, size_t src_bytes, const uint64_t 
     return HGX_OK;
 }
 
-// test / tool entry (hgx.h): a whole BGZF file in host memory -> its payload in host memory, inflated on the device
-extern "C" int hgx_bgzf_inflate(const void *bgzf, size_t n_bytes, void *out, size_t out_cap, size_t *n_out, int32_t *bad_blocks, void *stream) {
-    ARGCHK(bgzf && n_out && bad_blocks && (out || out_cap == 0));
-    hipStream_t st = (hipStream_t)stream;
+// test / tool entry (hgx.h): a whole BGZF file in host memory -> its payload in host memory, inflated on the device.  `guard` bytes
+// behind the payload belong to the output too: the whole device buffer is set to 0xA5 before the launch and comes back as the kernel
+// left it, so a caller sees a write beyond the last block (and what a refused block left).  `verdicts` (optional): one per block.
+static int inflate_host_to_host(const void *bgzf, size_t n_bytes, void *out, size_t out_cap, size_t guard, size_t *n_out, int32_t *bad_blocks,
+                                uint32_t *verdicts, size_t verdict_cap, int64_t *n_blocks, hipStream_t st) {
     std::vector<hgx_bgzf_block> blocks;
     size_t total = 0;
     int rc = hgx_bgzf_scan((const unsigned char *)bgzf, n_bytes, blocks, &total);
     if (rc) return rc;
     *n_out = total;
     *bad_blocks = 0;
-    if (total > out_cap) { hgx_set_error("output buffer too small (%zu < %zu)", out_cap, total); return HGX_EINVAL; }
+    if (n_blocks) *n_blocks = (int64_t)blocks.size();
+    if (total + guard > out_cap) { hgx_set_error("output buffer too small (%zu < %zu)", out_cap, total + guard); return HGX_EINVAL; }
+    if (verdicts && blocks.size() > verdict_cap) { hgx_set_error("verdict array too small (%zu < %zu)", verdict_cap, blocks.size()); return HGX_EINVAL; }
     DevBuf b_in, b_out;
     ALLOC(b_in, n_bytes + 2048);
-    ALLOC(b_out, std::max<size_t>(total, 16));
+    ALLOC(b_out, std::max<size_t>(total + guard, 16));
     Drain drain{st};
     HIPCHK(hipMemcpyAsync(b_in.p, bgzf, n_bytes, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync((char *)b_in.p + n_bytes, 0, 2048, st));
+    if (guard) HIPCHK(hipMemsetAsync(b_out.p, 0xA5, total + guard, st));
     int bad = 0;
-    rc = hgx_bgzf_inflate_dev(b_in.as<unsigned char>(), blocks.data(), blocks.size(), b_out.as<unsigned char>(), st, &bad, nullptr);
+    rc = inflate_dev(b_in.as<unsigned char>(), blocks.data(), blocks.size(), b_out.as<unsigned char>(), st, &bad, nullptr, verdicts);
     if (rc) return rc;
     *bad_blocks = bad;
-    if (total) HIPCHK(hipMemcpyAsync(out, b_out.p, total, hipMemcpyDeviceToHost, st));
+    if (total + guard) HIPCHK(hipMemcpyAsync(out, b_out.p, total + guard, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return HGX_OK;
+}
+extern "C" int hgx_bgzf_inflate(const void *bgzf, size_t n_bytes, void *out, size_t out_cap, size_t *n_out, int32_t *bad_blocks, void *stream) {
+    ARGCHK(bgzf && n_out && bad_blocks && (out || out_cap == 0));
+    return inflate_host_to_host(bgzf, n_bytes, out, out_cap, 0, n_out, bad_blocks, nullptr, 0, nullptr, (hipStream_t)stream);
+}
+// test entry (hgx.h): the same with every block's verdict and HGX_INFLATE_GUARD bytes of 0xA5 behind the payload
+extern "C" int hgx_bgzf_inflate_verdicts(const void *bgzf, size_t n_bytes, void *out, size_t out_cap, size_t *n_out, uint32_t *verdicts, size_t verdict_cap,
+                                         int64_t *n_blocks, void *stream) {
+    ARGCHK(bgzf && out && n_out && verdicts && n_blocks);
+    int32_t bad = 0;
+    return inflate_host_to_host(bgzf, n_bytes, out, out_cap, HGX_INFLATE_GUARD, n_out, &bad, verdicts, verdict_cap, n_blocks, (hipStream_t)stream);
 }

@@ -646,6 +646,18 @@ int hgx_type_many_loci(int32_t n_loci, hgx_typing ***out, int32_t **rc_out_or_nu
  * out_cap is too small: HGX_EINVAL).  What hgx_parse_alignment_file_dev / hgx_type_file do with a BAM goes through the same
  * kernel, the payload staying in HBM.  Replaces the reference's `samtools view` decompression (typing_core.py:436-468).          */
 int hgx_bgzf_inflate(const void *bgzf, size_t n_bytes, void *out, size_t out_cap, size_t *n_out, int32_t *bad_blocks, void *stream);
+/* Test entry: hgx_bgzf_inflate with the verdict of every block -- verdicts[0 .. *n_blocks), verdict_cap = room in `verdicts` -- and
+ * HGX_INFLATE_GUARD bytes behind the payload: the device output (payload + guard) is set to 0xA5 before the launch and copied back
+ * whole, so out_cap >= *n_out + HGX_INFLATE_GUARD, out[*n_out ...) shows a write beyond the last block, and the bytes of a refused
+ * block are 0xA5 or whatever the kernel left there (unspecified).  The verdicts (csrc/hgx_inflate.hip, INF_*):
+ *   0 inflated, CRC-32 and ISIZE right       1 BAD_BLOCK_TYPE (block type 3)       2 BAD_STORED (LEN / NLEN of a stored block)
+ *   3 BAD_CODE (bits that are no code, a literal/length symbol above 285, a distance symbol above 29)
+ *   4 BAD_DIST (a distance beyond the member's first byte)          5 OVERRUN (more output than ISIZE)
+ *   6 BAD_SIZE (less output than ISIZE)      7 BAD_CRC                             8 BAD_LENGTHS (a dynamic block's code lengths)
+ *   9 INPUT_END (the stream runs beyond the member's compressed bytes)                                                            */
+#define HGX_INFLATE_GUARD 4096
+int hgx_bgzf_inflate_verdicts(const void *bgzf, size_t n_bytes, void *out, size_t out_cap, size_t *n_out, uint32_t *verdicts, size_t verdict_cap,
+                              int64_t *n_blocks, void *stream);
 /* Test entry, host only: the block chain of a BGZF file walked by one thread and in ranges by n_threads (what the reader does in front
  * of the device inflate: each range finds a block start and the ranges must link up, csrc/hgx_bgzf.cpp hgx_bgzf_scan_par).
  * *n_blocks = blocks of the file (-1: not a BGZF container), *same = 1 iff both walks gave the same verdict and descriptors.   */

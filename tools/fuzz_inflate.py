@@ -2,18 +2,26 @@
 """Randomised parity of the device BGZF inflate (csrc/hgx_inflate.hip) with zlib: payloads of every texture (uniform bytes over
 alphabets of 1 - 256 symbols, skewed alphabets that need 15-bit codes, runs, periodic data with periods up to 40 KB -- matches from
 far beyond the 8 KB ring --, text, mixtures), deflated per block with a random level / strategy / memLevel and block sizes from 1
-byte to 0xff00; every case one BGZF file of several blocks through hgx_bgzf_inflate.  Usage: tools/fuzz_inflate.py [n_cases] [seed]"""
+byte to 0xff00; every case one BGZF file of several blocks through hgx_bgzf_inflate.  A ninth kind does not go through zlib's deflate:
+random token lists written by tests/deflate_craft.py (random complete sets of code lengths, 258 as 284 + 31, distances up to 32 768),
+checked against their LZ77 expansion.  Usage: tools/fuzz_inflate.py [n_cases] [seed]"""
 import os, sys, random, struct, zlib, time, ctypes as C
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 import numpy as np
+import deflate_craft as dc
 from hisatgenotype_amd import capi
 if os.environ.get("INF_LIB"):                              # a variant build of the library (tools/inf_subpool_check.sh)
     capi.LIB_PATH = os.environ["INF_LIB"]
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 500
 seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 
-def payload(rng):
-    kind = rng.randrange(8)
+CRAFTED = object()
+
+def payload(rng, top=True):
+    kind = rng.randrange(9 if top else 8)
+    if kind == 8:                                            # not zlib's deflate: see crafted()
+        return CRAFTED
     n = rng.choice([0, 1, 2, 7, 100, 1000, 5000, 70000, 200000, 400000])
     n = rng.randint(max(0, n // 2), n) if n else 0
     if kind == 0:
@@ -48,7 +56,21 @@ def payload(rng):
         return bytes(out[:n])
     if kind == 6:
         return bytes(rng.getrandbits(8) for _ in range(min(n, 100000)))
-    return b"".join(payload(rng)[:rng.randint(0, 30000)] for _ in range(rng.randint(1, 4)))
+    return b"".join(payload(rng, False)[:rng.randint(0, 30000)] for _ in range(rng.randint(1, 4)))
+
+def crafted(rng):
+    """(payload, BGZF file) of one to four members written by deflate_craft.random_member"""
+    data, out = bytearray(), bytearray()
+    for _ in range(rng.randint(1, 4)):
+        raw, cdata = dc.random_member(rng)
+        while len(cdata) > dc.MAX_CDATA:
+            raw, cdata = dc.random_member(rng, 30000)
+        assert dc.host_verdict(cdata, zlib.crc32(raw), len(raw)) == (True, raw, None)
+        data += raw
+        out += dc.member(cdata, zlib.crc32(raw), len(raw))
+    if rng.random() < 0.7:
+        out += dc.EOF_MEMBER
+    return bytes(data), bytes(out)
 
 def bgzf(rng, data):
     out = bytearray()
@@ -84,7 +106,7 @@ t0 = time.time(); bad_cases = 0; total = 0
 for k in range(n_cases):
     rng = random.Random(seed0 * 1000003 + k)
     data = payload(rng)
-    f = bgzf(rng, data)
+    data, f = crafted(rng) if data is CRAFTED else (data, bgzf(rng, data))
     nb = f.count(b"\x1f\x8b\x08\x04")
     cap = max(len(data) + 64, 64)
     buf = np.zeros(cap, np.uint8)
