@@ -3,7 +3,7 @@ variants in `Vars` -- end to end, at most `max_edits` unknown mismatches, known 
 dialect the front end consumes (NM, MD, Zs, NH, YT as simulate._truth_record renders them).
 
 It is NOT HISAT2 and its output is not compared with HISAT2's anywhere: no whole-genome index, no novel indels, no soft clips, no
-secondary records, mates placed independently.  The rules are stated in plain Python in tests/align_ref.py; the kernels
+secondary records; mates placed independently unless pair="aware" (tests/align_pair_ref.py).  The rules are stated in plain Python in tests/align_ref.py; the kernels
 (csrc/hgx_align.hip) and the host route (csrc/hgx_align_host.cpp) run one shared core (csrc/hgx_align_core.hpp, and csrc/hgx_align_states.hpp for the search over states).
 """
 import ctypes as C
@@ -13,11 +13,12 @@ from . import capi
 _TYPES = {"insertion": capi.VAR_INSERTION, "single": capi.VAR_SINGLE, "deletion": capi.VAR_DELETION}
 ROUTES = {"auto": 0, "host": 1, "device": 2}
 SEARCHES = {"ways": 0, "states": 1, "states_all": 2}
+PAIRS = {"independent": 0, "aware": 1}
 
 
 class AlignOpts(C.Structure):
     _fields_ = [("max_edits", C.c_int32), ("max_fragment", C.c_int32), ("fastq", C.c_int32), ("route", C.c_int32),
-                ("search", C.c_int32)]
+                ("search", C.c_int32), ("pair", C.c_int32)]
 
 
 class AlignIndex:
@@ -44,14 +45,17 @@ class AlignIndex:
             (C.c_int32 * len(off))(*off), (C.c_int32 * max(n, 1))(*vtype), (C.c_int32 * max(n, 1))(*vpos),
             (C.c_char_p * max(n, 1))(*vdata), (C.c_char_p * max(n, 1))(*vid)))
 
-    def align(self, reads, max_edits=2, max_fragment=1000, fastq=None, route="auto", search="ways"):
+    def align(self, reads, max_edits=2, max_fragment=1000, fastq=None, route="auto", search="ways", pair="independent"):
         """SAM text (bytes) for `reads` = one or two FASTA / FASTQ[.gz] paths (str) or in-memory texts (bytes).  `search`: "ways"
         (per anchor, the ways through the known indels), "states" (reads that pass the kernels' anchor slots, stack or step limit
         -- on the host route: every read -- are searched over (read base, backbone position) states instead), "states_all" (every
-        read is); an int is passed through as hgx_align_opts.search.  The bytes are the same."""
+        read is); an int is passed through as hgx_align_opts.search.  The bytes are the same.  `pair`: "independent" (each mate's
+        smallest alignment, as before) or "aware" (where a combination of the mates' candidates is concordant, both records come
+        from the smallest such combination and NH counts the pair's placements: tests/align_pair_ref.py); an int is passed
+        through as hgx_align_opts.pair.  "aware" needs search="ways"."""
         assert len(reads) in (1, 2)
         opts = AlignOpts(int(max_edits), int(max_fragment), -1 if fastq is None else int(bool(fastq)), ROUTES[route],
-                         search if isinstance(search, int) else SEARCHES[search])
+                         search if isinstance(search, int) else SEARCHES[search], pair if isinstance(pair, int) else PAIRS[pair])
         out_p, n = C.c_void_p(), C.c_size_t(0)
         if all(isinstance(r, str) for r in reads):
             paths = (C.c_char_p * len(reads))(*[r.encode() for r in reads])
@@ -82,14 +86,19 @@ class AlignIndex:
 def align_last():
     """dict(route, reads, aligned, pairs_concordant, decline, states_reads, states_anchors, states_cells) of the calling thread's
     last align(): route 2 = the kernels, 0 = the host route (decline says why: HGX_ALN_DECLINE_* of csrc/hgx_align_core.hpp and
-    hgx_align_states.hpp); states_* = the reads, anchors and table cells the states search took on that route."""
+    hgx_align_states.hpp); states_* = the reads, anchors and table cells the states search took on that route; pairs_searched /
+    pairs_placed / pairs_changed (pair="aware") = pairs with candidates on both mates, with a concordant combination, and with a
+    record that differs from the independent one in alignment or NH."""
     route, dec = C.c_int32(0), C.c_int32(0)
     reads, aligned, conc = C.c_int64(0), C.c_int64(0), C.c_int64(0)
     capi.check(capi.lib().hgx_align_last(C.byref(route), C.byref(reads), C.byref(aligned), C.byref(conc), C.byref(dec)))
     sr, sa, sc = C.c_int64(0), C.c_int64(0), C.c_int64(0)
     capi.check(capi.lib().hgx_align_last_states(C.byref(sr), C.byref(sa), C.byref(sc)))
+    ps, pp, pc = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    capi.check(capi.lib().hgx_align_last_pairs(C.byref(ps), C.byref(pp), C.byref(pc)))
     return dict(route=route.value, reads=reads.value, aligned=aligned.value, pairs_concordant=conc.value, decline=dec.value,
-                states_reads=sr.value, states_anchors=sa.value, states_cells=sc.value)
+                states_reads=sr.value, states_anchors=sa.value, states_cells=sc.value,
+                pairs_searched=ps.value, pairs_placed=pp.value, pairs_changed=pc.value)
 
 
 DECLINE_GATE, DECLINE_READ_LEN, DECLINE_ANCHORS, DECLINE_STACK, DECLINE_VARS, DECLINE_STEPS, DECLINE_SWITCH = 1, 2, 3, 4, 5, 6, 7

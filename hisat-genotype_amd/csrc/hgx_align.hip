@@ -6,6 +6,8 @@
 //   k_aln_extend   a lane per anchor slot: canon(a) by the core's depth-first search, scratch in the lane's private memory; a limit
 //                  reached raises the decline code and writes nothing
 //   k_aln_pick     a lane per read: the smallest canon(a) and NH
+//   k_aln_pair_pick  (paired input with opts.pair = 1 only) a wavefront per pair: where a combination of the two mates' canon(a) is
+//                  concordant, best[] and nh[] of both mates are rewritten from the smallest one (the core's pair order)
 //   k_aln_emit     a lane per read, twice: record sizes, (exclusive scan,) then the SAM lines at their offsets; the pair's flags are
 //                  read off the mate's pick
 // Every write is bounds-checked by construction: slots < HGX_ALN_DEV_ANCHORS, a record's bytes = the size the same code counted.
@@ -100,6 +102,126 @@ k_aln_pick(int nc, const int32_t *cnt, const DevRes *res, int32_t *best, int32_t
     int h = 0;
     best[i] = hgx_aln_pick(res + (long)i * HGX_ALN_DEV_ANCHORS, n, &h);
     nh[i] = h;
+}
+
+// opts.pair = 1: the pair pick (hgx_align_core.hpp), one wavefront (= one workgroup) per pair over the two mates' slots.  LDS per
+// pair: the 2 x 128 slot heads (8 KB), their in-use marks, starts and placements (0.75 KB), the 128 x 128-bit set of (placement, placement)
+// (2 KB) -- 10.75 KB, so a CU's 160 KB hold 14 pairs.  Lanes run over mate 1's slots, each with a loop over mate 2's; the lists stay in
+// global memory and are read only where two combinations tie in everything else.  Every index is a slot below HGX_ALN_DEV_ANCHORS.
+// pairs[0 .. 2]: pairs searched, placed, changed.
+__device__ inline int pp_cmp(const hgx_aln_head (*h)[HGX_ALN_DEV_ANCHORS], const DevRes *r1, const DevRes *r2, int x, int y) {
+    return hgx_aln_pair_cmp(h[0][x >> 8], r1[x >> 8].vl, h[1][x & 255], r2[x & 255].vl, h[0][y >> 8], r1[y >> 8].vl, h[1][y & 255],
+                            r2[y & 255].vl);
+}
+
+__global__ void __launch_bounds__(64)
+k_aln_pair_pick(int nc, int max_fragment, const int32_t *cnt, const DevRes *res, int32_t *best, int32_t *nh, unsigned long long *pairs) {
+    constexpr int N = HGX_ALN_DEV_ANCHORS;
+    __shared__ hgx_aln_head s_h[2][N];
+    __shared__ uint8_t s_used[2][N], s_start[2][N], s_place[2][N];
+    __shared__ uint32_t s_set[N * N / 32];
+    const int lane = threadIdx.x, i = 2 * blockIdx.x, j = i + 1;
+    if (j >= nc || best[i] < 0 || best[j] < 0) return;                 // (the whole wavefront)
+    const int n[2] = {cnt[i] < N ? cnt[i] : N, cnt[j] < N ? cnt[j] : N};
+    const DevRes *r[2] = {res + (long)i * N, res + (long)j * N};
+    for (int k = lane; k < 2 * N; k += 64) {
+        const int m = k / N, e = k % N;
+        hgx_aln_head h{0, 0, 0, 0, 0, 0, 0, 0};
+        if (e < n[m]) {
+            const int4 *p = (const int4 *)&r[m][e];                   // (a DevRes is 160 bytes: 16-byte aligned)
+            const int4 lo = p[0], hi = p[1];
+            h = hgx_aln_head{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+        }
+        s_h[m][e] = h;
+        s_used[m][e] = 0;
+    }
+    for (int k = lane; k < N * N / 32; k += 64) s_set[k] = 0;
+    __syncthreads();
+    // the smallest sums over the concordant combinations, then the smallest combination among those that have them
+    uint64_t sums = ~0ull;
+    for (int a = lane; a < n[0]; a += 64) {
+        const hgx_aln_head h1 = s_h[0][a];
+        if (!h1.ok) continue;
+        for (int b = 0; b < n[1]; ++b)
+            if (hgx_aln_concordant(h1, s_h[1][b], max_fragment)) {
+                const uint64_t s = hgx_aln_pair_sums(h1, s_h[1][b]);
+                sums = s < sums ? s : sums;
+            }
+    }
+    for (int d = 32; d; d >>= 1) {
+        const uint64_t o = (uint64_t)__shfl_xor((long long)sums, d, 64);
+        sums = o < sums ? o : sums;
+    }
+    if (lane == 0) atomicAdd(pairs, 1ull);
+    if (sums == ~0ull) return;                                         // no concordant combination: the independent picks stand
+    const int nm = hgx_aln_pair_sums_nm(sums);
+    int win = -1;                                                      // slot of c1 << 8 | slot of c2
+    for (int a = lane; a < n[0]; a += 64) {
+        const hgx_aln_head h1 = s_h[0][a];
+        if (!h1.ok) continue;
+        for (int b = 0; b < n[1]; ++b) {
+            if (!hgx_aln_concordant(h1, s_h[1][b], max_fragment) || h1.nm + s_h[1][b].nm != nm) continue;
+            s_used[0][a] = 1;                                          // (several lanes may write the same 1 to mate 2's)
+            s_used[1][b] = 1;
+            if (hgx_aln_pair_sums(h1, s_h[1][b]) != sums) continue;
+            const int x = (a << 8) | b;
+            if (win < 0 || pp_cmp(s_h, r[0], r[1], x, win) < 0) win = x;
+        }
+    }
+    for (int d = 32; d; d >>= 1) {
+        const int o = __shfl_xor(win, d, 64);
+        if (o < 0) continue;
+        const int c = win < 0 ? -1 : pp_cmp(s_h, r[0], r[1], o, win);
+        if (c < 0 || (c == 0 && o < win)) win = o;                     // (equal combinations: the same canon through two anchors)
+    }
+    __syncthreads();
+    // placements of the candidates in use: which of them start one, then each one's start
+    for (int k = lane; k < 2 * N; k += 64) {
+        const int m = k / N, e = k % N;
+        if (e >= n[m] || !s_used[m][e]) continue;
+        const hgx_aln_head he = s_h[m][e];
+        int start = 1;
+        for (int x = 0; x < n[m] && start; ++x)
+            if (s_used[m][x] && hgx_aln_covers(s_h[m][x], x, he, e)) start = 0;
+        s_start[m][e] = (uint8_t)start;
+    }
+    __syncthreads();
+    for (int k = lane; k < 2 * N; k += 64) {
+        const int m = k / N, e = k % N;
+        if (e >= n[m] || !s_used[m][e]) continue;
+        const hgx_aln_head he = s_h[m][e];
+        int p = e;                                                     // the last start at or before e on its locus and strand
+        if (!s_start[m][e]) {
+            p = -1;
+            for (int x = 0; x < n[m]; ++x)
+                if (s_used[m][x] && s_start[m][x] && s_h[m][x].locus == he.locus && s_h[m][x].strand == he.strand &&
+                    hgx_aln_before(s_h[m][x], x, he, e) && (p < 0 || hgx_aln_before(s_h[m][p], p, s_h[m][x], x))) p = x;
+        }
+        s_place[m][e] = (uint8_t)(p < 0 ? e : p);                      // (p < 0 cannot be: the first in order is a start)
+    }
+    __syncthreads();
+    for (int a = lane; a < n[0]; a += 64) {
+        const hgx_aln_head h1 = s_h[0][a];
+        if (!h1.ok || !s_used[0][a]) continue;
+        for (int b = 0; b < n[1]; ++b)
+            if (s_used[1][b] && h1.nm + s_h[1][b].nm == nm && hgx_aln_concordant(h1, s_h[1][b], max_fragment)) {
+                const int bit = (int)s_place[0][a] * N + s_place[1][b];
+                atomicOr(&s_set[bit >> 5], 1u << (bit & 31));
+            }
+    }
+    __syncthreads();
+    int count = 0;
+    for (int k = lane; k < N * N / 32; k += 64) count += __popc(s_set[k]);
+    for (int d = 32; d; d >>= 1) count += __shfl_xor(count, d, 64);
+    if (lane == 0 && win >= 0) {                                       // (win < 0 cannot be: some combination has `sums`)
+        const int a = win >> 8, b = win & 255;
+        const DevRes &o1 = r[0][best[i]], &o2 = r[1][best[j]];
+        const bool changed = hgx_aln_res_cmp(r[0][a], o1) != 0 || hgx_aln_res_cmp(r[1][b], o2) != 0 || nh[i] != count || nh[j] != count;
+        best[i] = a; best[j] = b;
+        nh[i] = count; nh[j] = count;
+        atomicAdd(pairs + 1, 1ull);
+        if (changed) atomicAdd(pairs + 2, 1ull);
+    }
 }
 
 // out == nullptr: sizes[i] and flags[i] (1 aligned, 2 = mate 1 of a concordant pair); else the line at out + off[i]
@@ -471,15 +593,18 @@ int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
     ALLOC(d_best, (size_t)cmax * 4); ALLOC(d_nh, (size_t)cmax * 4); ALLOC(d_sizes, (size_t)cmax * 4); ALLOC(d_off, (size_t)cmax * 4);
     ALLOC(d_flags, (size_t)cmax * 4);
     ALLOC(d_scan, hgx_scan_u32_scratch_bytes(cmax) + 16);
-    ALLOC(d_misc, 16);                       // [0] decline code, [1] total bytes, [2] reads marked for the second tier
+    ALLOC(d_misc, 48);                       // [0] decline code, [1] total bytes, [2] reads marked for the second tier; pair mode: bytes 16 .. 40 = pairs searched, placed, changed
     int *d_decline = d_misc.as<int>();
     uint32_t *d_total = d_misc.as<uint32_t>() + 1;
+    const bool pair_aware = reads.paired && opts->pair == 1;
+    const size_t misc_bytes = pair_aware ? 40 : 16;
+    int64_t pairs[3] = {0, 0, 0};
     std::vector<int32_t> flags(cmax);
     std::string text;
     for (long first = 0; first < n; first += CHUNK) {
         const int nc = (int)std::min<long>(CHUNK, n - first);
         HIPCHK(hipMemsetAsync(d_cnt.p, 0, (size_t)nc * 4, st));
-        HIPCHK(hipMemsetAsync(d_misc.p, 0, 16, st));
+        HIPCHK(hipMemsetAsync(d_misc.p, 0, misc_bytes, st));
         if (search) HIPCHK(hipMemsetAsync(d_mark.p, 0, (size_t)nc * 4, st));
         const long n_seed = (long)nc * 2 * n_off_max;
         if (n_seed > 0)
@@ -508,13 +633,22 @@ int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
             return HGX_OK;
         }
         k_aln_pick<<<nblk(nc, 64), 64, 0, st>>>(nc, d_cnt.as<int32_t>(), d_res.as<DevRes>(), d_best.as<int32_t>(), d_nh.as<int32_t>(), mark);
+        if (pair_aware)
+            k_aln_pair_pick<<<nc / 2, 64, 0, st>>>(nc, opts->max_fragment, d_cnt.as<int32_t>(), d_res.as<DevRes>(), d_best.as<int32_t>(),
+                                                   d_nh.as<int32_t>(), (unsigned long long *)(d_misc.as<char>() + 16));
         k_aln_emit<<<nblk(nc, 64), 64, 0, st>>>(ix->dv, rd, first, nc, opts->max_fragment, d_res.as<DevRes>(), d_best.as<int32_t>(),
                                                 d_nh.as<int32_t>(), d_sizes.as<uint32_t>(), d_flags.as<int32_t>(), nullptr, nullptr);
         HIPCHK(hipGetLastError());
         rc = hgx_scan_u32_dev(d_sizes.as<uint32_t>(), d_off.as<uint32_t>(), nc, d_scan.p, d_total, st);
         if (rc) return rc;
-        uint32_t total = 0;
-        HIPCHK(hipMemcpy(&total, d_total, 4, hipMemcpyDeviceToHost));
+        uint32_t back[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};                // total bytes; pair mode: the rest of d_misc with it
+        HIPCHK(hipMemcpy(back, d_total, pair_aware ? 36 : 4, hipMemcpyDeviceToHost));
+        const uint32_t total = back[0];
+        for (int k = 0; k < 3; ++k) {
+            uint64_t v;
+            memcpy(&v, back + 3 + 2 * k, 8);
+            pairs[k] += (int64_t)v;
+        }
         HIPCHK(hipMemcpy(flags.data(), d_flags.p, (size_t)nc * 4, hipMemcpyDeviceToHost));
         for (int i = 0; i < nc; ++i) { *aligned += flags[i] & 1; *concordant += (flags[i] >> 1) & 1; }
         if (total) {
@@ -529,5 +663,6 @@ int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
         }
     }
     HIPCHK(hipStreamSynchronize(st));
+    if (pair_aware) hgx_align_pairs_count(pairs[0], pairs[1], pairs[2]);
     return HGX_OK;
 }

@@ -343,12 +343,20 @@ HGX_ALN_HD int hgx_aln_canon(const hgx_aln_view &V, const hgx_aln_read &R, int o
     return 0;
 }
 
-template <int MAXV> HGX_ALN_HD int hgx_aln_res_cmp(const hgx_aln_res<MAXV> &a, const hgx_aln_res<MAXV> &b) {
+// the eight words in front of an alignment's list: what the pair pick keeps of a candidate (the kernels: in LDS)
+struct hgx_aln_head { int32_t ok, nm, nind, nvar, locus, strand, pos0, end; };
+
+// the order of two alignments by their key (NM, indels, variants, locus, strand, pos0, list); H = hgx_aln_res or hgx_aln_head with
+// the list beside it (read only where everything in front of it ties)
+template <class H> HGX_ALN_HD int hgx_aln_key_cmp(const H &a, const int32_t *avl, const H &b, const int32_t *bvl) {
     int c = hgx_aln_cmp3(a.nm, a.nind, a.nvar, b.nm, b.nind, b.nvar);
     if (c) return c;
     c = hgx_aln_cmp3(a.locus, a.strand, a.pos0, b.locus, b.strand, b.pos0);
-    for (int i = 0; c == 0 && i < a.nvar; ++i) c = a.vl[i] != b.vl[i] ? (a.vl[i] < b.vl[i] ? -1 : 1) : 0;
+    for (int i = 0; c == 0 && i < a.nvar; ++i) c = avl[i] != bvl[i] ? (avl[i] < bvl[i] ? -1 : 1) : 0;
     return c;
+}
+template <int MAXV> HGX_ALN_HD int hgx_aln_res_cmp(const hgx_aln_res<MAXV> &a, const hgx_aln_res<MAXV> &b) {
+    return hgx_aln_key_cmp(a, a.vl, b, b.vl);
 }
 
 // the read's alignment among the canon(a) of its anchors: index of the smallest (-1: unaligned) and NH, the number of placements
@@ -465,13 +473,45 @@ HGX_ALN_HD inline int hgx_aln_walk_text(const hgx_aln_view &V, const hgx_aln_rea
 }
 
 // FLAG / RNEXT / PNEXT / YT of a record: `mate` = the other mate's alignment (nullptr: single-end; ok == 0: unaligned)
-template <int MAXV>
-HGX_ALN_HD bool hgx_aln_concordant(const hgx_aln_res<MAXV> &a, const hgx_aln_res<MAXV> &b, int max_fragment) {
+template <class H> HGX_ALN_HD bool hgx_aln_concordant(const H &a, const H &b, int max_fragment) {
     if (!a.ok || !b.ok || a.locus != b.locus || a.strand == b.strand) return false;
-    const hgx_aln_res<MAXV> &plus = a.strand == 0 ? a : b, &minus = a.strand == 0 ? b : a;
+    const H &plus = a.strand == 0 ? a : b, &minus = a.strand == 0 ? b : a;
     if (plus.pos0 > minus.pos0) return false;
     const int32_t left = a.pos0 < b.pos0 ? a.pos0 : b.pos0, right = a.end > b.end ? a.end : b.end;
     return right - left <= max_fragment;
+}
+
+// ---- pair-aware placement (opts.pair = 1; the rule in plain Python: tests/align_pair_ref.py) ----------------------------------------
+// A mate's candidates are the canon(a) of its anchors (a canon reached through several anchors stands several times: harmless in
+// all that follows).  A combination (c1, c2) takes one of each mate.  If one is concordant, the pair is written from the smallest
+// concordant one by (NM1 + NM2, indels1 + indels2, variants1 + variants2, key of c1, key of c2); NH of both records = the number of
+// distinct (placement of c1, placement of c2) over the concordant combinations of the smallest NM sum, the placements being those of
+// the candidates these combinations use.  The pieces both routes run (the host route in loops, k_aln_pair_pick with lanes over
+// mate 1's candidates):
+//   hgx_aln_pair_sums   the first three components of a combination's order, packed: smaller word = smaller sums
+//   hgx_aln_pair_cmp    the whole order of two combinations
+//   hgx_aln_covers      x stands before e in (locus, strand, pos0, slot) order, on e's locus and strand, and ends behind e's pos0:
+//                       e STARTS a placement iff no candidate in use covers it (the running maximum of the statement: every
+//                       candidate of an earlier placement ends at or before the start of the later one), and e's placement is the
+//                       last start at or before e
+template <class H> HGX_ALN_HD uint64_t hgx_aln_pair_sums(const H &a, const H &b) {
+    return ((uint64_t)(uint32_t)(a.nm + b.nm) << 42) | ((uint64_t)(uint32_t)(a.nind + b.nind) << 21) | (uint64_t)(uint32_t)(a.nvar + b.nvar);
+}
+HGX_ALN_HD inline int hgx_aln_pair_sums_nm(uint64_t sums) { return (int)(sums >> 42); }
+template <class H>
+HGX_ALN_HD int hgx_aln_pair_cmp(const H &a1, const int32_t *a1vl, const H &a2, const int32_t *a2vl, const H &b1, const int32_t *b1vl,
+                                const H &b2, const int32_t *b2vl) {
+    const uint64_t sa = hgx_aln_pair_sums(a1, a2), sb = hgx_aln_pair_sums(b1, b2);
+    if (sa != sb) return sa < sb ? -1 : 1;
+    const int c = hgx_aln_key_cmp(a1, a1vl, b1, b1vl);
+    return c ? c : hgx_aln_key_cmp(a2, a2vl, b2, b2vl);
+}
+template <class H> HGX_ALN_HD bool hgx_aln_before(const H &x, int ix, const H &e, int ie) {      // in (locus, strand, pos0, slot) order
+    const int c = hgx_aln_cmp3(x.locus, x.strand, x.pos0, e.locus, e.strand, e.pos0);
+    return c < 0 || (c == 0 && ix < ie);
+}
+template <class H> HGX_ALN_HD bool hgx_aln_covers(const H &x, int ix, const H &e, int ie) {
+    return x.locus == e.locus && x.strand == e.strand && hgx_aln_before(x, ix, e, ie) && x.end > e.pos0;
 }
 
 // the whole line (with its '\n'); `name` / `qual` as the file has them (qual == nullptr: 'I' x L)

@@ -23,6 +23,7 @@ namespace {
 thread_local int g_route = 0, g_decline = 0;
 thread_local int64_t g_reads = 0, g_aligned = 0, g_conc = 0;
 thread_local int64_t g_st_reads = 0, g_st_anchors = 0, g_st_cells = 0;
+thread_local int64_t g_pr_searched = 0, g_pr_placed = 0, g_pr_changed = 0;
 
 template <class T> void csr(const std::vector<std::pair<int32_t, int32_t>> &items, int32_t n_pos, std::vector<T> &off, std::vector<T> &list) {
     off.assign((size_t)n_pos + 1, 0);
@@ -313,12 +314,67 @@ int align_one_states(const hgx_aln_view &V, const char *seq, int L, int max_edit
     return HGX_OK;
 }
 
+// the pair pick (hgx_align_core.hpp) in plain loops over the two mates' candidates: false = no concordant combination
+struct PairScratch {
+    std::vector<HostRes> cand[2];
+    std::vector<char> used[2];
+    std::vector<int32_t> place[2], order;
+    std::vector<uint64_t> seen;
+};
+
+bool pair_pick(PairScratch &S, int max_fragment, int *b1, int *b2, int *nh) {
+    const std::vector<HostRes> &c1 = S.cand[0], &c2 = S.cand[1];
+    const int n1 = (int)c1.size(), n2 = (int)c2.size();
+    int a = -1, b = -1;
+    for (int i = 0; i < n1; ++i)
+        for (int j = 0; j < n2; ++j)
+            if (hgx_aln_concordant(c1[i], c2[j], max_fragment) &&
+                (a < 0 || hgx_aln_pair_cmp(c1[i], c1[i].vl, c2[j], c2[j].vl, c1[a], c1[a].vl, c2[b], c2[b].vl) < 0)) { a = i; b = j; }
+    if (a < 0) return false;
+    const int nm = c1[a].nm + c2[b].nm;
+    S.used[0].assign((size_t)n1, 0);
+    S.used[1].assign((size_t)n2, 0);
+    for (int i = 0; i < n1; ++i)
+        for (int j = 0; j < n2; ++j)
+            if (c1[i].nm + c2[j].nm == nm && hgx_aln_concordant(c1[i], c2[j], max_fragment)) S.used[0][(size_t)i] = S.used[1][(size_t)j] = 1;
+    for (int m = 0; m < 2; ++m) {                        // place[m][e]: the candidate that starts e's placement
+        const std::vector<HostRes> &c = S.cand[m];
+        const std::vector<char> &u = S.used[m];
+        const int n = (int)c.size();
+        S.order.clear();
+        for (int e = 0; e < n; ++e)
+            if (u[(size_t)e]) S.order.push_back(e);
+        std::sort(S.order.begin(), S.order.end(), [&](int x, int y) { return hgx_aln_before(c[(size_t)x], x, c[(size_t)y], y); });
+        S.place[m].assign((size_t)n, -1);
+        int cur = -1;
+        for (size_t k = 0; k < S.order.size(); ++k) {
+            const int e = S.order[k];
+            bool start = true;
+            for (size_t q = 0; q < k && start; ++q) start = !hgx_aln_covers(c[(size_t)S.order[q]], S.order[q], c[(size_t)e], e);
+            if (start) cur = e;
+            S.place[m][(size_t)e] = cur;
+        }
+    }
+    S.seen.clear();
+    for (int i = 0; i < n1; ++i)
+        for (int j = 0; j < n2; ++j)
+            if (c1[i].nm + c2[j].nm == nm && hgx_aln_concordant(c1[i], c2[j], max_fragment))
+                S.seen.push_back(((uint64_t)(uint32_t)S.place[0][(size_t)i] << 32) | (uint32_t)S.place[1][(size_t)j]);
+    std::sort(S.seen.begin(), S.seen.end());
+    *nh = (int)(std::unique(S.seen.begin(), S.seen.end()) - S.seen.begin());
+    *b1 = a;
+    *b2 = b;
+    return true;
+}
+
 int host_route(const hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_align_opts *o, std::string &body, int64_t *aligned,
                int64_t *conc, int *gave_up) {
     const hgx_aln_view &V = ix->hv;
     HostScratch S;
     StatesScratch SS;
+    PairScratch PS;
     const int per = reads.paired ? 2 : 1;
+    const bool pair_aware = per == 2 && o->pair == 1;
     std::vector<HostRes> best(per);
     int nh[2] = {0, 0};
     std::vector<char> line;
@@ -328,6 +384,20 @@ int host_route(const hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
             const int rc = o->search ? align_one_states(V, seq, reads.len[k + m], o->max_edits, SS, best[m], &nh[m], gave_up)
                                      : align_one(V, seq, reads.len[k + m], o->max_edits, S, best[m], &nh[m], gave_up);
             if (rc) return rc;
+            if (pair_aware) PS.cand[m].swap(S.res);      // (a mate that gave up: none)
+        }
+        if (pair_aware && best[0].ok && best[1].ok) {
+            int b1 = -1, b2 = -1, pnh = 0;
+            const bool placed = pair_pick(PS, o->max_fragment, &b1, &b2, &pnh);
+            bool changed = false;
+            if (placed) {
+                const HostRes &n1 = PS.cand[0][(size_t)b1], &n2 = PS.cand[1][(size_t)b2];
+                changed = hgx_aln_res_cmp(n1, best[0]) != 0 || hgx_aln_res_cmp(n2, best[1]) != 0 || nh[0] != pnh || nh[1] != pnh;
+                best[0] = n1;
+                best[1] = n2;
+                nh[0] = nh[1] = pnh;
+            }
+            hgx_align_pairs_count(1, placed, changed);
         }
         if (per == 2 && hgx_aln_concordant(best[0], best[1], o->max_fragment)) ++*conc;
         for (int m = 0; m < per; ++m) {
@@ -354,6 +424,11 @@ void hgx_align_states_count(int64_t reads, int64_t anchors, int64_t cells) {
     g_st_reads += reads;
     g_st_anchors += anchors;
     g_st_cells += cells;
+}
+void hgx_align_pairs_count(int64_t searched, int64_t placed, int64_t changed) {
+    g_pr_searched += searched;
+    g_pr_placed += placed;
+    g_pr_changed += changed;
 }
 
 #ifdef HGX_ALIGN_STANDALONE
@@ -472,7 +547,8 @@ extern "C" int hgx_align_index_free(hgx_align_index *ix) {
 extern "C" int hgx_align_reads(hgx_align_index *ix, int32_t n_inputs, const char *const *paths, const char *const *texts,
                                const size_t *text_bytes, const hgx_align_opts *opts, char **sam_out, size_t *n_bytes_out) {
     if (!ix || (n_inputs != 1 && n_inputs != 2) || (!paths && !(texts && text_bytes)) || !opts || !sam_out || !n_bytes_out ||
-        opts->max_edits < 0 || opts->route < 0 || opts->route > 2 || opts->search < 0 || opts->search > 2) {
+        opts->max_edits < 0 || opts->route < 0 || opts->route > 2 || opts->search < 0 || opts->search > 2 ||
+        opts->pair < 0 || opts->pair > 1 || (opts->pair && opts->search)) {      // (the states form keeps no candidates to pair)
         hgx_set_error("invalid argument: hgx_align_reads");
         return HGX_EINVAL;
     }
@@ -480,6 +556,7 @@ extern "C" int hgx_align_reads(hgx_align_index *ix, int32_t n_inputs, const char
     *n_bytes_out = 0;
     g_route = 0; g_decline = 0; g_reads = g_aligned = g_conc = 0;
     g_st_reads = g_st_anchors = g_st_cells = 0;
+    g_pr_searched = g_pr_placed = g_pr_changed = 0;
     try {
         hgx_aln_reads reads;
         int rc = load_reads(n_inputs, paths, texts, text_bytes, opts->fastq, reads);
@@ -498,6 +575,7 @@ extern "C" int hgx_align_reads(hgx_align_index *ix, int32_t n_inputs, const char
             body.clear();
             aligned = conc = 0;
             g_st_reads = g_st_anchors = g_st_cells = 0;          // what the kernels took before they declined is not this call's answer
+            g_pr_searched = g_pr_placed = g_pr_changed = 0;
             int gave_up = 0;
             if ((rc = host_route(ix, reads, opts, body, &aligned, &conc, &gave_up))) return rc;
             if (gave_up) fprintf(stderr, "[hgx_align_reads] a read's search passed the host route's limits (code %d): left unaligned\n", gave_up);
@@ -534,5 +612,12 @@ extern "C" int hgx_align_last_states(int64_t *reads, int64_t *anchors, int64_t *
     if (reads) *reads = g_st_reads;
     if (anchors) *anchors = g_st_anchors;
     if (cells) *cells = g_st_cells;
+    return HGX_OK;
+}
+
+extern "C" int hgx_align_last_pairs(int64_t *searched, int64_t *placed, int64_t *changed) {
+    if (searched) *searched = g_pr_searched;
+    if (placed) *placed = g_pr_placed;
+    if (changed) *changed = g_pr_changed;
     return HGX_OK;
 }

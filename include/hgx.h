@@ -846,7 +846,7 @@ int hgx_extract_close(hgx_extract *h);
 /* ---- the "hgx" aligner: reads of a locus family -> SAM text in the front end's dialect ------------------------------
  * Stands in for typing_common.align_reads (common:985-1056) for reads already known to belong to the loci: end to end, at most
  * max_edits unknown mismatches, known variants free; no whole-genome index, no novel indels, no soft clips, no secondary records,
- * mates placed independently.  NOT HISAT2 and not compared with its output: the rules are those of tests/align_ref.py.
+ * mates placed independently (unless opts.pair = 1, below).  NOT HISAT2 and not compared with its output: the rules are those of tests/align_ref.py.
  * index_create (the `hisat2 -x <index>` argument of common:1013-1023: what the reads are aligned to): n_loci loci in the caller's
  * order, names[g] = the backbone's reference name, backbones[g] its bases; the variants of locus g are
  * var_off[g] .. var_off[g + 1] in Var_list order with var_type (0 insertion, 1 single, 2 deletion), var_pos (0-based backbone
@@ -868,10 +868,23 @@ int hgx_extract_close(hgx_extract *h);
  * and timing form).  The bytes are the same in all three.  The kernels decline a states search whose window of backbone
  * positions is wider than 8 192 or has an option that leaves it (HGX_ALN_DECLINE_WINDOW); the host route widens the window.
  * Any other value is HGX_EINVAL.  align_last_states: reads, anchors and table cells the states form took in the calling
- * thread's last call, on the route that gave the bytes.                                                                         */
+ * thread's last call, on the route that gave the bytes.
+ * opts.pair: how the mates of a pair are placed.  0 "independent" (the default: every byte as before) = each mate's smallest
+ * alignment, NH = that mate's placements.  1 "aware" (the rule in plain Python: tests/align_pair_ref.py) = a mate's candidates are
+ * the smallest alignments through each of its anchors; if a combination of one candidate per mate is concordant (same locus,
+ * opposite strands, the + mate not behind the - mate, span <= max_fragment), both records are written from the smallest concordant
+ * combination by (NM1 + NM2, indels1 + indels2, variants1 + variants2, key of mate 1's, key of mate 2's) as a concordant pair
+ * (flags 99/147 or 83/163, YT:Z:CP), and NH of both = the distinct (placement of mate 1, placement of mate 2) among the concordant
+ * combinations of the smallest NM sum (MAPQ 60 if 1, else 1).  A pair without a concordant combination, a pair with an unaligned
+ * mate and single-end input are written exactly as with 0.  On the kernels' route this is k_aln_pair_pick (a wavefront per pair,
+ * 10.75 KB of LDS); a read past the 128 anchor slots moves the call to the host route as before, which applies the same rule.
+ * pair = 1 with search != 0 is HGX_EINVAL (the states form keeps a read's winner, not its candidates); any other value of pair too.
+ * align_last_pairs: of the calling thread's last call, on the route that gave the bytes -- pairs with candidates on both mates,
+ * pairs with a concordant combination, pairs of which a record differs from the independent one in alignment or NH; 0 with pair = 0. */
 typedef struct hgx_align_opts {
     int32_t max_edits, max_fragment, fastq, route;
     int32_t search;            /* 0 ways (the default), 1 states, 2 states_all */
+    int32_t pair;              /* 0 independent (the default), 1 aware */
 } hgx_align_opts;
 typedef struct hgx_align_index hgx_align_index;
 int hgx_align_index_create(hgx_align_index **out, int32_t n_loci, const char *const *names, const char *const *backbones,
@@ -882,6 +895,7 @@ int hgx_align_reads(hgx_align_index *ix, int32_t n_inputs, const char *const *pa
                     const size_t *text_bytes, const hgx_align_opts *opts, char **sam_out, size_t *n_bytes_out);
 int hgx_align_last(int32_t *route, int64_t *reads, int64_t *aligned, int64_t *pairs_concordant, int32_t *decline_code);
 int hgx_align_last_states(int64_t *reads, int64_t *anchors, int64_t *cells);
+int hgx_align_last_pairs(int64_t *searched, int64_t *placed, int64_t *changed);
 
 #ifdef __cplusplus
 }

@@ -1,13 +1,17 @@
 """Time the "hgx" aligner's device route against its host route: reads/s of AlignIndex.align, upload and copy
 back included, at a few read counts.
 
-    python tools/align_timing.py [--workload synth|tandem] [--search ways|states|states_all] [--err 0.5] [--reps 5]
-                                 [--sizes 250,500,1000,2000,4000,16000,64000] [--tandem-indels 12] [--no-host]
+    python tools/align_timing.py [--workload synth|tandem|paralog] [--search ways|states|states_all] [--pair] [--err 0.5]
+                                 [--reps 5] [--sizes 250,500,1000,2000,4000,16000,64000] [--tandem-indels 12] [--no-host]
 
 --workload synth   simulated 100-base pairs of a synth HLA-like locus, at read counts round the route gate
 --workload tandem  150-base single reads across a GATA x 40 repeat with --tandem-indels known unit deletions and as many known
                    unit insertions (two alleles: the backbone's, and one with three units fewer).  Reads inside the plain repeat
                    pass the kernels' anchor slots: with --search ways the call goes to the host route (default --sizes 64).
+--workload paralog 100-base pairs of two loci that share a 300-base stretch (one base of the copy differs): mate 1 inside the
+                   stretch, cut from either locus, mate 2 unique and 300 to 500 bases on at home (default --sizes 16000,64000)
+--pair             time the device route with pair="aware" beside pair="independent" (hgx_align_opts.pair) and print the pair
+                   counters; the texts differ by design, so they are not compared with each other
 --search           the search form of the device-route call (hgx_align_opts.search).  The host route is timed with "ways" and,
                    when --search is not "ways", with "states" as well.
 
@@ -75,6 +79,32 @@ def tandem_reads(n_indels, n_reads, units=40, flank=300, read_len=150, stride=11
     return dict(Genes={"T": {"T*BACKBONE": bb}}, Vars={"T": Vars}, Var_list={"T": Var_list}, refGenes={"T": "T*BACKBONE"}), [text]
 
 
+def paralog_reads(n_pairs):
+    """(reference dicts, [mate-1 FASTA, mate-2 FASTA]): P (2 500 bases) and Q (900 bases), Q[300:600] = P[1000:1300] but for one base."""
+    rng = random.Random(9)
+    seq = lambda n: "".join(rng.choice("ACGT") for _ in range(n))          # noqa: E731
+    comp = {"A": "T", "C": "G", "G": "C", "T": "A"}
+    rc = lambda s: "".join(comp[b] for b in reversed(s))                   # noqa: E731
+    p = seq(2500)
+    q = list(seq(300) + p[1000:1300] + seq(300))
+    q[450] = "ACGT"[("ACGT".index(q[450]) + 1) % 4]
+    q = "".join(q)
+    m1, m2 = [], []
+    for k in range(n_pairs):
+        a = 1000 + (k * 7) % 200                                           # mate 1 at P[a : a + 100], inside the stretch
+        home = (k // 3) % 2                                                # 0: the fragment is P's, 1: Q's
+        if home == 0:
+            b = a + 300 + (k * 13) % 200
+            m1.append((p if k % 3 else q)[a if k % 3 else a - 700:][:100])   # every third: mate 1 reads as Q's copy does
+            m2.append(rc(p[b:b + 100]))
+        else:
+            m1.append(q[a - 700:a - 600])
+            m2.append(rc(q[700 + (k * 13) % 100:][:100]))
+    texts = ["".join(">r%d\n%s\n" % (k, s) for k, s in enumerate(m)).encode() for m in (m1, m2)]
+    return dict(Genes={"P": {"P*BACKBONE": p}, "Q": {"Q*BACKBONE": q}}, Vars={}, Var_list={},
+                refGenes={"P": "P*BACKBONE", "Q": "Q*BACKBONE"}), texts
+
+
 def timed(ix, texts, reps, **kw):
     out = ix.align(texts, **kw)                                       # warm-up
     last = align.align_last()
@@ -88,7 +118,8 @@ def timed(ix, texts, reps, **kw):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=("synth", "tandem"), default="synth")
+    ap.add_argument("--workload", choices=("synth", "tandem", "paralog"), default="synth")
+    ap.add_argument("--pair", action="store_true", help="also time the device route with pair=\"aware\"")
     ap.add_argument("--search", choices=sorted(align.SEARCHES), default="ways")
     ap.add_argument("--err", type=float, default=0.5)
     ap.add_argument("--reps", type=int, default=5)
@@ -96,7 +127,7 @@ def main():
     ap.add_argument("--tandem-indels", type=int, default=12)
     ap.add_argument("--no-host", action="store_true", help="time the device-route call only")
     args = ap.parse_args()
-    sizes = args.sizes or ("250,500,1000,2000,4000,16000,64000" if args.workload == "synth" else "64")
+    sizes = args.sizes or {"synth": "250,500,1000,2000,4000,16000,64000", "tandem": "64", "paralog": "16000,64000"}[args.workload]
     capi.set_device(0)
     search = {} if args.search == "ways" else {"search": args.search}
     configs = [("device " + args.search, dict(route="device", **search))]
@@ -104,14 +135,24 @@ def main():
         configs.append(("host ways", dict(route="host")))
         if search:
             configs.append(("host states", dict(route="host", search="states")))
+    if args.pair:
+        assert not search, "pair=\"aware\" needs --search ways"
+        configs.insert(1, ("device ways pairs", dict(route="device", pair="aware")))
     rows = []
     for n in [int(x) for x in sizes.split(",")]:
-        d, texts = reads_of(args.err, n // 2) if args.workload == "synth" else tandem_reads(args.tandem_indels, n)
+        d, texts = (reads_of(args.err, n // 2) if args.workload == "synth" else paralog_reads(n // 2) if args.workload == "paralog"
+                    else tandem_reads(args.tandem_indels, n))
         ix = align.AlignIndex(d["Genes"], d["Vars"], d["Var_list"], d["refGenes"])
         outs, med = [], {}
         for name, kw in configs:
             out, last, ts = timed(ix, texts, args.reps, **kw)
-            outs.append(out)
+            if kw.get("pair") == "aware":
+                chunks = -(-n // 8192)
+                print("%7d reads  %-18s pairs searched %d placed %d changed %d; %+.3f ms per 8 192-read chunk against %s" % (
+                    n, name, last["pairs_searched"], last["pairs_placed"], last["pairs_changed"],
+                    (statistics.median(ts) - med[configs[0][0]]) * 1e3 / chunks, configs[0][0]), flush=True)
+            else:
+                outs.append(out)
             med[name] = statistics.median(ts)
             print("%7d reads  %-18s median %10.3f ms  range %10.3f .. %10.3f ms  %10.0f reads/s   route %d decline %d aligned %d  "
                   "states: reads %d anchors %d cells %d" % (
