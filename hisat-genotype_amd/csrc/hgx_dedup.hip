@@ -37,9 +37,13 @@ __global__ __launch_bounds__(256) void k_hash_rows(const uint64_t *__restrict__ 
 // ------------------------------------------------------------------------------------------------
 #define SCAN_T 1024
 #define SCAN_TILE (4 * SCAN_T)
-__global__ __launch_bounds__(SCAN_T) void k_scan_u32(const uint32_t *__restrict__ in, uint32_t *__restrict__ out, long n,
-                                                     unsigned long long *__restrict__ state, uint32_t *__restrict__ ticket,
-                                                     uint32_t *__restrict__ total_out) {
+// FIN (the class numbering of a dedup, k_scan_classes): the values are the first-row flags of the rows, and the tile that numbers a
+// flagged row also writes the class' first row and count -- what a pass over the whole table (k_ht_finalize) did before.
+struct ScanFin { const uint32_t *slot_of; const unsigned long long *cnt; int64_t *out_first, *out_count; };
+template <bool FIN>
+__device__ __forceinline__ void scan_u32_body(const uint32_t *__restrict__ in, uint32_t *__restrict__ out, long n,
+                                              unsigned long long *__restrict__ state, uint32_t *__restrict__ ticket,
+                                              uint32_t *__restrict__ total_out, const ScanFin fin) {
     __shared__ uint32_t s_tile;
     __shared__ uint32_t s_wave[SCAN_T / 64];
     __shared__ unsigned long long s_prefix;
@@ -55,6 +59,12 @@ __global__ __launch_bounds__(SCAN_T) void k_scan_u32(const uint32_t *__restrict_
     } else {
 #pragma unroll
         for (int k = 0; k < 4; ++k) v[k] = i0 + k < n ? in[i0 + k] : 0u;
+    }
+    unsigned long long cv[4] = {0, 0, 0, 0};                // (FIN) counts of the classes founded here: loaded ahead of the look-back
+    if (FIN) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (v[k]) cv[k] = fin.cnt[fin.slot_of[i0 + k]];
     }
     const uint32_t mine = v[0] + v[1] + v[2] + v[3];
     uint32_t incl = mine;                                   // inclusive scan of the threads' sums inside the wavefront
@@ -94,6 +104,14 @@ __global__ __launch_bounds__(SCAN_T) void k_scan_u32(const uint32_t *__restrict_
     }
     __syncthreads();
     uint32_t run = (uint32_t)s_prefix + s_wave[wv] + (incl - mine);
+    if (FIN) {
+        uint32_t c = run;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (v[k]) { fin.out_first[c] = (int64_t)(i0 + k); fin.out_count[c] = (int64_t)cv[k]; }
+            c += v[k];
+        }
+    }
     if (i0 + 3 < n) {
         uint4 o;
         o.x = run; run += v[0];
@@ -109,6 +127,16 @@ __global__ __launch_bounds__(SCAN_T) void k_scan_u32(const uint32_t *__restrict_
         }
     }
 }
+__global__ __launch_bounds__(SCAN_T) void k_scan_u32(const uint32_t *__restrict__ in, uint32_t *__restrict__ out, long n,
+                                                     unsigned long long *__restrict__ state, uint32_t *__restrict__ ticket,
+                                                     uint32_t *__restrict__ total_out) {
+    scan_u32_body<false>(in, out, n, state, ticket, total_out, ScanFin{nullptr, nullptr, nullptr, nullptr});
+}
+__global__ __launch_bounds__(SCAN_T) void k_scan_classes(const uint32_t *__restrict__ flag, uint32_t *__restrict__ rank, long n,
+                                                         unsigned long long *__restrict__ state, uint32_t *__restrict__ ticket,
+                                                         uint32_t *__restrict__ total_out, const ScanFin fin) {
+    scan_u32_body<true>(flag, rank, n, state, ticket, total_out, fin);
+}
 static size_t scan_scratch_bytes(long n) { return ((size_t)((n + SCAN_TILE - 1) / SCAN_TILE) + 2) * 8; }
 // out = exclusive prefix sums of in[0..n), *total_dev = their total; scratch from scan_scratch_bytes(n)
 // (scratch_is_zero: the caller's own kernel has zeroed the scratch -- k_ht_init does it with the table -- so that the chain of a
@@ -118,6 +146,15 @@ static int scan_u32(const uint32_t *in, uint32_t *out, long n, void *scratch, ui
     if (!scratch_is_zero) HIPCHK(hipMemsetAsync(scratch, 0, scan_scratch_bytes(n), st));
     hipLaunchKernelGGL(k_scan_u32, dim3((unsigned)tiles), dim3(SCAN_T), 0, st, in, out, n, (unsigned long long *)scratch,
                        (uint32_t *)((unsigned long long *)scratch + tiles), total_dev);
+    HIPCHK(hipGetLastError());
+    return HGX_OK;
+}
+// class ids in first-seen order from the first-row flags (0 / 1) of the n rows, first row and count of every class with them;
+// the scratch has been zeroed by the caller's own kernel (k_ht_init / k_sig_keys)
+static int scan_classes(const uint32_t *flag, uint32_t *rank, long n, void *scratch, uint32_t *total_dev, const ScanFin &fin, hipStream_t st) {
+    const long tiles = (n + SCAN_TILE - 1) / SCAN_TILE;
+    hipLaunchKernelGGL(k_scan_classes, dim3((unsigned)tiles), dim3(SCAN_T), 0, st, flag, rank, n, (unsigned long long *)scratch,
+                       (uint32_t *)((unsigned long long *)scratch + tiles), total_dev, fin);
     HIPCHK(hipGetLastError());
     return HGX_OK;
 }
@@ -135,13 +172,14 @@ int hgx_scan_u32_dev(const uint32_t *in, uint32_t *out, long n, void *scratch, u
 // ------------------------------------------------------------------------------------------------
 // Hash-table form of the dedup (default).  Sorting 500 k 64-bit keys costs ~25 short library launches; the dict
 // semantics the reference needs -- {class: count} in first-seen order -- fall out of one insert pass:
-//   k_ht_insert   a workgroup of 1024 rows first merges equal keys in an LDS table (min row, summed weight; the hot
-//                 classes hold a fifth of all rows, so un-merged global atomics would serialise on a few addresses),
-//                 then one global insert (CAS on the key, min on the first row, add on the count) per distinct key;
-//   k_ht_mark     flags the first row of every class; an exclusive scan of the flags over the ROWS is the class id in
-//                 first-seen order (= Python dict order);
-//   k_ht_finalize class id -> first row, count;   k_verify_ht: exact check of every row against its class' first row
-//                 (streaming, original order);   k_ht_gather: class rows.
+//   k_ht_insert   a workgroup of 1024 rows first merges equal keys -- inside a wavefront, then in an LDS table (min row, summed
+//                 weight; the hot classes hold a fifth of all rows, so un-merged global atomics would serialise on a few
+//                 addresses) -- then one global insert (CAS on the key, min on the first row, add on the count) per distinct key;
+//   k_verify_ht   exact check of every row against its class' first row (streaming, original order); it also flags the first
+//                 row of every class: an exclusive scan of the flags over the ROWS is the class id in first-seen order (= Python
+//                 dict order);
+//   k_scan_classes  that scan, which also writes class id -> first row, count;   k_ht_gather: class rows.
+//   (k_ht_mark / k_ht_finalize do the flags and the first rows / counts by a pass over the table: after a key collision only)
 // min / add / CAS are order independent, so the result is deterministic.
 // ------------------------------------------------------------------------------------------------
 #define HT_NONE 0xFFFFFFFFu
@@ -158,50 +196,142 @@ __device__ __forceinline__ uint32_t ht_global_insert(unsigned long long *keys, u
     }
 }
 
-template <int BS>
+__device__ __forceinline__ uint64_t readlane_u64(uint64_t v, int l) {      // l: the same in every lane
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)v, l), hi = (uint32_t)__builtin_amdgcn_readlane((int)(v >> 32), l);
+    return ((uint64_t)hi << 32) | lo;
+}
+__device__ __forceinline__ uint64_t shfl_u64(uint64_t v, int l) {
+    const uint32_t lo = __shfl((uint32_t)v, l, 64), hi = __shfl((uint32_t)(v >> 32), l, 64);
+    return ((uint64_t)hi << 32) | lo;
+}
+
+// A workgroup of BS lanes takes BS * RPT consecutive rows (row = base + r * BS + lane: a wavefront holds 64 consecutive rows per
+// round r).  The global table receives three atomics (CAS, min, add) per DISTINCT key of a workgroup, scattered over the table,
+// and the kernel's time is their number: equal keys of different workgroups are paid once per workgroup
+// and meet at one address -- hence 1024 rows per workgroup at every call site, on 4 wavefronts (RPT = 4) where the insert runs
+// beside kernels that fill the chip (a 16-wave workgroup waits for a whole CU's worth of wave slots there).
+//   1. wavefront: lanes with equal keys elect the lowest lane (= the smallest row) as leader, which carries the summed weight;
+//      only lanes that found their key at another lane (a 256-bucket byte table per wavefront: write lane, read winner, compare
+//      keys) enter the match-any loop (readlane of the key, ballot of equality, retire), one trip per REPEATED key of the
+//      wavefront -- a loop over all 64 lanes would cost more than the LDS atomics it saves when most keys are distinct;
+//   2. leaders merge in the workgroup's LDS table (CAS on the key, min row, summed weight);
+//   3. the distinct keys of the workgroup go to the global table level by level -- every lane owns 2 * RPT LDS slots and issues
+//      their probes together, then the CASes that empty-looking slots need, then the looks at the first row, then min / add --
+//      so a lane has up to 2 * RPT round trips in flight instead of one chain per slot.
+// Sums are integer adds, first rows a min: the result does not depend on the order of anything.
+template <int BS, int RPT>
 __global__ __launch_bounds__(BS) void k_ht_insert(const uint64_t *__restrict__ hash, const int64_t *__restrict__ weight, long n,
                                                     unsigned long long *__restrict__ keys, uint32_t *__restrict__ first,
                                                     unsigned long long *__restrict__ cnt, uint32_t tmask,
                                                     uint32_t *__restrict__ slot_of) {
-    constexpr int SLOTS = 2 * BS;
+    constexpr int ROWS = BS * RPT, SLOTS = 2 * ROWS, SPT = SLOTS / BS;
     __shared__ unsigned long long lkey[SLOTS], lcnt[SLOTS];
-    __shared__ uint32_t lmin[SLOTS], lg[SLOTS];
-    const int tid = threadIdx.x;
+    __shared__ uint32_t lmin[SLOTS];             // smallest row of the key; after the global insert: the key's global slot
+    __shared__ uint8_t wtab[BS / 64][256];       // per wavefront: bucket -> some lane whose key falls into it (never cleared: a
+                                                 // lane reads only the bucket it has just written)
+    const int tid = threadIdx.x, lane = tid & 63;
     for (int s = tid; s < SLOTS; s += BS) { lkey[s] = HGX_EMPTY_KEY; lcnt[s] = 0; lmin[s] = HT_NONE; }
-    __syncthreads();
-    const long i = (long)blockIdx.x * BS + tid;
-    const uint64_t key = i < n ? hash[i] : HGX_EMPTY_KEY;
-    const bool valid = key != HGX_EMPTY_KEY;
-    uint32_t ls = 0;
-    if (valid) {
-        ls = (uint32_t)(key >> 40) & (SLOTS - 1);
-        for (;;) {
-            const unsigned long long old = atomicCAS(&lkey[ls], (unsigned long long)HGX_EMPTY_KEY, (unsigned long long)key);
-            if (old == HGX_EMPTY_KEY || old == key) break;
-            ls = (ls + 1) & (SLOTS - 1);
-        }
-        atomicMin(&lmin[ls], (uint32_t)i);
-        atomicAdd(&lcnt[ls], (unsigned long long)(weight ? weight[i] : 1));
+    const long base = (long)blockIdx.x * ROWS;
+    uint64_t key[RPT];
+    unsigned long long w[RPT];
+#pragma unroll
+    for (int r = 0; r < RPT; ++r) {
+        const long i = base + (long)r * BS + tid;
+        key[r] = i < n ? hash[i] : HGX_EMPTY_KEY;
+        w[r] = weight && i < n ? (unsigned long long)weight[i] : 1ull;
     }
     __syncthreads();
-    for (int s = tid; s < SLOTS; s += BS) {
-        if (lkey[s] != HGX_EMPTY_KEY) {
-            const uint32_t g = ht_global_insert(keys, tmask, lkey[s]);
+    volatile uint8_t *wt = wtab[tid >> 6];
+    uint32_t ls[RPT];
+#pragma unroll
+    for (int r = 0; r < RPT; ++r) {
+        const bool valid = key[r] != HGX_EMPTY_KEY;
+        const uint32_t bucket = (uint32_t)(key[r] >> 24) & 255u;
+        if (valid) wt[bucket] = (uint8_t)lane;
+        __builtin_amdgcn_wave_barrier();         // (LDS operations of one wavefront complete in order: the read below sees the stores)
+        const int win = valid ? (int)wt[bucket] : lane;
+        const bool dup = valid && win != lane && shfl_u64(key[r], win) == key[r];
+        int leader = lane;
+        unsigned long long wsum = w[r];
+        for (uint64_t pend = __ballot(dup); pend;) {
+            const uint64_t k = readlane_u64(key[r], __ffsll((unsigned long long)pend) - 1);
+            const bool eq = valid && key[r] == k;
+            const uint64_t em = __ballot(eq);
+            const unsigned long long s = weight ? wave_sum_u64(eq ? w[r] : 0ull) : (unsigned long long)__popcll(em);
+            if (eq) { leader = __ffsll((unsigned long long)em) - 1; wsum = s; }
+            pend &= ~em;
+        }
+        uint32_t s = 0;
+        if (valid && leader == lane) {
+            s = (uint32_t)(key[r] >> 40) & (SLOTS - 1);
+            for (;;) {
+                const unsigned long long old = atomicCAS(&lkey[s], (unsigned long long)HGX_EMPTY_KEY, (unsigned long long)key[r]);
+                if (old == HGX_EMPTY_KEY || old == key[r]) break;
+                s = (s + 1) & (SLOTS - 1);
+            }
+            atomicMin(&lmin[s], (uint32_t)(base + (long)r * BS + tid));
+            atomicAdd(&lcnt[s], wsum);
+        }
+        ls[r] = __shfl(s, leader, 64);
+    }
+    __syncthreads();
+    // A slot never changes once it holds a key: a plain look settles most inserts -- the hot keys are in the table after the
+    // first few workgroups -- and only an empty-looking slot costs a CAS.
+    uint64_t k[SPT];
+    uint32_t h[SPT];
+    bool any_key = false;
+#pragma unroll
+    for (int j = 0; j < SPT; ++j) {
+        k[j] = lkey[j * BS + tid];
+        h[j] = (uint32_t)k[j] & tmask;
+        any_key = any_key || k[j] != HGX_EMPTY_KEY;
+    }
+    uint32_t todo = 0;                           // bit j: slot j still probing
+#pragma unroll
+    for (int j = 0; j < SPT; ++j) todo |= (k[j] != HGX_EMPTY_KEY ? 1u : 0u) << j;
+    while (todo) {
+        unsigned long long old[SPT];
+#pragma unroll
+        for (int j = 0; j < SPT; ++j)
+            old[j] = (todo >> j) & 1u ? __hip_atomic_load(&keys[h[j]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
+#pragma unroll
+        for (int j = 0; j < SPT; ++j)
+            if (((todo >> j) & 1u) && old[j] == HGX_EMPTY_KEY)
+                old[j] = atomicCAS(&keys[h[j]], (unsigned long long)HGX_EMPTY_KEY, (unsigned long long)k[j]);
+#pragma unroll
+        for (int j = 0; j < SPT; ++j) {
+            if (!((todo >> j) & 1u)) continue;
+            if (old[j] == HGX_EMPTY_KEY || old[j] == k[j]) todo &= ~(1u << j);
+            else h[j] = (h[j] + 1) & tmask;
+        }
+    }
+    if (any_key) {
+        uint32_t f[SPT];
+#pragma unroll
+        for (int j = 0; j < SPT; ++j)
+            f[j] = k[j] != HGX_EMPTY_KEY ? __hip_atomic_load(&first[h[j]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+#pragma unroll
+        for (int j = 0; j < SPT; ++j) {
+            if (k[j] == HGX_EMPTY_KEY) continue;
+            const int s = j * BS + tid;
             // (the first row only ever goes down: a value already below mine needs no atomic; a stale, larger one merely costs it)
-            if (__hip_atomic_load(&first[g], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > lmin[s]) atomicMin(&first[g], lmin[s]);
-            atomicAdd(&cnt[g], lcnt[s]);
-            lg[s] = g;
+            if (f[j] > lmin[s]) atomicMin(&first[h[j]], lmin[s]);
+            atomicAdd(&cnt[h[j]], lcnt[s]);
+            lmin[s] = h[j];
         }
     }
     __syncthreads();
-    if (i < n) slot_of[i] = valid ? lg[ls] : HT_NONE;
+#pragma unroll
+    for (int r = 0; r < RPT; ++r) {
+        const long i = base + (long)r * BS + tid;
+        if (i < n) slot_of[i] = key[r] != HGX_EMPTY_KEY ? lmin[ls[r]] : HT_NONE;
+    }
 }
+// (the first-row flags need no clearing: k_verify_ht / k_sig_verify write one per row)
 __global__ void k_ht_init(unsigned long long *__restrict__ keys, uint32_t *__restrict__ first, unsigned long long *__restrict__ cnt,
-                          long T, uint32_t *__restrict__ flag, long n, uint32_t *__restrict__ meta,
-                          unsigned long long *__restrict__ scan_state, long n_state) {
+                          long T, uint32_t *__restrict__ meta, unsigned long long *__restrict__ scan_state, long n_state) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < T) { keys[i] = HGX_EMPTY_KEY; first[i] = HT_NONE; cnt[i] = 0; }
-    if (i < n) flag[i] = 0;
     if (i < 4) meta[i] = 0;
     if (i < n_state) scan_state[i] = 0;                 // (the tile states + ticket of the scan that numbers the classes)
 }
@@ -223,6 +353,7 @@ __global__ void k_ht_finalize(const unsigned long long *__restrict__ keys, const
 // row per wave the kernel is a chain of three memory round trips per row and runs at a quarter of the bandwidth.
 __global__ __launch_bounds__(256) void k_verify_ht(const uint64_t *__restrict__ rows, int w64, const uint64_t *__restrict__ mask,
                                                    const uint32_t *__restrict__ slot_of, const uint32_t *__restrict__ first, long n,
+                                                   uint32_t *__restrict__ is_first,
                                                    int *__restrict__ bad, uint32_t *__restrict__ bad_rows = nullptr,
                                                    uint32_t *__restrict__ n_bad = nullptr, const uint32_t *__restrict__ seg = nullptr) {
     // seg (many tasks in one dedup): rows of different segments never share a class -- their keys are salted with the segment,
@@ -236,6 +367,14 @@ __global__ __launch_bounds__(256) void k_verify_ht(const uint64_t *__restrict__ 
     for (int k = 0; k < R; ++k) sl[k] = r0 + k < n ? slot_of[r0 + k] : HT_NONE;
 #pragma unroll
     for (int k = 0; k < R; ++k) h[k] = sl[k] != HT_NONE ? first[sl[k]] : 0u;
+    // the first-row flag of every row (what k_ht_mark made of a pass over the table): the scan over them numbers the classes
+    if (lane < R && r0 + lane < n) {
+        uint32_t fl = 0;
+#pragma unroll
+        for (int k = 0; k < R; ++k)
+            if (lane == k) fl = sl[k] != HT_NONE && h[k] == (uint32_t)(r0 + k) ? 1u : 0u;
+        is_first[r0 + lane] = fl;
+    }
     typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
     const u64x2 *m = (const u64x2 *)mask;
     bool diff = false;
@@ -368,9 +507,9 @@ __global__ void k_salt_keys(const uint64_t *__restrict__ in, const uint32_t *__r
 }
 
 static hgx_classes *new_classes(int32_t a_pad);
-// small_blocks: insert with 256-row workgroups instead of 1024-row ones.  Alone the large ones win (4x fewer global atomics
-// on the hot classes); beside a kernel that fills the chip (hgx_level_classes runs next to the gene level's per-pair rows)
-// a 16-wave workgroup with 48 KB of LDS waits for a whole CU's worth of slots and the insert takes 3-4x longer.
+// small_blocks: insert with 4-wave workgroups (4 rows per lane) instead of 16-wave ones; both take 1024 rows, so the hot classes
+// receive the same number of global adds.  Beside a kernel that fills the chip (hgx_level_classes runs next to the gene level's
+// per-pair rows) a 16-wave workgroup waits for a whole CU's worth of wave slots and the insert takes 3-4x longer.
 static int dedup_hash_table(hgx_classes *cl, const uint64_t *rows, const uint64_t *keys_in, const int64_t *row_weight, long n,
                             int w64, const uint64_t *and_mask, hipStream_t st, bool small_blocks = false,
                             const uint32_t *seg = nullptr) {
@@ -386,7 +525,7 @@ static int dedup_hash_table(hgx_classes *cl, const uint64_t *rows, const uint64_
     ALLOC(b_slot, (size_t)n * 4); ALLOC(b_flag, (size_t)n * 4); ALLOC(b_rank, (size_t)n * 4); ALLOC(b_meta, 16);
     ALLOC(b_bad, (size_t)n * 4);
     ALLOC(b_tmp, scan_scratch_bytes(n));
-    // first rows of the classes -> flags -> class ids in first-seen order (single-pass scan), class count in meta[1]
+    // (after the re-keying rounds of a collision) first rows of the classes -> flags -> class ids in first-seen order, class count in meta[1]
     auto number_classes = [&](bool scratch_is_zero) -> int {
         hipLaunchKernelGGL(k_ht_mark, dim3(nblk(T, 256)), dim3(256), 0, st, b_keys.as<unsigned long long>(), b_first.as<uint32_t>(), T,
                            b_flag.as<uint32_t>());
@@ -423,20 +562,30 @@ static int dedup_hash_table(hgx_classes *cl, const uint64_t *rows, const uint64_
         { int rc_ = hgx_sync(st); if (rc_) return rc_; }
         return HGX_OK;
     };
-    // one launch instead of five memsets: table = empty, flags = 0, meta = {collision flag, number of classes} = 0
-    hipLaunchKernelGGL(k_ht_init, dim3(nblk(std::max(T, n), 256)), dim3(256), 0, st, b_keys.as<unsigned long long>(),
-                       b_first.as<uint32_t>(), b_cnt.as<unsigned long long>(), T, b_flag.as<uint32_t>(), n, b_meta.as<uint32_t>(),
+    // class id -> first row, count: written by the scan that numbers the classes, so sized for the worst case before the count is known
+    cl->d_count = (decltype(cl->d_count))hgx_pool_alloc((size_t)n * 8);
+    cl->d_first_row = (decltype(cl->d_first_row))hgx_pool_alloc((size_t)n * 8);
+    if (!cl->d_count || !cl->d_first_row) { hgx_set_error("device allocation failed"); return HGX_ENOMEM; }
+    // one launch instead of four memsets: table = empty, meta = {collision flag, number of classes} = 0, scan state = 0.
+    // Then four dispatches up to the class count: insert, exact check (+ first-row flags), scan (+ first row and count per class).
+    hipLaunchKernelGGL(k_ht_init, dim3(nblk(T, 256)), dim3(256), 0, st, b_keys.as<unsigned long long>(),
+                       b_first.as<uint32_t>(), b_cnt.as<unsigned long long>(), T, b_meta.as<uint32_t>(),
                        b_tmp.as<unsigned long long>(), (long)(scan_scratch_bytes(n) / 8));
     if (small_blocks)
-        hipLaunchKernelGGL(k_ht_insert<256>, dim3(nblk(n, 256)), dim3(256), 0, st, keys_in, row_weight, n, b_keys.as<unsigned long long>(),
+        hipLaunchKernelGGL((k_ht_insert<256, 4>), dim3(nblk(n, 1024)), dim3(256), 0, st, keys_in, row_weight, n, b_keys.as<unsigned long long>(),
                            b_first.as<uint32_t>(), b_cnt.as<unsigned long long>(), (uint32_t)(T - 1), b_slot.as<uint32_t>());
     else
-        hipLaunchKernelGGL(k_ht_insert<1024>, dim3(nblk(n, 1024)), dim3(1024), 0, st, keys_in, row_weight, n, b_keys.as<unsigned long long>(),
+        hipLaunchKernelGGL((k_ht_insert<1024, 1>), dim3(nblk(n, 1024)), dim3(1024), 0, st, keys_in, row_weight, n, b_keys.as<unsigned long long>(),
                            b_first.as<uint32_t>(), b_cnt.as<unsigned long long>(), (uint32_t)(T - 1), b_slot.as<uint32_t>());
-    { int rc_ = number_classes(true); if (rc_) return rc_; }
-    // the exact check does not need the class count: queue it before the D2H that sizes the output
     hipLaunchKernelGGL(k_verify_ht, dim3(nblk((n + 3) / 4, 4)), dim3(256), 0, st, rows, w64, and_mask, b_slot.as<uint32_t>(),
-                       b_first.as<uint32_t>(), n, b_meta.as<int>(), b_bad.as<uint32_t>(), b_meta.as<uint32_t>() + 2, seg);
+                       b_first.as<uint32_t>(), n, b_flag.as<uint32_t>(), b_meta.as<int>(), b_bad.as<uint32_t>(), b_meta.as<uint32_t>() + 2, seg);
+    { int rc_ = scan_classes(b_flag.as<uint32_t>(), b_rank.as<uint32_t>(), n, b_tmp.p, b_meta.as<uint32_t>() + 1,
+                             ScanFin{b_slot.as<uint32_t>(), b_cnt.as<unsigned long long>(), cl->d_first_row, cl->d_count}, st); if (rc_) return rc_; }
+    // after collisions (forged keys only) the table is final only after the re-keying rounds: first rows / counts again, per slot
+    auto finalize_again = [&]() {
+        hipLaunchKernelGGL(k_ht_finalize, dim3(nblk(T, 256)), dim3(256), 0, st, b_keys.as<unsigned long long>(), b_first.as<uint32_t>(),
+                           b_cnt.as<unsigned long long>(), T, b_rank.as<uint32_t>(), cl->d_first_row, cl->d_count);
+    };
     // Small inputs (the hand-off dedup: a few thousand gene classes) size the output for the worst case and finish in
     // ONE host round trip; large ones first learn the class count (the worst case would be the whole input again).
     const bool one_trip = n <= 65536;
@@ -445,16 +594,12 @@ static int dedup_hash_table(hgx_classes *cl, const uint64_t *rows, const uint64_
         { int rc_ = hgx_d2h(meta, b_meta.p, 16, st); if (rc_) return rc_; }
         { int rc_ = hgx_sync(st); if (rc_) return rc_; }
         HIPCHK(hipGetLastError());
-        if (meta[2]) { int rc_ = resolve_collisions(); if (rc_) return rc_; }
+        if (meta[2]) { int rc_ = resolve_collisions(); if (rc_) return rc_; finalize_again(); }
         n_alloc = (int)meta[1];
         if (n_alloc == 0) return HGX_OK;
     }
     cl->d_bits = (decltype(cl->d_bits))hgx_pool_alloc((size_t)n_alloc * w64 * 8);
-    cl->d_count = (decltype(cl->d_count))hgx_pool_alloc((size_t)n_alloc * 8);
-    cl->d_first_row = (decltype(cl->d_first_row))hgx_pool_alloc((size_t)n_alloc * 8);
-    if (!cl->d_bits || !cl->d_count || !cl->d_first_row) { hgx_set_error("device allocation failed"); return HGX_ENOMEM; }
-    hipLaunchKernelGGL(k_ht_finalize, dim3(nblk(T, 256)), dim3(256), 0, st, b_keys.as<unsigned long long>(), b_first.as<uint32_t>(),
-                       b_cnt.as<unsigned long long>(), T, b_rank.as<uint32_t>(), cl->d_first_row, cl->d_count);
+    if (!cl->d_bits) { hgx_set_error("device allocation failed"); return HGX_ENOMEM; }
     if (one_trip)      // gather per table slot (class id = rank of the slot's first row): needs no host-side class count
         hipLaunchKernelGGL(k_ht_gather_slots, dim3(nblk(T, 4)), dim3(256), 0, st, rows, w64, and_mask, b_keys.as<unsigned long long>(),
                            b_first.as<uint32_t>(), b_rank.as<uint32_t>(), T, cl->d_bits);
@@ -466,15 +611,14 @@ static int dedup_hash_table(hgx_classes *cl, const uint64_t *rows, const uint64_
         { int rc_ = hgx_sync(st); if (rc_) return rc_; }
         if (meta[2]) {      // collided rows: after re-keying, first rows / counts / class rows are produced again
             { int rc_ = resolve_collisions(); if (rc_) return rc_; }
-            hipLaunchKernelGGL(k_ht_finalize, dim3(nblk(T, 256)), dim3(256), 0, st, b_keys.as<unsigned long long>(), b_first.as<uint32_t>(),
-                               b_cnt.as<unsigned long long>(), T, b_rank.as<uint32_t>(), cl->d_first_row, cl->d_count);
+            finalize_again();
             hipLaunchKernelGGL(k_ht_gather_slots, dim3(nblk(T, 4)), dim3(256), 0, st, rows, w64, and_mask, b_keys.as<unsigned long long>(),
                                b_first.as<uint32_t>(), b_rank.as<uint32_t>(), T, cl->d_bits);
             HIPCHK(hipGetLastError());
             { int rc_ = hgx_sync(st); if (rc_) return rc_; }
         }
     } else {
-        // large input: class count and collision flag are known since the first round trip; the finalize / gather kernels are
+        // large input: class count and collision flag are known since the first round trip; the gather kernel is
         // queued, and the scratch they read stays with the class set (freed with it) so that the caller's next launches
         // follow without another host sync
         cl->made_on = st;
@@ -528,15 +672,14 @@ static int dedup_classes_impl(hgx_classes **out, const uint64_t *rows, const uin
 // Same result as hgx_pair_classes + hgx_dedup_classes (classes in first-seen order, counts, first pair), with the
 // 896-byte-per-pair row traffic divided by the repeat factor.
 // ------------------------------------------------------------------------------------------------
-// (the launch also empties the hash table, the flags, the meta words and the scan state of the grouping that follows -- what
+// (the launch also empties the hash table, the meta words and the scan state of the grouping that follows -- what
 // k_ht_init does for a dedup: one dispatch less in front of the insert)
-struct HtInit { unsigned long long *keys; uint32_t *first; unsigned long long *cnt; long T; uint32_t *flag; uint32_t *meta;
+struct HtInit { unsigned long long *keys; uint32_t *first; unsigned long long *cnt; long T; uint32_t *meta;
                 unsigned long long *scan_state; long n_state; };
 __global__ void k_sig_keys(const int32_t *__restrict__ pair_off, const uint32_t *__restrict__ refs, int n_pairs, uint32_t level,
                            uint64_t *__restrict__ key, const uint32_t *__restrict__ seg, HtInit init) {
     const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
     for (long s = p; s < init.T; s += (long)gridDim.x * blockDim.x) { init.keys[s] = HGX_EMPTY_KEY; init.first[s] = HT_NONE; init.cnt[s] = 0; }
-    if (p < n_pairs) init.flag[p] = 0;
     if (p < 4) init.meta[p] = 0;
     if (p < init.n_state) init.scan_state[p] = 0;
     if (p >= n_pairs) return;
@@ -552,13 +695,15 @@ __global__ void k_sig_keys(const int32_t *__restrict__ pair_off, const uint32_t 
     if (seg) h = mix64(h ^ (0xd6e8feb86659fd93ull * (uint64_t)(seg[p] + 1u)));      // pairs of different tasks never share a group
     key[p] = h == HGX_EMPTY_KEY ? HGX_EMPTY_KEY - 1 : h;       // never the "dropped row" key: a pair without refs has a class (Q4)
 }
-// exact check of the grouping: every pair's ref list equals the list of its group's first pair
+// exact check of the grouping: every pair's ref list equals the list of its group's first pair; and the first-pair flag of
+// every pair (the scan over them numbers the groups in first-seen order)
 __global__ void k_sig_verify(const int32_t *__restrict__ pair_off, const uint32_t *__restrict__ refs, int n_pairs, uint32_t level,
-                             const uint32_t *__restrict__ slot_of, const uint32_t *__restrict__ first, int *__restrict__ bad,
-                             const uint32_t *__restrict__ seg = nullptr) {
+                             const uint32_t *__restrict__ slot_of, const uint32_t *__restrict__ first, uint32_t *__restrict__ is_first,
+                             int *__restrict__ bad, const uint32_t *__restrict__ seg = nullptr) {
     const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n_pairs) return;
     const uint32_t f = first[slot_of[p]];
+    is_first[p] = f == (uint32_t)p ? 1u : 0u;
     if (f == (uint32_t)p) return;
     if (seg && seg[p] != seg[f]) { atomicOr(bad, 1); return; }
     int a = pair_off[p], b = pair_off[f];
@@ -645,21 +790,19 @@ static int group_pairs_impl(hgx_groups **out, const int32_t *pair_off, const uin
     ALLOC(b_keys, (size_t)T * 8); ALLOC(b_first, (size_t)T * 4); ALLOC(b_cnt, (size_t)T * 8);
     ALLOC(b_slot, (size_t)n * 4); ALLOC(b_flag, (size_t)n * 4); ALLOC(b_rank, (size_t)n * 4); ALLOC(b_meta, 16);
     ALLOC(b_tmp, scan_scratch_bytes(n));
-    const HtInit init{b_keys.as<unsigned long long>(), b_first.as<uint32_t>(), b_cnt.as<unsigned long long>(), T, b_flag.as<uint32_t>(),
+    const HtInit init{b_keys.as<unsigned long long>(), b_first.as<uint32_t>(), b_cnt.as<unsigned long long>(), T,
                       b_meta.as<uint32_t>(), b_tmp.as<unsigned long long>(), (long)(scan_scratch_bytes(n) / 8)};
+    // four dispatches: keys (+ table clear), insert, exact check (+ first-pair flags), scan (+ first pair and size of every group)
     hipLaunchKernelGGL(k_sig_keys, dim3(nblk(std::max<long>(n, 1024), 256)), dim3(256), 0, st, pair_off, refs, n_pairs, (uint32_t)level, b_key.as<uint64_t>(),
                        seg, init);
-    hipLaunchKernelGGL(k_ht_insert<256>, dim3(nblk(n, 256)), dim3(256), 0, st, b_key.as<uint64_t>(), (const int64_t *)nullptr, n,
+    hipLaunchKernelGGL((k_ht_insert<256, 4>), dim3(nblk(n, 1024)), dim3(256), 0, st, b_key.as<uint64_t>(), (const int64_t *)nullptr, n,
                        b_keys.as<unsigned long long>(), b_first.as<uint32_t>(), b_cnt.as<unsigned long long>(), (uint32_t)(T - 1),
                        b_slot.as<uint32_t>());
-    hipLaunchKernelGGL(k_ht_mark, dim3(nblk(T, 256)), dim3(256), 0, st, b_keys.as<unsigned long long>(), b_first.as<uint32_t>(), T,
-                       b_flag.as<uint32_t>());
-    { int rc_ = scan_u32(b_flag.as<uint32_t>(), b_rank.as<uint32_t>(), n, b_tmp.p, b_meta.as<uint32_t>() + 1, st, true); if (rc_) return rc_; }
     hipLaunchKernelGGL(k_sig_verify, dim3(nblk(n, 256)), dim3(256), 0, st, pair_off, refs, n_pairs, (uint32_t)level,
-                       b_slot.as<uint32_t>(), b_first.as<uint32_t>(), b_meta.as<int>(), seg);
+                       b_slot.as<uint32_t>(), b_first.as<uint32_t>(), b_flag.as<uint32_t>(), b_meta.as<int>(), seg);
     // group id (first-seen order) -> first pair, group size; sized for the worst case: no host-side group count needed yet
-    hipLaunchKernelGGL(k_ht_finalize, dim3(nblk(T, 256)), dim3(256), 0, st, b_keys.as<unsigned long long>(), b_first.as<uint32_t>(),
-                       b_cnt.as<unsigned long long>(), T, b_rank.as<uint32_t>(), g->d_first, g->d_count);
+    { int rc_ = scan_classes(b_flag.as<uint32_t>(), b_rank.as<uint32_t>(), n, b_tmp.p, b_meta.as<uint32_t>() + 1,
+                             ScanFin{b_slot.as<uint32_t>(), b_cnt.as<unsigned long long>(), g->d_first, g->d_count}, st); if (rc_) return rc_; }
     HIPCHK(hipGetLastError());
     { int rc_ = hgx_d2h(g->meta, b_meta.p, 16, st); if (rc_) return rc_; }
     // everything is queued; the scratch stays with the group set until groups_finish

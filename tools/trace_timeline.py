@@ -2,8 +2,8 @@
 import csv, sys, collections
 rows = list(csv.DictReader(open(sys.argv[1])))
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-# steps start with k_piece_compat_tiled
-starts = [i for i, r in enumerate(rows) if "k_piece_compat_tiled" in r["Kernel_Name"]]
+# steps start with the piece x allele kernel (k_piece_compat_pat; k_piece_compat_tiled in older traces)
+starts = [i for i, r in enumerate(rows) if "k_piece_compat" in r["Kernel_Name"]]
 i0 = starts[-1]
 t0 = int(rows[i0]["Start_Timestamp"])
 last_end = {}
