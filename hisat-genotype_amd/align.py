@@ -2,8 +2,9 @@
 variants in `Vars` -- end to end, at most `max_edits` unknown mismatches, known variants free -- and written as SAM text in the
 dialect the front end consumes (NM, MD, Zs, NH, YT as simulate._truth_record renders them).
 
-It is NOT HISAT2 and its output is not compared with HISAT2's anywhere: no whole-genome index, no novel indels, no soft clips, no
-secondary records; mates placed independently unless pair="aware" (tests/align_pair_ref.py).  The rules are stated in plain Python in tests/align_ref.py; the kernels
+It is NOT HISAT2 and its output is not compared with HISAT2's anywhere: no whole-genome index, no novel indels, no secondary
+records; mates placed independently unless pair="aware" (tests/align_pair_ref.py); soft clips only with clip=N, and only for a read
+that has no end-to-end alignment (tests/align_clip_ref.py).  The rules are stated in plain Python in tests/align_ref.py; the kernels
 (csrc/hgx_align.hip) and the host route (csrc/hgx_align_host.cpp) run one shared core (csrc/hgx_align_core.hpp, and csrc/hgx_align_states.hpp for the search over states).
 """
 import ctypes as C
@@ -14,11 +15,13 @@ _TYPES = {"insertion": capi.VAR_INSERTION, "single": capi.VAR_SINGLE, "deletion"
 ROUTES = {"auto": 0, "host": 1, "device": 2}
 SEARCHES = {"ways": 0, "states": 1, "states_all": 2}
 PAIRS = {"independent": 0, "aware": 1}
+NAMED_CLIP = 32                      # the clip budget of the aligner name "hgx.clip"
+CLIP_MAX, CLIP_MAX_EDITS = 255, 4    # HGX_ALN_CLIP_MAX, HGX_ALN_CLIP_EDITS of csrc/hgx_align_core.hpp
 
 
 class AlignOpts(C.Structure):
     _fields_ = [("max_edits", C.c_int32), ("max_fragment", C.c_int32), ("fastq", C.c_int32), ("route", C.c_int32),
-                ("search", C.c_int32), ("pair", C.c_int32)]
+                ("search", C.c_int32), ("pair", C.c_int32), ("clip", C.c_int32)]
 
 
 class AlignIndex:
@@ -45,17 +48,22 @@ class AlignIndex:
             (C.c_int32 * len(off))(*off), (C.c_int32 * max(n, 1))(*vtype), (C.c_int32 * max(n, 1))(*vpos),
             (C.c_char_p * max(n, 1))(*vdata), (C.c_char_p * max(n, 1))(*vid)))
 
-    def align(self, reads, max_edits=2, max_fragment=1000, fastq=None, route="auto", search="ways", pair="independent"):
+    def align(self, reads, max_edits=2, max_fragment=1000, fastq=None, route="auto", search="ways", pair="independent",
+              clip=0):
         """SAM text (bytes) for `reads` = one or two FASTA / FASTQ[.gz] paths (str) or in-memory texts (bytes).  `search`: "ways"
         (per anchor, the ways through the known indels), "states" (reads that pass the kernels' anchor slots, stack or step limit
         -- on the host route: every read -- are searched over (read base, backbone position) states instead), "states_all" (every
         read is); an int is passed through as hgx_align_opts.search.  The bytes are the same.  `pair`: "independent" (each mate's
         smallest alignment, as before) or "aware" (where a combination of the mates' candidates is concordant, both records come
         from the smallest such combination and NH counts the pair's placements: tests/align_pair_ref.py); an int is passed
-        through as hgx_align_opts.pair.  "aware" needs search="ways"."""
+        through as hgx_align_opts.pair.  "aware" needs search="ways".  `clip`: 0 (end to end only, every byte as before) or N <= 255:
+        a read WITHOUT an end-to-end alignment may be written with up to N bases soft-clipped in total (an overhang over a backbone
+        end, a tail that does not match), by the order (clipped bases, then the usual key) of tests/align_clip_ref.py; a read that
+        aligns end to end is written as with 0, except for the mate fields of a record whose mate is aligned only now.  Needs
+        search="ways", pair="independent" and max_edits <= 4."""
         assert len(reads) in (1, 2)
         opts = AlignOpts(int(max_edits), int(max_fragment), -1 if fastq is None else int(bool(fastq)), ROUTES[route],
-                         search if isinstance(search, int) else SEARCHES[search], pair if isinstance(pair, int) else PAIRS[pair])
+                         search if isinstance(search, int) else SEARCHES[search], pair if isinstance(pair, int) else PAIRS[pair], int(clip))
         out_p, n = C.c_void_p(), C.c_size_t(0)
         if all(isinstance(r, str) for r in reads):
             paths = (C.c_char_p * len(reads))(*[r.encode() for r in reads])
@@ -88,7 +96,8 @@ def align_last():
     last align(): route 2 = the kernels, 0 = the host route (decline says why: HGX_ALN_DECLINE_* of csrc/hgx_align_core.hpp and
     hgx_align_states.hpp); states_* = the reads, anchors and table cells the states search took on that route; pairs_searched /
     pairs_placed / pairs_changed (pair="aware") = pairs with candidates on both mates, with a concordant combination, and with a
-    record that differs from the independent one in alignment or NH."""
+    record that differs from the independent one in alignment or NH; clip_searched / clip_clipped / clip_bases (clip=N) = reads
+    without an end-to-end alignment that the clip tier searched, reads written with a clip, bases clipped."""
     route, dec = C.c_int32(0), C.c_int32(0)
     reads, aligned, conc = C.c_int64(0), C.c_int64(0), C.c_int64(0)
     capi.check(capi.lib().hgx_align_last(C.byref(route), C.byref(reads), C.byref(aligned), C.byref(conc), C.byref(dec)))
@@ -96,9 +105,18 @@ def align_last():
     capi.check(capi.lib().hgx_align_last_states(C.byref(sr), C.byref(sa), C.byref(sc)))
     ps, pp, pc = C.c_int64(0), C.c_int64(0), C.c_int64(0)
     capi.check(capi.lib().hgx_align_last_pairs(C.byref(ps), C.byref(pp), C.byref(pc)))
+    cs, cc, cb = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    capi.check(capi.lib().hgx_align_last_clip(C.byref(cs), C.byref(cc), C.byref(cb)))
     return dict(route=route.value, reads=reads.value, aligned=aligned.value, pairs_concordant=conc.value, decline=dec.value,
                 states_reads=sr.value, states_anchors=sa.value, states_cells=sc.value,
-                pairs_searched=ps.value, pairs_placed=pp.value, pairs_changed=pc.value)
+                pairs_searched=ps.value, pairs_placed=pp.value, pairs_changed=pc.value,
+                clip_searched=cs.value, clip_clipped=cc.value, clip_bases=cb.value)
+
+
+def align_last_clip():
+    """(searched, clipped, bases) of hgx_align_last_clip for the calling thread's last align()."""
+    last = align_last()
+    return last["clip_searched"], last["clip_clipped"], last["clip_bases"]
 
 
 DECLINE_GATE, DECLINE_READ_LEN, DECLINE_ANCHORS, DECLINE_STACK, DECLINE_VARS, DECLINE_STEPS, DECLINE_SWITCH = 1, 2, 3, 4, 5, 6, 7

@@ -10,6 +10,7 @@
 //                  concordant, best[] and nh[] of both mates are rewritten from the smallest one (the core's pair order)
 //   k_aln_emit     a lane per read, twice: record sizes, (exclusive scan,) then the SAM lines at their offsets; the pair's flags are
 //                  read off the mate's pick
+//   (opts.clip > 0 only) the clip tier between the picks and k_aln_emit: k_aln_clip_mark / _fill / _extend / _pick, below
 // Every write is bounds-checked by construction: slots < HGX_ALN_DEV_ANCHORS, a record's bytes = the size the same code counted.
 //
 // opts.search != 0 adds a second tier, the search over STATES (hgx_align_states.hpp), for the reads of a chunk that are MARKED: in
@@ -224,10 +225,11 @@ k_aln_pair_pick(int nc, int max_fragment, const int32_t *cnt, const DevRes *res,
     }
 }
 
-// out == nullptr: sizes[i] and flags[i] (1 aligned, 2 = mate 1 of a concordant pair); else the line at out + off[i]
-__global__ void __launch_bounds__(64)
+// out == nullptr: sizes[i] and flags[i] (1 aligned, 2 = mate 1 of a concordant pair); else the line at out + off[i].  CLIP
+// (opts.clip > 0): clipc[i] = the read's clip counts for the S ops; nullptr with clip = 0.
+template <bool CLIP> __global__ void __launch_bounds__(64)
 k_aln_emit(hgx_aln_view V, DevReads rd, long first, int nc, int max_fragment, const DevRes *res, const int32_t *best, const int32_t *nh,
-           uint32_t *sizes, int32_t *flags, const uint32_t *off, char *out) {
+           uint32_t *sizes, int32_t *flags, const uint32_t *off, char *out, const uint32_t *clipc) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nc) return;
     if (best[i] < 0) {
@@ -244,14 +246,108 @@ k_aln_emit(hgx_aln_view V, DevReads rd, long first, int nc, int max_fragment, co
     }
     const long r = first + i;
     hgx_aln_out w{out ? out + off[i] : nullptr, 0};
-    hgx_aln_line(V, rd.text + rd.name_off[r], rd.name_len[r], rd.text + rd.seq_off[r], rd.qual_off[r] >= 0 ? rd.text + rd.qual_off[r] : nullptr,
-                 rd.len[r], a, nh[i], mate, i & 1, max_fragment, w);
+    const uint32_t cc = CLIP ? clipc[i] : 0;
+    hgx_aln_line<HGX_ALN_DEV_VARS, CLIP>(V, rd.text + rd.name_off[r], rd.name_len[r], rd.text + rd.seq_off[r],
+                                         rd.qual_off[r] >= 0 ? rd.text + rd.qual_off[r] : nullptr, rd.len[r], a, nh[i], mate, i & 1, max_fragment, w,
+                                         hgx_aln_clip_l(cc), hgx_aln_clip_r(cc));
     if (!out) {
         sizes[i] = (uint32_t)w.n;
         flags[i] = 1 | ((rd.paired && !(i & 1) && hgx_aln_concordant(a, *mate, max_fragment)) ? 2 : 0);
     }
 }
 
+// ---- the clip tier (opts.clip > 0; hgx_align_core.hpp "soft clips") ----------------------------------------------------------------
+// For a chunk that holds a read with anchors that k_aln_pick left unaligned.  Count, scan, fill -- no atomic decides a position:
+//   k_aln_clip_mark    a lane per read: nslot[i] = its anchor slots if it has some and no alignment, else 0
+//   (hgx_scan_u32_dev) soff[i] = the read's first compacted slot, the total
+//   k_aln_clip_fill    a lane per (read, slot): compact[soff[i] + slot] = the slot's index in res[]
+//   k_aln_clip_extend  a lane per compacted slot: the clip canon by the core's CLIP walks into res[] and clips[]; the per-e entries of
+//                      both sides in the lane's private memory (2 x 5 entries of 37 words, the stack of 32 frames of 6 words and
+//                      the list of 32: 2 376 bytes of scratch per lane)
+//   k_aln_clip_pick    a lane per read with nslot[i] > 0: the pick and NH over its slots (the CLIP order), best[], nh[], clipc[]
+// Every loop bound is the read length, the slot count, max_edits + 1, the options at a position or the step limit; every index is a
+// slot below nc * HGX_ALN_DEV_ANCHORS or a compacted slot below the scan's total.
+__global__ void __launch_bounds__(256)
+k_aln_clip_mark(int nc, const int32_t *cnt, const int32_t *best, uint32_t *nslot) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nc) return;
+    nslot[i] = (best[i] < 0 && cnt[i] > 0 && cnt[i] <= HGX_ALN_DEV_ANCHORS) ? (uint32_t)cnt[i] : 0u;
+}
+
+__global__ void __launch_bounds__(256)
+k_aln_clip_fill(int nc, const uint32_t *nslot, const uint32_t *soff, uint32_t total, int32_t *compact) {
+    const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (long)nc * HGX_ALN_DEV_ANCHORS) return;
+    const int i = (int)(gid / HGX_ALN_DEV_ANCHORS);
+    const uint32_t slot = (uint32_t)(gid % HGX_ALN_DEV_ANCHORS);
+    if (slot >= nslot[i] || soff[i] + slot >= total) return;
+    compact[soff[i] + slot] = (int32_t)gid;
+}
+
+__global__ void __launch_bounds__(64)
+k_aln_clip_extend(hgx_aln_view V, DevReads rd, long first, uint32_t total, int max_edits, int clip, const int32_t *compact, const int2 *anch,
+                  DevRes *res, uint32_t *clips, int *decline) {
+    const long j = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= (long)total) return;
+    const int32_t gid = compact[j];
+    const int i = gid / HGX_ALN_DEV_ANCHORS;
+    hgx_aln_frame stk[HGX_ALN_DEV_STK];
+    int32_t cur[HGX_ALN_DEV_VARS];
+    hgx_aln_side<HGX_ALN_DEV_VARS> left[HGX_ALN_CLIP_EDITS + 1], right[HGX_ALN_CLIP_EDITS + 1];
+    const int2 a = anch[gid];
+    const hgx_aln_read R{rd.text + rd.seq_off[first + i], rd.len[first + i], a.x >> 16};
+    uint32_t cc = 0;
+    const int rc = hgx_aln_clip_canon<HGX_ALN_DEV_STK, HGX_ALN_DEV_VARS>(V, R, a.x & 0xffff, a.y, max_edits, clip, HGX_ALN_DEV_STEPS, stk, cur,
+                                                                        left, right, res[gid], &cc);
+    clips[gid] = cc;
+    if (rc) {
+        res[gid].ok = 0;
+        atomicMax(decline, rc);
+    }
+}
+
+__global__ void __launch_bounds__(64)
+k_aln_clip_pick(int nc, const uint32_t *nslot, const DevRes *res, const uint32_t *clips, int32_t *best, int32_t *nh, uint32_t *clipc) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nc || nslot[i] == 0) return;
+    int h = 0;
+    const int b = hgx_aln_pick<HGX_ALN_DEV_VARS, true>(res + (long)i * HGX_ALN_DEV_ANCHORS, (int)nslot[i], &h, clips + (long)i * HGX_ALN_DEV_ANCHORS);
+    best[i] = b;
+    nh[i] = h;
+    clipc[i] = b >= 0 ? clips[(long)i * HGX_ALN_DEV_ANCHORS + b] : 0u;
+}
+
+// the clip tier of one chunk, behind k_aln_pick: *decline != 0: the call goes to the host route
+int clip_tier(hgx_align_index *ix, const DevReads &rd, const hgx_align_opts *opts, long first, int nc, const int32_t *d_cnt, const int2 *d_anch,
+              DevRes *d_res, int32_t *d_best, int32_t *d_nh, uint32_t *d_clipc, uint32_t *d_nslot, uint32_t *d_soff, void *d_scan,
+              uint32_t *d_clips, int32_t *d_compact, int *d_decline, uint32_t *d_total, hipStream_t st, int64_t *counts, int *decline) {
+    k_aln_clip_mark<<<nblk(nc, 256), 256, 0, st>>>(nc, d_cnt, d_best, d_nslot);
+    HIPCHK(hipGetLastError());
+    const int rc = hgx_scan_u32_dev(d_nslot, d_soff, nc, d_scan, d_total, st);
+    if (rc) return rc;
+    uint32_t total = 0;
+    HIPCHK(hipMemcpy(&total, d_total, 4, hipMemcpyDeviceToHost));
+    if (!total) return HGX_OK;
+    k_aln_clip_fill<<<nblk((long)nc * HGX_ALN_DEV_ANCHORS, 256), 256, 0, st>>>(nc, d_nslot, d_soff, total, d_compact);
+    k_aln_clip_extend<<<nblk(total, 64), 64, 0, st>>>(ix->dv, rd, first, total, opts->max_edits, opts->clip, d_compact, d_anch, d_res, d_clips,
+                                                      d_decline);
+    HIPCHK(hipGetLastError());
+    int dec = 0;
+    HIPCHK(hipMemcpy(&dec, d_decline, 4, hipMemcpyDeviceToHost));
+    if (dec) { *decline = dec; return HGX_OK; }
+    k_aln_clip_pick<<<nblk(nc, 64), 64, 0, st>>>(nc, d_nslot, d_res, d_clips, d_best, d_nh, d_clipc);
+    HIPCHK(hipGetLastError());
+    std::vector<uint32_t> nslot((size_t)nc), clipc((size_t)nc);
+    HIPCHK(hipMemcpy(nslot.data(), d_nslot, (size_t)nc * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(clipc.data(), d_clipc, (size_t)nc * 4, hipMemcpyDeviceToHost));
+    for (int i = 0; i < nc; ++i) {
+        if (!nslot[i]) continue;
+        counts[0] += 1;
+        counts[1] += clipc[i] != 0;
+        counts[2] += hgx_aln_clip_total(clipc[i]);
+    }
+    return HGX_OK;
+}
 
 // ---- the second tier: the search over states (hgx_align_states.hpp) ------------------------------------------------------------
 struct StInfo { int32_t n, dmin, dmax, a0, a1; };                  // of one (marked read, strand, locus): anchors [a0, a1) are the (read, strand)'s
@@ -596,6 +692,14 @@ int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
     ALLOC(d_misc, 48);                       // [0] decline code, [1] total bytes, [2] reads marked for the second tier; pair mode: bytes 16 .. 40 = pairs searched, placed, changed
     int *d_decline = d_misc.as<int>();
     uint32_t *d_total = d_misc.as<uint32_t>() + 1;
+    const int clip = opts->clip;
+    DevBuf d_clipc, d_nslot, d_soff, d_clips, d_compact;
+    if (clip > 0) {
+        ALLOC(d_clipc, (size_t)cmax * 4); ALLOC(d_nslot, (size_t)cmax * 4); ALLOC(d_soff, (size_t)cmax * 4);
+        ALLOC(d_clips, (size_t)cmax * HGX_ALN_DEV_ANCHORS * 4); ALLOC(d_compact, (size_t)cmax * HGX_ALN_DEV_ANCHORS * 4);
+    }
+    const uint32_t *clipc = clip > 0 ? d_clipc.as<uint32_t>() : nullptr;
+    int64_t clip_counts[3] = {0, 0, 0};
     const bool pair_aware = reads.paired && opts->pair == 1;
     const size_t misc_bytes = pair_aware ? 40 : 16;
     int64_t pairs[3] = {0, 0, 0};
@@ -636,8 +740,24 @@ int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
         if (pair_aware)
             k_aln_pair_pick<<<nc / 2, 64, 0, st>>>(nc, opts->max_fragment, d_cnt.as<int32_t>(), d_res.as<DevRes>(), d_best.as<int32_t>(),
                                                    d_nh.as<int32_t>(), (unsigned long long *)(d_misc.as<char>() + 16));
-        k_aln_emit<<<nblk(nc, 64), 64, 0, st>>>(ix->dv, rd, first, nc, opts->max_fragment, d_res.as<DevRes>(), d_best.as<int32_t>(),
-                                                d_nh.as<int32_t>(), d_sizes.as<uint32_t>(), d_flags.as<int32_t>(), nullptr, nullptr);
+        if (clip > 0) {
+            HIPCHK(hipMemsetAsync(d_clipc.p, 0, (size_t)nc * 4, st));
+            rc = clip_tier(ix, rd, opts, first, nc, d_cnt.as<int32_t>(), d_anch.as<int2>(), d_res.as<DevRes>(), d_best.as<int32_t>(),
+                           d_nh.as<int32_t>(), d_clipc.as<uint32_t>(), d_nslot.as<uint32_t>(), d_soff.as<uint32_t>(), d_scan.p,
+                           d_clips.as<uint32_t>(), d_compact.as<int32_t>(), d_decline, d_total, st, clip_counts, &dec);
+            if (rc) return rc;
+            if (dec) {
+                body.resize(body0);
+                *aligned = aligned0;
+                *concordant = concordant0;
+                *decline = dec;
+                return HGX_OK;
+            }
+            k_aln_emit<true><<<nblk(nc, 64), 64, 0, st>>>(ix->dv, rd, first, nc, opts->max_fragment, d_res.as<DevRes>(), d_best.as<int32_t>(),
+                                                          d_nh.as<int32_t>(), d_sizes.as<uint32_t>(), d_flags.as<int32_t>(), nullptr, nullptr, clipc);
+        } else
+            k_aln_emit<false><<<nblk(nc, 64), 64, 0, st>>>(ix->dv, rd, first, nc, opts->max_fragment, d_res.as<DevRes>(), d_best.as<int32_t>(),
+                                                           d_nh.as<int32_t>(), d_sizes.as<uint32_t>(), d_flags.as<int32_t>(), nullptr, nullptr, nullptr);
         HIPCHK(hipGetLastError());
         rc = hgx_scan_u32_dev(d_sizes.as<uint32_t>(), d_off.as<uint32_t>(), nc, d_scan.p, d_total, st);
         if (rc) return rc;
@@ -654,8 +774,12 @@ int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
         if (total) {
             DevBuf d_out;
             ALLOC(d_out, (size_t)total);
-            k_aln_emit<<<nblk(nc, 64), 64, 0, st>>>(ix->dv, rd, first, nc, opts->max_fragment, d_res.as<DevRes>(), d_best.as<int32_t>(),
-                                                    d_nh.as<int32_t>(), nullptr, nullptr, d_off.as<uint32_t>(), d_out.as<char>());
+            if (clip > 0)
+                k_aln_emit<true><<<nblk(nc, 64), 64, 0, st>>>(ix->dv, rd, first, nc, opts->max_fragment, d_res.as<DevRes>(), d_best.as<int32_t>(),
+                                                              d_nh.as<int32_t>(), nullptr, nullptr, d_off.as<uint32_t>(), d_out.as<char>(), clipc);
+            else
+                k_aln_emit<false><<<nblk(nc, 64), 64, 0, st>>>(ix->dv, rd, first, nc, opts->max_fragment, d_res.as<DevRes>(), d_best.as<int32_t>(),
+                                                               d_nh.as<int32_t>(), nullptr, nullptr, d_off.as<uint32_t>(), d_out.as<char>(), nullptr);
             HIPCHK(hipGetLastError());
             text.resize(total);
             HIPCHK(hipMemcpy(&text[0], d_out.p, total, hipMemcpyDeviceToHost));
@@ -664,5 +788,6 @@ int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
     }
     HIPCHK(hipStreamSynchronize(st));
     if (pair_aware) hgx_align_pairs_count(pairs[0], pairs[1], pairs[2]);
+    if (clip > 0) hgx_align_clip_count(clip_counts[0], clip_counts[1], clip_counts[2]);
     return HGX_OK;
 }

@@ -45,3 +45,5 @@ void hgx_align_device_free(hgx_align_index *ix);
 void hgx_align_states_count(int64_t reads, int64_t anchors, int64_t cells);
 // what the pair pick did in the calling thread's current call (hgx_align_last_pairs): added to by the route that gives the bytes
 void hgx_align_pairs_count(int64_t searched, int64_t placed, int64_t changed);
+// what the clip tier did in the calling thread's current call (hgx_align_last_clip): added to by the route that gives the bytes
+void hgx_align_clip_count(int64_t searched, int64_t clipped, int64_t bases);

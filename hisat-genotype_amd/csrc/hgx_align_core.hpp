@@ -1,5 +1,6 @@
 // hgx_align_core.hpp -- the "hgx" aligner's per-anchor and per-read logic, compiled into the kernels
-// (hgx_align.hip) and into the host route (hgx_align_host.cpp).  The rules are stated in plain Python in tests/align_ref.py.
+// (hgx_align.hip) and into the host route (hgx_align_host.cpp).  The rules are stated in plain Python in tests/align_ref.py
+// (pair-aware placement: tests/align_pair_ref.py; soft clips: tests/align_clip_ref.py).
 //
 // An alignment of an oriented read at a locus = a start pos0 + an ordered list of known variants.  The walk of
 // simulate._truth_record consumes the read with them: at state (r, p), r > 0, at most one known insertion and one known deletion
@@ -127,6 +128,38 @@ template <int MAXV> struct hgx_aln_res {
 };
 struct hgx_aln_frame { int32_t r, P, nm, nind, nl, k; };
 
+HGX_ALN_HD inline int hgx_aln_cmp3(int a0, int a1, int a2, int b0, int b1, int b2) {
+    return a0 != b0 ? (a0 < b0 ? -1 : 1) : a1 != b1 ? (a1 < b1 ? -1 : 1) : a2 != b2 ? (a2 < b2 ? -1 : 1) : 0;
+}
+
+// ---- soft clips (opts.clip > 0; the rule in plain Python: tests/align_clip_ref.py) -------------------------------------------------
+// The clip tier runs the same two walks with CLIP = true.  A side then has one more option at every state it ENTERS: stop there
+// and clip what is left of the read (right: the L - r bases from r on; left: the r bases in front of "base r sits on Q").  What a
+// side returns is one entry per e = 0 .. max_nm: the smallest (clip, indels, variants, [pos0,] list) among its ways with exactly e
+// unknown mismatches (hgx_aln_clip_canon combines the two sides).  Along one way the stop with the fewest clipped bases for e is the
+// last state entered with e mismatches, so a state's stop is offered only where the step from it does not simply go on: the
+// mismatch e + 1 is taken, the backbone ends or the walk dies.  The cut by the best found and the memo are off (neither is lossless
+// once a side keeps an entry per e); a stop that alone clips more than the budget is not offered, which loses nothing.
+#define HGX_ALN_CLIP_EDITS 4           // clip > 0 takes max_edits up to this (the per-e entries are of fixed size)
+#define HGX_ALN_CLIP_MAX 255
+// A side's entries are hgx_aln_side[HGX_ALN_CLIP_EDITS + 1], indexed by e, whose `nm` word holds the CLIP count; the CLIP walks
+// take the array through their `best` argument.
+// a way of the walk (its list in cur[0 .. nl), backwards if `rev`) against the side's entry for its e
+template <int MAXV>
+HGX_ALN_HD inline void hgx_aln_clip_offer(hgx_aln_side<MAXV> &b, int clip, int nind, int nl, int32_t pos, bool use_pos, const int32_t *cur,
+                                          bool rev) {
+    int c = b.found ? hgx_aln_cmp3(clip, nind, nl, b.nm, b.nind, b.nl) : -1;
+    if (c == 0 && use_pos && pos != b.pos) c = pos < b.pos ? -1 : 1;
+    for (int i = 0; c == 0 && i < nl; ++i) {
+        const int32_t a = rev ? cur[nl - 1 - i] : cur[i];
+        c = a != b.vl[i] ? (a < b.vl[i] ? -1 : 1) : 0;
+    }
+    if (c < 0) {
+        b.found = 1; b.nm = clip; b.nind = nind; b.nl = nl; b.pos = pos;
+        for (int i = 0; i < nl; ++i) b.vl[i] = rev ? cur[nl - 1 - i] : cur[i];
+    }
+}
+
 // MEMO: what a route remembers about the states a side's search has reached through a known indel.  dominated(side, r, P, cost, list)
 // == true cuts the path: an earlier path reached the same state (side 0: (r, P) before its events; side 1: base r on P) with a
 // smaller cost, or the same cost and a list that sorts first -- every way to finish from here is then a way to finish from there
@@ -138,22 +171,19 @@ struct hgx_aln_no_memo {
     HGX_ALN_HD bool dominated(int, int, int32_t, int, int, int, const int32_t *) { return false; }
 };
 
-HGX_ALN_HD inline int hgx_aln_cmp3(int a0, int a1, int a2, int b0, int b1, int b2) {
-    return a0 != b0 ? (a0 < b0 ? -1 : 1) : a1 != b1 ? (a1 < b1 ? -1 : 1) : a2 != b2 ? (a2 < b2 ? -1 : 1) : 0;
-}
-
 // every way to finish from state (r0, P0), r0 > 0, inside the locus [lo, hi): the smallest by (NM, indels, variants, list)
-template <int MAXSTK, int MAXV, class MEMO>
+template <int MAXSTK, int MAXV, class MEMO, bool CLIP = false>
 HGX_ALN_HD int hgx_aln_right(const hgx_aln_view &V, const hgx_aln_read &R, int32_t hi, int r0, int32_t P0, int max_nm, long max_steps,
-                             hgx_aln_frame *stk, int32_t *cur, hgx_aln_side<MAXV> &best, MEMO &memo) {
+                             hgx_aln_frame *stk, int32_t *cur, hgx_aln_side<MAXV> &best, MEMO &memo, int clip = 0) {
     int sp = 0;
     long steps = 0;
-    best.found = 0;
+    if (!CLIP) best.found = 0;
     int r = r0, nm = 0, nind = 0, nl = 0, k = 0;
     int32_t P = P0;
     for (;;) {
         bool dead = false, done = false;
         int32_t end = P;
+        const int r_in = r, nm_in = nm, nind_in = nind, nl_in = nl;      // (CLIP: the state entered, for its stop)
         if (r == R.L) done = true;
         else if (P >= hi) dead = true;
         else {
@@ -203,11 +233,18 @@ HGX_ALN_HD int hgx_aln_right(const hgx_aln_view &V, const hgx_aln_read &R, int32
                     r = rr + 1;
                     P = PP + 1;
                     k = 0;
-                    if (!dead && best.found && hgx_aln_cmp3(nm, nind, nl, best.nm, best.nind, best.nl) > 0) dead = true;
-                    if (!dead && nind > 0 && r < R.L && memo.dominated(0, r, P, nm, nind, nl, cur)) dead = true;
+                    if (!CLIP && !dead && best.found && hgx_aln_cmp3(nm, nind, nl, best.nm, best.nind, best.nl) > 0) dead = true;
+                    if (!CLIP && !dead && nind > 0 && r < R.L && memo.dominated(0, r, P, nm, nind, nl, cur)) dead = true;
                 }
             }
         }
+        if constexpr (CLIP) {
+            if (r_in < R.L && (dead || nm != nm_in) && R.L - r_in <= clip)
+                hgx_aln_clip_offer((&best)[nm_in], R.L - r_in, nind_in, nl_in, end, false, cur, false);
+            if (done) hgx_aln_clip_offer((&best)[nm], 0, nind, nl, end, false, cur, false);
+            done = dead || done;
+            dead = done;
+        } else
         if (done) {
             int c = best.found ? hgx_aln_cmp3(nm, nind, nl, best.nm, best.nind, best.nl) : -1;
             for (int i = 0; c == 0 && i < nl; ++i) c = cur[i] != best.vl[i] ? (cur[i] < best.vl[i] ? -1 : 1) : 0;
@@ -227,16 +264,18 @@ HGX_ALN_HD int hgx_aln_right(const hgx_aln_view &V, const hgx_aln_read &R, int32
 
 // every way to have arrived at "read base r0 sits on backbone base Q0" inside the locus [lo, hi): the smallest by
 // (NM, indels, variants, pos0, list).  `cur` holds the list backwards.
-template <int MAXSTK, int MAXV, class MEMO>
+template <int MAXSTK, int MAXV, class MEMO, bool CLIP = false>
 HGX_ALN_HD int hgx_aln_left(const hgx_aln_view &V, const hgx_aln_read &R, int32_t lo, int r0, int32_t Q0, int max_nm, long max_steps,
-                            hgx_aln_frame *stk, int32_t *cur, hgx_aln_side<MAXV> &best, MEMO &memo) {
+                            hgx_aln_frame *stk, int32_t *cur, hgx_aln_side<MAXV> &best, MEMO &memo, int clip = 0) {
     int sp = 0;
     long steps = 0;
-    best.found = 0;
+    if (!CLIP) best.found = 0;
     int r = r0, nm = 0, nind = 0, nl = 0, k = 0;
     int32_t Q = Q0;
     for (;;) {
         bool dead = false, done = false;
+        const int r_in = r, nm_in = nm, nind_in = nind, nl_in = nl;      // (CLIP: the state entered, for its clip)
+        const int32_t Q_in = Q;
         if (r == 0) done = true;
         else {
             if (++steps > max_steps) return HGX_ALN_DECLINE_STEPS;
@@ -292,11 +331,17 @@ HGX_ALN_HD int hgx_aln_left(const hgx_aln_view &V, const hgx_aln_read &R, int32_
                     r = r1 - 1;
                     Q = P1 - 1;
                     k = 0;
-                    if (!dead && best.found && hgx_aln_cmp3(nm, nind, nl, best.nm, best.nind, best.nl) > 0) dead = true;
-                    if (!dead && nind > 0 && r > 0 && memo.dominated(1, r, Q, nm, nind, nl, cur)) dead = true;
+                    if (!CLIP && !dead && best.found && hgx_aln_cmp3(nm, nind, nl, best.nm, best.nind, best.nl) > 0) dead = true;
+                    if (!CLIP && !dead && nind > 0 && r > 0 && memo.dominated(1, r, Q, nm, nind, nl, cur)) dead = true;
                 }
             }
         }
+        if constexpr (CLIP) {
+            if (r_in > 0 && (dead || nm != nm_in) && r_in <= clip) hgx_aln_clip_offer((&best)[nm_in], r_in, nind_in, nl_in, Q_in, true, cur, true);
+            if (done) hgx_aln_clip_offer((&best)[nm], 0, nind, nl, Q, true, cur, true);
+            done = dead || done;
+            dead = done;
+        } else
         if (done) {
             int c = best.found ? hgx_aln_cmp3(nm, nind, nl, best.nm, best.nind, best.nl) : -1;
             if (c == 0 && Q != best.pos) c = Q < best.pos ? -1 : 1;
@@ -343,6 +388,62 @@ HGX_ALN_HD int hgx_aln_canon(const hgx_aln_view &V, const hgx_aln_read &R, int o
     return 0;
 }
 
+// the clip counts of an alignment in one word (clipL, clipR <= HGX_ALN_CLIP_MAX)
+HGX_ALN_HD inline uint32_t hgx_aln_clip_pack(int clipL, int clipR) { return (uint32_t)clipL | ((uint32_t)clipR << 16); }
+HGX_ALN_HD inline int hgx_aln_clip_l(uint32_t c) { return (int)(c & 0xffff); }
+HGX_ALN_HD inline int hgx_aln_clip_r(uint32_t c) { return (int)(c >> 16); }
+HGX_ALN_HD inline int hgx_aln_clip_total(uint32_t c) { return hgx_aln_clip_l(c) + hgx_aln_clip_r(c); }
+
+// canon(a) of the clip tier: the smallest by (clipL + clipR, NM, indels, variants, pos0, list) among the alignments through the
+// anchor with NM <= max_edits (<= HGX_ALN_CLIP_EDITS) and clipL + clipR <= clip.  For a fixed split (eL, eR) of the edits every
+// component in front of pos0 is a sum over the sides and pos0 is the left side's, so the smallest combination of the split is made
+// of each side's smallest entry for its e; the canon is the smallest over the splits.  `left` / `right`: scratch for the sides'
+// HGX_ALN_CLIP_EDITS + 1 entries each.
+template <int MAXSTK, int MAXV>
+HGX_ALN_HD int hgx_aln_clip_canon(const hgx_aln_view &V, const hgx_aln_read &R, int o, int32_t b, int max_edits, int clip, long max_steps,
+                                  hgx_aln_frame *stk, int32_t *cur, hgx_aln_side<MAXV> *left, hgx_aln_side<MAXV> *right,
+                                  hgx_aln_res<MAXV> &res, uint32_t *clips) {
+    const int g = hgx_aln_locus_of(V, b);
+    const int32_t lo = V.bb_off[g], hi = V.bb_off[g + 1];
+    res.ok = 0;
+    *clips = 0;
+    for (int e = 0; e <= HGX_ALN_CLIP_EDITS; ++e) left[e].found = right[e].found = 0;
+    hgx_aln_no_memo memo;
+    int rc = hgx_aln_left<MAXSTK, MAXV, hgx_aln_no_memo, true>(V, R, lo, o, b, max_edits, max_steps, stk, cur, *left, memo, clip);
+    if (rc) return rc;
+    rc = hgx_aln_right<MAXSTK, MAXV, hgx_aln_no_memo, true>(V, R, hi, o + HGX_ALN_K, b + HGX_ALN_K, max_edits, max_steps, stk, cur, *right,
+                                                            memo, clip);
+    if (rc) return rc;
+    int bl = -1, br = -1;
+    for (int el = 0; el <= max_edits; ++el) {
+        if (!left[el].found) continue;
+        for (int er = 0; el + er <= max_edits; ++er) {
+            if (!right[er].found || left[el].nm + right[er].nm > clip) continue;
+            const hgx_aln_side<MAXV> &x = left[el], &y = right[er];
+            int c = -1;
+            if (bl >= 0) {
+                const hgx_aln_side<MAXV> &p = left[bl], &q = right[br];
+                c = hgx_aln_cmp3(x.nm + y.nm, el + er, x.nind + y.nind, p.nm + q.nm, bl + br, p.nind + q.nind);
+                if (c == 0) c = hgx_aln_cmp3(x.nl + y.nl, x.pos, 0, p.nl + q.nl, p.pos, 0);
+                for (int i = 0; c == 0 && i < x.nl + y.nl; ++i) {
+                    const int32_t u = i < x.nl ? x.vl[i] : y.vl[i - x.nl], w = i < p.nl ? p.vl[i] : q.vl[i - p.nl];
+                    c = u != w ? (u < w ? -1 : 1) : 0;
+                }
+            }
+            if (c < 0) { bl = el; br = er; }
+        }
+    }
+    if (bl < 0) return 0;
+    const hgx_aln_side<MAXV> &x = left[bl], &y = right[br];
+    if (x.nl + y.nl > MAXV) return HGX_ALN_DECLINE_VARS;
+    for (int i = 0; i < x.nl; ++i) res.vl[i] = x.vl[i];
+    for (int i = 0; i < y.nl; ++i) res.vl[x.nl + i] = y.vl[i];
+    res.nm = bl + br; res.nind = x.nind + y.nind; res.nvar = x.nl + y.nl; res.pos0 = x.pos; res.end = y.pos;
+    res.locus = g; res.strand = R.strand; res.ok = 1;
+    *clips = hgx_aln_clip_pack(x.nm, y.nm);
+    return 0;
+}
+
 // the eight words in front of an alignment's list: what the pair pick keeps of a candidate (the kernels: in LDS)
 struct hgx_aln_head { int32_t ok, nm, nind, nvar, locus, strand, pos0, end; };
 
@@ -360,14 +461,27 @@ template <int MAXV> HGX_ALN_HD int hgx_aln_res_cmp(const hgx_aln_res<MAXV> &a, c
 }
 
 // the read's alignment among the canon(a) of its anchors: index of the smallest (-1: unaligned) and NH, the number of placements
-// of those with the smallest NM
-template <int MAXV> HGX_ALN_HD int hgx_aln_pick(const hgx_aln_res<MAXV> *res, int n, int *nh_out) {
+// of those with the smallest NM.  CLIP (the clip tier; clips[i] = hgx_aln_clip_pack of res[i]): the order is (clipL + clipR, the key,
+// clipL) and NH is taken over those with the smallest (clipL + clipR, NM).
+template <int MAXV, bool CLIP = false>
+HGX_ALN_HD int hgx_aln_pick(const hgx_aln_res<MAXV> *res, int n, int *nh_out, const uint32_t *clips = nullptr) {
     int best = -1;
-    for (int i = 0; i < n; ++i)
-        if (res[i].ok && (best < 0 || hgx_aln_res_cmp(res[i], res[best]) < 0)) best = i;
+    for (int i = 0; i < n; ++i) {
+        if (!res[i].ok) continue;
+        int c = -1;
+        if (best >= 0) {
+            if constexpr (CLIP) {
+                const int ti = hgx_aln_clip_total(clips[i]), tb = hgx_aln_clip_total(clips[best]);
+                c = ti != tb ? (ti < tb ? -1 : 1) : hgx_aln_res_cmp(res[i], res[best]);
+                if (c == 0 && clips[i] != clips[best]) c = hgx_aln_clip_l(clips[i]) < hgx_aln_clip_l(clips[best]) ? -1 : 1;
+            } else c = hgx_aln_res_cmp(res[i], res[best]);
+        }
+        if (c < 0) best = i;
+    }
     *nh_out = 0;
     if (best < 0) return -1;
     const int nm = res[best].nm;
+    const int ct = CLIP ? hgx_aln_clip_total(clips[best]) : 0;
     // walk those with NM == nm in (locus, strand, pos0, slot) order
     int nh = 0, last = -1, cur_g = -1, cur_s = -1;
     int32_t cur_end = 0;
@@ -375,6 +489,7 @@ template <int MAXV> HGX_ALN_HD int hgx_aln_pick(const hgx_aln_res<MAXV> *res, in
         int nxt = -1;
         for (int i = 0; i < n; ++i) {
             if (!res[i].ok || res[i].nm != nm) continue;
+            if (CLIP && hgx_aln_clip_total(clips[i]) != ct) continue;
             if (last >= 0) {
                 const int c = hgx_aln_cmp3(res[i].locus, res[i].strand, res[i].pos0, res[last].locus, res[last].strand, res[last].pos0);
                 if (c < 0 || (c == 0 && i <= last)) continue;
@@ -412,9 +527,13 @@ struct hgx_aln_out {                       // p == nullptr: count only
 };
 
 // one of CIGAR (what = 0), MD (1), Zs (2) of the walk, as simulate._truth_record renders them; returns the number of Zs items
+// CLIP: the aligned part is read bases [clipL, L - clipR); the walk is that of the part alone (no indel in front of its first base,
+// the first Zs gap counts from it) and the CIGAR carries the two S ops around it.
+template <bool CLIP = false>
 HGX_ALN_HD inline int hgx_aln_walk_text(const hgx_aln_view &V, const hgx_aln_read &R, int32_t pos0, const int32_t *vl, int nvar, int what,
-                                        hgx_aln_out &out) {
-    int r = 0, vi = 0, md_run = 0, gap = 0, n_zs = 0, run = 0;
+                                        hgx_aln_out &out, int clipL = 0, int clipR = 0) {
+    const int r_first = CLIP ? clipL : 0, r_end = CLIP ? R.L - clipR : R.L;
+    int r = r_first, vi = 0, md_run = 0, gap = 0, n_zs = 0, run = 0;
     char op = 0;
     int32_t P = pos0;
     auto cigar = [&](char o, int n) {
@@ -432,8 +551,9 @@ HGX_ALN_HD inline int hgx_aln_walk_text(const hgx_aln_view &V, const hgx_aln_rea
         }
         ++n_zs;
     };
-    while (r < R.L) {
-        if (r > 0) {
+    if (CLIP && clipL > 0 && what == 0) { out.num(clipL); out.ch('S'); }
+    while (r < r_end) {
+        if (r > r_first) {
             const int32_t at = P;
             while (vi < nvar && V.vtype[vl[vi]] != HGX_ALN_SGL && V.vpos[vl[vi]] == at) {
                 const int32_t v = vl[vi++];
@@ -447,7 +567,7 @@ HGX_ALN_HD inline int hgx_aln_walk_text(const hgx_aln_view &V, const hgx_aln_rea
                     P += n;
                 } else {
                     int n = V.vlen[v];
-                    if (n > R.L - r) n = R.L - r;
+                    if (n > r_end - r) n = r_end - r;
                     zs('I', v);
                     gap = n;
                     cigar('I', n);
@@ -455,7 +575,7 @@ HGX_ALN_HD inline int hgx_aln_walk_text(const hgx_aln_view &V, const hgx_aln_rea
                 }
             }
         }
-        if (r >= R.L) break;
+        if (r >= r_end) break;
         if (R.at(r) == V.bb[P]) { ++md_run; ++gap; }
         else {
             if (what == 1) { out.num(md_run); out.ch(V.bb[P]); }
@@ -468,6 +588,7 @@ HGX_ALN_HD inline int hgx_aln_walk_text(const hgx_aln_view &V, const hgx_aln_rea
         ++P;
     }
     if (what == 0 && op) { out.num(run); out.ch(op); }
+    if (CLIP && clipR > 0 && what == 0) { out.num(clipR); out.ch('S'); }
     if (what == 1) out.num(md_run);
     return n_zs;
 }
@@ -515,10 +636,10 @@ template <class H> HGX_ALN_HD bool hgx_aln_covers(const H &x, int ix, const H &e
 }
 
 // the whole line (with its '\n'); `name` / `qual` as the file has them (qual == nullptr: 'I' x L)
-template <int MAXV>
+template <int MAXV, bool CLIP = false>
 HGX_ALN_HD void hgx_aln_line(const hgx_aln_view &V, const char *name, int name_len, const char *seq, const char *qual, int L,
                              const hgx_aln_res<MAXV> &a, int nh, const hgx_aln_res<MAXV> *mate, int mate_no, int max_fragment,
-                             hgx_aln_out &out) {
+                             hgx_aln_out &out, int clipL = 0, int clipR = 0) {
     const hgx_aln_read R{seq, L, a.strand};
     const int32_t lo = V.bb_off[a.locus];
     int flag = a.strand ? 16 : 0;
@@ -541,7 +662,7 @@ HGX_ALN_HD void hgx_aln_line(const hgx_aln_view &V, const char *name, int name_l
     out.str(V.pool + V.name_off[a.locus], V.name_len[a.locus]); out.ch('\t');
     out.num(a.pos0 - lo + 1); out.ch('\t');
     out.num(nh == 1 ? 60 : 1); out.ch('\t');
-    hgx_aln_walk_text(V, R, a.pos0, a.vl, a.nvar, 0, out); out.ch('\t');
+    hgx_aln_walk_text<CLIP>(V, R, a.pos0, a.vl, a.nvar, 0, out, clipL, clipR); out.ch('\t');
     if (rnext == 0) out.ch('*');
     else if (rnext == 1) out.ch('=');
     else out.str(V.pool + V.name_off[mate->locus], V.name_len[mate->locus]);
@@ -553,11 +674,11 @@ HGX_ALN_HD void hgx_aln_line(const hgx_aln_view &V, const char *name, int name_l
     for (int r = 0; r < L; ++r) out.ch(qual ? qual[a.strand ? L - 1 - r : r] : 'I');
     out.str("\tNM:i:", 6); out.num(a.nm);
     out.str("\tMD:Z:", 6);
-    hgx_aln_walk_text(V, R, a.pos0, a.vl, a.nvar, 1, out);
+    hgx_aln_walk_text<CLIP>(V, R, a.pos0, a.vl, a.nvar, 1, out, clipL, clipR);
     hgx_aln_out count{nullptr, 0};
-    if (hgx_aln_walk_text(V, R, a.pos0, a.vl, a.nvar, 2, count)) {
+    if (hgx_aln_walk_text<CLIP>(V, R, a.pos0, a.vl, a.nvar, 2, count, clipL, clipR)) {
         out.str("\tZs:Z:", 6);
-        hgx_aln_walk_text(V, R, a.pos0, a.vl, a.nvar, 2, out);
+        hgx_aln_walk_text<CLIP>(V, R, a.pos0, a.vl, a.nvar, 2, out, clipL, clipR);
     }
     out.str("\tNH:i:", 6); out.num(nh);
     out.str("\tYT:Z:", 6); out.str(yt, 2);

@@ -24,6 +24,7 @@ thread_local int g_route = 0, g_decline = 0;
 thread_local int64_t g_reads = 0, g_aligned = 0, g_conc = 0;
 thread_local int64_t g_st_reads = 0, g_st_anchors = 0, g_st_cells = 0;
 thread_local int64_t g_pr_searched = 0, g_pr_placed = 0, g_pr_changed = 0;
+thread_local int64_t g_cl_searched = 0, g_cl_clipped = 0, g_cl_bases = 0;
 
 template <class T> void csr(const std::vector<std::pair<int32_t, int32_t>> &items, int32_t n_pos, std::vector<T> &off, std::vector<T> &list) {
     off.assign((size_t)n_pos + 1, 0);
@@ -232,6 +233,48 @@ int align_one(const hgx_aln_view &V, const char *seq, int L, int max_edits, Host
     return HGX_OK;
 }
 
+// the clip tier (opts.clip > 0) for a read align_one found nothing for: the clip canons of the same anchors, without the memo
+struct ClipScratch {
+    std::vector<hgx_aln_side<HGX_ALN_HOST_VARS>> left, right;
+    std::vector<HostRes> res;
+    std::vector<uint32_t> clips;
+    ClipScratch() : left(HGX_ALN_CLIP_EDITS + 1), right(HGX_ALN_CLIP_EDITS + 1) {}
+};
+
+void align_one_clip(const hgx_aln_view &V, const char *seq, int L, int max_edits, int clip, HostScratch &S, ClipScratch &C, HostRes &best,
+                    int *nh, uint32_t *clips, int *n_anchors, int *gave_up) {
+    C.res.clear();
+    C.clips.clear();
+    best.ok = 0;
+    *nh = 0;
+    *clips = 0;
+    for (int strand = 0; strand < 2; ++strand) {
+        const hgx_aln_read R{seq, L, strand};
+        const int n_off = hgx_aln_n_offsets(L);
+        for (int k = 0; k < n_off; ++k) {
+            const int o = hgx_aln_offset(L, k);
+            uint32_t code;
+            if (!hgx_aln_seed_code(R, o, &code)) continue;
+            for (uint32_t h = hgx_aln_hash(code) & V.hmask; V.hpos[h] >= 0; h = (h + 1) & V.hmask) {
+                if (V.hkey[h] != code) continue;
+                ++*n_anchors;
+                C.res.emplace_back();
+                C.clips.push_back(0);
+                const int rc = hgx_aln_clip_canon<HGX_ALN_HOST_VARS, HGX_ALN_HOST_VARS>(V, R, o, V.hpos[h], max_edits, clip, HGX_ALN_HOST_STEPS,
+                                                                                       S.stk.data(), S.cur.data(), C.left.data(),
+                                                                                       C.right.data(), C.res.back(), &C.clips.back());
+                if (rc) {                     // beyond the host route's own limits: left unaligned, as align_one does
+                    *gave_up = rc;
+                    return;
+                }
+                if (!C.res.back().ok) { C.res.pop_back(); C.clips.pop_back(); }
+            }
+        }
+    }
+    const int b = hgx_aln_pick<HGX_ALN_HOST_VARS, true>(C.res.data(), (int)C.res.size(), nh, C.clips.data());
+    if (b >= 0) { best = C.res[(size_t)b]; *clips = C.clips[(size_t)b]; }
+}
+
 // ---- the host route's states form (hgx_align_states.hpp): the same cells as the kernels, in loops --------------------------------
 struct StatesScratch {
     struct A { int32_t strand, locus; hgx_st_anchor a; };
@@ -373,6 +416,8 @@ int host_route(const hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
     HostScratch S;
     StatesScratch SS;
     PairScratch PS;
+    std::unique_ptr<ClipScratch> CS(o->clip > 0 ? new ClipScratch : nullptr);
+    uint32_t clips[2] = {0, 0};
     const int per = reads.paired ? 2 : 1;
     const bool pair_aware = per == 2 && o->pair == 1;
     std::vector<HostRes> best(per);
@@ -381,10 +426,18 @@ int host_route(const hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
     for (size_t k = 0; k < reads.n(); k += per) {
         for (int m = 0; m < per; ++m) {
             const char *seq = reads.text.data() + reads.seq_off[k + m];
-            const int rc = o->search ? align_one_states(V, seq, reads.len[k + m], o->max_edits, SS, best[m], &nh[m], gave_up)
-                                     : align_one(V, seq, reads.len[k + m], o->max_edits, S, best[m], &nh[m], gave_up);
+            int gu = 0;                                  // this read's own "gave up"
+            const int rc = o->search ? align_one_states(V, seq, reads.len[k + m], o->max_edits, SS, best[m], &nh[m], &gu)
+                                     : align_one(V, seq, reads.len[k + m], o->max_edits, S, best[m], &nh[m], &gu);
             if (rc) return rc;
             if (pair_aware) PS.cand[m].swap(S.res);      // (a mate that gave up: none)
+            clips[m] = 0;
+            if (CS && !best[m].ok && !gu) {              // no end-to-end alignment: the clip tier over the same anchors
+                int n_anchors = 0;
+                align_one_clip(V, seq, reads.len[k + m], o->max_edits, o->clip, S, *CS, best[m], &nh[m], &clips[m], &n_anchors, &gu);
+                if (n_anchors > 0) hgx_align_clip_count(1, best[m].ok && clips[m] != 0, best[m].ok ? hgx_aln_clip_total(clips[m]) : 0);
+            }
+            if (gu) *gave_up = gu;
         }
         if (pair_aware && best[0].ok && best[1].ok) {
             int b1 = -1, b2 = -1, pnh = 0;
@@ -406,13 +459,14 @@ int host_route(const hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
             const size_t i = k + m;
             const char *qual = reads.qual_off[i] >= 0 ? reads.text.data() + reads.qual_off[i] : nullptr;
             const HostRes *mate = per == 2 ? &best[1 - m] : nullptr;
+            const int cl = hgx_aln_clip_l(clips[m]), cr = hgx_aln_clip_r(clips[m]);
             hgx_aln_out cnt{nullptr, 0};
-            hgx_aln_line(V, reads.text.data() + reads.name_off[i], reads.name_len[i], reads.text.data() + reads.seq_off[i], qual,
-                         reads.len[i], best[m], nh[m], mate, m, o->max_fragment, cnt);
+            hgx_aln_line<HGX_ALN_HOST_VARS, true>(V, reads.text.data() + reads.name_off[i], reads.name_len[i], reads.text.data() + reads.seq_off[i],
+                                                  qual, reads.len[i], best[m], nh[m], mate, m, o->max_fragment, cnt, cl, cr);
             line.resize((size_t)cnt.n);
             hgx_aln_out w{line.data(), 0};
-            hgx_aln_line(V, reads.text.data() + reads.name_off[i], reads.name_len[i], reads.text.data() + reads.seq_off[i], qual,
-                         reads.len[i], best[m], nh[m], mate, m, o->max_fragment, w);
+            hgx_aln_line<HGX_ALN_HOST_VARS, true>(V, reads.text.data() + reads.name_off[i], reads.name_len[i], reads.text.data() + reads.seq_off[i],
+                                                  qual, reads.len[i], best[m], nh[m], mate, m, o->max_fragment, w, cl, cr);
             body.append(line.data(), line.size());
         }
     }
@@ -424,6 +478,11 @@ void hgx_align_states_count(int64_t reads, int64_t anchors, int64_t cells) {
     g_st_reads += reads;
     g_st_anchors += anchors;
     g_st_cells += cells;
+}
+void hgx_align_clip_count(int64_t searched, int64_t clipped, int64_t bases) {
+    g_cl_searched += searched;
+    g_cl_clipped += clipped;
+    g_cl_bases += bases;
 }
 void hgx_align_pairs_count(int64_t searched, int64_t placed, int64_t changed) {
     g_pr_searched += searched;
@@ -548,7 +607,9 @@ extern "C" int hgx_align_reads(hgx_align_index *ix, int32_t n_inputs, const char
                                const size_t *text_bytes, const hgx_align_opts *opts, char **sam_out, size_t *n_bytes_out) {
     if (!ix || (n_inputs != 1 && n_inputs != 2) || (!paths && !(texts && text_bytes)) || !opts || !sam_out || !n_bytes_out ||
         opts->max_edits < 0 || opts->route < 0 || opts->route > 2 || opts->search < 0 || opts->search > 2 ||
-        opts->pair < 0 || opts->pair > 1 || (opts->pair && opts->search)) {      // (the states form keeps no candidates to pair)
+        opts->pair < 0 || opts->pair > 1 || (opts->pair && opts->search) ||      // (the states form keeps no candidates to pair)
+        opts->clip < 0 || opts->clip > HGX_ALN_CLIP_MAX ||
+        (opts->clip && (opts->search || opts->pair || opts->max_edits > HGX_ALN_CLIP_EDITS))) {      // (neither keeps clip counts)
         hgx_set_error("invalid argument: hgx_align_reads");
         return HGX_EINVAL;
     }
@@ -557,6 +618,7 @@ extern "C" int hgx_align_reads(hgx_align_index *ix, int32_t n_inputs, const char
     g_route = 0; g_decline = 0; g_reads = g_aligned = g_conc = 0;
     g_st_reads = g_st_anchors = g_st_cells = 0;
     g_pr_searched = g_pr_placed = g_pr_changed = 0;
+    g_cl_searched = g_cl_clipped = g_cl_bases = 0;
     try {
         hgx_aln_reads reads;
         int rc = load_reads(n_inputs, paths, texts, text_bytes, opts->fastq, reads);
@@ -576,6 +638,7 @@ extern "C" int hgx_align_reads(hgx_align_index *ix, int32_t n_inputs, const char
             aligned = conc = 0;
             g_st_reads = g_st_anchors = g_st_cells = 0;          // what the kernels took before they declined is not this call's answer
             g_pr_searched = g_pr_placed = g_pr_changed = 0;
+            g_cl_searched = g_cl_clipped = g_cl_bases = 0;
             int gave_up = 0;
             if ((rc = host_route(ix, reads, opts, body, &aligned, &conc, &gave_up))) return rc;
             if (gave_up) fprintf(stderr, "[hgx_align_reads] a read's search passed the host route's limits (code %d): left unaligned\n", gave_up);
@@ -619,5 +682,12 @@ extern "C" int hgx_align_last_pairs(int64_t *searched, int64_t *placed, int64_t 
     if (searched) *searched = g_pr_searched;
     if (placed) *placed = g_pr_placed;
     if (changed) *changed = g_pr_changed;
+    return HGX_OK;
+}
+
+extern "C" int hgx_align_last_clip(int64_t *searched, int64_t *clipped, int64_t *bases) {
+    if (searched) *searched = g_cl_searched;
+    if (clipped) *clipped = g_cl_clipped;
+    if (bases) *bases = g_cl_bases;
     return HGX_OK;
 }

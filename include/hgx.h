@@ -844,9 +844,11 @@ int hgx_extract_stats(const hgx_extract *h, int64_t *records, int64_t *groups, i
 int hgx_extract_close(hgx_extract *h);
 
 /* ---- the "hgx" aligner: reads of a locus family -> SAM text in the front end's dialect ------------------------------
- * Stands in for typing_common.align_reads (common:985-1056) for reads already known to belong to the loci: end to end, at most
- * max_edits unknown mismatches, known variants free; no whole-genome index, no novel indels, no soft clips, no secondary records,
- * mates placed independently (unless opts.pair = 1, below).  NOT HISAT2 and not compared with its output: the rules are those of tests/align_ref.py.
+ * Stands in for typing_common.align_reads (common:985-1056) for reads already known to belong to the loci: at most max_edits
+ * unknown mismatches, known variants free; end to end, unless opts.clip > 0 (below) lets a read that has no end-to-end alignment
+ * be written with soft-clipped ends; no whole-genome index, no novel indels, no secondary records, mates placed independently
+ * (unless opts.pair = 1, below).  NOT HISAT2 and not compared with its output (its soft clipping, scored by --sp, included): the
+ * rules are those of tests/align_ref.py, tests/align_pair_ref.py and tests/align_clip_ref.py.
  * index_create (the `hisat2 -x <index>` argument of common:1013-1023: what the reads are aligned to): n_loci loci in the caller's
  * order, names[g] = the backbone's reference name, backbones[g] its bases; the variants of locus g are
  * var_off[g] .. var_off[g + 1] in Var_list order with var_type (0 insertion, 1 single, 2 deletion), var_pos (0-based backbone
@@ -880,11 +882,25 @@ int hgx_extract_close(hgx_extract *h);
  * 10.75 KB of LDS); a read past the 128 anchor slots moves the call to the host route as before, which applies the same rule.
  * pair = 1 with search != 0 is HGX_EINVAL (the states form keeps a read's winner, not its candidates); any other value of pair too.
  * align_last_pairs: of the calling thread's last call, on the route that gave the bytes -- pairs with candidates on both mates,
- * pairs with a concordant combination, pairs of which a record differs from the independent one in alignment or NH; 0 with pair = 0. */
+ * pairs with a concordant combination, pairs of which a record differs from the independent one in alignment or NH; 0 with pair = 0.
+ * opts.clip: 0 (the default: every byte, every word of hgx_align_last*, every kernel launched and every byte copied as before) or
+ * N <= 255 (the rule in plain Python: tests/align_clip_ref.py).  A read that has an end-to-end alignment is searched and written as
+ * with 0, NH included.  A read that has none may be written with up to N bases soft-clipped in total: the search may stop on
+ * entry to any state right of the anchor (the rest of the read is clipped; where the backbone ends it must) and may start at any
+ * read base left of it (the bases in front are clipped); no known indel at a clip boundary.  NM <= max_edits over the aligned
+ * part; order (clipL + clipR, NM, indels, variants, locus, strand, pos0, list, clipL); NH = placements of the alignments with the
+ * smallest (clip total, NM); CIGAR [clipL]S..[clipR]S, SEQ / QUAL the whole oriented read, POS, NM, MD, Zs of the aligned part.  A
+ * record that 0 writes can change only in FLAG 0x8 / 0x20 / 0x2, RNEXT, PNEXT and YT, where its mate is aligned only now.
+ * clip < 0, clip > 255, clip with search != 0 or pair != 0 (neither keeps clip counts) and clip with max_edits > 4 are HGX_EINVAL.
+ * On the kernels' route the tier runs per chunk for the reads with anchors that the pick left unaligned (k_aln_clip_*); a read past
+ * a device limit declines with today's codes and the host route gives the bytes.
+ * align_last_clip: of the calling thread's last call, on the route that gave the bytes -- reads without an end-to-end alignment
+ * that the tier searched (they have an anchor), reads written with a clip, bases clipped; 0 with clip = 0. */
 typedef struct hgx_align_opts {
     int32_t max_edits, max_fragment, fastq, route;
     int32_t search;            /* 0 ways (the default), 1 states, 2 states_all */
     int32_t pair;              /* 0 independent (the default), 1 aware */
+    int32_t clip;              /* 0 end to end only (the default); N: a read without an end-to-end alignment may be written with up to N bases soft-clipped */
 } hgx_align_opts;
 typedef struct hgx_align_index hgx_align_index;
 int hgx_align_index_create(hgx_align_index **out, int32_t n_loci, const char *const *names, const char *const *backbones,
@@ -896,6 +912,7 @@ int hgx_align_reads(hgx_align_index *ix, int32_t n_inputs, const char *const *pa
 int hgx_align_last(int32_t *route, int64_t *reads, int64_t *aligned, int64_t *pairs_concordant, int32_t *decline_code);
 int hgx_align_last_states(int64_t *reads, int64_t *anchors, int64_t *cells);
 int hgx_align_last_pairs(int64_t *searched, int64_t *placed, int64_t *changed);
+int hgx_align_last_clip(int64_t *searched, int64_t *clipped, int64_t *bases);
 
 #ifdef __cplusplus
 }

@@ -1,8 +1,8 @@
 """Time the "hgx" aligner's device route against its host route: reads/s of AlignIndex.align, upload and copy
 back included, at a few read counts.
 
-    python tools/align_timing.py [--workload synth|tandem|paralog] [--search ways|states|states_all] [--pair] [--err 0.5]
-                                 [--reps 5] [--sizes 250,500,1000,2000,4000,16000,64000] [--tandem-indels 12] [--no-host]
+    python tools/align_timing.py [--workload synth|tandem|paralog|overhang] [--search ways|states|states_all] [--pair] [--clip N]
+                                 [--err 0.5] [--reps 5] [--sizes 250,500,1000,2000,4000,16000,64000] [--tandem-indels 12] [--no-host]
 
 --workload synth   simulated 100-base pairs of a synth HLA-like locus, at read counts round the route gate
 --workload tandem  150-base single reads across a GATA x 40 repeat with --tandem-indels known unit deletions and as many known
@@ -10,6 +10,11 @@ back included, at a few read counts.
                    pass the kernels' anchor slots: with --search ways the call goes to the host route (default --sizes 64).
 --workload paralog 100-base pairs of two loci that share a 300-base stretch (one base of the copy differs): mate 1 inside the
                    stretch, cut from either locus, mate 2 unique and 300 to 500 bases on at home (default --sizes 16000,64000)
+--workload overhang 100-base single reads tiled every 7 bases from 50 bases in front of a synth locus' backbone to 50 bases behind it
+                   (random bases outside), every fifth with a ten-base random tail, --err errors, cycled to the read count
+                   (default --sizes 16000,64000): the reads the clip tier exists for
+--clip N           time both routes with clip=N (hgx_align_opts.clip) beside clip=0 and print the counters of hgx_align_last_clip and
+                   the cost per 8 192-read chunk; the two clip texts are compared with each other, not with the clip=0 texts
 --pair             time the device route with pair="aware" beside pair="independent" (hgx_align_opts.pair) and print the pair
                    counters; the texts differ by design, so they are not compared with each other
 --search           the search form of the device-route call (hgx_align_opts.search).  The host route is timed with "ways" and,
@@ -105,6 +110,27 @@ def paralog_reads(n_pairs):
                 refGenes={"P": "P*BACKBONE", "Q": "Q*BACKBONE"}), texts
 
 
+def overhang_reads(err_percent, n_reads, read_len=100, step=7, tail_every=5):
+    """(reference dicts, [one FASTA text])"""
+    loc = synth.make_hla_like_locus(n_alleles=200, n_vars=1500, seed=5)
+    d = loc.reference_dicts()
+    rng = random.Random(11)
+    seq = lambda n: "".join(rng.choice("ACGT") for _ in range(n))          # noqa: E731
+    ext = seq(read_len) + loc.backbone.upper() + seq(read_len)
+    pool = []
+    for k, start in enumerate(range(read_len // 2, len(ext) - read_len - read_len // 2 + 1, step)):
+        r = list(ext[start:start + read_len])
+        if k % tail_every == 0:
+            r[-10:] = seq(10)
+        for i in range(read_len):
+            if rng.random() * 100.0 < err_percent:
+                r[i] = "ACGT"[("ACGT".index(r[i]) + rng.randrange(1, 4)) % 4]
+        pool.append("".join(r))
+    rng.shuffle(pool)
+    text = "".join(">o%d\n%s\n" % (k, pool[k % len(pool)]) for k in range(n_reads)).encode()
+    return d, [text]
+
+
 def timed(ix, texts, reps, **kw):
     out = ix.align(texts, **kw)                                       # warm-up
     last = align.align_last()
@@ -118,8 +144,9 @@ def timed(ix, texts, reps, **kw):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=("synth", "tandem", "paralog"), default="synth")
+    ap.add_argument("--workload", choices=("synth", "tandem", "paralog", "overhang"), default="synth")
     ap.add_argument("--pair", action="store_true", help="also time the device route with pair=\"aware\"")
+    ap.add_argument("--clip", type=int, default=0, help="also time both routes with clip=N")
     ap.add_argument("--search", choices=sorted(align.SEARCHES), default="ways")
     ap.add_argument("--err", type=float, default=0.5)
     ap.add_argument("--reps", type=int, default=5)
@@ -127,7 +154,8 @@ def main():
     ap.add_argument("--tandem-indels", type=int, default=12)
     ap.add_argument("--no-host", action="store_true", help="time the device-route call only")
     args = ap.parse_args()
-    sizes = args.sizes or {"synth": "250,500,1000,2000,4000,16000,64000", "tandem": "64", "paralog": "16000,64000"}[args.workload]
+    sizes = args.sizes or {"synth": "250,500,1000,2000,4000,16000,64000", "tandem": "64", "paralog": "16000,64000",
+                           "overhang": "16000,64000"}[args.workload]
     capi.set_device(0)
     search = {} if args.search == "ways" else {"search": args.search}
     configs = [("device " + args.search, dict(route="device", **search))]
@@ -138,15 +166,27 @@ def main():
     if args.pair:
         assert not search, "pair=\"aware\" needs --search ways"
         configs.insert(1, ("device ways pairs", dict(route="device", pair="aware")))
+    if args.clip:
+        assert not search and not args.pair, "clip needs --search ways and no --pair"
+        configs.append(("device ways clip", dict(route="device", clip=args.clip)))
+        if not args.no_host:
+            configs.append(("host ways clip", dict(route="host", clip=args.clip)))
     rows = []
     for n in [int(x) for x in sizes.split(",")]:
         d, texts = (reads_of(args.err, n // 2) if args.workload == "synth" else paralog_reads(n // 2) if args.workload == "paralog"
-                    else tandem_reads(args.tandem_indels, n))
+                    else overhang_reads(args.err, n) if args.workload == "overhang" else tandem_reads(args.tandem_indels, n))
         ix = align.AlignIndex(d["Genes"], d["Vars"], d["Var_list"], d["refGenes"])
-        outs, med = [], {}
+        outs, clip_outs, med = [], [], {}
         for name, kw in configs:
             out, last, ts = timed(ix, texts, args.reps, **kw)
-            if kw.get("pair") == "aware":
+            if kw.get("clip"):
+                base = name[:-5]
+                chunks = -(-n // 8192)
+                clip_outs.append(out)
+                print("%7d reads  %-18s clip %d: searched %d clipped %d bases %d; %+.3f ms per 8 192-read chunk against %s" % (
+                    n, name, kw["clip"], last["clip_searched"], last["clip_clipped"], last["clip_bases"],
+                    (statistics.median(ts) - med[base]) * 1e3 / chunks, base), flush=True)
+            elif kw.get("pair") == "aware":
                 chunks = -(-n // 8192)
                 print("%7d reads  %-18s pairs searched %d placed %d changed %d; %+.3f ms per 8 192-read chunk against %s" % (
                     n, name, last["pairs_searched"], last["pairs_placed"], last["pairs_changed"],
@@ -159,7 +199,7 @@ def main():
                       n, name, med[name] * 1e3, min(ts) * 1e3, max(ts) * 1e3, n / med[name], last["route"], last["decline"],
                       last["aligned"], last["states_reads"], last["states_anchors"], last["states_cells"]),
                   flush=True)
-        assert all(o == outs[0] for o in outs)
+        assert all(o == outs[0] for o in outs) and all(o == clip_outs[0] for o in clip_outs)
         rows.append((n, med[configs[0][0]], med.get("host ways")))
         ix.close()
     if args.workload == "synth" and not args.no_host:
