@@ -661,10 +661,14 @@ def test_level_classes_falls_back_to_per_pair_rows_on_a_list_key_collision(orc, 
 
 
 def test_pairs_with_hundreds_of_refs_and_very_wide_pieces(orc):
-    """No 255 ceilings (the reference has none, typing_core.py:1250-1270): pairs with 16 / 255 / 256 / 700 /
-    1500 add_count calls per level (the slab-wise 16-plane counters beyond 255, on their own and beside a short pair in the
-    two-pairs-per-wavefront kernel, in the two-level kernel and in the single-level one) and pieces spanning more than 255
-    variant words, bit-exact against the C oracle -- class rows of both levels and, through them, the row hashes' dedup."""
+    """No 255 ceilings (the reference has none, typing_core.py:1250-1270): pairs with 1 / 2 / 3 / 16 / 255 / 256 /
+    300 / 700 / 1500 add_count calls per level -- one piece PER LEVEL for each of them, so the pairs carry 4, 1400, 2, 32, 510,
+    512, 6, 3000, 600 and 4 refs in all, and it is that total by which the kernels choose their counters (<= 3, <= 15, <= 255,
+    slab-wise beyond).  This covers the slab-wise 16-plane counters, on their own and beside a short pair in the
+    two-pairs-per-wavefront kernel, in the two-level kernel and in the single-level one, and pieces spanning more than 255
+    variant words, bit-exact against the C oracle -- class rows of both levels and, through them, the row hashes' dedup.  No
+    pair here stands on a cut-off (3, 15, 16, 255 or 256 refs in all) and no allele reaches a counter's capacity: those edges
+    are tests/test_gpu_score_edges.py's."""
     from hisatgenotype_amd import synth
     loc = synth.make_hla_like_locus(n_alleles=2500, n_vars=9000, length=30000, seed=78, unlinked_vars=6)
     t = tables.oracle_tables(loc)
