@@ -24,7 +24,9 @@ class Result:
     """alleles: surviving allele ids, ascending; prob: their abundances; n_iter; first_class: lowest class index holding each
     survivor; prune_margin / stop_margin (inf when no such comparison was made); sv_failed; clamped; n_present: alleles in the
     estimate after every iteration; after_first_prune: allele ids in the estimate after iteration index 10 (None if the EM
-    never got there or does not prune)."""
+    never got there or does not prune); first_walked: the class at which each survivor entered the LAST dict (the reference's
+    result list keeps ties in that dict's order: (first_walked, key order), which is (first_class, key order) unless an earlier
+    class of the allele was skipped because none of its members had a positive value)."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -49,9 +51,12 @@ class Problem:
         self.cls = np.repeat(np.arange(len(self.counts)), self.size)
         self.cnt_el = self.counts[self.cls].astype(np.float64)
         self.starts = self.off[:-1]
+        self.on_step = None     # optional recorder: on_step(values [n], presence [n]) sees the INPUT of every application of the map
 
     # one application of the EM map (common:1311-1336) to (values, presence) over the compact alleles
     def _step(self, p, pres, ln):
+        if self.on_step is not None:
+            self.on_step(np.where(pres, p, 0.0), pres.copy())
         x = np.where(pres, p, 0.0)[self.cidx]
         s = np.add.reduceat(x, self.starts)
         ok = (s > 0.0)[self.cls] & pres[self.cidx]
@@ -59,6 +64,9 @@ class Problem:
         contrib[ok] = self.cnt_el[ok] * x[ok] / s[self.cls][ok]
         q = np.bincount(self.cidx, weights=contrib, minlength=self.n)
         qp = np.bincount(self.cidx, weights=ok, minlength=self.n) > 0
+        fw = np.full(self.n, -1, np.int64)
+        fw[self.cidx[ok][::-1]] = self.cls[ok][::-1]              # the class at which the allele enters the next dict
+        self._first_walked = fw
         return self._norm(q, qp, ln), qp
 
     @staticmethod
@@ -85,9 +93,10 @@ class Problem:
             keep = pres & (p >= thr)
             return np.where(keep, p, 0.0), keep
 
-        diff, it = 1.0, 0
+        diff, it, fw = 1.0, 0, np.full(n, -1, np.int64)
         while diff > STOP and it < MAX_ITER:
             p1, pr1 = self._step(p, pres, ln)
+            fw = self._first_walked
             p2, pr2 = self._step(p1, pr1, ln)
             if (pres & ~(pr1 & pr2)).any():
                 raise KeyError("reference KeyError (common:1365-1369)")
@@ -99,6 +108,7 @@ class Problem:
                 x = p - 2 * g * r + g * g * v
                 clamped |= bool((pres & (x < 0.0)).any())
                 p1, pr1 = self._step(np.where(pres, np.maximum(0.0, x), 0.0), pres.copy(), ln)
+                fw = self._first_walked
             else:
                 sv_failed = True
             diff = float(np.where(pr1, np.abs(p - p1), p)[pres].sum())
@@ -117,7 +127,7 @@ class Problem:
         first[self.cidx[::-1]] = self.cls[::-1]                  # (the lowest class index wins the last assignment)
         return Result(alleles=self.ids[pres], prob=out[pres], n_iter=it, first_class=first[pres], prune_margin=prune_margin,
                       stop_margin=stop_margin, sv_failed=sv_failed, clamped=clamped, n_present=n_present,
-                      after_first_prune=after_first)
+                      after_first_prune=after_first, first_walked=fw[pres])
 
     def without(self, alleles=(), classes=()):
         """The problem with the given allele ids cleared from every class and the given classes' counts zeroed.  (A class that
