@@ -2,9 +2,10 @@
 variants in `Vars` -- end to end, at most `max_edits` unknown mismatches, known variants free -- and written as SAM text in the
 dialect the front end consumes (NM, MD, Zs, NH, YT as simulate._truth_record renders them).
 
-It is NOT HISAT2 and its output is not compared with HISAT2's anywhere: no whole-genome index, no novel indels, no secondary
-records; mates placed independently unless pair="aware" (tests/align_pair_ref.py); soft clips only with clip=N, and only for a read
-that has no end-to-end alignment (tests/align_clip_ref.py).  The rules are stated in plain Python in tests/align_ref.py; the kernels
+It is NOT HISAT2 and its output is not compared with HISAT2's anywhere: no whole-genome index, no secondary records; mates placed
+independently unless pair="aware" (tests/align_pair_ref.py); soft clips only with clip=N, and only for a read that has no
+end-to-end alignment (tests/align_clip_ref.py); a novel indel only with gap=N, one per read, and only for a read that has no
+end-to-end alignment (tests/align_gap_ref.py).  The rules are stated in plain Python in tests/align_ref.py; the kernels
 (csrc/hgx_align.hip) and the host route (csrc/hgx_align_host.cpp) run one shared core (csrc/hgx_align_core.hpp, and csrc/hgx_align_states.hpp for the search over states).
 """
 import ctypes as C
@@ -17,11 +18,18 @@ SEARCHES = {"ways": 0, "states": 1, "states_all": 2}
 PAIRS = {"independent": 0, "aware": 1}
 NAMED_CLIP = 32                      # the clip budget of the aligner name "hgx.clip"
 CLIP_MAX, CLIP_MAX_EDITS = 255, 4    # HGX_ALN_CLIP_MAX, HGX_ALN_CLIP_EDITS of csrc/hgx_align_core.hpp
+NAMED_GAP = 16                       # the longest novel gap of the aligner name "hgx.gap"
+GAP_MAX = 16                         # HGX_ALN_GAP_MAX of include/hgx.h
 
 
 class AlignOpts(C.Structure):
     _fields_ = [("max_edits", C.c_int32), ("max_fragment", C.c_int32), ("fastq", C.c_int32), ("route", C.c_int32),
                 ("search", C.c_int32), ("pair", C.c_int32), ("clip", C.c_int32)]
+
+
+class AlignMore(C.Structure):
+    """hgx_align_more: the options behind hgx_align_opts (which keeps its seven words); `bytes` = sizeof."""
+    _fields_ = [("bytes", C.c_int32), ("gap", C.c_int32)]
 
 
 class AlignIndex:
@@ -49,7 +57,7 @@ class AlignIndex:
             (C.c_char_p * max(n, 1))(*vdata), (C.c_char_p * max(n, 1))(*vid)))
 
     def align(self, reads, max_edits=2, max_fragment=1000, fastq=None, route="auto", search="ways", pair="independent",
-              clip=0):
+              clip=0, gap=0):
         """SAM text (bytes) for `reads` = one or two FASTA / FASTQ[.gz] paths (str) or in-memory texts (bytes).  `search`: "ways"
         (per anchor, the ways through the known indels), "states" (reads that pass the kernels' anchor slots, stack or step limit
         -- on the host route: every read -- are searched over (read base, backbone position) states instead), "states_all" (every
@@ -60,19 +68,26 @@ class AlignIndex:
         a read WITHOUT an end-to-end alignment may be written with up to N bases soft-clipped in total (an overhang over a backbone
         end, a tail that does not match), by the order (clipped bases, then the usual key) of tests/align_clip_ref.py; a read that
         aligns end to end is written as with 0, except for the mate fields of a record whose mate is aligned only now.  Needs
-        search="ways", pair="independent" and max_edits <= 4."""
+        search="ways", pair="independent" and max_edits <= 4.  `gap`: 0 (no novel indels, every byte as before) or N <= 16: a read
+        WITHOUT an end-to-end alignment may be written with ONE novel deletion of up to N backbone bases or insertion of up to N read
+        bases, its length counted into NM <= max_edits, by the order of tests/align_gap_ref.py (the usual key, then the leftmost
+        gap); a read that aligns end to end is written as with 0, except for the mate fields of a record whose mate is aligned only
+        now.  Needs search="ways", pair="independent" and clip=0."""
         assert len(reads) in (1, 2)
         opts = AlignOpts(int(max_edits), int(max_fragment), -1 if fastq is None else int(bool(fastq)), ROUTES[route],
                          search if isinstance(search, int) else SEARCHES[search], pair if isinstance(pair, int) else PAIRS[pair], int(clip))
+        more = AlignMore(C.sizeof(AlignMore), int(gap))
         out_p, n = C.c_void_p(), C.c_size_t(0)
         if all(isinstance(r, str) for r in reads):
             paths = (C.c_char_p * len(reads))(*[r.encode() for r in reads])
-            rc = capi.lib().hgx_align_reads(self.h, C.c_int32(len(reads)), paths, None, None, C.byref(opts), C.byref(out_p), C.byref(n))
+            rc = capi.lib().hgx_align_reads_x(self.h, C.c_int32(len(reads)), paths, None, None, C.byref(opts), C.byref(more), C.byref(out_p),
+                                              C.byref(n))
         else:
             bufs = [bytes(r) for r in reads]
             texts = (C.c_char_p * len(bufs))(*bufs)
             sizes = (C.c_size_t * len(bufs))(*[len(b) for b in bufs])
-            rc = capi.lib().hgx_align_reads(self.h, C.c_int32(len(bufs)), None, texts, sizes, C.byref(opts), C.byref(out_p), C.byref(n))
+            rc = capi.lib().hgx_align_reads_x(self.h, C.c_int32(len(bufs)), None, texts, sizes, C.byref(opts), C.byref(more), C.byref(out_p),
+                                              C.byref(n))
         capi.check(rc)
         try:
             return C.string_at(out_p.value, n.value)
@@ -97,7 +112,8 @@ def align_last():
     hgx_align_states.hpp); states_* = the reads, anchors and table cells the states search took on that route; pairs_searched /
     pairs_placed / pairs_changed (pair="aware") = pairs with candidates on both mates, with a concordant combination, and with a
     record that differs from the independent one in alignment or NH; clip_searched / clip_clipped / clip_bases (clip=N) = reads
-    without an end-to-end alignment that the clip tier searched, reads written with a clip, bases clipped."""
+    without an end-to-end alignment that the clip tier searched, reads written with a clip, bases clipped; gap_searched /
+    gap_gapped / gap_bases (gap=N) = the same of the gap tier: reads searched, reads written with a novel gap, gap bases."""
     route, dec = C.c_int32(0), C.c_int32(0)
     reads, aligned, conc = C.c_int64(0), C.c_int64(0), C.c_int64(0)
     capi.check(capi.lib().hgx_align_last(C.byref(route), C.byref(reads), C.byref(aligned), C.byref(conc), C.byref(dec)))
@@ -107,16 +123,25 @@ def align_last():
     capi.check(capi.lib().hgx_align_last_pairs(C.byref(ps), C.byref(pp), C.byref(pc)))
     cs, cc, cb = C.c_int64(0), C.c_int64(0), C.c_int64(0)
     capi.check(capi.lib().hgx_align_last_clip(C.byref(cs), C.byref(cc), C.byref(cb)))
+    gs, gg, gb = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    capi.check(capi.lib().hgx_align_last_gap(C.byref(gs), C.byref(gg), C.byref(gb)))
     return dict(route=route.value, reads=reads.value, aligned=aligned.value, pairs_concordant=conc.value, decline=dec.value,
                 states_reads=sr.value, states_anchors=sa.value, states_cells=sc.value,
                 pairs_searched=ps.value, pairs_placed=pp.value, pairs_changed=pc.value,
-                clip_searched=cs.value, clip_clipped=cc.value, clip_bases=cb.value)
+                clip_searched=cs.value, clip_clipped=cc.value, clip_bases=cb.value,
+                gap_searched=gs.value, gap_gapped=gg.value, gap_bases=gb.value)
 
 
 def align_last_clip():
     """(searched, clipped, bases) of hgx_align_last_clip for the calling thread's last align()."""
     last = align_last()
     return last["clip_searched"], last["clip_clipped"], last["clip_bases"]
+
+
+def align_last_gap():
+    """(searched, gapped, bases) of hgx_align_last_gap for the calling thread's last align()."""
+    last = align_last()
+    return last["gap_searched"], last["gap_gapped"], last["gap_bases"]
 
 
 DECLINE_GATE, DECLINE_READ_LEN, DECLINE_ANCHORS, DECLINE_STACK, DECLINE_VARS, DECLINE_STEPS, DECLINE_SWITCH = 1, 2, 3, 4, 5, 6, 7

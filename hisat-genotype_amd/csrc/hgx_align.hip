@@ -11,6 +11,7 @@
 //   k_aln_emit     a lane per read, twice: record sizes, (exclusive scan,) then the SAM lines at their offsets; the pair's flags are
 //                  read off the mate's pick
 //   (opts.clip > 0 only) the clip tier between the picks and k_aln_emit: k_aln_clip_mark / _fill / _extend / _pick, below
+//   (hgx_align_more.gap > 0 only) the gap tier in the same place: the clip tier's mark and fill, k_aln_gap_extend / _pick, below
 // Every write is bounds-checked by construction: slots < HGX_ALN_DEV_ANCHORS, a record's bytes = the size the same code counted.
 //
 // opts.search != 0 adds a second tier, the search over STATES (hgx_align_states.hpp), for the reads of a chunk that are MARKED: in
@@ -226,8 +227,9 @@ k_aln_pair_pick(int nc, int max_fragment, const int32_t *cnt, const DevRes *res,
 }
 
 // out == nullptr: sizes[i] and flags[i] (1 aligned, 2 = mate 1 of a concordant pair); else the line at out + off[i].  CLIP
-// (opts.clip > 0): clipc[i] = the read's clip counts for the S ops; nullptr with clip = 0.
-template <bool CLIP> __global__ void __launch_bounds__(64)
+// (opts.clip > 0): clipc[i] = the read's clip counts for the S ops; nullptr with clip = 0.  GAP (gap > 0): clipc[i] = the read's gap
+// descriptor (0: none) instead.
+template <bool CLIP, bool GAP = false> __global__ void __launch_bounds__(64)
 k_aln_emit(hgx_aln_view V, DevReads rd, long first, int nc, int max_fragment, const DevRes *res, const int32_t *best, const int32_t *nh,
            uint32_t *sizes, int32_t *flags, const uint32_t *off, char *out, const uint32_t *clipc) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -246,10 +248,10 @@ k_aln_emit(hgx_aln_view V, DevReads rd, long first, int nc, int max_fragment, co
     }
     const long r = first + i;
     hgx_aln_out w{out ? out + off[i] : nullptr, 0};
-    const uint32_t cc = CLIP ? clipc[i] : 0;
-    hgx_aln_line<HGX_ALN_DEV_VARS, CLIP>(V, rd.text + rd.name_off[r], rd.name_len[r], rd.text + rd.seq_off[r],
-                                         rd.qual_off[r] >= 0 ? rd.text + rd.qual_off[r] : nullptr, rd.len[r], a, nh[i], mate, i & 1, max_fragment, w,
-                                         hgx_aln_clip_l(cc), hgx_aln_clip_r(cc));
+    const uint32_t cc = CLIP || GAP ? clipc[i] : 0;
+    hgx_aln_line<HGX_ALN_DEV_VARS, CLIP, GAP>(V, rd.text + rd.name_off[r], rd.name_len[r], rd.text + rd.seq_off[r],
+                                              rd.qual_off[r] >= 0 ? rd.text + rd.qual_off[r] : nullptr, rd.len[r], a, nh[i], mate, i & 1,
+                                              max_fragment, w, CLIP ? hgx_aln_clip_l(cc) : 0, CLIP ? hgx_aln_clip_r(cc) : 0, GAP ? cc : 0);
     if (!out) {
         sizes[i] = (uint32_t)w.n;
         flags[i] = 1 | ((rd.paired && !(i & 1) && hgx_aln_concordant(a, *mate, max_fragment)) ? 2 : 0);
@@ -345,6 +347,80 @@ int clip_tier(hgx_align_index *ix, const DevReads &rd, const hgx_align_opts *opt
         counts[0] += 1;
         counts[1] += clipc[i] != 0;
         counts[2] += hgx_aln_clip_total(clipc[i]);
+    }
+    return HGX_OK;
+}
+
+// ---- the gap tier (hgx_align_more.gap > 0; hgx_align_core.hpp "novel gaps") -------------------------------------------------------
+// For a chunk that holds a read with anchors that k_aln_pick left unaligned.  The marks, the scan and the compacted slots are the
+// clip tier's (k_aln_clip_mark, hgx_scan_u32_dev, k_aln_clip_fill: the same question, "which slots belong to a read without an
+// alignment"); then
+//   k_aln_gap_extend   a lane per compacted slot: the gap canon by the core's GAP walks into res[] and gds[].  Private memory per
+//                      lane: the outer and the inner walks' stacks (2 x 32 frames of 6 words) and lists (2 x 32), three side entries
+//                      of 37 words
+//   k_aln_gap_pick     a lane per read with nslot[i] > 0: the pick and NH over its slots, best[], nh[], gapc[] (the descriptor)
+// Every loop bound is the read length, the slot count, the longest gap, the options at a position or the step limit (one per side,
+// shared by its inner walks); every index is a slot below nc * HGX_ALN_DEV_ANCHORS or a compacted slot below the scan's total.
+__global__ void __launch_bounds__(64)
+k_aln_gap_extend(hgx_aln_view V, DevReads rd, long first, uint32_t total, int max_edits, int gap, const int32_t *compact, const int2 *anch,
+                 DevRes *res, uint32_t *gds, int *decline) {
+    const long j = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= (long)total) return;
+    const int32_t gid = compact[j];
+    const int i = gid / HGX_ALN_DEV_ANCHORS;
+    hgx_aln_frame stk[HGX_ALN_DEV_STK], stk2[HGX_ALN_DEV_STK];
+    int32_t cur[HGX_ALN_DEV_VARS], cur2[HGX_ALN_DEV_VARS];
+    hgx_aln_side<HGX_ALN_DEV_VARS> sides[3];
+    const int2 a = anch[gid];
+    const hgx_aln_read R{rd.text + rd.seq_off[first + i], rd.len[first + i], a.x >> 16};
+    uint32_t gd = 0;
+    const int rc = hgx_aln_gap_canon<HGX_ALN_DEV_STK, HGX_ALN_DEV_VARS>(V, R, a.x & 0xffff, a.y, max_edits, gap, HGX_ALN_DEV_STEPS, stk, cur, stk2,
+                                                                       cur2, sides, res[gid], &gd);
+    gds[gid] = gd;
+    if (rc) {
+        res[gid].ok = 0;
+        atomicMax(decline, rc);
+    }
+}
+
+__global__ void __launch_bounds__(64)
+k_aln_gap_pick(int nc, const uint32_t *nslot, const DevRes *res, const uint32_t *gds, int32_t *best, int32_t *nh, uint32_t *gapc) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nc || nslot[i] == 0) return;
+    int h = 0;
+    const int b = hgx_aln_gap_pick(res + (long)i * HGX_ALN_DEV_ANCHORS, (int)nslot[i], &h, gds + (long)i * HGX_ALN_DEV_ANCHORS);
+    best[i] = b;
+    nh[i] = h;
+    gapc[i] = b >= 0 ? gds[(long)i * HGX_ALN_DEV_ANCHORS + b] : 0u;
+}
+
+// the gap tier of one chunk, behind k_aln_pick: *decline != 0: the call goes to the host route
+int gap_tier(hgx_align_index *ix, const DevReads &rd, const hgx_align_opts *opts, int gap, long first, int nc, const int32_t *d_cnt,
+             const int2 *d_anch, DevRes *d_res, int32_t *d_best, int32_t *d_nh, uint32_t *d_gapc, uint32_t *d_nslot, uint32_t *d_soff, void *d_scan,
+             uint32_t *d_gds, int32_t *d_compact, int *d_decline, uint32_t *d_total, hipStream_t st, int64_t *counts, int *decline) {
+    k_aln_clip_mark<<<nblk(nc, 256), 256, 0, st>>>(nc, d_cnt, d_best, d_nslot);
+    HIPCHK(hipGetLastError());
+    const int rc = hgx_scan_u32_dev(d_nslot, d_soff, nc, d_scan, d_total, st);
+    if (rc) return rc;
+    uint32_t total = 0;
+    HIPCHK(hipMemcpy(&total, d_total, 4, hipMemcpyDeviceToHost));
+    if (!total) return HGX_OK;
+    k_aln_clip_fill<<<nblk((long)nc * HGX_ALN_DEV_ANCHORS, 256), 256, 0, st>>>(nc, d_nslot, d_soff, total, d_compact);
+    k_aln_gap_extend<<<nblk(total, 64), 64, 0, st>>>(ix->dv, rd, first, total, opts->max_edits, gap, d_compact, d_anch, d_res, d_gds, d_decline);
+    HIPCHK(hipGetLastError());
+    int dec = 0;
+    HIPCHK(hipMemcpy(&dec, d_decline, 4, hipMemcpyDeviceToHost));
+    if (dec) { *decline = dec; return HGX_OK; }
+    k_aln_gap_pick<<<nblk(nc, 64), 64, 0, st>>>(nc, d_nslot, d_res, d_gds, d_best, d_nh, d_gapc);
+    HIPCHK(hipGetLastError());
+    std::vector<uint32_t> nslot((size_t)nc), gapc((size_t)nc);
+    HIPCHK(hipMemcpy(nslot.data(), d_nslot, (size_t)nc * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(gapc.data(), d_gapc, (size_t)nc * 4, hipMemcpyDeviceToHost));
+    for (int i = 0; i < nc; ++i) {
+        if (!nslot[i]) continue;
+        counts[0] += 1;
+        counts[1] += gapc[i] != 0;
+        counts[2] += hgx_aln_gap_len(gapc[i]);
     }
     return HGX_OK;
 }
@@ -654,7 +730,7 @@ void hgx_align_device_free(hgx_align_index *ix) {
     ix->dev_ready = -1;
 }
 
-int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_align_opts *opts, std::string &body, int64_t *aligned,
+int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_align_opts *opts, int gap, std::string &body, int64_t *aligned,
                      int64_t *concordant, int *decline) {
     *decline = 0;
     const size_t body0 = body.size();
@@ -693,13 +769,13 @@ int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
     int *d_decline = d_misc.as<int>();
     uint32_t *d_total = d_misc.as<uint32_t>() + 1;
     const int clip = opts->clip;
-    DevBuf d_clipc, d_nslot, d_soff, d_clips, d_compact;
-    if (clip > 0) {
+    DevBuf d_clipc, d_nslot, d_soff, d_clips, d_compact;      // (the gap tier: the same buffers, descriptors for clip counts)
+    if (clip > 0 || gap > 0) {
         ALLOC(d_clipc, (size_t)cmax * 4); ALLOC(d_nslot, (size_t)cmax * 4); ALLOC(d_soff, (size_t)cmax * 4);
         ALLOC(d_clips, (size_t)cmax * HGX_ALN_DEV_ANCHORS * 4); ALLOC(d_compact, (size_t)cmax * HGX_ALN_DEV_ANCHORS * 4);
     }
-    const uint32_t *clipc = clip > 0 ? d_clipc.as<uint32_t>() : nullptr;
-    int64_t clip_counts[3] = {0, 0, 0};
+    const uint32_t *clipc = clip > 0 || gap > 0 ? d_clipc.as<uint32_t>() : nullptr;
+    int64_t clip_counts[3] = {0, 0, 0}, gap_counts[3] = {0, 0, 0};
     const bool pair_aware = reads.paired && opts->pair == 1;
     const size_t misc_bytes = pair_aware ? 40 : 16;
     int64_t pairs[3] = {0, 0, 0};
@@ -755,6 +831,21 @@ int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
             }
             k_aln_emit<true><<<nblk(nc, 64), 64, 0, st>>>(ix->dv, rd, first, nc, opts->max_fragment, d_res.as<DevRes>(), d_best.as<int32_t>(),
                                                           d_nh.as<int32_t>(), d_sizes.as<uint32_t>(), d_flags.as<int32_t>(), nullptr, nullptr, clipc);
+        } else if (gap > 0) {
+            HIPCHK(hipMemsetAsync(d_clipc.p, 0, (size_t)nc * 4, st));
+            rc = gap_tier(ix, rd, opts, gap, first, nc, d_cnt.as<int32_t>(), d_anch.as<int2>(), d_res.as<DevRes>(), d_best.as<int32_t>(),
+                          d_nh.as<int32_t>(), d_clipc.as<uint32_t>(), d_nslot.as<uint32_t>(), d_soff.as<uint32_t>(), d_scan.p,
+                          d_clips.as<uint32_t>(), d_compact.as<int32_t>(), d_decline, d_total, st, gap_counts, &dec);
+            if (rc) return rc;
+            if (dec) {
+                body.resize(body0);
+                *aligned = aligned0;
+                *concordant = concordant0;
+                *decline = dec;
+                return HGX_OK;
+            }
+            k_aln_emit<false, true><<<nblk(nc, 64), 64, 0, st>>>(ix->dv, rd, first, nc, opts->max_fragment, d_res.as<DevRes>(), d_best.as<int32_t>(),
+                                                                 d_nh.as<int32_t>(), d_sizes.as<uint32_t>(), d_flags.as<int32_t>(), nullptr, nullptr, clipc);
         } else
             k_aln_emit<false><<<nblk(nc, 64), 64, 0, st>>>(ix->dv, rd, first, nc, opts->max_fragment, d_res.as<DevRes>(), d_best.as<int32_t>(),
                                                            d_nh.as<int32_t>(), d_sizes.as<uint32_t>(), d_flags.as<int32_t>(), nullptr, nullptr, nullptr);
@@ -777,6 +868,10 @@ int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
             if (clip > 0)
                 k_aln_emit<true><<<nblk(nc, 64), 64, 0, st>>>(ix->dv, rd, first, nc, opts->max_fragment, d_res.as<DevRes>(), d_best.as<int32_t>(),
                                                               d_nh.as<int32_t>(), nullptr, nullptr, d_off.as<uint32_t>(), d_out.as<char>(), clipc);
+            else if (gap > 0)
+                k_aln_emit<false, true><<<nblk(nc, 64), 64, 0, st>>>(ix->dv, rd, first, nc, opts->max_fragment, d_res.as<DevRes>(),
+                                                                     d_best.as<int32_t>(), d_nh.as<int32_t>(), nullptr, nullptr, d_off.as<uint32_t>(),
+                                                                     d_out.as<char>(), clipc);
             else
                 k_aln_emit<false><<<nblk(nc, 64), 64, 0, st>>>(ix->dv, rd, first, nc, opts->max_fragment, d_res.as<DevRes>(), d_best.as<int32_t>(),
                                                                d_nh.as<int32_t>(), nullptr, nullptr, d_off.as<uint32_t>(), d_out.as<char>(), nullptr);
@@ -789,5 +884,6 @@ int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
     HIPCHK(hipStreamSynchronize(st));
     if (pair_aware) hgx_align_pairs_count(pairs[0], pairs[1], pairs[2]);
     if (clip > 0) hgx_align_clip_count(clip_counts[0], clip_counts[1], clip_counts[2]);
+    if (gap > 0) hgx_align_gap_count(gap_counts[0], gap_counts[1], gap_counts[2]);
     return HGX_OK;
 }

@@ -37,7 +37,8 @@ struct hgx_aln_reads {
 
 // the kernels' route: the records of `reads` appended to `body`, per-read flags (1 aligned, 2 concordant).  *decline != 0: nothing
 // was appended and the host route finishes the call.
-int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_align_opts *opts, std::string &body,
+// `gap`: hgx_align_more.gap (0: no gap tier).
+int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_align_opts *opts, int gap, std::string &body,
                      int64_t *aligned, int64_t *concordant, int *decline);
 void hgx_align_device_free(hgx_align_index *ix);
 
@@ -47,3 +48,5 @@ void hgx_align_states_count(int64_t reads, int64_t anchors, int64_t cells);
 void hgx_align_pairs_count(int64_t searched, int64_t placed, int64_t changed);
 // what the clip tier did in the calling thread's current call (hgx_align_last_clip): added to by the route that gives the bytes
 void hgx_align_clip_count(int64_t searched, int64_t clipped, int64_t bases);
+// what the gap tier did in the calling thread's current call (hgx_align_last_gap): added to by the route that gives the bytes
+void hgx_align_gap_count(int64_t searched, int64_t gapped, int64_t bases);

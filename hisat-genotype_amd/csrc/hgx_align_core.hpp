@@ -1,6 +1,6 @@
 // hgx_align_core.hpp -- the "hgx" aligner's per-anchor and per-read logic, compiled into the kernels
 // (hgx_align.hip) and into the host route (hgx_align_host.cpp).  The rules are stated in plain Python in tests/align_ref.py
-// (pair-aware placement: tests/align_pair_ref.py; soft clips: tests/align_clip_ref.py).
+// (pair-aware placement: tests/align_pair_ref.py; soft clips: tests/align_clip_ref.py; novel gaps: tests/align_gap_ref.py).
 //
 // An alignment of an oriented read at a locus = a start pos0 + an ordered list of known variants.  The walk of
 // simulate._truth_record consumes the read with them: at state (r, p), r > 0, at most one known insertion and one known deletion
@@ -160,6 +160,53 @@ HGX_ALN_HD inline void hgx_aln_clip_offer(hgx_aln_side<MAXV> &b, int clip, int n
     }
 }
 
+
+// ---- novel gaps (hgx_align_more.gap > 0; the rule in plain Python: tests/align_gap_ref.py) -----------------------------------------
+// The gap tier runs the same two walks with GAP = 1.  Such a walk is the plain enumeration with one edit of the budget held back
+// (a gap costs at least 1); it offers nothing at its own end.  On ENTRY to each state it runs, for every novel deletion and
+// insertion of 1 .. n bases that the edits left allow, an inner PLAIN walk (GAP = 2: the plain walk that also reports its steps)
+// from the state behind the gap, with a stack and a list of its own, and offers prefix + gap + the inner walk's best to the side's
+// best.  The prefix is fixed while the inner walk runs and every component of the order is a sum or a concatenation, so the inner
+// best gives the smallest way through that gap; costs only grow along a way, so the cut "partial cost (with the 1 held back)
+// passes the best found" stays lossless, and so does giving an inner walk no more edits than the best found leaves.  The gap is
+// not a pending frame of the depth-first stack (every state on a way would hold one).  The memo is off in the tier: an arrival
+// that a plain search may drop can still be the prefix of the smallest way with a gap.  All inner walks of a side share the side's
+// step limit.  The descriptor (read offset, kind, length) is the last component of the order; it packs into one word whose order
+// as a number is the descriptor's.
+#define HGX_ALN_GAP_MAX 16
+HGX_ALN_HD inline uint32_t hgx_aln_gap_pack(int r, int kind, int len) { return ((uint32_t)r << 8) | ((uint32_t)kind << 7) | (uint32_t)len; }
+HGX_ALN_HD inline int hgx_aln_gap_r(uint32_t gd) { return (int)(gd >> 8); }
+HGX_ALN_HD inline int hgx_aln_gap_kind(uint32_t gd) { return (int)((gd >> 7) & 1); }      // 0 deletion, 1 insertion
+HGX_ALN_HD inline int hgx_aln_gap_len(uint32_t gd) { return (int)(gd & 0x7f); }
+template <int MAXV> struct hgx_aln_gap_ctx {
+    hgx_aln_frame *stk;                        // the inner walks' scratch
+    int32_t *cur;
+    hgx_aln_side<MAXV> *inner;
+    int n;                                     // the longest gap
+    uint32_t gd;                               // the descriptor of the side's best
+    long used;                                 // steps the inner walks took
+};
+// prefix (nm, nind, the list in `pre`: backwards if `rev`, then in front of the inner list) + an optional single + the inner best
+// `in` against the side's best; returns true if it became the best
+template <int MAXV>
+HGX_ALN_HD inline bool hgx_aln_gap_offer(hgx_aln_side<MAXV> &b, uint32_t *bgd, int nm, int nind, const int32_t *pre, int npre, int32_t sv,
+                                         const hgx_aln_side<MAXV> &in, bool rev, uint32_t gd) {
+    const int nsv = sv >= 0, nl = npre + nsv + in.nl;
+    auto at = [&](int i) -> int32_t {
+        if (!rev) return i < npre ? pre[i] : in.vl[i - npre];
+        return i < in.nl ? in.vl[i] : (nsv && i == in.nl) ? sv : pre[npre - 1 - (i - in.nl - nsv)];
+    };
+    int c = b.found ? hgx_aln_cmp3(nm + in.nm, nind + in.nind, nl, b.nm, b.nind, b.nl) : -1;
+    if (c == 0 && rev && in.pos != b.pos) c = in.pos < b.pos ? -1 : 1;
+    for (int i = 0; c == 0 && i < nl; ++i) c = at(i) != b.vl[i] ? (at(i) < b.vl[i] ? -1 : 1) : 0;
+    if (c == 0 && gd != *bgd) c = gd < *bgd ? -1 : 1;
+    if (c >= 0) return false;
+    b.found = 1; b.nm = nm + in.nm; b.nind = nind + in.nind; b.nl = nl; b.pos = in.pos;
+    for (int i = 0; i < nl; ++i) b.vl[i] = at(i);
+    *bgd = gd;
+    return true;
+}
+
 // MEMO: what a route remembers about the states a side's search has reached through a known indel.  dominated(side, r, P, cost, list)
 // == true cuts the path: an earlier path reached the same state (side 0: (r, P) before its events; side 1: base r on P) with a
 // smaller cost, or the same cost and a list that sorts first -- every way to finish from here is then a way to finish from there
@@ -172,12 +219,20 @@ struct hgx_aln_no_memo {
 };
 
 // every way to finish from state (r0, P0), r0 > 0, inside the locus [lo, hi): the smallest by (NM, indels, variants, list)
-template <int MAXSTK, int MAXV, class MEMO, bool CLIP = false>
+// GAP = 1 (max_nm counts the gap; `gx`): the smallest with ONE novel gap, by (NM, indels, variants, list, descriptor)
+template <int MAXSTK, int MAXV, class MEMO, bool CLIP = false, int GAP = 0>
 HGX_ALN_HD int hgx_aln_right(const hgx_aln_view &V, const hgx_aln_read &R, int32_t hi, int r0, int32_t P0, int max_nm, long max_steps,
-                             hgx_aln_frame *stk, int32_t *cur, hgx_aln_side<MAXV> &best, MEMO &memo, int clip = 0) {
+                             hgx_aln_frame *stk, int32_t *cur, hgx_aln_side<MAXV> &best, MEMO &memo, int clip = 0,
+                             hgx_aln_gap_ctx<MAXV> *gx = nullptr) {
     int sp = 0;
     long steps = 0;
     if (!CLIP) best.found = 0;
+    if constexpr (GAP == 1) {
+        gx->gd = 0;
+        gx->used = 0;
+        if (max_nm < 1) return 0;
+    }
+    const int walk_nm = GAP == 1 ? max_nm - 1 : max_nm;
     int r = r0, nm = 0, nind = 0, nl = 0, k = 0;
     int32_t P = P0;
     for (;;) {
@@ -188,6 +243,26 @@ HGX_ALN_HD int hgx_aln_right(const hgx_aln_view &V, const hgx_aln_read &R, int32
         else if (P >= hi) dead = true;
         else {
             if (++steps > max_steps) return HGX_ALN_DECLINE_STEPS;
+            if constexpr (GAP == 1) {
+                if (steps + gx->used > max_steps) return HGX_ALN_DECLINE_STEPS;
+                if (k == 0) {                                        // the state is entered: the gap in front of its known indels
+                    hgx_aln_no_memo none;
+                    int room = (best.found ? best.nm : max_nm) - nm;   // edits left for the gap and what follows it
+                    for (int kind = 0; kind < 2; ++kind)
+                        for (int g = 1; g <= gx->n && g <= room; ++g) {
+                            const int r2 = kind ? r + g : r;
+                            const int32_t P2 = kind ? P : P + g;
+                            if (r2 >= R.L || P2 >= hi) break;
+                            const int rc = hgx_aln_right<MAXSTK, MAXV, hgx_aln_no_memo, false, 2>(
+                                V, R, hi, r2, P2, room - g, max_steps - steps - gx->used, gx->stk, gx->cur, *gx->inner, none, 0, gx);
+                            if (rc) return rc;
+                            if (!gx->inner->found) continue;
+                            if (nl + gx->inner->nl > MAXV) return HGX_ALN_DECLINE_VARS;
+                            if (hgx_aln_gap_offer(best, &gx->gd, nm + g, nind, cur, nl, -1, *gx->inner, false, hgx_aln_gap_pack(r, kind, g)))
+                                room = best.nm - nm;
+                        }
+                }
+            }
             const int nd = V.dls_off[P + 1] - V.dls_off[P], ni = V.ins_off[P + 1] - V.ins_off[P];
             const int nopt = 1 + nd + ni + nd * ni;
             if (k + 1 < nopt) {
@@ -225,7 +300,7 @@ HGX_ALN_HD int hgx_aln_right(const hgx_aln_view &V, const hgx_aln_read &R, int32
                 else {
                     int32_t sv = -1;
                     const int c = hgx_aln_base(V, R, rr, PP, &sv);
-                    if (c == 1) { if (++nm > max_nm) dead = true; }
+                    if (c == 1) { if (++nm > walk_nm) dead = true; }
                     else if (c == 2) {
                         if (nl == MAXV) return HGX_ALN_DECLINE_VARS;
                         cur[nl++] = sv;
@@ -233,8 +308,8 @@ HGX_ALN_HD int hgx_aln_right(const hgx_aln_view &V, const hgx_aln_read &R, int32
                     r = rr + 1;
                     P = PP + 1;
                     k = 0;
-                    if (!CLIP && !dead && best.found && hgx_aln_cmp3(nm, nind, nl, best.nm, best.nind, best.nl) > 0) dead = true;
-                    if (!CLIP && !dead && nind > 0 && r < R.L && memo.dominated(0, r, P, nm, nind, nl, cur)) dead = true;
+                    if (!CLIP && !dead && best.found && hgx_aln_cmp3(nm + (GAP == 1), nind, nl, best.nm, best.nind, best.nl) > 0) dead = true;
+                    if (!CLIP && GAP != 1 && !dead && nind > 0 && r < R.L && memo.dominated(0, r, P, nm, nind, nl, cur)) dead = true;
                 }
             }
         }
@@ -245,7 +320,7 @@ HGX_ALN_HD int hgx_aln_right(const hgx_aln_view &V, const hgx_aln_read &R, int32
             done = dead || done;
             dead = done;
         } else
-        if (done) {
+        if (done && GAP != 1) {
             int c = best.found ? hgx_aln_cmp3(nm, nind, nl, best.nm, best.nind, best.nl) : -1;
             for (int i = 0; c == 0 && i < nl; ++i) c = cur[i] != best.vl[i] ? (cur[i] < best.vl[i] ? -1 : 1) : 0;
             if (c < 0) {
@@ -259,17 +334,28 @@ HGX_ALN_HD int hgx_aln_right(const hgx_aln_view &V, const hgx_aln_read &R, int32
             r = f.r; P = f.P; nm = f.nm; nind = f.nind; nl = f.nl; k = f.k;
         }
     }
+    if constexpr (GAP == 2) gx->used += steps;
     return 0;
 }
 
 // every way to have arrived at "read base r0 sits on backbone base Q0" inside the locus [lo, hi): the smallest by
 // (NM, indels, variants, pos0, list).  `cur` holds the list backwards.
-template <int MAXSTK, int MAXV, class MEMO, bool CLIP = false>
+// GAP = 1: the smallest with ONE novel gap, by (NM, indels, variants, pos0, list, descriptor).  The mirror of the right side: the
+// state (r1, P1) from which an option's known events lead to "base r sits on Q" was itself reached by the gap, from (r1, P1 - g)
+// or from (r1 - g, P1), and that state was entered from the base in front of it.
+template <int MAXSTK, int MAXV, class MEMO, bool CLIP = false, int GAP = 0>
 HGX_ALN_HD int hgx_aln_left(const hgx_aln_view &V, const hgx_aln_read &R, int32_t lo, int r0, int32_t Q0, int max_nm, long max_steps,
-                            hgx_aln_frame *stk, int32_t *cur, hgx_aln_side<MAXV> &best, MEMO &memo, int clip = 0) {
+                            hgx_aln_frame *stk, int32_t *cur, hgx_aln_side<MAXV> &best, MEMO &memo, int clip = 0,
+                            hgx_aln_gap_ctx<MAXV> *gx = nullptr) {
     int sp = 0;
     long steps = 0;
     if (!CLIP) best.found = 0;
+    if constexpr (GAP == 1) {
+        gx->gd = 0;
+        gx->used = 0;
+        if (max_nm < 1) return 0;
+    }
+    const int walk_nm = GAP == 1 ? max_nm - 1 : max_nm;
     int r = r0, nm = 0, nind = 0, nl = 0, k = 0;
     int32_t Q = Q0;
     for (;;) {
@@ -279,6 +365,7 @@ HGX_ALN_HD int hgx_aln_left(const hgx_aln_view &V, const hgx_aln_read &R, int32_
         if (r == 0) done = true;
         else {
             if (++steps > max_steps) return HGX_ALN_DECLINE_STEPS;
+            if constexpr (GAP == 1) if (steps + gx->used > max_steps) return HGX_ALN_DECLINE_STEPS;
             const int nde = V.dle_off[Q + 1] - V.dle_off[Q], niq = V.ins_off[Q + 1] - V.ins_off[Q];
             int nopt = 1 + nde + niq;
             for (int j = 0; j < nde; ++j) {
@@ -319,11 +406,33 @@ HGX_ALN_HD int hgx_aln_left(const hgx_aln_view &V, const hgx_aln_read &R, int32_
                     cur[nl++] = v;
                     ++nind;
                 }
+                if constexpr (GAP == 1) {
+                    hgx_aln_no_memo none;
+                    int room = (best.found ? best.nm : max_nm) - nm;
+                    for (int kind = 0; kind < 2; ++kind)
+                        for (int g = 1; g <= gx->n && g <= room; ++g) {
+                            const int rg = kind ? r1 - g : r1;               // the state the gap was taken in
+                            const int32_t Pg = kind ? P1 : P1 - g;
+                            if (rg < 1 || Pg - 1 < lo) break;
+                            int32_t sv = -1;
+                            const int cb = hgx_aln_base(V, R, rg - 1, Pg - 1, &sv);
+                            const int e = g + (cb == 1);
+                            if (e > room) continue;
+                            const int rc = hgx_aln_left<MAXSTK, MAXV, hgx_aln_no_memo, false, 2>(
+                                V, R, lo, rg - 1, Pg - 1, room - e, max_steps - steps - gx->used, gx->stk, gx->cur, *gx->inner, none, 0, gx);
+                            if (rc) return rc;
+                            if (!gx->inner->found) continue;
+                            if (nl + (cb == 2) + gx->inner->nl > MAXV) return HGX_ALN_DECLINE_VARS;
+                            if (hgx_aln_gap_offer(best, &gx->gd, nm + e, nind, cur, nl, cb == 2 ? sv : -1, *gx->inner, true,
+                                                  hgx_aln_gap_pack(rg, kind, g)))
+                                room = best.nm - nm;
+                        }
+                }
                 if (P1 - 1 < lo) dead = true;
                 else {
                     int32_t sv = -1;
                     const int c = hgx_aln_base(V, R, r1 - 1, P1 - 1, &sv);
-                    if (c == 1) { if (++nm > max_nm) dead = true; }
+                    if (c == 1) { if (++nm > walk_nm) dead = true; }
                     else if (c == 2) {
                         if (nl == MAXV) return HGX_ALN_DECLINE_VARS;
                         cur[nl++] = sv;
@@ -331,8 +440,8 @@ HGX_ALN_HD int hgx_aln_left(const hgx_aln_view &V, const hgx_aln_read &R, int32_
                     r = r1 - 1;
                     Q = P1 - 1;
                     k = 0;
-                    if (!CLIP && !dead && best.found && hgx_aln_cmp3(nm, nind, nl, best.nm, best.nind, best.nl) > 0) dead = true;
-                    if (!CLIP && !dead && nind > 0 && r > 0 && memo.dominated(1, r, Q, nm, nind, nl, cur)) dead = true;
+                    if (!CLIP && !dead && best.found && hgx_aln_cmp3(nm + (GAP == 1), nind, nl, best.nm, best.nind, best.nl) > 0) dead = true;
+                    if (!CLIP && GAP != 1 && !dead && nind > 0 && r > 0 && memo.dominated(1, r, Q, nm, nind, nl, cur)) dead = true;
                 }
             }
         }
@@ -342,7 +451,7 @@ HGX_ALN_HD int hgx_aln_left(const hgx_aln_view &V, const hgx_aln_read &R, int32_
             done = dead || done;
             dead = done;
         } else
-        if (done) {
+        if (done && GAP != 1) {
             int c = best.found ? hgx_aln_cmp3(nm, nind, nl, best.nm, best.nind, best.nl) : -1;
             if (c == 0 && Q != best.pos) c = Q < best.pos ? -1 : 1;
             for (int i = 0; c == 0 && i < nl; ++i) {
@@ -360,6 +469,7 @@ HGX_ALN_HD int hgx_aln_left(const hgx_aln_view &V, const hgx_aln_read &R, int32_
             r = f.r; Q = f.P; nm = f.nm; nind = f.nind; nl = f.nl; k = f.k;
         }
     }
+    if constexpr (GAP == 2) gx->used += steps;
     return 0;
 }
 
@@ -385,6 +495,67 @@ HGX_ALN_HD int hgx_aln_canon(const hgx_aln_view &V, const hgx_aln_read &R, int o
     for (int i = 0; i < side.nl; ++i) res.vl[res.nvar + i] = side.vl[i];
     res.nm += side.nm; res.nind += side.nind; res.nvar += side.nl; res.end = side.pos;
     res.locus = g; res.strand = R.strand; res.ok = 1;
+    return 0;
+}
+
+// canon(a) of the gap tier: the smallest by (NM, indels, variants, pos0, list, descriptor) among the alignments through the anchor
+// with ONE novel gap of up to `gap` bases and NM <= max_edits, the gap counted.  The anchor's bases are plain matches, so the gap is
+// on one side: the canon is the smaller of (left side with the gap + plain right side) and (plain left side + right side with the
+// gap), each made of its sides' smallest as hgx_aln_canon's is.  stk / cur: the outer walks' scratch, stk2 / cur2: the inner
+// walks'; `sides`: three entries (the two sides' bests and the inner walks' best).
+template <int MAXSTK, int MAXV>
+HGX_ALN_HD int hgx_aln_gap_canon(const hgx_aln_view &V, const hgx_aln_read &R, int o, int32_t b, int max_edits, int gap, long max_steps,
+                                 hgx_aln_frame *stk, int32_t *cur, hgx_aln_frame *stk2, int32_t *cur2, hgx_aln_side<MAXV> *sides,
+                                 hgx_aln_res<MAXV> &res, uint32_t *gd_out) {
+    const int g = hgx_aln_locus_of(V, b);
+    const int32_t lo = V.bb_off[g], hi = V.bb_off[g + 1];
+    res.ok = 0;
+    *gd_out = 0;
+    if (max_edits < 1) return 0;
+    hgx_aln_no_memo memo;
+    hgx_aln_side<MAXV> &x = sides[0], &y = sides[1];
+    hgx_aln_gap_ctx<MAXV> gx{stk2, cur2, &sides[2], gap, 0, 0};
+    // the gap on the left
+    int rc = hgx_aln_left<MAXSTK, MAXV, hgx_aln_no_memo, false, 1>(V, R, lo, o, b, max_edits, max_steps, stk, cur, x, memo, 0, &gx);
+    if (rc) return rc;
+    if (x.found) {
+        rc = hgx_aln_right<MAXSTK, MAXV>(V, R, hi, o + HGX_ALN_K, b + HGX_ALN_K, max_edits - x.nm, max_steps, stk, cur, y, memo);
+        if (rc) return rc;
+        if (y.found) {
+            if (x.nl + y.nl > MAXV) return HGX_ALN_DECLINE_VARS;
+            for (int i = 0; i < x.nl; ++i) res.vl[i] = x.vl[i];
+            for (int i = 0; i < y.nl; ++i) res.vl[x.nl + i] = y.vl[i];
+            res.nm = x.nm + y.nm; res.nind = x.nind + y.nind; res.nvar = x.nl + y.nl; res.pos0 = x.pos; res.end = y.pos;
+            res.locus = g; res.strand = R.strand; res.ok = 1;
+            *gd_out = gx.gd;
+        }
+    }
+    // the gap on the right
+    rc = hgx_aln_left<MAXSTK, MAXV>(V, R, lo, o, b, max_edits - 1, max_steps, stk, cur, x, memo);
+    if (rc) return rc;
+    if (!x.found) return 0;
+    rc = hgx_aln_right<MAXSTK, MAXV, hgx_aln_no_memo, false, 1>(V, R, hi, o + HGX_ALN_K, b + HGX_ALN_K, max_edits - x.nm, max_steps, stk, cur,
+                                                                 y, memo, 0, &gx);
+    if (rc) return rc;
+    if (!y.found) return 0;
+    if (x.nl + y.nl > MAXV) return HGX_ALN_DECLINE_VARS;
+    int c = -1;
+    if (res.ok) {
+        c = hgx_aln_cmp3(x.nm + y.nm, x.nind + y.nind, x.nl + y.nl, res.nm, res.nind, res.nvar);
+        if (c == 0 && x.pos != res.pos0) c = x.pos < res.pos0 ? -1 : 1;
+        for (int i = 0; c == 0 && i < res.nvar; ++i) {
+            const int32_t u = i < x.nl ? x.vl[i] : y.vl[i - x.nl];
+            c = u != res.vl[i] ? (u < res.vl[i] ? -1 : 1) : 0;
+        }
+        if (c == 0) c = gx.gd < *gd_out ? -1 : 1;
+    }
+    if (c < 0) {
+        for (int i = 0; i < x.nl; ++i) res.vl[i] = x.vl[i];
+        for (int i = 0; i < y.nl; ++i) res.vl[x.nl + i] = y.vl[i];
+        res.nm = x.nm + y.nm; res.nind = x.nind + y.nind; res.nvar = x.nl + y.nl; res.pos0 = x.pos; res.end = y.pos;
+        res.locus = g; res.strand = R.strand; res.ok = 1;
+        *gd_out = gx.gd;
+    }
     return 0;
 }
 
@@ -510,6 +681,14 @@ HGX_ALN_HD int hgx_aln_pick(const hgx_aln_res<MAXV> *res, int n, int *nh_out, co
     *nh_out = nh;
     return best;
 }
+// the gap tier (gds[i] = the gap descriptor of res[i]): the plain pick and NH, and among the canons that equal the smallest in the
+// whole key the one with the smallest descriptor
+template <int MAXV> HGX_ALN_HD int hgx_aln_gap_pick(const hgx_aln_res<MAXV> *res, int n, int *nh_out, const uint32_t *gds) {
+    int best = hgx_aln_pick(res, n, nh_out);
+    for (int i = 0; best >= 0 && i < n; ++i)
+        if (res[i].ok && gds[i] < gds[best] && hgx_aln_res_cmp(res[i], res[best]) == 0) best = i;
+    return best;
+}
 
 // ---- the SAM record ----------------------------------------------------------------------------------------------------------------
 struct hgx_aln_out {                       // p == nullptr: count only
@@ -529,9 +708,12 @@ struct hgx_aln_out {                       // p == nullptr: count only
 // one of CIGAR (what = 0), MD (1), Zs (2) of the walk, as simulate._truth_record renders them; returns the number of Zs items
 // CLIP: the aligned part is read bases [clipL, L - clipR); the walk is that of the part alone (no indel in front of its first base,
 // the first Zs gap counts from it) and the CIGAR carries the two S ops around it.
-template <bool CLIP = false>
+// GAP: `gd` = the alignment's novel gap (0: none), written on entry to its state, in front of the known indels of the state it
+// leads to: D and ^bases for a deletion, I for an insertion, no Zs item (inserted bases count into the next item's gap, deleted
+// bases do not), as synth._align_read writes them.
+template <bool CLIP = false, bool GAP = false>
 HGX_ALN_HD inline int hgx_aln_walk_text(const hgx_aln_view &V, const hgx_aln_read &R, int32_t pos0, const int32_t *vl, int nvar, int what,
-                                        hgx_aln_out &out, int clipL = 0, int clipR = 0) {
+                                        hgx_aln_out &out, int clipL = 0, int clipR = 0, uint32_t gd = 0) {
     const int r_first = CLIP ? clipL : 0, r_end = CLIP ? R.L - clipR : R.L;
     int r = r_first, vi = 0, md_run = 0, gap = 0, n_zs = 0, run = 0;
     char op = 0;
@@ -553,6 +735,22 @@ HGX_ALN_HD inline int hgx_aln_walk_text(const hgx_aln_view &V, const hgx_aln_rea
     };
     if (CLIP && clipL > 0 && what == 0) { out.num(clipL); out.ch('S'); }
     while (r < r_end) {
+        if constexpr (GAP) {
+            if (gd && r == hgx_aln_gap_r(gd)) {
+                const int n = hgx_aln_gap_len(gd);
+                if (hgx_aln_gap_kind(gd) == 0) {
+                    if (what == 1) { out.num(md_run); out.ch('^'); out.str(V.bb + P, n); }
+                    md_run = 0;
+                    cigar('D', n);
+                    P += n;
+                } else {
+                    cigar('I', n);
+                    gap += n;
+                    r += n;
+                }
+                gd = 0;
+            }
+        }
         if (r > r_first) {
             const int32_t at = P;
             while (vi < nvar && V.vtype[vl[vi]] != HGX_ALN_SGL && V.vpos[vl[vi]] == at) {
@@ -636,10 +834,10 @@ template <class H> HGX_ALN_HD bool hgx_aln_covers(const H &x, int ix, const H &e
 }
 
 // the whole line (with its '\n'); `name` / `qual` as the file has them (qual == nullptr: 'I' x L)
-template <int MAXV, bool CLIP = false>
+template <int MAXV, bool CLIP = false, bool GAP = false>
 HGX_ALN_HD void hgx_aln_line(const hgx_aln_view &V, const char *name, int name_len, const char *seq, const char *qual, int L,
                              const hgx_aln_res<MAXV> &a, int nh, const hgx_aln_res<MAXV> *mate, int mate_no, int max_fragment,
-                             hgx_aln_out &out, int clipL = 0, int clipR = 0) {
+                             hgx_aln_out &out, int clipL = 0, int clipR = 0, uint32_t gd = 0) {
     const hgx_aln_read R{seq, L, a.strand};
     const int32_t lo = V.bb_off[a.locus];
     int flag = a.strand ? 16 : 0;
@@ -662,7 +860,7 @@ HGX_ALN_HD void hgx_aln_line(const hgx_aln_view &V, const char *name, int name_l
     out.str(V.pool + V.name_off[a.locus], V.name_len[a.locus]); out.ch('\t');
     out.num(a.pos0 - lo + 1); out.ch('\t');
     out.num(nh == 1 ? 60 : 1); out.ch('\t');
-    hgx_aln_walk_text<CLIP>(V, R, a.pos0, a.vl, a.nvar, 0, out, clipL, clipR); out.ch('\t');
+    hgx_aln_walk_text<CLIP, GAP>(V, R, a.pos0, a.vl, a.nvar, 0, out, clipL, clipR, gd); out.ch('\t');
     if (rnext == 0) out.ch('*');
     else if (rnext == 1) out.ch('=');
     else out.str(V.pool + V.name_off[mate->locus], V.name_len[mate->locus]);
@@ -674,11 +872,11 @@ HGX_ALN_HD void hgx_aln_line(const hgx_aln_view &V, const char *name, int name_l
     for (int r = 0; r < L; ++r) out.ch(qual ? qual[a.strand ? L - 1 - r : r] : 'I');
     out.str("\tNM:i:", 6); out.num(a.nm);
     out.str("\tMD:Z:", 6);
-    hgx_aln_walk_text<CLIP>(V, R, a.pos0, a.vl, a.nvar, 1, out, clipL, clipR);
+    hgx_aln_walk_text<CLIP, GAP>(V, R, a.pos0, a.vl, a.nvar, 1, out, clipL, clipR, gd);
     hgx_aln_out count{nullptr, 0};
-    if (hgx_aln_walk_text<CLIP>(V, R, a.pos0, a.vl, a.nvar, 2, count, clipL, clipR)) {
+    if (hgx_aln_walk_text<CLIP, GAP>(V, R, a.pos0, a.vl, a.nvar, 2, count, clipL, clipR, gd)) {
         out.str("\tZs:Z:", 6);
-        hgx_aln_walk_text<CLIP>(V, R, a.pos0, a.vl, a.nvar, 2, out, clipL, clipR);
+        hgx_aln_walk_text<CLIP, GAP>(V, R, a.pos0, a.vl, a.nvar, 2, out, clipL, clipR, gd);
     }
     out.str("\tNH:i:", 6); out.num(nh);
     out.str("\tYT:Z:", 6); out.str(yt, 2);

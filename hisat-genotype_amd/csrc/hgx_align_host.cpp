@@ -25,6 +25,7 @@ thread_local int64_t g_reads = 0, g_aligned = 0, g_conc = 0;
 thread_local int64_t g_st_reads = 0, g_st_anchors = 0, g_st_cells = 0;
 thread_local int64_t g_pr_searched = 0, g_pr_placed = 0, g_pr_changed = 0;
 thread_local int64_t g_cl_searched = 0, g_cl_clipped = 0, g_cl_bases = 0;
+thread_local int64_t g_gp_searched = 0, g_gp_gapped = 0, g_gp_bases = 0;
 
 template <class T> void csr(const std::vector<std::pair<int32_t, int32_t>> &items, int32_t n_pos, std::vector<T> &off, std::vector<T> &list) {
     off.assign((size_t)n_pos + 1, 0);
@@ -275,6 +276,52 @@ void align_one_clip(const hgx_aln_view &V, const char *seq, int L, int max_edits
     if (b >= 0) { best = C.res[(size_t)b]; *clips = C.clips[(size_t)b]; }
 }
 
+// the gap tier (hgx_align_more.gap > 0) for a read align_one found nothing for: the gap canons of the same anchors.  The memo is off,
+// as in the clip tier: it drops an arrival that a plain search never needs, and that arrival may be the prefix of the smallest way
+// with a gap (hgx_align_core.hpp).
+struct GapScratch {
+    std::vector<hgx_aln_frame> stk2;
+    std::vector<int32_t> cur2;
+    std::vector<hgx_aln_side<HGX_ALN_HOST_VARS>> sides;
+    std::vector<HostRes> res;
+    std::vector<uint32_t> gds;
+    GapScratch() : stk2(HGX_ALN_HOST_VARS), cur2(HGX_ALN_HOST_VARS), sides(3) {}
+};
+
+void align_one_gap(const hgx_aln_view &V, const char *seq, int L, int max_edits, int gap, HostScratch &S, GapScratch &G, HostRes &best, int *nh,
+                   uint32_t *gd, int *n_anchors, int *gave_up) {
+    G.res.clear();
+    G.gds.clear();
+    best.ok = 0;
+    *nh = 0;
+    *gd = 0;
+    for (int strand = 0; strand < 2; ++strand) {
+        const hgx_aln_read R{seq, L, strand};
+        const int n_off = hgx_aln_n_offsets(L);
+        for (int k = 0; k < n_off; ++k) {
+            const int o = hgx_aln_offset(L, k);
+            uint32_t code;
+            if (!hgx_aln_seed_code(R, o, &code)) continue;
+            for (uint32_t h = hgx_aln_hash(code) & V.hmask; V.hpos[h] >= 0; h = (h + 1) & V.hmask) {
+                if (V.hkey[h] != code) continue;
+                ++*n_anchors;
+                G.res.emplace_back();
+                G.gds.push_back(0);
+                const int rc = hgx_aln_gap_canon<HGX_ALN_HOST_VARS, HGX_ALN_HOST_VARS>(V, R, o, V.hpos[h], max_edits, gap, HGX_ALN_HOST_STEPS,
+                                                                                      S.stk.data(), S.cur.data(), G.stk2.data(), G.cur2.data(),
+                                                                                      G.sides.data(), G.res.back(), &G.gds.back());
+                if (rc) {                     // beyond the host route's own limits: left unaligned, as align_one does
+                    *gave_up = rc;
+                    return;
+                }
+                if (!G.res.back().ok) { G.res.pop_back(); G.gds.pop_back(); }
+            }
+        }
+    }
+    const int b = hgx_aln_gap_pick(G.res.data(), (int)G.res.size(), nh, G.gds.data());
+    if (b >= 0) { best = G.res[(size_t)b]; *gd = G.gds[(size_t)b]; }
+}
+
 // ---- the host route's states form (hgx_align_states.hpp): the same cells as the kernels, in loops --------------------------------
 struct StatesScratch {
     struct A { int32_t strand, locus; hgx_st_anchor a; };
@@ -410,14 +457,15 @@ bool pair_pick(PairScratch &S, int max_fragment, int *b1, int *b2, int *nh) {
     return true;
 }
 
-int host_route(const hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_align_opts *o, std::string &body, int64_t *aligned,
+int host_route(const hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_align_opts *o, int gap, std::string &body, int64_t *aligned,
                int64_t *conc, int *gave_up) {
     const hgx_aln_view &V = ix->hv;
     HostScratch S;
     StatesScratch SS;
     PairScratch PS;
     std::unique_ptr<ClipScratch> CS(o->clip > 0 ? new ClipScratch : nullptr);
-    uint32_t clips[2] = {0, 0};
+    std::unique_ptr<GapScratch> GS(gap > 0 ? new GapScratch : nullptr);
+    uint32_t clips[2] = {0, 0}, gds[2] = {0, 0};
     const int per = reads.paired ? 2 : 1;
     const bool pair_aware = per == 2 && o->pair == 1;
     std::vector<HostRes> best(per);
@@ -436,6 +484,12 @@ int host_route(const hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
                 int n_anchors = 0;
                 align_one_clip(V, seq, reads.len[k + m], o->max_edits, o->clip, S, *CS, best[m], &nh[m], &clips[m], &n_anchors, &gu);
                 if (n_anchors > 0) hgx_align_clip_count(1, best[m].ok && clips[m] != 0, best[m].ok ? hgx_aln_clip_total(clips[m]) : 0);
+            }
+            gds[m] = 0;
+            if (GS && !best[m].ok && !gu) {              // no end-to-end alignment: the gap tier over the same anchors
+                int n_anchors = 0;
+                align_one_gap(V, seq, reads.len[k + m], o->max_edits, gap, S, *GS, best[m], &nh[m], &gds[m], &n_anchors, &gu);
+                if (n_anchors > 0) hgx_align_gap_count(1, best[m].ok, best[m].ok ? hgx_aln_gap_len(gds[m]) : 0);
             }
             if (gu) *gave_up = gu;
         }
@@ -460,13 +514,22 @@ int host_route(const hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
             const char *qual = reads.qual_off[i] >= 0 ? reads.text.data() + reads.qual_off[i] : nullptr;
             const HostRes *mate = per == 2 ? &best[1 - m] : nullptr;
             const int cl = hgx_aln_clip_l(clips[m]), cr = hgx_aln_clip_r(clips[m]);
-            hgx_aln_out cnt{nullptr, 0};
-            hgx_aln_line<HGX_ALN_HOST_VARS, true>(V, reads.text.data() + reads.name_off[i], reads.name_len[i], reads.text.data() + reads.seq_off[i],
-                                                  qual, reads.len[i], best[m], nh[m], mate, m, o->max_fragment, cnt, cl, cr);
-            line.resize((size_t)cnt.n);
-            hgx_aln_out w{line.data(), 0};
-            hgx_aln_line<HGX_ALN_HOST_VARS, true>(V, reads.text.data() + reads.name_off[i], reads.name_len[i], reads.text.data() + reads.seq_off[i],
-                                                  qual, reads.len[i], best[m], nh[m], mate, m, o->max_fragment, w, cl, cr);
+            hgx_aln_out cnt{nullptr, 0}, w{nullptr, 0};
+            for (int pass = 0; pass < 2; ++pass) {       // the size, then the bytes
+                hgx_aln_out &dst = pass ? w : cnt;
+                if (gds[m])
+                    hgx_aln_line<HGX_ALN_HOST_VARS, false, true>(V, reads.text.data() + reads.name_off[i], reads.name_len[i],
+                                                                 reads.text.data() + reads.seq_off[i], qual, reads.len[i], best[m], nh[m], mate, m,
+                                                                 o->max_fragment, dst, 0, 0, gds[m]);
+                else
+                    hgx_aln_line<HGX_ALN_HOST_VARS, true>(V, reads.text.data() + reads.name_off[i], reads.name_len[i],
+                                                          reads.text.data() + reads.seq_off[i], qual, reads.len[i], best[m], nh[m], mate, m,
+                                                          o->max_fragment, dst, cl, cr);
+                if (!pass) {
+                    line.resize((size_t)cnt.n);
+                    w.p = line.data();
+                }
+            }
             body.append(line.data(), line.size());
         }
     }
@@ -484,6 +547,11 @@ void hgx_align_clip_count(int64_t searched, int64_t clipped, int64_t bases) {
     g_cl_clipped += clipped;
     g_cl_bases += bases;
 }
+void hgx_align_gap_count(int64_t searched, int64_t gapped, int64_t bases) {
+    g_gp_searched += searched;
+    g_gp_gapped += gapped;
+    g_gp_bases += bases;
+}
 void hgx_align_pairs_count(int64_t searched, int64_t placed, int64_t changed) {
     g_pr_searched += searched;
     g_pr_placed += placed;
@@ -495,7 +563,7 @@ void hgx_align_pairs_count(int64_t searched, int64_t placed, int64_t changed) {
 extern "C" void hgx_set_error(const char *fmt, ...) { va_list ap; va_start(ap, fmt); vfprintf(stderr, fmt, ap); va_end(ap); fputc('\n', stderr); }
 extern "C" const char *hgx_test_switch(const char *) { return "host"; }
 void *hgx_host_alloc(size_t bytes) { return malloc(bytes); }
-int hgx_align_device(hgx_align_index *, const hgx_aln_reads &, const hgx_align_opts *, std::string &, int64_t *, int64_t *, int *decline) {
+int hgx_align_device(hgx_align_index *, const hgx_aln_reads &, const hgx_align_opts *, int, std::string &, int64_t *, int64_t *, int *decline) {
     *decline = HGX_ALN_DECLINE_SWITCH;
     return HGX_OK;
 }
@@ -605,6 +673,22 @@ extern "C" int hgx_align_index_free(hgx_align_index *ix) {
 
 extern "C" int hgx_align_reads(hgx_align_index *ix, int32_t n_inputs, const char *const *paths, const char *const *texts,
                                const size_t *text_bytes, const hgx_align_opts *opts, char **sam_out, size_t *n_bytes_out) {
+    return hgx_align_reads_x(ix, n_inputs, paths, texts, text_bytes, opts, nullptr, sam_out, n_bytes_out);
+}
+
+extern "C" int hgx_align_reads_x(hgx_align_index *ix, int32_t n_inputs, const char *const *paths, const char *const *texts,
+                                 const size_t *text_bytes, const hgx_align_opts *opts, const hgx_align_more *more, char **sam_out,
+                                 size_t *n_bytes_out) {
+    // (`more` is read up to the fields this build knows and no further than more->bytes)
+    if (more && more->bytes < (int32_t)sizeof(hgx_align_more)) {
+        hgx_set_error("invalid argument: hgx_align_reads_x (more.bytes)");
+        return HGX_EINVAL;
+    }
+    const int gap = more ? more->gap : 0;
+    if (opts && (gap < 0 || gap > HGX_ALN_GAP_MAX || (gap && (opts->search || opts->pair || opts->clip)))) {      // (one fallback tier per call)
+        hgx_set_error("invalid argument: hgx_align_reads_x (gap)");
+        return HGX_EINVAL;
+    }
     if (!ix || (n_inputs != 1 && n_inputs != 2) || (!paths && !(texts && text_bytes)) || !opts || !sam_out || !n_bytes_out ||
         opts->max_edits < 0 || opts->route < 0 || opts->route > 2 || opts->search < 0 || opts->search > 2 ||
         opts->pair < 0 || opts->pair > 1 || (opts->pair && opts->search) ||      // (the states form keeps no candidates to pair)
@@ -619,6 +703,7 @@ extern "C" int hgx_align_reads(hgx_align_index *ix, int32_t n_inputs, const char
     g_st_reads = g_st_anchors = g_st_cells = 0;
     g_pr_searched = g_pr_placed = g_pr_changed = 0;
     g_cl_searched = g_cl_clipped = g_cl_bases = 0;
+    g_gp_searched = g_gp_gapped = g_gp_bases = 0;
     try {
         hgx_aln_reads reads;
         int rc = load_reads(n_inputs, paths, texts, text_bytes, opts->fastq, reads);
@@ -631,7 +716,7 @@ extern "C" int hgx_align_reads(hgx_align_index *ix, int32_t n_inputs, const char
         if (opts->route == 1 || (opts->route == 0 && sw && !strcmp(sw, "host"))) decline = HGX_ALN_DECLINE_SWITCH;
         else if (opts->route == 0 && !(sw && !strcmp(sw, "device")) && reads.n() < 1000) decline = HGX_ALN_DECLINE_GATE;
         if (!decline && reads.n() > 0) {
-            if ((rc = hgx_align_device(ix, reads, opts, body, &aligned, &conc, &decline))) return rc;
+            if ((rc = hgx_align_device(ix, reads, opts, gap, body, &aligned, &conc, &decline))) return rc;
         }
         if (decline) {
             body.clear();
@@ -639,8 +724,9 @@ extern "C" int hgx_align_reads(hgx_align_index *ix, int32_t n_inputs, const char
             g_st_reads = g_st_anchors = g_st_cells = 0;          // what the kernels took before they declined is not this call's answer
             g_pr_searched = g_pr_placed = g_pr_changed = 0;
             g_cl_searched = g_cl_clipped = g_cl_bases = 0;
+            g_gp_searched = g_gp_gapped = g_gp_bases = 0;
             int gave_up = 0;
-            if ((rc = host_route(ix, reads, opts, body, &aligned, &conc, &gave_up))) return rc;
+            if ((rc = host_route(ix, reads, opts, gap, body, &aligned, &conc, &gave_up))) return rc;
             if (gave_up) fprintf(stderr, "[hgx_align_reads] a read's search passed the host route's limits (code %d): left unaligned\n", gave_up);
         }
         g_route = decline ? 0 : 2;
@@ -689,5 +775,12 @@ extern "C" int hgx_align_last_clip(int64_t *searched, int64_t *clipped, int64_t 
     if (searched) *searched = g_cl_searched;
     if (clipped) *clipped = g_cl_clipped;
     if (bases) *bases = g_cl_bases;
+    return HGX_OK;
+}
+
+extern "C" int hgx_align_last_gap(int64_t *searched, int64_t *gapped, int64_t *bases) {
+    if (searched) *searched = g_gp_searched;
+    if (gapped) *gapped = g_gp_gapped;
+    if (bases) *bases = g_gp_bases;
     return HGX_OK;
 }

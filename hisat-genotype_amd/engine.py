@@ -655,4 +655,4 @@ def em_set_backend(backend):
     capi.check(capi.lib().hgx_em_set_backend(C.c_int(backend)))
 
 
-from .align import AlignIndex, align_last, align_last_clip          # noqa: E402,F401  (the "hgx" aligner)
+from .align import AlignIndex, align_last, align_last_clip, align_last_gap          # noqa: E402,F401  (the "hgx" aligner)

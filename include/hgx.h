@@ -846,9 +846,9 @@ int hgx_extract_close(hgx_extract *h);
 /* ---- the "hgx" aligner: reads of a locus family -> SAM text in the front end's dialect ------------------------------
  * Stands in for typing_common.align_reads (common:985-1056) for reads already known to belong to the loci: at most max_edits
  * unknown mismatches, known variants free; end to end, unless opts.clip > 0 (below) lets a read that has no end-to-end alignment
- * be written with soft-clipped ends; no whole-genome index, no novel indels, no secondary records, mates placed independently
- * (unless opts.pair = 1, below).  NOT HISAT2 and not compared with its output (its soft clipping, scored by --sp, included): the
- * rules are those of tests/align_ref.py, tests/align_pair_ref.py and tests/align_clip_ref.py.
+ * be written with soft-clipped ends; no whole-genome index, no novel indels (unless more.gap > 0, below, lets such a read be
+ * written with one), no secondary records, mates placed independently (unless opts.pair = 1, below).  NOT HISAT2 and not compared with its output (its soft clipping, scored by --sp, included): the
+ * rules are those of tests/align_ref.py, tests/align_pair_ref.py, tests/align_clip_ref.py and tests/align_gap_ref.py.
  * index_create (the `hisat2 -x <index>` argument of common:1013-1023: what the reads are aligned to): n_loci loci in the caller's
  * order, names[g] = the backbone's reference name, backbones[g] its bases; the variants of locus g are
  * var_off[g] .. var_off[g + 1] in Var_list order with var_type (0 insertion, 1 single, 2 deletion), var_pos (0-based backbone
@@ -895,13 +895,38 @@ int hgx_extract_close(hgx_extract *h);
  * On the kernels' route the tier runs per chunk for the reads with anchors that the pick left unaligned (k_aln_clip_*); a read past
  * a device limit declines with today's codes and the host route gives the bytes.
  * align_last_clip: of the calling thread's last call, on the route that gave the bytes -- reads without an end-to-end alignment
- * that the tier searched (they have an anchor), reads written with a clip, bases clipped; 0 with clip = 0. */
+ * that the tier searched (they have an anchor), reads written with a clip, bases clipped; 0 with clip = 0.
+ * align_reads_x: align_reads with further options in `more` (hgx_align_opts keeps its seven words: a caller compiled against them
+ * never has an eighth read).  more == NULL is align_reads; more->bytes = sizeof(hgx_align_more) of the caller's build, so that later
+ * options join without a new entry point (bytes smaller than the fields of this header: HGX_EINVAL).
+ * more.gap: 0 (the default: every byte, every word of hgx_align_last*, every kernel launched and every byte copied as before) or
+ * N <= 16 (the rule in plain Python: tests/align_gap_ref.py).  A read that has an end-to-end alignment is searched and written as
+ * with 0, NH included.  A read that has none may be written with ONE novel gap: on entry to a state (r, p), 0 < r < L, in front of
+ * the state's known indels, a novel deletion of 1 .. N backbone bases or a novel insertion of 1 .. N read bases (a base follows
+ * the gap on both sides; a gap at a read end would be a clip).  A gap of g bases adds g to NM, and NM <= max_edits with the gap
+ * counted (the front end drops NM > num_editdist: core:843); the anchor's 16 bases are plain matches, the gap lies left or right of
+ * them.  Order (NM, indels, variants, locus, strand, pos0, list, then the gap's read offset, kind -- deletion first -- and length:
+ * in a repeat the leftmost placement is the record); the gap does not count into indels; NH = placements of the alignments with
+ * the smallest NM.  The record is the one synth._align_read writes: I / D in the CIGAR, ^bases in MD for a deletion, no Zs item
+ * for the gap (inserted bases count into the next item's gap).  A record that 0 writes can change only in FLAG 0x8 / 0x20 / 0x2,
+ * RNEXT, PNEXT and YT, where its mate is aligned only now.
+ * gap < 0, gap > 16 and gap with search != 0, pair != 0 or clip != 0 (one fallback tier per call) are HGX_EINVAL.
+ * On the kernels' route the tier runs per chunk for the reads with anchors that the pick left unaligned (k_aln_gap_extend /
+ * k_aln_gap_pick behind the clip tier's mark and fill); a read past a device limit declines with today's codes and the host route
+ * gives the bytes.  NOT HISAT2's gap scoring (--rdg / --rfg), and not compared with it.
+ * align_last_gap: of the calling thread's last call, on the route that gave the bytes -- reads without an end-to-end alignment
+ * that the tier searched (they have an anchor), reads written with a gap, gap bases; 0 with gap = 0. */
 typedef struct hgx_align_opts {
     int32_t max_edits, max_fragment, fastq, route;
     int32_t search;            /* 0 ways (the default), 1 states, 2 states_all */
     int32_t pair;              /* 0 independent (the default), 1 aware */
     int32_t clip;              /* 0 end to end only (the default); N: a read without an end-to-end alignment may be written with up to N bases soft-clipped */
 } hgx_align_opts;
+#define HGX_ALN_GAP_MAX 16
+typedef struct hgx_align_more {
+    int32_t bytes;             /* sizeof(hgx_align_more) of the caller's build */
+    int32_t gap;               /* 0 no novel gaps (the default); N: a read without an end-to-end alignment may be written with one novel gap of up to N bases */
+} hgx_align_more;
 typedef struct hgx_align_index hgx_align_index;
 int hgx_align_index_create(hgx_align_index **out, int32_t n_loci, const char *const *names, const char *const *backbones,
                            const int32_t *var_off, const int32_t *var_type, const int32_t *var_pos, const char *const *var_data,
@@ -909,10 +934,14 @@ int hgx_align_index_create(hgx_align_index **out, int32_t n_loci, const char *co
 int hgx_align_index_free(hgx_align_index *ix);
 int hgx_align_reads(hgx_align_index *ix, int32_t n_inputs, const char *const *paths, const char *const *texts,
                     const size_t *text_bytes, const hgx_align_opts *opts, char **sam_out, size_t *n_bytes_out);
+int hgx_align_reads_x(hgx_align_index *ix, int32_t n_inputs, const char *const *paths, const char *const *texts,
+                      const size_t *text_bytes, const hgx_align_opts *opts, const hgx_align_more *more, char **sam_out,
+                      size_t *n_bytes_out);
 int hgx_align_last(int32_t *route, int64_t *reads, int64_t *aligned, int64_t *pairs_concordant, int32_t *decline_code);
 int hgx_align_last_states(int64_t *reads, int64_t *anchors, int64_t *cells);
 int hgx_align_last_pairs(int64_t *searched, int64_t *placed, int64_t *changed);
 int hgx_align_last_clip(int64_t *searched, int64_t *clipped, int64_t *bases);
+int hgx_align_last_gap(int64_t *searched, int64_t *gapped, int64_t *bases);
 
 #ifdef __cplusplus
 }

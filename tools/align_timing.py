@@ -1,7 +1,8 @@
 """Time the "hgx" aligner's device route against its host route: reads/s of AlignIndex.align, upload and copy
 back included, at a few read counts.
 
-    python tools/align_timing.py [--workload synth|tandem|paralog|overhang] [--search ways|states|states_all] [--pair] [--clip N]
+    python tools/align_timing.py [--workload synth|tandem|paralog|overhang|novel] [--search ways|states|states_all] [--pair] [--clip N]
+                                 [--gap N]
                                  [--err 0.5] [--reps 5] [--sizes 250,500,1000,2000,4000,16000,64000] [--tandem-indels 12] [--no-host]
 
 --workload synth   simulated 100-base pairs of a synth HLA-like locus, at read counts round the route gate
@@ -13,6 +14,11 @@ back included, at a few read counts.
 --workload overhang 100-base single reads tiled every 7 bases from 50 bases in front of a synth locus' backbone to 50 bases behind it
                    (random bases outside), every fifth with a ten-base random tail, --err errors, cycled to the read count
                    (default --sizes 16000,64000): the reads the clip tier exists for
+--workload novel   100-base pairs of synth.simulate_pairs over the synth locus, a tenth of the reads with a novel one-base deletion
+                   (novel_del_frac) and a tenth with a novel one- or two-base insertion (novel_ins_frac), --err errors, cycled to
+                   the read count (default --sizes 16000,64000): the reads the gap tier exists for
+--gap N            time both routes with gap=N (hgx_align_more.gap) beside gap=0 and print the counters of hgx_align_last_gap and the
+                   cost per 8 192-read chunk; the two gap texts are compared with each other, not with the gap=0 texts
 --clip N           time both routes with clip=N (hgx_align_opts.clip) beside clip=0 and print the counters of hgx_align_last_clip and
                    the cost per 8 192-read chunk; the two clip texts are compared with each other, not with the clip=0 texts
 --pair             time the device route with pair="aware" beside pair="independent" (hgx_align_opts.pair) and print the pair
@@ -131,6 +137,21 @@ def overhang_reads(err_percent, n_reads, read_len=100, step=7, tail_every=5):
     return d, [text]
 
 
+def novel_reads(err_percent, n_pairs, pool_pairs=2000, read_len=100):
+    """(reference dicts, [mate-1 FASTA, mate-2 FASTA])"""
+    loc = synth.make_hla_like_locus(n_alleles=200, n_vars=1500, seed=5)
+    d = loc.reference_dicts()
+    comp = {"A": "T", "C": "G", "G": "C", "T": "A"}
+    rc = lambda s: "".join(comp.get(b, b) for b in reversed(s))           # noqa: E731
+    als = synth.simulate_pairs(loc, loc.allele_names[1:7], pool_pairs, read_len=read_len, frag_len=(300, 400), err_rate=err_percent / 100.0,
+                               seed=13, novel_del_frac=0.1, novel_ins_frac=0.1)
+    mates = [[], []]
+    for a in als:
+        mates[0 if a.flag & 0x40 else 1].append((rc(a.seq) if a.flag & 0x10 else a.seq).upper())
+    texts = ["".join(">r%d\n%s\n" % (k, m[k % len(m)]) for k in range(n_pairs)).encode() for m in mates]
+    return d, texts
+
+
 def timed(ix, texts, reps, **kw):
     out = ix.align(texts, **kw)                                       # warm-up
     last = align.align_last()
@@ -144,9 +165,10 @@ def timed(ix, texts, reps, **kw):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=("synth", "tandem", "paralog", "overhang"), default="synth")
+    ap.add_argument("--workload", choices=("synth", "tandem", "paralog", "overhang", "novel"), default="synth")
     ap.add_argument("--pair", action="store_true", help="also time the device route with pair=\"aware\"")
     ap.add_argument("--clip", type=int, default=0, help="also time both routes with clip=N")
+    ap.add_argument("--gap", type=int, default=0, help="also time both routes with gap=N")
     ap.add_argument("--search", choices=sorted(align.SEARCHES), default="ways")
     ap.add_argument("--err", type=float, default=0.5)
     ap.add_argument("--reps", type=int, default=5)
@@ -155,7 +177,7 @@ def main():
     ap.add_argument("--no-host", action="store_true", help="time the device-route call only")
     args = ap.parse_args()
     sizes = args.sizes or {"synth": "250,500,1000,2000,4000,16000,64000", "tandem": "64", "paralog": "16000,64000",
-                           "overhang": "16000,64000"}[args.workload]
+                           "overhang": "16000,64000", "novel": "16000,64000"}[args.workload]
     capi.set_device(0)
     search = {} if args.search == "ways" else {"search": args.search}
     configs = [("device " + args.search, dict(route="device", **search))]
@@ -171,10 +193,16 @@ def main():
         configs.append(("device ways clip", dict(route="device", clip=args.clip)))
         if not args.no_host:
             configs.append(("host ways clip", dict(route="host", clip=args.clip)))
+    if args.gap:
+        assert not search and not args.pair and not args.clip, "gap needs --search ways, no --pair and no --clip"
+        configs.append(("device ways gap", dict(route="device", gap=args.gap)))
+        if not args.no_host:
+            configs.append(("host ways gap", dict(route="host", gap=args.gap)))
     rows = []
     for n in [int(x) for x in sizes.split(",")]:
         d, texts = (reads_of(args.err, n // 2) if args.workload == "synth" else paralog_reads(n // 2) if args.workload == "paralog"
-                    else overhang_reads(args.err, n) if args.workload == "overhang" else tandem_reads(args.tandem_indels, n))
+                    else overhang_reads(args.err, n) if args.workload == "overhang" else novel_reads(args.err, n // 2)
+                    if args.workload == "novel" else tandem_reads(args.tandem_indels, n))
         ix = align.AlignIndex(d["Genes"], d["Vars"], d["Var_list"], d["refGenes"])
         outs, clip_outs, med = [], [], {}
         for name, kw in configs:
@@ -185,6 +213,13 @@ def main():
                 clip_outs.append(out)
                 print("%7d reads  %-18s clip %d: searched %d clipped %d bases %d; %+.3f ms per 8 192-read chunk against %s" % (
                     n, name, kw["clip"], last["clip_searched"], last["clip_clipped"], last["clip_bases"],
+                    (statistics.median(ts) - med[base]) * 1e3 / chunks, base), flush=True)
+            elif kw.get("gap"):
+                base = name[:-4]
+                chunks = -(-n // 8192)
+                clip_outs.append(out)
+                print("%7d reads  %-18s gap %d: searched %d gapped %d bases %d; %+.3f ms per 8 192-read chunk against %s" % (
+                    n, name, kw["gap"], last["gap_searched"], last["gap_gapped"], last["gap_bases"],
                     (statistics.median(ts) - med[base]) * 1e3 / chunks, base), flush=True)
             elif kw.get("pair") == "aware":
                 chunks = -(-n // 8192)
