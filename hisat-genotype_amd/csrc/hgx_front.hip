@@ -927,7 +927,7 @@ int front_stages(const FeLocus &F, const DevInput &di, const hgx_parse_opts &o, 
     pools.cand_mask_off = b_cmoff.as<uint32_t>(); pools.cand_cap = (uint32_t)cand_cap; pools.cand_cursor = &ctl->cand_cursor;
     pools.mask_pool = b_mpool.as<uint32_t>(); pools.mask_cap = (uint32_t)mask_cap; pools.mask_cursor = &ctl->mask_cursor;
     pools.trace_pool = nullptr; pools.trace_cap = 0; pools.trace_cursor = &ctl->trace_cursor; pools.key_trace_off = nullptr;
-    const size_t trace_cap = (size_t)S * 96 + 4096;
+    const size_t trace_cap = (size_t)S * FE_TRACE_MAX_WORDS + 4096;       // (no key can outgrow its share: a trace never declines a call)
     const bool tracing = o.keep_trace && n_tasks == 1 && di.host_locus && trace_cap < (1ull << 31);
     if (tracing) {                                                    // (tests: the intermediates of every decoded key, see FePools)
         ALLOC(b_trace, trace_cap * 4);

@@ -929,6 +929,9 @@ struct FePools {
 };
 #define FE_HT_HDR 5
 #define FE_TRACE_HDR 6
+// the most one key's trace record holds (every scratch limit above at once): the trace pool is sized by it, so that a stream of long
+// reads on a dense locus (2x301: ~300 words a key) declines with the limit it met, not with FE_E_POOL -- or not at all
+#define FE_TRACE_MAX_WORDS (FE_TRACE_HDR + 7 * FE_MAX_CMP + 4 * FE_MAX_SIDE + 2 * FE_MAX_SIDE_IDS)
 #define FE_NO_TRACE 0xFFFFFFFFu
 
 #if defined(__HIP_DEVICE_COMPILE__)

@@ -189,7 +189,7 @@ int hgx_front_emulate(hgx_batch **out, hgx_locus &L, const hgx_front_input &in, 
     uint32_t trace_cur = 0;
     pools.trace_pool = nullptr; pools.trace_cap = 0; pools.trace_cursor = &trace_cur; pools.key_trace_off = nullptr;
     if (opts.keep_trace && n_tasks == 1) {
-        trace_pool.resize(S * 96 + 4096);
+        trace_pool.resize(S * FE_TRACE_MAX_WORDS + 4096);
         trace_off.assign(std::max<size_t>(S, 1), FE_NO_TRACE);
         pools.trace_pool = trace_pool.data(); pools.trace_cap = (uint32_t)trace_pool.size(); pools.key_trace_off = trace_off.data();
     }

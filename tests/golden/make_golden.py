@@ -397,6 +397,125 @@ def codis_d18s51():
     return dict(locus=loc, sample=sample, al=al, simulation=True, read_len=100, frag_len=250)
 
 
+# ---- long and odd-length reads, and the device front end's fixed scratch limits (golden_util.LONG) ----------------------------
+@scenario
+def hla_long_251():
+    """2x251 (MiSeq): an odd length, longer than the device decode's staging of a text SEQ, shorter than that of a packed one."""
+    loc = synth.make_hla_like_locus(n_alleles=120, n_vars=500, seed=41, insertion_frac=0.08, deletion_frac=0.1)
+    sample = synth.pick_sample(loc, 7)
+    al = synth.simulate_pairs(loc, sample, 120, read_len=251, frag_len=(450, 600), err_rate=0.004, seed=12,
+                              novel_ins_frac=0.05, novel_del_frac=0.03, softclip_frac=0.05)
+    return dict(locus=loc, sample=sample, al=al, simulation=False, read_len=251, frag_len=525)
+
+
+LEN_EDGES = (75, 171, 172, 173, 251, 343, 344, 345)
+
+
+@scenario
+def hla_len_edges():
+    """One stream of eight read lengths around the staging limits (172 | 173 text bases, 344 | 345 packed ones), lengths that are
+    no multiple of 4 (text) or 8 (packed) among them.  One simulate_pairs call per length; the names ("e<k>_len<n>") put the
+    lengths in turn, record group by record group, so neighbours in the stream never share a length."""
+    loc = synth.make_hla_like_locus(n_alleles=100, n_vars=450, seed=42, insertion_frac=0.05, deletion_frac=0.1)
+    sample = synth.pick_sample(loc, 8)
+    al = []
+    for j, n in enumerate(LEN_EDGES):
+        part = synth.simulate_pairs(loc, sample, 16, read_len=n, frag_len=(max(n, 300) + 20, max(n, 300) + 150), err_rate=0.004,
+                                    seed=50 + j, novel_ins_frac=0.05, novel_del_frac=0.05, softclip_frac=0.08)
+        for a in part:
+            k = int(a.qname[1:]) - 1
+            a.qname = "e%03d_len%d" % (k * len(LEN_EDGES) + j, n)
+        al += part
+    return dict(locus=loc, sample=sample, al=al, simulation=False, read_len=345, frag_len=450)
+
+
+@scenario
+def hla_dense_301(n_vars=2400):
+    """2x301 on a locus dense enough for cmp_list to outgrow the device front end's FE_MAX_CMP on some records."""
+    loc = synth.make_hla_like_locus(n_alleles=64, n_vars=n_vars, seed=43, sibling_frac=0.2, insertion_frac=0.08, deletion_frac=0.15)
+    sample = synth.pick_sample(loc, 10)
+    al = synth.simulate_pairs(loc, sample, 150, read_len=301, frag_len=(500, 700), err_rate=0.003, seed=13)
+    return dict(locus=loc, sample=sample, al=al, simulation=False, read_len=301, frag_len=600)
+
+
+def _hybrid_read(loc, qname, var_idx, start, read_len=301, softclip=(0, 0)):
+    """One error-free single-end read of an allele that carries exactly the known variants `var_idx` (as hla_novel_sample builds its
+    recombinant), from allele base `start` on."""
+    import random
+    hyb = copy.deepcopy(loc)
+    name = "%s*98:01:01:01" % loc.gene
+    hyb.allele_vars[name] = sorted(var_idx)
+    pos, cigar, seq, md, zs, nm = synth._align_read(synth.AlleleMap(hyb, name), start, read_len, random.Random(1), 0.0, softclip)
+    return synth.Alignment(qname=qname, flag=0, pos=pos, cigar=cigar, seq=seq, md=md, zs=zs, nm=nm, mate_pos=pos)
+
+
+def _spaced(loc, kind, lo, min_gap):
+    """Variants of one kind from backbone position `lo` on, one per position, at least `min_gap` bases between two of them."""
+    out, last = [], -10**9
+    for vi, (t, p, d) in enumerate(zip(loc.var_type, loc.var_pos, loc.var_data)):
+        right = p + int(d) if t == "deletion" else p + 1
+        if t == kind and p >= lo and p >= last + min_gap:
+            out.append(vi)
+            last = right
+    return out
+
+
+CAP_M = (30, 31, 32, 33, 34)
+
+
+@scenario
+def hla_cap_cmp():
+    """Single-end reads whose cmp_list2 crosses the device front end's FE_MAX_CMP = 64 one entry at a time: read "c<m>a" carries m
+    known SNPs at non-adjacent positions (match, mismatch, ..., match: 2m + 1 entries), read "c<m>b" starts ON its first SNP (2m)."""
+    loc = synth.make_hla_like_locus(n_alleles=80, n_vars=1500, seed=44, deletion_frac=0.0, multi_allelic_frac=0.0)
+    sample = synth.pick_sample(loc, 10)
+    snps = _spaced(loc, "single", 600, 3)
+    al = []
+    for m in CAP_M:
+        p0 = loc.var_pos[snps[0]]
+        assert loc.var_pos[snps[m - 1]] < p0 + 290
+        al.append(_hybrid_read(loc, "c%da" % m, snps[:m], p0 - 5))
+        al.append(_hybrid_read(loc, "c%db" % m, snps[:m], p0))
+    return dict(locus=loc, sample=sample, al=al, simulation=False, error_correction=False, allow_discordant=True, read_len=301)
+
+
+CAP_D = (10, 11, 12, 13)
+
+
+@scenario
+def hla_cap_ops():
+    """The same for FE_MAX_OPS = 24 CIGAR ops: read "d<n>" spans n known deletions (2n + 1 ops: 21, 23, 25, 27); "d11s" adds a soft
+    clip in front of 11 deletions (24 ops, the most the device takes)."""
+    loc = synth.make_hla_like_locus(n_alleles=80, n_vars=1500, seed=45, deletion_frac=0.35, multi_allelic_frac=0.0)
+    sample = synth.pick_sample(loc, 11)
+    dels = _spaced(loc, "deletion", 600, 8)
+    p0 = loc.var_pos[dels[0]]
+    assert loc.var_pos[dels[CAP_D[-1] - 1]] < p0 + 250
+    al = [_hybrid_read(loc, "d%d" % d, dels[:d], p0 - 12) for d in CAP_D]
+    al.append(_hybrid_read(loc, "d11s", dels[:11], p0 - 12, softclip=(4, 0)))
+    return dict(locus=loc, sample=sample, al=al, simulation=False, error_correction=False, allow_discordant=True, read_len=301)
+
+
+CAP_Z = (46, 47, 48, 49, 50)
+
+
+@scenario
+def hla_cap_zs():
+    """The same for FE_MAX_ZS = 48 Zs items (and FE_MAX_MID = 48 ids between cmp_left and cmp_right): on a locus with a known SNP at
+    85 % of its positions read "z<n>" carries n SNPs at the n consecutive variant sites with the fewest gaps between them -- runs of
+    adjacent mismatches, so cmp_list2 stays far below FE_MAX_CMP."""
+    loc = synth.make_hla_like_locus(n_alleles=80, n_vars=3000, seed=46, deletion_frac=0.0, multi_allelic_frac=0.0)
+    sample = synth.pick_sample(loc, 12)
+    z_max = CAP_Z[-1]
+    sites = [vi for vi, p in enumerate(loc.var_pos) if p >= 400]
+    runs = lambda sel: sum(1 for a, b in zip(sel, sel[1:]) if loc.var_pos[b] != loc.var_pos[a] + 1)
+    first = min(range(len(sites) - z_max), key=lambda i: (runs(sites[i:i + z_max]), i))
+    sel = sites[first:first + z_max]
+    assert loc.var_pos[sel[-1]] - loc.var_pos[sel[0]] < 250
+    al = [_hybrid_read(loc, "z%d" % z, sel[:z], loc.var_pos[sel[0]] - 20) for z in CAP_Z]
+    return dict(locus=loc, sample=sample, al=al, simulation=False, error_correction=False, allow_discordant=True, read_len=301)
+
+
 def main():
     names = sys.argv[1:] or list(SCENARIOS)
     tmp = setup_reference()

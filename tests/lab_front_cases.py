@@ -87,6 +87,148 @@ def test_emulated_kernels_against_the_reference_per_record(name, tmp_path):
         check_trace(fx, b)
 
 
+def _three_routes(fx, pl, tmp_path, sam=None, **kw):
+    """The key route, the record route from text and the record route from a coordinate-sorted BAM (binary CIGAR, packed SEQ) of one
+    stream: [(batch, record-route decline, key-route decline)]."""
+    from hisatgenotype_amd import bamio
+    loc = fx["_locus"]
+    sam = fx["sam"] if sam is None else sam
+    p_bam = str(tmp_path / "s.bam")
+    bamio.write_bam_native(p_bam, sam.encode(), [(loc.ref_allele, len(loc.backbone))], sort_by_coordinate=True)
+    emu, dec = emulated(pl, sam, **kw)
+    out = [(emu, dec, dec)]
+    for run in (dict(sam=sam), dict(path=p_bam, regions=loc.ref_allele)):
+        emu, dec = emulated_records(pl, **run, **kw)
+        out.append((emu,) + dec)
+    return out
+
+
+def _long_kw(fx):
+    o = fx["options"]
+    return dict(num_editdist=o["num_editdist"], error_correction=o["error_correction"], allow_discordant=o["allow_discordant"],
+                simulation=o["simulation"], keep_trace=True)
+
+
+@pytest.mark.parametrize("name", gu.LONG_TAKEN)
+def test_emulated_stages_on_long_and_odd_length_reads(name, tmp_path):
+    """2x251 and the stream of lengths 75 .. 345 (odd lengths: the last byte of a packed SEQ holds one base; FeSeq::at, fe_rec_key,
+    the 32-byte / 8-byte / tail stages of fe_hash_bytes at many residues): taken by all three routes, the host's batch, the
+    reference's per-record trace and pileup."""
+    from trace_util import check_pileup, check_trace
+    fx = gu.load(name)
+    pl = hl.PackedLocus.from_synth(fx["_locus"])
+    kw = _long_kw(fx)
+    host = pl.parse_sam(fx["sam"], **kw)
+    for emu, dec_r, dec_k in _three_routes(fx, pl, tmp_path, **kw):
+        assert (dec_r, dec_k) == (0, 0)
+        same_batch(host, emu, len(fx["_locus"].backbone))
+        check_pileup(fx, emu)
+        check_trace(fx, emu)
+
+
+def nibble_case(fx, tmp_path):
+    """hla_long_251 with every 9th line twice (the second is dropped as a duplicate line of its mate) as a coordinate-sorted BAM, and
+    the same BAM with the unused low nibble of every odd-length SEQ set, differently from record to record: the two lines of a
+    duplicate then differ in that nibble and nothing else."""
+    from hisatgenotype_amd import bamio
+    loc = fx["_locus"]
+    lines = [l for l in fx["sam"].split("\n") if l]
+    sam = "".join(l + "\n" + (l + "\n" if k % 9 == 0 else "") for k, l in enumerate(lines))
+    p_clean, p_junk = str(tmp_path / "clean.bam"), str(tmp_path / "junk.bam")
+    bamio.write_bam_native(p_clean, sam.encode(), [(loc.ref_allele, len(loc.backbone))], sort_by_coordinate=True)
+    assert gu.junk_nibble_bam(p_clean, p_junk) > len(lines) * 3 // 4
+    return sam, p_clean, p_junk
+
+
+def test_unused_nibble_of_an_odd_packed_seq_is_no_part_of_the_read(tmp_path):
+    """FeSeq::at, the pileup and fe_rec_key / fe_rec_same_key leave the low nibble of an odd length's last byte alone: a BAM whose
+    writer left something there gives the batch and the trace of the clean one, duplicates that differ only there are one key (a
+    key compare that looked at the nibble would report two pieces of one hash: decline 5)."""
+    fx = gu.load("hla_long_251")
+    loc = fx["_locus"]
+    pl = hl.PackedLocus.from_synth(loc)
+    kw = _long_kw(fx)
+    sam, p_clean, p_junk = nibble_case(fx, tmp_path)
+    host = pl.parse_sam(sam, **kw)
+    assert host.n_reads == len(fx["records"])                   # (the second line of a duplicate counts for nothing)
+    for path in (p_clean, p_junk):
+        same_batch(host, pl.parse_alignment_file(path, loc.ref_allele, **{k: v for k, v in kw.items() if k != "keep_trace"}), len(loc.backbone))
+        emu, dec = emulated_records(pl, path=path, regions=loc.ref_allele, **kw)
+        assert dec == (0, 0), (path, dec)
+        same_batch(host, emu, len(loc.backbone))
+        assert emu.trace_text() == host.trace_text()
+
+
+def test_emulated_stages_decline_a_dense_long_read_sample_with_the_cap_code(tmp_path):
+    """hla_dense_301: some record's cmp_list outgrows FE_MAX_CMP; both device routes decline with FE_E_CAP -- not with the trace pool's
+    FE_E_POOL, which a stream of such reads met first while that pool was sized at 96 words a key -- and the host stages return the
+    batch the host front end makes of it, with the reference's trace."""
+    from trace_util import check_pileup, check_trace
+    fx = gu.load("hla_dense_301")
+    pl = hl.PackedLocus.from_synth(fx["_locus"])
+    kw = _long_kw(fx)
+    host = pl.parse_sam(fx["sam"], **kw)
+    for emu, dec_r, dec_k in _three_routes(fx, pl, tmp_path, **kw):
+        assert (dec_r, dec_k) == (gu.FE_E_CAP, gu.FE_E_CAP)
+        same_batch(host, emu, len(fx["_locus"].backbone))
+        check_pileup(fx, emu)
+        check_trace(fx, emu)
+
+
+@pytest.mark.parametrize("name", sorted(gu.LONG_FAMILIES))
+def test_emulated_stages_take_a_cap_family_up_to_the_limit_and_decline_beyond(name, tmp_path):
+    """hla_cap_cmp / hla_cap_ops / hla_cap_zs, one read per call: the emulation takes exactly the members whose RECORDED cmp_list2 has at
+    most FE_MAX_CMP entries (whose CIGAR has at most FE_MAX_OPS ops, whose Zs tag at most FE_MAX_ZS items) and declines the others with FE_E_CAP; taken or not, the batch is the
+    host's and the trace line is the reference's.  The whole family in one stream declines."""
+    from trace_util import fmt_record
+    fx = gu.load(name)
+    kind = gu.LONG_FAMILIES[name]
+    pl = hl.PackedLocus.from_synth(fx["_locus"])
+    kw = _long_kw(fx)
+    n_taken = n_declined = 0
+    for qname, line, k, n_cmp, n_ops, n_zs in gu.family_members(fx):
+        want = 0 if gu.member_taken(kind, n_cmp, n_ops, n_zs) else gu.FE_E_CAP
+        n_taken += want == 0
+        n_declined += want != 0
+        host = pl.parse_sam(line, **kw)
+        assert host.n_reads == 1
+        for emu, dec_r, dec_k in _three_routes(fx, pl, tmp_path, sam=line, **kw):
+            assert (dec_r, dec_k) == (want, want), (qname, n_cmp, n_ops, n_zs, dec_r, dec_k)
+            same_batch(host, emu, len(fx["_locus"].backbone))
+            assert emu.trace_text().splitlines() == [fmt_record(fx["records"][k])], qname
+    assert n_taken >= 2 and n_declined >= 2
+    host = pl.parse_sam(fx["sam"], **kw)
+    for emu, dec_r, dec_k in _three_routes(fx, pl, tmp_path, **kw):
+        assert (dec_r, dec_k) == (gu.FE_E_CAP, gu.FE_E_CAP)
+        same_batch(host, emu, len(fx["_locus"].backbone))
+
+
+def test_emulated_stages_on_fuzz_cases_of_other_read_lengths(tmp_path):
+    """tools/fuzz_parity.py's cases with reads of 75, 151, 173, 251 and 345 bases, by the three routes (the cases
+    tests/test_gpu_front_edges.py gives the kernels).  Dense cases may decline: the codes are printed, not asserted."""
+    import os
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+    import fuzz_parity
+    why = {}
+    for k in range(20):
+        loc, sam, single = fuzz_parity.make_case(990000, k, 1, read_len=(75, 151, 173, 251, 345)[k % 5])
+        pl = hl.PackedLocus.from_synth(loc)
+        kw = dict(error_correction=k % 2 == 0, allow_discordant=single)
+        try:
+            host = pl.parse_sam(sam, **kw)
+        except capi.HgxError:
+            with pytest.raises(capi.HgxError):
+                emulated(pl, sam, **kw)
+            continue
+        (tmp_path / str(k)).mkdir()
+        for emu, dec_r, dec_k in _three_routes({"_locus": loc}, pl, tmp_path / str(k), sam=sam, **kw):
+            why[(dec_r, dec_k)] = why.get((dec_r, dec_k), 0) + 1
+            same_batch(host, emu, len(loc.backbone))
+        pl.close()
+    print("read lengths 75 .. 345: (record-route, key-route) decline codes -> runs: %s" % sorted(why.items()))
+
+
 def test_two_or_more_unparseable_records_decline_without_touching_their_bytes(tmp_path):
     """records the kernels cannot take apart are made inert (FE_R_FAILED: zero offsets and lengths) and the call declines
     after the record stage -- the filters, the key table and the byte-for-byte key compare never follow a stale offset.  Two and

@@ -57,6 +57,40 @@ def test_records_pieces_classes(name):
             assert np.array_equal(got_e[p, :w], gu.class_bits(fx, exp["exon_cls"], A)), p
 
 
+@pytest.mark.parametrize("name", gu.LONG)
+def test_long_and_odd_length_reads_and_cap_families(name):
+    """golden_util.LONG (2x251, eight lengths from 75 to 345 in one stream, a dense 2x301 sample, the FE_MAX_CMP, FE_MAX_OPS and FE_MAX_ZS families):
+    the host front end -- which has no scratch limits -- gives the reference's per-record trace (G3) and pileup (G5).  This is the side
+    the device front end is compared with (tests/lab_front_cases.py on the CPU, tests/test_gpu_front_edges.py on the GPU)."""
+    fx = gu.load(name)
+    assert fx["error"] is None
+    n_lines = sum(1 for l in fx["sam"].split("\n") if l)
+    assert n_lines <= 300 and len(fx["records"]) > 0
+    pl, batch = _parse(fx)
+    assert batch.n_reads == len(fx["records"]) and batch.n_pairs == len(fx["pairs"])
+    check_trace(fx, batch)
+    check_pileup(fx, batch)
+
+
+def test_long_fixtures_hold_the_lengths_and_counts_they_are_for():
+    """What the reference recorded decides which member of a family lies on which side of a limit; the families must hold both sides."""
+    lens = lambda n: [len(l.split("\t")[9]) for l in gu.load(n)["sam"].split("\n") if l]
+    assert set(lens("hla_long_251")) >= {251} and max(lens("hla_long_251")) <= 344
+    got = lens("hla_len_edges")
+    assert set(got) >= {75, 171, 172, 173, 251, 343, 344, 345}
+    names = [l.split("\t")[0] for l in gu.load("hla_len_edges")["sam"].split("\n") if l]
+    groups = [n for k, n in enumerate(names) if k == 0 or names[k - 1] != n]
+    assert all(a.split("_")[1] != b.split("_")[1] for a, b in zip(groups, groups[1:]))     # neighbouring pairs never share a length
+    assert max(len(r["cmp"]) for r in gu.load("hla_dense_301")["records"]) >= gu.FE_MAX_CMP
+    cmp_counts = [m[3] for m in gu.family_members(gu.load("hla_cap_cmp"))]
+    assert set(cmp_counts) >= {63, 64, 65, 66} and min(cmp_counts) <= 61 and max(cmp_counts) >= 69
+    ops = gu.family_members(gu.load("hla_cap_ops"))
+    assert sorted(m[4] for m in ops) == [21, 23, 24, 25, 27]
+    assert max(m[3] for m in ops) <= gu.FE_MAX_CMP                            # (only the op count separates these members)
+    zs = gu.family_members(gu.load("hla_cap_zs"))
+    assert [m[5] for m in zs] == [46, 47, 48, 49, 50] and max(m[3] for m in zs) <= gu.FE_MAX_CMP
+
+
 def test_missing_nm_tag_is_an_error():
     """Quirk Q8: the reference raises on a record without NM; the front-end reports it instead of guessing."""
     from hisatgenotype_amd import capi

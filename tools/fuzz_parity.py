@@ -9,14 +9,20 @@ import hisatgenotype_amd as hgx
 from hisatgenotype_amd import synth, locus as hl
 import pyref
 
-def make_case(seed0, k, scale=1):
-    """Case k of the batch that starts at seed `seed0`: (locus, SAM text, single-end?).  tests/test_gpu_typing.py replays single cases."""
+def make_case(seed0, k, scale=1, read_len=None):
+    """Case k of the batch that starts at seed `seed0`: (locus, SAM text, single-end?).  tests/test_gpu_typing.py replays single cases.
+    `read_len`: None = the lengths these cases have always had (100 on the STR loci, 150 on the HLA-like ones); a number = reads of that
+    length on either kind, the fragments widened to hold them (tests/test_gpu_front_edges.py: 75 .. 345)."""
     rng = random.Random(seed0 + k)
+    str_len, str_frag, hla_kw = 100, (250, 250), {}
+    if read_len is not None:
+        str_len, str_frag = read_len, (max(250, read_len + 40),) * 2
+        hla_kw = dict(read_len=read_len, frag_len=(max(400, read_len + 50),) * 2)
     if rng.random() < 0.25:
         loc = synth.make_str_like_locus(gene=rng.choice(["D8S1179", "D18S51"]), unit=rng.choice(["TCTA", "AGAA"]), seed=seed0 + k,
                                         max_repeats=rng.randint(8, 18), min_repeats=rng.randint(3, 6))
         sample = synth.pick_sample(loc, seed0 + k)
-        al = synth.simulate_pairs(loc, sample, scale * rng.randint(40, 160), read_len=100, frag_len=(250, 250), seed=k,
+        al = synth.simulate_pairs(loc, sample, scale * rng.randint(40, 160), read_len=str_len, frag_len=str_frag, seed=k,
                                   err_rate=rng.choice([0.0, 0.002]))
     else:
         loc = synth.make_hla_like_locus(n_alleles=rng.randint(30, 1200), n_vars=rng.randint(60, 900), seed=seed0 + k,
@@ -25,7 +31,7 @@ def make_case(seed0, k, scale=1):
         al = synth.simulate_pairs(loc, sample, scale * rng.randint(60, 220), err_rate=rng.choice([0.0, 0.003, 0.01]), seed=k,
                                   softclip_frac=rng.choice([0.0, 0.05]), novel_del_frac=rng.choice([0.0, 0.03]),
                                   multi_hit_frac=rng.choice([0.0, 0.02]), dup_frac=rng.choice([0.0, 0.02]),
-                                  novel_ins_frac=rng.choice([0.0, 0.02]), single_end=rng.random() < 0.15)
+                                  novel_ins_frac=rng.choice([0.0, 0.02]), single_end=rng.random() < 0.15, **hla_kw)
     sam = synth.sam_text(loc, al)
     single = any(a.flag & 1 == 0 for a in al) if al else False
     return loc, sam, single
