@@ -10,8 +10,9 @@
 //                  concordant, best[] and nh[] of both mates are rewritten from the smallest one (the core's pair order)
 //   k_aln_emit     a lane per read, twice: record sizes, (exclusive scan,) then the SAM lines at their offsets; the pair's flags are
 //                  read off the mate's pick
-//   (opts.clip > 0 only) the clip tier between the picks and k_aln_emit: k_aln_clip_mark / _fill / _extend / _pick, below
-//   (hgx_align_more.gap > 0 only) the gap tier in the same place: the clip tier's mark and fill, k_aln_gap_extend / _pick, below
+//   (opts.clip > 0 or hgx_align_more.gap > 0 only) the FALLBACK TIER between the picks and k_aln_emit, for the reads with anchors and
+//                  no alignment: k_aln_tier_mark / _fill / _extend<T> / _pick<T>, below.  One tier, two instances: T = ClipTier or
+//                  GapTier names the canon, the pick, the lane's scratch and what a read's extra word means; a call runs one of them
 // Every write is bounds-checked by construction: slots < HGX_ALN_DEV_ANCHORS, a record's bytes = the size the same code counted.
 //
 // opts.search != 0 adds a second tier, the search over STATES (hgx_align_states.hpp), for the reads of a chunk that are MARKED: in
@@ -43,6 +44,22 @@ struct DevReads {
     const int64_t *name_off, *seq_off, *qual_off;
     const int32_t *name_len, *len;
     int paired;
+};
+
+// the device buffers of one chunk, made once per call (hgx_align_device) and handed to the tiers
+struct Chunk {
+    int32_t *cnt;                     // per read: anchors found
+    int2 *anch;                       // per slot (read * HGX_ALN_DEV_ANCHORS + k)
+    DevRes *res;                      // per slot: canon(a)
+    int32_t *best, *nh;               // per read: the pick
+    int32_t *mark;                    // per read: marked for the states tier (opts.search; else nullptr)
+    // the fallback tier's (nullptr without one)
+    uint32_t *slot_word, *read_word;  // the tier's extra word (clip counts / gap descriptor) per slot and of the read's pick
+    uint32_t *nslot, *soff;           // per read: slots to extend, their first compacted index
+    int32_t *compact;                 // per compacted index: the slot
+    void *scan;                       // hgx_scan_u32_dev's scratch
+    int *decline;                     // the chunk's decline word
+    uint32_t *total;                  // a scan's total
 };
 
 __global__ void __launch_bounds__(256)
@@ -226,12 +243,12 @@ k_aln_pair_pick(int nc, int max_fragment, const int32_t *cnt, const DevRes *res,
     }
 }
 
-// out == nullptr: sizes[i] and flags[i] (1 aligned, 2 = mate 1 of a concordant pair); else the line at out + off[i].  CLIP
-// (opts.clip > 0): clipc[i] = the read's clip counts for the S ops; nullptr with clip = 0.  GAP (gap > 0): clipc[i] = the read's gap
-// descriptor (0: none) instead.
+// out == nullptr: sizes[i] and flags[i] (1 aligned, 2 = mate 1 of a concordant pair); else the line at out + off[i].  word[i] = the
+// read's extra word from the fallback tier (nullptr without one).  CLIP (opts.clip > 0): its clip counts for the S ops; GAP (gap > 0):
+// its gap descriptor (0: none).
 template <bool CLIP, bool GAP = false> __global__ void __launch_bounds__(64)
 k_aln_emit(hgx_aln_view V, DevReads rd, long first, int nc, int max_fragment, const DevRes *res, const int32_t *best, const int32_t *nh,
-           uint32_t *sizes, int32_t *flags, const uint32_t *off, char *out, const uint32_t *clipc) {
+           uint32_t *sizes, int32_t *flags, const uint32_t *off, char *out, const uint32_t *word) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nc) return;
     if (best[i] < 0) {
@@ -248,7 +265,7 @@ k_aln_emit(hgx_aln_view V, DevReads rd, long first, int nc, int max_fragment, co
     }
     const long r = first + i;
     hgx_aln_out w{out ? out + off[i] : nullptr, 0};
-    const uint32_t cc = CLIP || GAP ? clipc[i] : 0;
+    const uint32_t cc = CLIP || GAP ? word[i] : 0;
     hgx_aln_line<HGX_ALN_DEV_VARS, CLIP, GAP>(V, rd.text + rd.name_off[r], rd.name_len[r], rd.text + rd.seq_off[r],
                                               rd.qual_off[r] >= 0 ? rd.text + rd.qual_off[r] : nullptr, rd.len[r], a, nh[i], mate, i & 1,
                                               max_fragment, w, CLIP ? hgx_aln_clip_l(cc) : 0, CLIP ? hgx_aln_clip_r(cc) : 0, GAP ? cc : 0);
@@ -258,26 +275,62 @@ k_aln_emit(hgx_aln_view V, DevReads rd, long first, int nc, int max_fragment, co
     }
 }
 
-// ---- the clip tier (opts.clip > 0; hgx_align_core.hpp "soft clips") ----------------------------------------------------------------
-// For a chunk that holds a read with anchors that k_aln_pick left unaligned.  Count, scan, fill -- no atomic decides a position:
-//   k_aln_clip_mark    a lane per read: nslot[i] = its anchor slots if it has some and no alignment, else 0
-//   (hgx_scan_u32_dev) soff[i] = the read's first compacted slot, the total
-//   k_aln_clip_fill    a lane per (read, slot): compact[soff[i] + slot] = the slot's index in res[]
-//   k_aln_clip_extend  a lane per compacted slot: the clip canon by the core's CLIP walks into res[] and clips[]; the per-e entries of
-//                      both sides in the lane's private memory (2 x 5 entries of 37 words, the stack of 32 frames of 6 words and
-//                      the list of 32: 2 376 bytes of scratch per lane)
-//   k_aln_clip_pick    a lane per read with nslot[i] > 0: the pick and NH over its slots (the CLIP order), best[], nh[], clipc[]
-// Every loop bound is the read length, the slot count, max_edits + 1, the options at a position or the step limit; every index is a
-// slot below nc * HGX_ALN_DEV_ANCHORS or a compacted slot below the scan's total.
+// ---- the fallback tier (opts.clip > 0: ClipTier, "soft clips"; hgx_align_more.gap > 0: GapTier, "novel gaps"; hgx_align_core.hpp) ----
+// For a chunk that holds a read with anchors that k_aln_pick left unaligned: a dearer canon over the same anchor slots, the pick
+// again, and one extra word per read for k_aln_emit.  Count, scan, fill -- no atomic decides a position:
+//   k_aln_tier_mark       a lane per read: nslot[i] = its anchor slots if it has some and no alignment, else 0
+//   (hgx_scan_u32_dev)    soff[i] = the read's first compacted slot, the total
+//   k_aln_tier_fill       a lane per (read, slot): compact[soff[i] + slot] = the slot's index in res[]
+//   k_aln_tier_extend<T>  a lane per compacted slot: T's canon into res[] and slot_word[]; a limit reached raises the decline word
+//   k_aln_tier_pick<T>    a lane per read with nslot[i] > 0: T's pick and NH over its slots, best[], nh[], read_word[]
+// A tier T names: canon() with the lane's private scratch as its own arrays (arrays, not one struct: as a struct the compiler lays
+// the lane's memory out otherwise and the kernels' registers and occupancy move), pick(), budget() (its argument of the call) and
+// bases() (what a read's word counts for, the third counter).  Every loop bound is the read length, the slot count, max_edits + 1,
+// the longest gap, the options at a position or the step limit; every index is a slot below nc * HGX_ALN_DEV_ANCHORS or a compacted
+// slot below the scan's total.
+//
+// ClipTier: the clip canon by the core's CLIP walks; the word = the clip counts.  Scratch: the per-e entries of both sides (2 x 5
+// entries of 37 words), the stack of 32 frames of 6 words and the list of 32: 2 376 bytes per lane.
+struct ClipTier {
+    static constexpr int id = HGX_ALN_TIER_CLIP;
+    static __device__ int canon(const hgx_aln_view &V, const hgx_aln_read &R, int o, int32_t b, int max_edits, int clip, DevRes &res, uint32_t *word) {
+        hgx_aln_frame stk[HGX_ALN_DEV_STK];
+        int32_t cur[HGX_ALN_DEV_VARS];
+        hgx_aln_side<HGX_ALN_DEV_VARS> left[HGX_ALN_CLIP_EDITS + 1], right[HGX_ALN_CLIP_EDITS + 1];
+        return hgx_aln_clip_canon<HGX_ALN_DEV_STK, HGX_ALN_DEV_VARS>(V, R, o, b, max_edits, clip, HGX_ALN_DEV_STEPS, stk, cur, left, right, res, word);
+    }
+    static __device__ int pick(const DevRes *res, int n, int *nh, const uint32_t *words) {
+        return hgx_aln_pick<HGX_ALN_DEV_VARS, true>(res, n, nh, words);
+    }
+    static int budget(const hgx_align_opts *opts, int) { return opts->clip; }
+    static int bases(uint32_t word) { return hgx_aln_clip_total(word); }
+};
+// GapTier: the gap canon by the core's GAP walks; the word = the gap descriptor.  Scratch: the outer and the inner walks' stacks
+// (2 x 32 frames of 6 words) and lists (2 x 32), three side entries of 37 words: 2 236 bytes per lane.  The step limit is one per
+// side, shared by its inner walks.
+struct GapTier {
+    static constexpr int id = HGX_ALN_TIER_GAP;
+    static __device__ int canon(const hgx_aln_view &V, const hgx_aln_read &R, int o, int32_t b, int max_edits, int gap, DevRes &res, uint32_t *word) {
+        hgx_aln_frame stk[HGX_ALN_DEV_STK], stk2[HGX_ALN_DEV_STK];
+        int32_t cur[HGX_ALN_DEV_VARS], cur2[HGX_ALN_DEV_VARS];
+        hgx_aln_side<HGX_ALN_DEV_VARS> sides[3];
+        return hgx_aln_gap_canon<HGX_ALN_DEV_STK, HGX_ALN_DEV_VARS>(V, R, o, b, max_edits, gap, HGX_ALN_DEV_STEPS, stk, cur, stk2, cur2, sides, res,
+                                                                   word);
+    }
+    static __device__ int pick(const DevRes *res, int n, int *nh, const uint32_t *words) { return hgx_aln_gap_pick(res, n, nh, words); }
+    static int budget(const hgx_align_opts *, int gap) { return gap; }
+    static int bases(uint32_t word) { return hgx_aln_gap_len(word); }
+};
+
 __global__ void __launch_bounds__(256)
-k_aln_clip_mark(int nc, const int32_t *cnt, const int32_t *best, uint32_t *nslot) {
+k_aln_tier_mark(int nc, const int32_t *cnt, const int32_t *best, uint32_t *nslot) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nc) return;
     nslot[i] = (best[i] < 0 && cnt[i] > 0 && cnt[i] <= HGX_ALN_DEV_ANCHORS) ? (uint32_t)cnt[i] : 0u;
 }
 
 __global__ void __launch_bounds__(256)
-k_aln_clip_fill(int nc, const uint32_t *nslot, const uint32_t *soff, uint32_t total, int32_t *compact) {
+k_aln_tier_fill(int nc, const uint32_t *nslot, const uint32_t *soff, uint32_t total, int32_t *compact) {
     const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= (long)nc * HGX_ALN_DEV_ANCHORS) return;
     const int i = (int)(gid / HGX_ALN_DEV_ANCHORS);
@@ -286,141 +339,65 @@ k_aln_clip_fill(int nc, const uint32_t *nslot, const uint32_t *soff, uint32_t to
     compact[soff[i] + slot] = (int32_t)gid;
 }
 
-__global__ void __launch_bounds__(64)
-k_aln_clip_extend(hgx_aln_view V, DevReads rd, long first, uint32_t total, int max_edits, int clip, const int32_t *compact, const int2 *anch,
-                  DevRes *res, uint32_t *clips, int *decline) {
+template <class T> __global__ void __launch_bounds__(64)
+k_aln_tier_extend(hgx_aln_view V, DevReads rd, long first, uint32_t total, int max_edits, int budget, const int32_t *compact, const int2 *anch,
+                  DevRes *res, uint32_t *slot_word, int *decline) {
     const long j = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= (long)total) return;
     const int32_t gid = compact[j];
     const int i = gid / HGX_ALN_DEV_ANCHORS;
-    hgx_aln_frame stk[HGX_ALN_DEV_STK];
-    int32_t cur[HGX_ALN_DEV_VARS];
-    hgx_aln_side<HGX_ALN_DEV_VARS> left[HGX_ALN_CLIP_EDITS + 1], right[HGX_ALN_CLIP_EDITS + 1];
     const int2 a = anch[gid];
     const hgx_aln_read R{rd.text + rd.seq_off[first + i], rd.len[first + i], a.x >> 16};
-    uint32_t cc = 0;
-    const int rc = hgx_aln_clip_canon<HGX_ALN_DEV_STK, HGX_ALN_DEV_VARS>(V, R, a.x & 0xffff, a.y, max_edits, clip, HGX_ALN_DEV_STEPS, stk, cur,
-                                                                        left, right, res[gid], &cc);
-    clips[gid] = cc;
+    uint32_t w = 0;
+    const int rc = T::canon(V, R, a.x & 0xffff, a.y, max_edits, budget, res[gid], &w);
+    slot_word[gid] = w;
     if (rc) {
         res[gid].ok = 0;
         atomicMax(decline, rc);
     }
 }
 
-__global__ void __launch_bounds__(64)
-k_aln_clip_pick(int nc, const uint32_t *nslot, const DevRes *res, const uint32_t *clips, int32_t *best, int32_t *nh, uint32_t *clipc) {
+template <class T> __global__ void __launch_bounds__(64)
+k_aln_tier_pick(int nc, const uint32_t *nslot, const DevRes *res, const uint32_t *slot_word, int32_t *best, int32_t *nh, uint32_t *read_word) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nc || nslot[i] == 0) return;
     int h = 0;
-    const int b = hgx_aln_pick<HGX_ALN_DEV_VARS, true>(res + (long)i * HGX_ALN_DEV_ANCHORS, (int)nslot[i], &h, clips + (long)i * HGX_ALN_DEV_ANCHORS);
+    const int b = T::pick(res + (long)i * HGX_ALN_DEV_ANCHORS, (int)nslot[i], &h, slot_word + (long)i * HGX_ALN_DEV_ANCHORS);
     best[i] = b;
     nh[i] = h;
-    clipc[i] = b >= 0 ? clips[(long)i * HGX_ALN_DEV_ANCHORS + b] : 0u;
+    read_word[i] = b >= 0 ? slot_word[(long)i * HGX_ALN_DEV_ANCHORS + b] : 0u;
 }
 
-// the clip tier of one chunk, behind k_aln_pick: *decline != 0: the call goes to the host route
-int clip_tier(hgx_align_index *ix, const DevReads &rd, const hgx_align_opts *opts, long first, int nc, const int32_t *d_cnt, const int2 *d_anch,
-              DevRes *d_res, int32_t *d_best, int32_t *d_nh, uint32_t *d_clipc, uint32_t *d_nslot, uint32_t *d_soff, void *d_scan,
-              uint32_t *d_clips, int32_t *d_compact, int *d_decline, uint32_t *d_total, hipStream_t st, int64_t *counts, int *decline) {
-    k_aln_clip_mark<<<nblk(nc, 256), 256, 0, st>>>(nc, d_cnt, d_best, d_nslot);
+// the fallback tier of one chunk, behind k_aln_pick: *decline != 0: the call goes to the host route.  counts[0 .. 2]: reads searched,
+// reads the tier aligned, the bases their words stand for.
+template <class T>
+int fallback_tier(hgx_align_index *ix, const DevReads &rd, const hgx_align_opts *opts, int gap, long first, int nc, const Chunk &c, hipStream_t st,
+                  int64_t *counts, int *decline) {
+    HIPCHK(hipMemsetAsync(c.read_word, 0, (size_t)nc * 4, st));
+    k_aln_tier_mark<<<nblk(nc, 256), 256, 0, st>>>(nc, c.cnt, c.best, c.nslot);
     HIPCHK(hipGetLastError());
-    const int rc = hgx_scan_u32_dev(d_nslot, d_soff, nc, d_scan, d_total, st);
+    const int rc = hgx_scan_u32_dev(c.nslot, c.soff, nc, c.scan, c.total, st);
     if (rc) return rc;
     uint32_t total = 0;
-    HIPCHK(hipMemcpy(&total, d_total, 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&total, c.total, 4, hipMemcpyDeviceToHost));
     if (!total) return HGX_OK;
-    k_aln_clip_fill<<<nblk((long)nc * HGX_ALN_DEV_ANCHORS, 256), 256, 0, st>>>(nc, d_nslot, d_soff, total, d_compact);
-    k_aln_clip_extend<<<nblk(total, 64), 64, 0, st>>>(ix->dv, rd, first, total, opts->max_edits, opts->clip, d_compact, d_anch, d_res, d_clips,
-                                                      d_decline);
+    k_aln_tier_fill<<<nblk((long)nc * HGX_ALN_DEV_ANCHORS, 256), 256, 0, st>>>(nc, c.nslot, c.soff, total, c.compact);
+    k_aln_tier_extend<T><<<nblk(total, 64), 64, 0, st>>>(ix->dv, rd, first, total, opts->max_edits, T::budget(opts, gap), c.compact, c.anch, c.res,
+                                                         c.slot_word, c.decline);
     HIPCHK(hipGetLastError());
     int dec = 0;
-    HIPCHK(hipMemcpy(&dec, d_decline, 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&dec, c.decline, 4, hipMemcpyDeviceToHost));
     if (dec) { *decline = dec; return HGX_OK; }
-    k_aln_clip_pick<<<nblk(nc, 64), 64, 0, st>>>(nc, d_nslot, d_res, d_clips, d_best, d_nh, d_clipc);
+    k_aln_tier_pick<T><<<nblk(nc, 64), 64, 0, st>>>(nc, c.nslot, c.res, c.slot_word, c.best, c.nh, c.read_word);
     HIPCHK(hipGetLastError());
-    std::vector<uint32_t> nslot((size_t)nc), clipc((size_t)nc);
-    HIPCHK(hipMemcpy(nslot.data(), d_nslot, (size_t)nc * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(clipc.data(), d_clipc, (size_t)nc * 4, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> nslot((size_t)nc), word((size_t)nc);
+    HIPCHK(hipMemcpy(nslot.data(), c.nslot, (size_t)nc * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(word.data(), c.read_word, (size_t)nc * 4, hipMemcpyDeviceToHost));
     for (int i = 0; i < nc; ++i) {
         if (!nslot[i]) continue;
         counts[0] += 1;
-        counts[1] += clipc[i] != 0;
-        counts[2] += hgx_aln_clip_total(clipc[i]);
-    }
-    return HGX_OK;
-}
-
-// ---- the gap tier (hgx_align_more.gap > 0; hgx_align_core.hpp "novel gaps") -------------------------------------------------------
-// For a chunk that holds a read with anchors that k_aln_pick left unaligned.  The marks, the scan and the compacted slots are the
-// clip tier's (k_aln_clip_mark, hgx_scan_u32_dev, k_aln_clip_fill: the same question, "which slots belong to a read without an
-// alignment"); then
-//   k_aln_gap_extend   a lane per compacted slot: the gap canon by the core's GAP walks into res[] and gds[].  Private memory per
-//                      lane: the outer and the inner walks' stacks (2 x 32 frames of 6 words) and lists (2 x 32), three side entries
-//                      of 37 words
-//   k_aln_gap_pick     a lane per read with nslot[i] > 0: the pick and NH over its slots, best[], nh[], gapc[] (the descriptor)
-// Every loop bound is the read length, the slot count, the longest gap, the options at a position or the step limit (one per side,
-// shared by its inner walks); every index is a slot below nc * HGX_ALN_DEV_ANCHORS or a compacted slot below the scan's total.
-__global__ void __launch_bounds__(64)
-k_aln_gap_extend(hgx_aln_view V, DevReads rd, long first, uint32_t total, int max_edits, int gap, const int32_t *compact, const int2 *anch,
-                 DevRes *res, uint32_t *gds, int *decline) {
-    const long j = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= (long)total) return;
-    const int32_t gid = compact[j];
-    const int i = gid / HGX_ALN_DEV_ANCHORS;
-    hgx_aln_frame stk[HGX_ALN_DEV_STK], stk2[HGX_ALN_DEV_STK];
-    int32_t cur[HGX_ALN_DEV_VARS], cur2[HGX_ALN_DEV_VARS];
-    hgx_aln_side<HGX_ALN_DEV_VARS> sides[3];
-    const int2 a = anch[gid];
-    const hgx_aln_read R{rd.text + rd.seq_off[first + i], rd.len[first + i], a.x >> 16};
-    uint32_t gd = 0;
-    const int rc = hgx_aln_gap_canon<HGX_ALN_DEV_STK, HGX_ALN_DEV_VARS>(V, R, a.x & 0xffff, a.y, max_edits, gap, HGX_ALN_DEV_STEPS, stk, cur, stk2,
-                                                                       cur2, sides, res[gid], &gd);
-    gds[gid] = gd;
-    if (rc) {
-        res[gid].ok = 0;
-        atomicMax(decline, rc);
-    }
-}
-
-__global__ void __launch_bounds__(64)
-k_aln_gap_pick(int nc, const uint32_t *nslot, const DevRes *res, const uint32_t *gds, int32_t *best, int32_t *nh, uint32_t *gapc) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nc || nslot[i] == 0) return;
-    int h = 0;
-    const int b = hgx_aln_gap_pick(res + (long)i * HGX_ALN_DEV_ANCHORS, (int)nslot[i], &h, gds + (long)i * HGX_ALN_DEV_ANCHORS);
-    best[i] = b;
-    nh[i] = h;
-    gapc[i] = b >= 0 ? gds[(long)i * HGX_ALN_DEV_ANCHORS + b] : 0u;
-}
-
-// the gap tier of one chunk, behind k_aln_pick: *decline != 0: the call goes to the host route
-int gap_tier(hgx_align_index *ix, const DevReads &rd, const hgx_align_opts *opts, int gap, long first, int nc, const int32_t *d_cnt,
-             const int2 *d_anch, DevRes *d_res, int32_t *d_best, int32_t *d_nh, uint32_t *d_gapc, uint32_t *d_nslot, uint32_t *d_soff, void *d_scan,
-             uint32_t *d_gds, int32_t *d_compact, int *d_decline, uint32_t *d_total, hipStream_t st, int64_t *counts, int *decline) {
-    k_aln_clip_mark<<<nblk(nc, 256), 256, 0, st>>>(nc, d_cnt, d_best, d_nslot);
-    HIPCHK(hipGetLastError());
-    const int rc = hgx_scan_u32_dev(d_nslot, d_soff, nc, d_scan, d_total, st);
-    if (rc) return rc;
-    uint32_t total = 0;
-    HIPCHK(hipMemcpy(&total, d_total, 4, hipMemcpyDeviceToHost));
-    if (!total) return HGX_OK;
-    k_aln_clip_fill<<<nblk((long)nc * HGX_ALN_DEV_ANCHORS, 256), 256, 0, st>>>(nc, d_nslot, d_soff, total, d_compact);
-    k_aln_gap_extend<<<nblk(total, 64), 64, 0, st>>>(ix->dv, rd, first, total, opts->max_edits, gap, d_compact, d_anch, d_res, d_gds, d_decline);
-    HIPCHK(hipGetLastError());
-    int dec = 0;
-    HIPCHK(hipMemcpy(&dec, d_decline, 4, hipMemcpyDeviceToHost));
-    if (dec) { *decline = dec; return HGX_OK; }
-    k_aln_gap_pick<<<nblk(nc, 64), 64, 0, st>>>(nc, d_nslot, d_res, d_gds, d_best, d_nh, d_gapc);
-    HIPCHK(hipGetLastError());
-    std::vector<uint32_t> nslot((size_t)nc), gapc((size_t)nc);
-    HIPCHK(hipMemcpy(nslot.data(), d_nslot, (size_t)nc * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(gapc.data(), d_gapc, (size_t)nc * 4, hipMemcpyDeviceToHost));
-    for (int i = 0; i < nc; ++i) {
-        if (!nslot[i]) continue;
-        counts[0] += 1;
-        counts[1] += gapc[i] != 0;
-        counts[2] += hgx_aln_gap_len(gapc[i]);
+        counts[1] += word[i] != 0;
+        counts[2] += T::bases(word[i]);
     }
     return HGX_OK;
 }
@@ -599,11 +576,10 @@ k_aln_states_pick(int n_marked, const int32_t *marked, const int32_t *t_first, c
 
 // the second tier of one chunk: *decline != 0: the call goes to the host route
 int states_tier(hgx_align_index *ix, const hgx_aln_reads &reads, const DevReads &rd, const hgx_align_opts *opts, long first, int nc,
-                int n_off_max, const int32_t *d_mark, DevRes *d_res, int32_t *d_best, int32_t *d_nh, int *d_decline,
-                uint32_t *d_total, hipStream_t st, int *decline) {
+                int n_off_max, const Chunk &c, hipStream_t st, int *decline) {
     const hgx_aln_view &V = ix->dv;
     std::vector<int32_t> mark(nc), marked;
-    HIPCHK(hipMemcpy(mark.data(), d_mark, (size_t)nc * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(mark.data(), c.mark, (size_t)nc * 4, hipMemcpyDeviceToHost));
     for (int i = 0; i < nc; ++i)
         if (mark[i]) marked.push_back(i);
     const int nm = (int)marked.size();
@@ -617,10 +593,10 @@ int states_tier(hgx_align_index *ix, const hgx_aln_reads &reads, const DevReads 
     k_aln_seed_marked<<<nblk(n_lanes, 256), 256, 0, st>>>(V, rd, first, d_marked.as<int32_t>(), nm, n_off_max, d_hits.as<uint32_t>(), nullptr,
                                                          nullptr, 0);
     HIPCHK(hipGetLastError());
-    int rc = hgx_scan_u32_dev(d_hits.as<uint32_t>(), d_off.as<uint32_t>(), n_lanes, d_scan2.p, d_total, st);
+    int rc = hgx_scan_u32_dev(d_hits.as<uint32_t>(), d_off.as<uint32_t>(), n_lanes, d_scan2.p, c.total, st);
     if (rc) return rc;
     uint32_t total = 0;
-    HIPCHK(hipMemcpy(&total, d_total, 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&total, c.total, 4, hipMemcpyDeviceToHost));
     if ((long)total > ST_ANCHOR_CAP) { *decline = HGX_ALN_DECLINE_ANCHORS; return HGX_OK; }
     ALLOC(d_anch, (size_t)std::max<uint32_t>(total, 1) * sizeof(hgx_st_anchor));
     k_aln_seed_marked<<<nblk(n_lanes, 256), 256, 0, st>>>(V, rd, first, d_marked.as<int32_t>(), nm, n_off_max, nullptr, d_off.as<uint32_t>(),
@@ -673,14 +649,14 @@ int states_tier(hgx_align_index *ix, const hgx_aln_reads &reads, const DevReads 
         const int t0 = batch_first[b], n = batch_first[b + 1] - t0;
         if (n <= 0) continue;
         k_aln_states<<<n, 256, 0, st>>>(V, rd, first, opts->max_edits, d_tasks.as<StTask>() + t0, d_anch.as<hgx_st_anchor>(), d_acost.as<int4>(),
-                                        d_cells.as<hgx_st_cell>(), d_tres.as<DevRes>() + t0, d_tnh.as<int32_t>() + t0, d_decline);
+                                        d_cells.as<hgx_st_cell>(), d_tres.as<DevRes>() + t0, d_tnh.as<int32_t>() + t0, c.decline);
         HIPCHK(hipGetLastError());
     }
-    k_aln_states_pick<<<nblk(nm, 64), 64, 0, st>>>(nm, d_marked.as<int32_t>(), d_tf.as<int32_t>(), d_tres.as<DevRes>(), d_tnh.as<int32_t>(), d_res,
-                                                   d_best, d_nh);
+    k_aln_states_pick<<<nblk(nm, 64), 64, 0, st>>>(nm, d_marked.as<int32_t>(), d_tf.as<int32_t>(), d_tres.as<DevRes>(), d_tnh.as<int32_t>(), c.res,
+                                                   c.best, c.nh);
     HIPCHK(hipGetLastError());
     int dec = 0;
-    HIPCHK(hipMemcpy(&dec, d_decline, 4, hipMemcpyDeviceToHost));      // (also: the tier is finished before its buffers go back to the pool)
+    HIPCHK(hipMemcpy(&dec, c.decline, 4, hipMemcpyDeviceToHost));     // (also: the tier is finished before its buffers go back to the pool)
     if (dec) { *decline = dec; return HGX_OK; }
     hgx_align_states_count(nm, (int64_t)total, cells);
     return HGX_OK;
@@ -758,7 +734,6 @@ int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
     DevBuf d_cnt, d_anch, d_res, d_best, d_nh, d_sizes, d_off, d_flags, d_scan, d_misc, d_mark;
     const int search = opts->search;
     if (search) ALLOC(d_mark, (size_t)cmax * 4);
-    int32_t *mark = search ? d_mark.as<int32_t>() : nullptr;
     ALLOC(d_cnt, (size_t)cmax * 4);
     ALLOC(d_anch, (size_t)cmax * HGX_ALN_DEV_ANCHORS * sizeof(int2));
     ALLOC(d_res, (size_t)cmax * HGX_ALN_DEV_ANCHORS * sizeof(DevRes));
@@ -766,16 +741,31 @@ int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
     ALLOC(d_flags, (size_t)cmax * 4);
     ALLOC(d_scan, hgx_scan_u32_scratch_bytes(cmax) + 16);
     ALLOC(d_misc, 48);                       // [0] decline code, [1] total bytes, [2] reads marked for the second tier; pair mode: bytes 16 .. 40 = pairs searched, placed, changed
-    int *d_decline = d_misc.as<int>();
-    uint32_t *d_total = d_misc.as<uint32_t>() + 1;
+    // the call's fallback tier (at most one: hgx_align_reads_x) and the k_aln_emit that reads its word, chosen here once
     const int clip = opts->clip;
-    DevBuf d_clipc, d_nslot, d_soff, d_clips, d_compact;      // (the gap tier: the same buffers, descriptors for clip counts)
-    if (clip > 0 || gap > 0) {
-        ALLOC(d_clipc, (size_t)cmax * 4); ALLOC(d_nslot, (size_t)cmax * 4); ALLOC(d_soff, (size_t)cmax * 4);
-        ALLOC(d_clips, (size_t)cmax * HGX_ALN_DEV_ANCHORS * 4); ALLOC(d_compact, (size_t)cmax * HGX_ALN_DEV_ANCHORS * 4);
+    const auto tier = clip > 0 ? fallback_tier<ClipTier> : gap > 0 ? fallback_tier<GapTier> : nullptr;
+    const auto emit = clip > 0 ? k_aln_emit<true> : gap > 0 ? k_aln_emit<false, true> : k_aln_emit<false>;
+    const int tier_id = clip > 0 ? ClipTier::id : gap > 0 ? GapTier::id : HGX_ALN_TIER_NONE;
+    DevBuf d_read_word, d_nslot, d_soff, d_slot_word, d_compact;
+    if (tier) {
+        ALLOC(d_read_word, (size_t)cmax * 4); ALLOC(d_nslot, (size_t)cmax * 4); ALLOC(d_soff, (size_t)cmax * 4);
+        ALLOC(d_slot_word, (size_t)cmax * HGX_ALN_DEV_ANCHORS * 4); ALLOC(d_compact, (size_t)cmax * HGX_ALN_DEV_ANCHORS * 4);
     }
-    const uint32_t *clipc = clip > 0 || gap > 0 ? d_clipc.as<uint32_t>() : nullptr;
-    int64_t clip_counts[3] = {0, 0, 0}, gap_counts[3] = {0, 0, 0};
+    const Chunk c{d_cnt.as<int32_t>(), d_anch.as<int2>(), d_res.as<DevRes>(), d_best.as<int32_t>(), d_nh.as<int32_t>(),
+                  search ? d_mark.as<int32_t>() : nullptr, d_slot_word.as<uint32_t>(), d_read_word.as<uint32_t>(), d_nslot.as<uint32_t>(),
+                  d_soff.as<uint32_t>(), d_compact.as<int32_t>(), d_scan.p, d_misc.as<int>(), d_misc.as<uint32_t>() + 1};
+    auto launch_emit = [&](long first, int nc, uint32_t *sizes, int32_t *flags, const uint32_t *off, char *out) {      // either pass
+        emit<<<nblk(nc, 64), 64, 0, st>>>(ix->dv, rd, first, nc, opts->max_fragment, c.res, c.best, c.nh, sizes, flags, off, out, c.read_word);
+        return hipGetLastError();
+    };
+    auto declined = [&](int dec) {                // what earlier chunks appended is taken back
+        body.resize(body0);
+        *aligned = aligned0;
+        *concordant = concordant0;
+        *decline = dec;
+        return HGX_OK;
+    };
+    int64_t tier_counts[3] = {0, 0, 0};
     const bool pair_aware = reads.paired && opts->pair == 1;
     const size_t misc_bytes = pair_aware ? 40 : 16;
     int64_t pairs[3] = {0, 0, 0};
@@ -789,71 +779,36 @@ int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
         const long n_seed = (long)nc * 2 * n_off_max;
         if (n_seed > 0)
             k_aln_seed<<<nblk(n_seed, 256), 256, 0, st>>>(ix->dv, rd, first, nc, n_off_max, d_cnt.as<int32_t>(), d_anch.as<int2>());
-        if (search == 2) k_aln_mark_all<<<nblk(nc, 256), 256, 0, st>>>(nc, d_cnt.as<int32_t>(), mark, d_decline);
+        if (search == 2) k_aln_mark_all<<<nblk(nc, 256), 256, 0, st>>>(nc, c.cnt, c.mark, c.decline);
         else if (search == 1)
-            k_aln_extend<true><<<nblk((long)nc * HGX_ALN_DEV_ANCHORS, 64), 64, 0, st>>>(ix->dv, rd, first, nc, opts->max_edits, d_cnt.as<int32_t>(),
-                                                                                         d_anch.as<int2>(), d_res.as<DevRes>(), d_decline, mark);
+            k_aln_extend<true><<<nblk((long)nc * HGX_ALN_DEV_ANCHORS, 64), 64, 0, st>>>(ix->dv, rd, first, nc, opts->max_edits, c.cnt, c.anch, c.res,
+                                                                                         c.decline, c.mark);
         else
-            k_aln_extend<false><<<nblk((long)nc * HGX_ALN_DEV_ANCHORS, 64), 64, 0, st>>>(ix->dv, rd, first, nc, opts->max_edits, d_cnt.as<int32_t>(),
-                                                                                          d_anch.as<int2>(), d_res.as<DevRes>(), d_decline, nullptr);
+            k_aln_extend<false><<<nblk((long)nc * HGX_ALN_DEV_ANCHORS, 64), 64, 0, st>>>(ix->dv, rd, first, nc, opts->max_edits, c.cnt, c.anch, c.res,
+                                                                                          c.decline, nullptr);
         HIPCHK(hipGetLastError());
         int misc[4] = {0, 0, 0, 0};
         HIPCHK(hipMemcpy(misc, d_misc.p, search ? 16 : 4, hipMemcpyDeviceToHost));
         int dec = misc[0];
         if (!dec && search && misc[2] > 0) {
-            rc = states_tier(ix, reads, rd, opts, first, nc, n_off_max, mark, d_res.as<DevRes>(), d_best.as<int32_t>(), d_nh.as<int32_t>(),
-                             d_decline, d_total, st, &dec);
+            rc = states_tier(ix, reads, rd, opts, first, nc, n_off_max, c, st, &dec);
             if (rc) return rc;
         }
-        if (dec) {                               // (a later chunk: what the earlier ones appended is taken back)
-            body.resize(body0);
-            *aligned = aligned0;
-            *concordant = concordant0;
-            *decline = dec;
-            return HGX_OK;
-        }
-        k_aln_pick<<<nblk(nc, 64), 64, 0, st>>>(nc, d_cnt.as<int32_t>(), d_res.as<DevRes>(), d_best.as<int32_t>(), d_nh.as<int32_t>(), mark);
+        if (dec) return declined(dec);
+        k_aln_pick<<<nblk(nc, 64), 64, 0, st>>>(nc, c.cnt, c.res, c.best, c.nh, c.mark);
         if (pair_aware)
-            k_aln_pair_pick<<<nc / 2, 64, 0, st>>>(nc, opts->max_fragment, d_cnt.as<int32_t>(), d_res.as<DevRes>(), d_best.as<int32_t>(),
-                                                   d_nh.as<int32_t>(), (unsigned long long *)(d_misc.as<char>() + 16));
-        if (clip > 0) {
-            HIPCHK(hipMemsetAsync(d_clipc.p, 0, (size_t)nc * 4, st));
-            rc = clip_tier(ix, rd, opts, first, nc, d_cnt.as<int32_t>(), d_anch.as<int2>(), d_res.as<DevRes>(), d_best.as<int32_t>(),
-                           d_nh.as<int32_t>(), d_clipc.as<uint32_t>(), d_nslot.as<uint32_t>(), d_soff.as<uint32_t>(), d_scan.p,
-                           d_clips.as<uint32_t>(), d_compact.as<int32_t>(), d_decline, d_total, st, clip_counts, &dec);
+            k_aln_pair_pick<<<nc / 2, 64, 0, st>>>(nc, opts->max_fragment, c.cnt, c.res, c.best, c.nh,
+                                                   (unsigned long long *)(d_misc.as<char>() + 16));
+        if (tier) {
+            rc = tier(ix, rd, opts, gap, first, nc, c, st, tier_counts, &dec);
             if (rc) return rc;
-            if (dec) {
-                body.resize(body0);
-                *aligned = aligned0;
-                *concordant = concordant0;
-                *decline = dec;
-                return HGX_OK;
-            }
-            k_aln_emit<true><<<nblk(nc, 64), 64, 0, st>>>(ix->dv, rd, first, nc, opts->max_fragment, d_res.as<DevRes>(), d_best.as<int32_t>(),
-                                                          d_nh.as<int32_t>(), d_sizes.as<uint32_t>(), d_flags.as<int32_t>(), nullptr, nullptr, clipc);
-        } else if (gap > 0) {
-            HIPCHK(hipMemsetAsync(d_clipc.p, 0, (size_t)nc * 4, st));
-            rc = gap_tier(ix, rd, opts, gap, first, nc, d_cnt.as<int32_t>(), d_anch.as<int2>(), d_res.as<DevRes>(), d_best.as<int32_t>(),
-                          d_nh.as<int32_t>(), d_clipc.as<uint32_t>(), d_nslot.as<uint32_t>(), d_soff.as<uint32_t>(), d_scan.p,
-                          d_clips.as<uint32_t>(), d_compact.as<int32_t>(), d_decline, d_total, st, gap_counts, &dec);
-            if (rc) return rc;
-            if (dec) {
-                body.resize(body0);
-                *aligned = aligned0;
-                *concordant = concordant0;
-                *decline = dec;
-                return HGX_OK;
-            }
-            k_aln_emit<false, true><<<nblk(nc, 64), 64, 0, st>>>(ix->dv, rd, first, nc, opts->max_fragment, d_res.as<DevRes>(), d_best.as<int32_t>(),
-                                                                 d_nh.as<int32_t>(), d_sizes.as<uint32_t>(), d_flags.as<int32_t>(), nullptr, nullptr, clipc);
-        } else
-            k_aln_emit<false><<<nblk(nc, 64), 64, 0, st>>>(ix->dv, rd, first, nc, opts->max_fragment, d_res.as<DevRes>(), d_best.as<int32_t>(),
-                                                           d_nh.as<int32_t>(), d_sizes.as<uint32_t>(), d_flags.as<int32_t>(), nullptr, nullptr, nullptr);
-        HIPCHK(hipGetLastError());
-        rc = hgx_scan_u32_dev(d_sizes.as<uint32_t>(), d_off.as<uint32_t>(), nc, d_scan.p, d_total, st);
+            if (dec) return declined(dec);
+        }
+        HIPCHK(launch_emit(first, nc, d_sizes.as<uint32_t>(), d_flags.as<int32_t>(), nullptr, nullptr));
+        rc = hgx_scan_u32_dev(d_sizes.as<uint32_t>(), d_off.as<uint32_t>(), nc, c.scan, c.total, st);
         if (rc) return rc;
         uint32_t back[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};                // total bytes; pair mode: the rest of d_misc with it
-        HIPCHK(hipMemcpy(back, d_total, pair_aware ? 36 : 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(back, c.total, pair_aware ? 36 : 4, hipMemcpyDeviceToHost));
         const uint32_t total = back[0];
         for (int k = 0; k < 3; ++k) {
             uint64_t v;
@@ -865,17 +820,7 @@ int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
         if (total) {
             DevBuf d_out;
             ALLOC(d_out, (size_t)total);
-            if (clip > 0)
-                k_aln_emit<true><<<nblk(nc, 64), 64, 0, st>>>(ix->dv, rd, first, nc, opts->max_fragment, d_res.as<DevRes>(), d_best.as<int32_t>(),
-                                                              d_nh.as<int32_t>(), nullptr, nullptr, d_off.as<uint32_t>(), d_out.as<char>(), clipc);
-            else if (gap > 0)
-                k_aln_emit<false, true><<<nblk(nc, 64), 64, 0, st>>>(ix->dv, rd, first, nc, opts->max_fragment, d_res.as<DevRes>(),
-                                                                     d_best.as<int32_t>(), d_nh.as<int32_t>(), nullptr, nullptr, d_off.as<uint32_t>(),
-                                                                     d_out.as<char>(), clipc);
-            else
-                k_aln_emit<false><<<nblk(nc, 64), 64, 0, st>>>(ix->dv, rd, first, nc, opts->max_fragment, d_res.as<DevRes>(), d_best.as<int32_t>(),
-                                                               d_nh.as<int32_t>(), nullptr, nullptr, d_off.as<uint32_t>(), d_out.as<char>(), nullptr);
-            HIPCHK(hipGetLastError());
+            HIPCHK(launch_emit(first, nc, nullptr, nullptr, d_off.as<uint32_t>(), d_out.as<char>()));
             text.resize(total);
             HIPCHK(hipMemcpy(&text[0], d_out.p, total, hipMemcpyDeviceToHost));
             body += text;
@@ -883,7 +828,6 @@ int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
     }
     HIPCHK(hipStreamSynchronize(st));
     if (pair_aware) hgx_align_pairs_count(pairs[0], pairs[1], pairs[2]);
-    if (clip > 0) hgx_align_clip_count(clip_counts[0], clip_counts[1], clip_counts[2]);
-    if (gap > 0) hgx_align_gap_count(gap_counts[0], gap_counts[1], gap_counts[2]);
+    if (tier) hgx_align_tier_count(tier_id, tier_counts[0], tier_counts[1], tier_counts[2]);
     return HGX_OK;
 }

@@ -46,7 +46,7 @@ void hgx_align_device_free(hgx_align_index *ix);
 void hgx_align_states_count(int64_t reads, int64_t anchors, int64_t cells);
 // what the pair pick did in the calling thread's current call (hgx_align_last_pairs): added to by the route that gives the bytes
 void hgx_align_pairs_count(int64_t searched, int64_t placed, int64_t changed);
-// what the clip tier did in the calling thread's current call (hgx_align_last_clip): added to by the route that gives the bytes
-void hgx_align_clip_count(int64_t searched, int64_t clipped, int64_t bases);
-// what the gap tier did in the calling thread's current call (hgx_align_last_gap): added to by the route that gives the bytes
-void hgx_align_gap_count(int64_t searched, int64_t gapped, int64_t bases);
+// what the call's fallback tier (a call runs at most one) did in the calling thread's current call: added to by the route that
+// gives the bytes; hgx_align_last_clip / hgx_align_last_gap report it for their tier and zeros for the other
+enum { HGX_ALN_TIER_NONE = 0, HGX_ALN_TIER_CLIP = 1, HGX_ALN_TIER_GAP = 2 };
+void hgx_align_tier_count(int tier, int64_t searched, int64_t found, int64_t bases);

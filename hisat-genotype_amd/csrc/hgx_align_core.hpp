@@ -131,6 +131,16 @@ struct hgx_aln_frame { int32_t r, P, nm, nind, nl, k; };
 HGX_ALN_HD inline int hgx_aln_cmp3(int a0, int a1, int a2, int b0, int b1, int b2) {
     return a0 != b0 ? (a0 < b0 ? -1 : 1) : a1 != b1 ? (a1 < b1 ? -1 : 1) : a2 != b2 ? (a2 < b2 ? -1 : 1) : 0;
 }
+// the left side's best x and the right side's best y as one alignment of locus g
+template <int MAXV>
+HGX_ALN_HD inline int hgx_aln_join(const hgx_aln_side<MAXV> &x, const hgx_aln_side<MAXV> &y, int g, int strand, hgx_aln_res<MAXV> &res) {
+    if (x.nl + y.nl > MAXV) return HGX_ALN_DECLINE_VARS;
+    for (int i = 0; i < x.nl; ++i) res.vl[i] = x.vl[i];
+    for (int i = 0; i < y.nl; ++i) res.vl[x.nl + i] = y.vl[i];
+    res.nm = x.nm + y.nm; res.nind = x.nind + y.nind; res.nvar = x.nl + y.nl; res.pos0 = x.pos; res.end = y.pos;
+    res.locus = g; res.strand = strand; res.ok = 1;
+    return 0;
+}
 
 // ---- soft clips (opts.clip > 0; the rule in plain Python: tests/align_clip_ref.py) -------------------------------------------------
 // The clip tier runs the same two walks with CLIP = true.  A side then has one more option at every state it ENTERS: stop there
@@ -144,7 +154,7 @@ HGX_ALN_HD inline int hgx_aln_cmp3(int a0, int a1, int a2, int b0, int b1, int b
 #define HGX_ALN_CLIP_MAX 255
 // A side's entries are hgx_aln_side[HGX_ALN_CLIP_EDITS + 1], indexed by e, whose `nm` word holds the CLIP count; the CLIP walks
 // take the array through their `best` argument.
-// a way of the walk (its list in cur[0 .. nl), backwards if `rev`) against the side's entry for its e
+// a way of the walk (its list in cur[0 .. nl), backwards if `rev`) against the side's entry for its e (not the plain arms')
 template <int MAXV>
 HGX_ALN_HD inline void hgx_aln_clip_offer(hgx_aln_side<MAXV> &b, int clip, int nind, int nl, int32_t pos, bool use_pos, const int32_t *cur,
                                           bool rev) {
@@ -159,7 +169,6 @@ HGX_ALN_HD inline void hgx_aln_clip_offer(hgx_aln_side<MAXV> &b, int clip, int n
         for (int i = 0; i < nl; ++i) b.vl[i] = rev ? cur[nl - 1 - i] : cur[i];
     }
 }
-
 
 // ---- novel gaps (hgx_align_more.gap > 0; the rule in plain Python: tests/align_gap_ref.py) -----------------------------------------
 // The gap tier runs the same two walks with GAP = 1.  Such a walk is the plain enumeration with one edit of the budget held back
@@ -474,7 +483,7 @@ HGX_ALN_HD int hgx_aln_left(const hgx_aln_view &V, const hgx_aln_read &R, int32_
 }
 
 // canon(a) of the anchor (read offset o, global backbone position b) of strand R.strand: res.ok = 0 if no alignment is admissible
-// through it.  `side` is scratch for one side's best.
+// through it.  `side` is scratch for ONE side's best: the left side's is parked in `res` meanwhile (so no hgx_aln_join here).
 template <int MAXSTK, int MAXV, class MEMO>
 HGX_ALN_HD int hgx_aln_canon(const hgx_aln_view &V, const hgx_aln_read &R, int o, int32_t b, int max_edits, long max_steps,
                              hgx_aln_frame *stk, int32_t *cur, hgx_aln_side<MAXV> &side, hgx_aln_res<MAXV> &res, MEMO &memo) {
@@ -522,11 +531,7 @@ HGX_ALN_HD int hgx_aln_gap_canon(const hgx_aln_view &V, const hgx_aln_read &R, i
         rc = hgx_aln_right<MAXSTK, MAXV>(V, R, hi, o + HGX_ALN_K, b + HGX_ALN_K, max_edits - x.nm, max_steps, stk, cur, y, memo);
         if (rc) return rc;
         if (y.found) {
-            if (x.nl + y.nl > MAXV) return HGX_ALN_DECLINE_VARS;
-            for (int i = 0; i < x.nl; ++i) res.vl[i] = x.vl[i];
-            for (int i = 0; i < y.nl; ++i) res.vl[x.nl + i] = y.vl[i];
-            res.nm = x.nm + y.nm; res.nind = x.nind + y.nind; res.nvar = x.nl + y.nl; res.pos0 = x.pos; res.end = y.pos;
-            res.locus = g; res.strand = R.strand; res.ok = 1;
+            if ((rc = hgx_aln_join(x, y, g, R.strand, res))) return rc;
             *gd_out = gx.gd;
         }
     }
@@ -550,10 +555,7 @@ HGX_ALN_HD int hgx_aln_gap_canon(const hgx_aln_view &V, const hgx_aln_read &R, i
         if (c == 0) c = gx.gd < *gd_out ? -1 : 1;
     }
     if (c < 0) {
-        for (int i = 0; i < x.nl; ++i) res.vl[i] = x.vl[i];
-        for (int i = 0; i < y.nl; ++i) res.vl[x.nl + i] = y.vl[i];
-        res.nm = x.nm + y.nm; res.nind = x.nind + y.nind; res.nvar = x.nl + y.nl; res.pos0 = x.pos; res.end = y.pos;
-        res.locus = g; res.strand = R.strand; res.ok = 1;
+        hgx_aln_join(x, y, g, R.strand, res);                  // (the lists fit: checked in front of the comparison)
         *gd_out = gx.gd;
     }
     return 0;
@@ -606,11 +608,8 @@ HGX_ALN_HD int hgx_aln_clip_canon(const hgx_aln_view &V, const hgx_aln_read &R, 
     }
     if (bl < 0) return 0;
     const hgx_aln_side<MAXV> &x = left[bl], &y = right[br];
-    if (x.nl + y.nl > MAXV) return HGX_ALN_DECLINE_VARS;
-    for (int i = 0; i < x.nl; ++i) res.vl[i] = x.vl[i];
-    for (int i = 0; i < y.nl; ++i) res.vl[x.nl + i] = y.vl[i];
-    res.nm = bl + br; res.nind = x.nind + y.nind; res.nvar = x.nl + y.nl; res.pos0 = x.pos; res.end = y.pos;
-    res.locus = g; res.strand = R.strand; res.ok = 1;
+    if ((rc = hgx_aln_join(x, y, g, R.strand, res))) return rc;
+    res.nm = bl + br;                                          // (the entries' `nm` words hold the clip counts)
     *clips = hgx_aln_clip_pack(x.nm, y.nm);
     return 0;
 }

@@ -24,8 +24,8 @@ thread_local int g_route = 0, g_decline = 0;
 thread_local int64_t g_reads = 0, g_aligned = 0, g_conc = 0;
 thread_local int64_t g_st_reads = 0, g_st_anchors = 0, g_st_cells = 0;
 thread_local int64_t g_pr_searched = 0, g_pr_placed = 0, g_pr_changed = 0;
-thread_local int64_t g_cl_searched = 0, g_cl_clipped = 0, g_cl_bases = 0;
-thread_local int64_t g_gp_searched = 0, g_gp_gapped = 0, g_gp_bases = 0;
+thread_local int g_tier = HGX_ALN_TIER_NONE;                             // the fallback tier the counters below are of
+thread_local int64_t g_tr_searched = 0, g_tr_found = 0, g_tr_bases = 0;
 
 template <class T> void csr(const std::vector<std::pair<int32_t, int32_t>> &items, int32_t n_pos, std::vector<T> &off, std::vector<T> &list) {
     off.assign((size_t)n_pos + 1, 0);
@@ -203,8 +203,9 @@ struct HostScratch {
     HostScratch() : stk(HGX_ALN_HOST_VARS), cur(HGX_ALN_HOST_VARS) {}
 };
 
-int align_one(const hgx_aln_view &V, const char *seq, int L, int max_edits, HostScratch &S, HostRes &best, int *nh, int *gave_up) {
-    S.res.clear();
+// every anchor of the read, both strands, in the order of the seed offsets and the table's probe run: fn(R, o, b) for the 16-mer at
+// offset o of the oriented read R that sits at backbone position b.  A call that returns non-zero ends the loop with that value.
+template <class F> int each_anchor(const hgx_aln_view &V, const char *seq, int L, F fn) {
     for (int strand = 0; strand < 2; ++strand) {
         const hgx_aln_read R{seq, L, strand};
         const int n_off = hgx_aln_n_offsets(L);
@@ -214,112 +215,105 @@ int align_one(const hgx_aln_view &V, const char *seq, int L, int max_edits, Host
             if (!hgx_aln_seed_code(R, o, &code)) continue;
             for (uint32_t h = hgx_aln_hash(code) & V.hmask; V.hpos[h] >= 0; h = (h + 1) & V.hmask) {
                 if (V.hkey[h] != code) continue;
-                S.res.emplace_back();
-                const int rc = hgx_aln_canon<HGX_ALN_HOST_VARS, HGX_ALN_HOST_VARS>(V, R, o, V.hpos[h], max_edits, HGX_ALN_HOST_STEPS,
-                                                                                  S.stk.data(), S.cur.data(), *S.side, S.res.back(), S.memo);
-                if (rc) {                     // beyond the host route's own limits: this read is left unaligned, the call goes on
-                    S.res.clear();
-                    best.ok = 0;
-                    *nh = 0;
-                    *gave_up = rc;
-                    return HGX_OK;
-                }
-                if (!S.res.back().ok) S.res.pop_back();
+                const int rc = fn(R, o, V.hpos[h]);
+                if (rc) return rc;
             }
         }
     }
-    const int b = hgx_aln_pick(S.res.data(), (int)S.res.size(), nh);
+    return 0;
+}
+
+int align_one(const hgx_aln_view &V, const char *seq, int L, int max_edits, HostScratch &S, HostRes &best, int *nh, int *gave_up) {
+    S.res.clear();
+    const int rc = each_anchor(V, seq, L, [&](const hgx_aln_read &R, int o, int32_t b) {
+        S.res.emplace_back();
+        const int rc = hgx_aln_canon<HGX_ALN_HOST_VARS, HGX_ALN_HOST_VARS>(V, R, o, b, max_edits, HGX_ALN_HOST_STEPS, S.stk.data(), S.cur.data(),
+                                                                          *S.side, S.res.back(), S.memo);
+        if (!rc && !S.res.back().ok) S.res.pop_back();
+        return rc;
+    });
     best.ok = 0;
+    if (rc) {                                 // beyond the host route's own limits: this read is left unaligned, the call goes on
+        S.res.clear();
+        *nh = 0;
+        *gave_up = rc;
+        return HGX_OK;
+    }
+    const int b = hgx_aln_pick(S.res.data(), (int)S.res.size(), nh);
     if (b >= 0) best = S.res[(size_t)b];
     return HGX_OK;
 }
 
-// the clip tier (opts.clip > 0) for a read align_one found nothing for: the clip canons of the same anchors, without the memo
-struct ClipScratch {
-    std::vector<hgx_aln_side<HGX_ALN_HOST_VARS>> left, right;
+// ---- the fallback tier (opts.clip > 0: ClipTier; hgx_align_more.gap > 0: GapTier) for a read align_one found nothing for: a dearer
+// canon over the same anchors, the tier's pick, one extra word for the record.  A tier names its canon, its pick, the scratch it
+// needs besides HostScratch's stack and list, its argument of the call and the bases a word counts for, as the kernels' tiers do.
+// Both run without the memo: it drops an arrival that a plain search never needs, and that arrival may be the prefix of the
+// smallest way with a clip or a gap (hgx_align_core.hpp).
+struct NoTier { static constexpr int id = HGX_ALN_TIER_NONE; static constexpr bool CLIP = false, GAP = false; struct Scratch {}; };
+struct ClipTier {
+    static constexpr int id = HGX_ALN_TIER_CLIP;
+    static constexpr bool CLIP = true, GAP = false;                      // (hgx_aln_line's)
+    struct Scratch {
+        std::vector<hgx_aln_side<HGX_ALN_HOST_VARS>> left, right;
+        Scratch() : left(HGX_ALN_CLIP_EDITS + 1), right(HGX_ALN_CLIP_EDITS + 1) {}
+    };
+    static int canon(const hgx_aln_view &V, const hgx_aln_read &R, int o, int32_t b, int max_edits, int clip, HostScratch &S, Scratch &X,
+                     HostRes &res, uint32_t *word) {
+        return hgx_aln_clip_canon<HGX_ALN_HOST_VARS, HGX_ALN_HOST_VARS>(V, R, o, b, max_edits, clip, HGX_ALN_HOST_STEPS, S.stk.data(), S.cur.data(),
+                                                                       X.left.data(), X.right.data(), res, word);
+    }
+    static int pick(const HostRes *res, int n, int *nh, const uint32_t *words) { return hgx_aln_pick<HGX_ALN_HOST_VARS, true>(res, n, nh, words); }
+    static int budget(const hgx_align_opts *o, int) { return o->clip; }
+    static int bases(uint32_t word) { return hgx_aln_clip_total(word); }
+};
+struct GapTier {
+    static constexpr int id = HGX_ALN_TIER_GAP;
+    static constexpr bool CLIP = false, GAP = true;
+    struct Scratch {
+        std::vector<hgx_aln_frame> stk2;
+        std::vector<int32_t> cur2;
+        std::vector<hgx_aln_side<HGX_ALN_HOST_VARS>> sides;
+        Scratch() : stk2(HGX_ALN_HOST_VARS), cur2(HGX_ALN_HOST_VARS), sides(3) {}
+    };
+    static int canon(const hgx_aln_view &V, const hgx_aln_read &R, int o, int32_t b, int max_edits, int gap, HostScratch &S, Scratch &X,
+                     HostRes &res, uint32_t *word) {
+        return hgx_aln_gap_canon<HGX_ALN_HOST_VARS, HGX_ALN_HOST_VARS>(V, R, o, b, max_edits, gap, HGX_ALN_HOST_STEPS, S.stk.data(), S.cur.data(),
+                                                                      X.stk2.data(), X.cur2.data(), X.sides.data(), res, word);
+    }
+    static int pick(const HostRes *res, int n, int *nh, const uint32_t *words) { return hgx_aln_gap_pick(res, n, nh, words); }
+    static int budget(const hgx_align_opts *, int gap) { return gap; }
+    static int bases(uint32_t word) { return hgx_aln_gap_len(word); }
+};
+template <class T> struct TierScratch {
+    typename T::Scratch own;
     std::vector<HostRes> res;
-    std::vector<uint32_t> clips;
-    ClipScratch() : left(HGX_ALN_CLIP_EDITS + 1), right(HGX_ALN_CLIP_EDITS + 1) {}
+    std::vector<uint32_t> words;
 };
 
-void align_one_clip(const hgx_aln_view &V, const char *seq, int L, int max_edits, int clip, HostScratch &S, ClipScratch &C, HostRes &best,
-                    int *nh, uint32_t *clips, int *n_anchors, int *gave_up) {
-    C.res.clear();
-    C.clips.clear();
+// *word = 0 and best.ok = 0 where the tier finds nothing or passes a limit (*gave_up); a read with an anchor counts as searched
+template <class T>
+void align_one_tier(const hgx_aln_view &V, const char *seq, int L, int max_edits, int budget, HostScratch &S, TierScratch<T> &X, HostRes &best,
+                    int *nh, uint32_t *word, int *gave_up) {
+    X.res.clear();
+    X.words.clear();
     best.ok = 0;
     *nh = 0;
-    *clips = 0;
-    for (int strand = 0; strand < 2; ++strand) {
-        const hgx_aln_read R{seq, L, strand};
-        const int n_off = hgx_aln_n_offsets(L);
-        for (int k = 0; k < n_off; ++k) {
-            const int o = hgx_aln_offset(L, k);
-            uint32_t code;
-            if (!hgx_aln_seed_code(R, o, &code)) continue;
-            for (uint32_t h = hgx_aln_hash(code) & V.hmask; V.hpos[h] >= 0; h = (h + 1) & V.hmask) {
-                if (V.hkey[h] != code) continue;
-                ++*n_anchors;
-                C.res.emplace_back();
-                C.clips.push_back(0);
-                const int rc = hgx_aln_clip_canon<HGX_ALN_HOST_VARS, HGX_ALN_HOST_VARS>(V, R, o, V.hpos[h], max_edits, clip, HGX_ALN_HOST_STEPS,
-                                                                                       S.stk.data(), S.cur.data(), C.left.data(),
-                                                                                       C.right.data(), C.res.back(), &C.clips.back());
-                if (rc) {                     // beyond the host route's own limits: left unaligned, as align_one does
-                    *gave_up = rc;
-                    return;
-                }
-                if (!C.res.back().ok) { C.res.pop_back(); C.clips.pop_back(); }
-            }
-        }
+    *word = 0;
+    int n_anchors = 0;
+    const int rc = each_anchor(V, seq, L, [&](const hgx_aln_read &R, int o, int32_t b) {
+        ++n_anchors;
+        X.res.emplace_back();
+        X.words.push_back(0);
+        const int rc = T::canon(V, R, o, b, max_edits, budget, S, X.own, X.res.back(), &X.words.back());
+        if (!rc && !X.res.back().ok) { X.res.pop_back(); X.words.pop_back(); }
+        return rc;
+    });
+    if (rc) *gave_up = rc;                    // beyond the host route's own limits: left unaligned, as align_one does
+    else {
+        const int b = T::pick(X.res.data(), (int)X.res.size(), nh, X.words.data());
+        if (b >= 0) { best = X.res[(size_t)b]; *word = X.words[(size_t)b]; }
     }
-    const int b = hgx_aln_pick<HGX_ALN_HOST_VARS, true>(C.res.data(), (int)C.res.size(), nh, C.clips.data());
-    if (b >= 0) { best = C.res[(size_t)b]; *clips = C.clips[(size_t)b]; }
-}
-
-// the gap tier (hgx_align_more.gap > 0) for a read align_one found nothing for: the gap canons of the same anchors.  The memo is off,
-// as in the clip tier: it drops an arrival that a plain search never needs, and that arrival may be the prefix of the smallest way
-// with a gap (hgx_align_core.hpp).
-struct GapScratch {
-    std::vector<hgx_aln_frame> stk2;
-    std::vector<int32_t> cur2;
-    std::vector<hgx_aln_side<HGX_ALN_HOST_VARS>> sides;
-    std::vector<HostRes> res;
-    std::vector<uint32_t> gds;
-    GapScratch() : stk2(HGX_ALN_HOST_VARS), cur2(HGX_ALN_HOST_VARS), sides(3) {}
-};
-
-void align_one_gap(const hgx_aln_view &V, const char *seq, int L, int max_edits, int gap, HostScratch &S, GapScratch &G, HostRes &best, int *nh,
-                   uint32_t *gd, int *n_anchors, int *gave_up) {
-    G.res.clear();
-    G.gds.clear();
-    best.ok = 0;
-    *nh = 0;
-    *gd = 0;
-    for (int strand = 0; strand < 2; ++strand) {
-        const hgx_aln_read R{seq, L, strand};
-        const int n_off = hgx_aln_n_offsets(L);
-        for (int k = 0; k < n_off; ++k) {
-            const int o = hgx_aln_offset(L, k);
-            uint32_t code;
-            if (!hgx_aln_seed_code(R, o, &code)) continue;
-            for (uint32_t h = hgx_aln_hash(code) & V.hmask; V.hpos[h] >= 0; h = (h + 1) & V.hmask) {
-                if (V.hkey[h] != code) continue;
-                ++*n_anchors;
-                G.res.emplace_back();
-                G.gds.push_back(0);
-                const int rc = hgx_aln_gap_canon<HGX_ALN_HOST_VARS, HGX_ALN_HOST_VARS>(V, R, o, V.hpos[h], max_edits, gap, HGX_ALN_HOST_STEPS,
-                                                                                      S.stk.data(), S.cur.data(), G.stk2.data(), G.cur2.data(),
-                                                                                      G.sides.data(), G.res.back(), &G.gds.back());
-                if (rc) {                     // beyond the host route's own limits: left unaligned, as align_one does
-                    *gave_up = rc;
-                    return;
-                }
-                if (!G.res.back().ok) { G.res.pop_back(); G.gds.pop_back(); }
-            }
-        }
-    }
-    const int b = hgx_aln_gap_pick(G.res.data(), (int)G.res.size(), nh, G.gds.data());
-    if (b >= 0) { best = G.res[(size_t)b]; *gd = G.gds[(size_t)b]; }
+    if (n_anchors > 0) hgx_align_tier_count(T::id, 1, *word != 0, T::bases(*word));
 }
 
 // ---- the host route's states form (hgx_align_states.hpp): the same cells as the kernels, in loops --------------------------------
@@ -339,17 +333,10 @@ int align_one_states(const hgx_aln_view &V, const char *seq, int L, int max_edit
     S.nh.clear();
     best.ok = 0;
     *nh = 0;
-    for (int strand = 0; strand < 2; ++strand) {
-        const hgx_aln_read R{seq, L, strand};
-        const int n_off = hgx_aln_n_offsets(L);
-        for (int k = 0; k < n_off; ++k) {
-            const int o = hgx_aln_offset(L, k);
-            uint32_t code;
-            if (!hgx_aln_seed_code(R, o, &code)) continue;
-            for (uint32_t h = hgx_aln_hash(code) & V.hmask; V.hpos[h] >= 0; h = (h + 1) & V.hmask)
-                if (V.hkey[h] == code) S.all.push_back({strand, hgx_aln_locus_of(V, V.hpos[h]), {o | (strand << 16), V.hpos[h]}});
-        }
-    }
+    each_anchor(V, seq, L, [&](const hgx_aln_read &R, int o, int32_t b) {
+        S.all.push_back({R.strand, hgx_aln_locus_of(V, b), {o | (R.strand << 16), b}});
+        return 0;
+    });
     if (S.all.empty()) return HGX_OK;
     std::stable_sort(S.all.begin(), S.all.end(), [](const StatesScratch::A &a, const StatesScratch::A &b) {
         return a.strand != b.strand ? a.strand < b.strand : a.locus < b.locus;
@@ -457,15 +444,16 @@ bool pair_pick(PairScratch &S, int max_fragment, int *b1, int *b2, int *nh) {
     return true;
 }
 
+// T: the call's fallback tier (NoTier: none); it also settles which hgx_aln_line writes the records
+template <class T>
 int host_route(const hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_align_opts *o, int gap, std::string &body, int64_t *aligned,
                int64_t *conc, int *gave_up) {
     const hgx_aln_view &V = ix->hv;
     HostScratch S;
     StatesScratch SS;
     PairScratch PS;
-    std::unique_ptr<ClipScratch> CS(o->clip > 0 ? new ClipScratch : nullptr);
-    std::unique_ptr<GapScratch> GS(gap > 0 ? new GapScratch : nullptr);
-    uint32_t clips[2] = {0, 0}, gds[2] = {0, 0};
+    TierScratch<T> TS;
+    uint32_t word[2] = {0, 0};                           // the tier's extra word of each mate (0: the tier did not align it)
     const int per = reads.paired ? 2 : 1;
     const bool pair_aware = per == 2 && o->pair == 1;
     std::vector<HostRes> best(per);
@@ -479,18 +467,10 @@ int host_route(const hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
                                      : align_one(V, seq, reads.len[k + m], o->max_edits, S, best[m], &nh[m], &gu);
             if (rc) return rc;
             if (pair_aware) PS.cand[m].swap(S.res);      // (a mate that gave up: none)
-            clips[m] = 0;
-            if (CS && !best[m].ok && !gu) {              // no end-to-end alignment: the clip tier over the same anchors
-                int n_anchors = 0;
-                align_one_clip(V, seq, reads.len[k + m], o->max_edits, o->clip, S, *CS, best[m], &nh[m], &clips[m], &n_anchors, &gu);
-                if (n_anchors > 0) hgx_align_clip_count(1, best[m].ok && clips[m] != 0, best[m].ok ? hgx_aln_clip_total(clips[m]) : 0);
-            }
-            gds[m] = 0;
-            if (GS && !best[m].ok && !gu) {              // no end-to-end alignment: the gap tier over the same anchors
-                int n_anchors = 0;
-                align_one_gap(V, seq, reads.len[k + m], o->max_edits, gap, S, *GS, best[m], &nh[m], &gds[m], &n_anchors, &gu);
-                if (n_anchors > 0) hgx_align_gap_count(1, best[m].ok, best[m].ok ? hgx_aln_gap_len(gds[m]) : 0);
-            }
+            word[m] = 0;
+            if constexpr (T::id != HGX_ALN_TIER_NONE)
+                if (!best[m].ok && !gu)                  // no end-to-end alignment: the tier over the same anchors
+                    align_one_tier<T>(V, seq, reads.len[k + m], o->max_edits, T::budget(o, gap), S, TS, best[m], &nh[m], &word[m], &gu);
             if (gu) *gave_up = gu;
         }
         if (pair_aware && best[0].ok && best[1].ok) {
@@ -513,18 +493,13 @@ int host_route(const hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
             const size_t i = k + m;
             const char *qual = reads.qual_off[i] >= 0 ? reads.text.data() + reads.qual_off[i] : nullptr;
             const HostRes *mate = per == 2 ? &best[1 - m] : nullptr;
-            const int cl = hgx_aln_clip_l(clips[m]), cr = hgx_aln_clip_r(clips[m]);
             hgx_aln_out cnt{nullptr, 0}, w{nullptr, 0};
             for (int pass = 0; pass < 2; ++pass) {       // the size, then the bytes
-                hgx_aln_out &dst = pass ? w : cnt;
-                if (gds[m])
-                    hgx_aln_line<HGX_ALN_HOST_VARS, false, true>(V, reads.text.data() + reads.name_off[i], reads.name_len[i],
+                // (a word of 0, a read aligned end to end, gives the plain line with either tier's arguments, as in k_aln_emit)
+                hgx_aln_line<HGX_ALN_HOST_VARS, T::CLIP, T::GAP>(V, reads.text.data() + reads.name_off[i], reads.name_len[i],
                                                                  reads.text.data() + reads.seq_off[i], qual, reads.len[i], best[m], nh[m], mate, m,
-                                                                 o->max_fragment, dst, 0, 0, gds[m]);
-                else
-                    hgx_aln_line<HGX_ALN_HOST_VARS, true>(V, reads.text.data() + reads.name_off[i], reads.name_len[i],
-                                                          reads.text.data() + reads.seq_off[i], qual, reads.len[i], best[m], nh[m], mate, m,
-                                                          o->max_fragment, dst, cl, cr);
+                                                                 o->max_fragment, pass ? w : cnt, T::CLIP ? hgx_aln_clip_l(word[m]) : 0,
+                                                                 T::CLIP ? hgx_aln_clip_r(word[m]) : 0, T::GAP ? word[m] : 0);
                 if (!pass) {
                     line.resize((size_t)cnt.n);
                     w.p = line.data();
@@ -542,15 +517,11 @@ void hgx_align_states_count(int64_t reads, int64_t anchors, int64_t cells) {
     g_st_anchors += anchors;
     g_st_cells += cells;
 }
-void hgx_align_clip_count(int64_t searched, int64_t clipped, int64_t bases) {
-    g_cl_searched += searched;
-    g_cl_clipped += clipped;
-    g_cl_bases += bases;
-}
-void hgx_align_gap_count(int64_t searched, int64_t gapped, int64_t bases) {
-    g_gp_searched += searched;
-    g_gp_gapped += gapped;
-    g_gp_bases += bases;
+void hgx_align_tier_count(int tier, int64_t searched, int64_t found, int64_t bases) {
+    g_tier = tier;
+    g_tr_searched += searched;
+    g_tr_found += found;
+    g_tr_bases += bases;
 }
 void hgx_align_pairs_count(int64_t searched, int64_t placed, int64_t changed) {
     g_pr_searched += searched;
@@ -702,8 +673,8 @@ extern "C" int hgx_align_reads_x(hgx_align_index *ix, int32_t n_inputs, const ch
     g_route = 0; g_decline = 0; g_reads = g_aligned = g_conc = 0;
     g_st_reads = g_st_anchors = g_st_cells = 0;
     g_pr_searched = g_pr_placed = g_pr_changed = 0;
-    g_cl_searched = g_cl_clipped = g_cl_bases = 0;
-    g_gp_searched = g_gp_gapped = g_gp_bases = 0;
+    g_tier = HGX_ALN_TIER_NONE;
+    g_tr_searched = g_tr_found = g_tr_bases = 0;
     try {
         hgx_aln_reads reads;
         int rc = load_reads(n_inputs, paths, texts, text_bytes, opts->fastq, reads);
@@ -723,10 +694,11 @@ extern "C" int hgx_align_reads_x(hgx_align_index *ix, int32_t n_inputs, const ch
             aligned = conc = 0;
             g_st_reads = g_st_anchors = g_st_cells = 0;          // what the kernels took before they declined is not this call's answer
             g_pr_searched = g_pr_placed = g_pr_changed = 0;
-            g_cl_searched = g_cl_clipped = g_cl_bases = 0;
-            g_gp_searched = g_gp_gapped = g_gp_bases = 0;
+            g_tier = HGX_ALN_TIER_NONE;
+            g_tr_searched = g_tr_found = g_tr_bases = 0;
             int gave_up = 0;
-            if ((rc = host_route(ix, reads, opts, gap, body, &aligned, &conc, &gave_up))) return rc;
+            const auto route = opts->clip > 0 ? host_route<ClipTier> : gap > 0 ? host_route<GapTier> : host_route<NoTier>;
+            if ((rc = route(ix, reads, opts, gap, body, &aligned, &conc, &gave_up))) return rc;
             if (gave_up) fprintf(stderr, "[hgx_align_reads] a read's search passed the host route's limits (code %d): left unaligned\n", gave_up);
         }
         g_route = decline ? 0 : 2;
@@ -771,16 +743,17 @@ extern "C" int hgx_align_last_pairs(int64_t *searched, int64_t *placed, int64_t 
     return HGX_OK;
 }
 
-extern "C" int hgx_align_last_clip(int64_t *searched, int64_t *clipped, int64_t *bases) {
-    if (searched) *searched = g_cl_searched;
-    if (clipped) *clipped = g_cl_clipped;
-    if (bases) *bases = g_cl_bases;
+// the last call's tier counters if `tier` is the one it ran, else zeros
+static int tier_last(int tier, int64_t *searched, int64_t *found, int64_t *bases) {
+    const bool ran = g_tier == tier;
+    if (searched) *searched = ran ? g_tr_searched : 0;
+    if (found) *found = ran ? g_tr_found : 0;
+    if (bases) *bases = ran ? g_tr_bases : 0;
     return HGX_OK;
 }
-
+extern "C" int hgx_align_last_clip(int64_t *searched, int64_t *clipped, int64_t *bases) {
+    return tier_last(HGX_ALN_TIER_CLIP, searched, clipped, bases);
+}
 extern "C" int hgx_align_last_gap(int64_t *searched, int64_t *gapped, int64_t *bases) {
-    if (searched) *searched = g_gp_searched;
-    if (gapped) *gapped = g_gp_gapped;
-    if (bases) *bases = g_gp_bases;
-    return HGX_OK;
+    return tier_last(HGX_ALN_TIER_GAP, searched, gapped, bases);
 }

@@ -211,6 +211,29 @@ def test_align_reads_takes_the_gap_name(tmp_path):
                              truth=(Genes, Vars, refGenes), var_list=Var_list)
 
 
+def test_the_tier_counters_do_not_leak_between_calls(capfd):
+    """The two tiers share one counter triple in the library: in calls that follow each other on one thread, each of
+    hgx_align_last_clip and hgx_align_last_gap reports its own tier's call and zeros after the other tier's or a default call."""
+    import align_clip_cases as cc
+    cst, gst = {}, {}
+    cc.ref_text("chand0", stats=cst)
+    gc.ref_text("ghand0", stats=gst)
+    assert cst["clipped"] > 0 and gst["gapped"] > 0
+    want_clip, want_gap = (cst["searched"], cst["clipped"], cst["bases"]), (gst["searched"], gst["gapped"], gst["bases"])
+
+    def six(which):
+        d, texts, me, n = cc.inputs()["chand0"] if which != "gap" else gc.inputs()["ghand0"]
+        last = _host(d, texts, me, capfd, **({} if which == "default" else {which: n}))[1]
+        return ((last["clip_searched"], last["clip_clipped"], last["clip_bases"]), (last["gap_searched"], last["gap_gapped"], last["gap_bases"]))
+
+    assert six("clip") == (want_clip, (0, 0, 0))
+    assert six("gap") == ((0, 0, 0), want_gap)
+    assert six("clip") == (want_clip, (0, 0, 0))
+    assert six("default") == ((0, 0, 0), (0, 0, 0))
+    assert six("gap") == ((0, 0, 0), want_gap)
+    assert six("default") == ((0, 0, 0), (0, 0, 0))
+
+
 def test_the_symbols_are_declared_and_bound():
     for name in ("hgx_align_reads_x", "hgx_align_last_gap"):
         assert name in capi.SYMBOLS and hasattr(capi.lib(), name)

@@ -1,4 +1,4 @@
-"""The clip tier's kernels (csrc/hgx_align.hip: k_aln_clip_mark / _fill / _extend / _pick, k_aln_emit<true>; route = 2) give the
+"""The clip tier's kernels (csrc/hgx_align.hip: k_aln_tier_mark / _fill / _extend<ClipTier> / _pick<ClipTier>, k_aln_emit<true>; route = 2) give the
 plain-Python statement's text (tests/align_clip_ref.py) byte for byte: on the host test's inputs, with 0, 1 and all reads of a call
 clipped, with the only clipped read first in, last in and alone in the second chunk, at the anchor and variant limits of the fixed
 scratch (past them the host route finishes the call), with clip = 0 (align_ref's bytes, counters zero: the tier's launches stand

@@ -1,4 +1,4 @@
-"""The gap tier's kernels (csrc/hgx_align.hip: the clip tier's mark and fill, k_aln_gap_extend, k_aln_gap_pick, k_aln_emit<false, true>;
+"""The gap tier's kernels (csrc/hgx_align.hip: k_aln_tier_mark / _fill / _extend<GapTier> / _pick<GapTier>, k_aln_emit<false, true>;
 route = 2) give the plain-Python statement's text (tests/align_gap_ref.py) byte for byte: on the host test's inputs and random loci,
 with 0, 1 and all reads of a call gapped, with the only gapped read first in, last in and alone in the second chunk, at the anchor,
 variant and stack limits of the fixed scratch (past them the host route finishes the call), with gap = 0 (align_ref's bytes,
@@ -205,6 +205,30 @@ def test_a_decline_behind_a_full_first_chunk():
     assert (last["route"], last["decline"]) == (0, align.DECLINE_ANCHORS), last
     assert got == want
     assert _counters(last) == {c: sum(stats[j][c] for j in pick) + st[c] for c in ("searched", "gapped", "bases")}
+
+
+def test_the_tier_counters_do_not_leak_between_calls():
+    """The two tiers share one counter triple in the library: in kernel-route calls that follow each other on one thread, each of
+    hgx_align_last_clip and hgx_align_last_gap reports its own tier's call and zeros after the other tier's or a default call."""
+    import align_clip_cases as cc
+    cst, gst = {}, {}
+    cc.ref_text("chand0", stats=cst)
+    gc.ref_text("ghand0", stats=gst)
+    assert cst["clipped"] > 0 and gst["gapped"] > 0
+    want_clip, want_gap = (cst["searched"], cst["clipped"], cst["bases"]), (gst["searched"], gst["gapped"], gst["bases"])
+
+    def six(which):
+        d, texts, me, n = cc.inputs()["chand0"] if which != "gap" else gc.inputs()["ghand0"]
+        last = _device(d, texts, me, **({} if which == "default" else {which: n}))[1]
+        assert (last["route"], last["decline"]) == (2, 0), last
+        return ((last["clip_searched"], last["clip_clipped"], last["clip_bases"]), (last["gap_searched"], last["gap_gapped"], last["gap_bases"]))
+
+    assert six("clip") == (want_clip, (0, 0, 0))
+    assert six("gap") == ((0, 0, 0), want_gap)
+    assert six("clip") == (want_clip, (0, 0, 0))
+    assert six("default") == ((0, 0, 0), (0, 0, 0))
+    assert six("gap") == ((0, 0, 0), want_gap)
+    assert six("default") == ((0, 0, 0), (0, 0, 0))
 
 
 def test_the_device_front_end_equals_the_host_front_end_on_the_gapped_text():
