@@ -95,8 +95,8 @@ LAB_UNITS = ["hgx_em.hip", "hgx_device.hip", "hgx_dedup.hip", "hgx_type.hip", "h
 
 
 def build_lab(force=False, verbose=True):
-    """libhgx_lab.so: the product objects with the LAB_UNITS recompiled under -DHGX_LAB -- hgx_em.hip (the int8-MFMA, persistent and
-    resident-grid EM back-ends in csrc/lab/*.inc) and hgx_front_host.cpp (the CPU emulation of the device front end's kernels, which
+    """libhgx_lab.so: the product objects with the LAB_UNITS recompiled under -DHGX_LAB -- hgx_em.hip (the VALU bit mat-vec, k_em_ref
+    and k_em_small in csrc/lab/*.inc) and hgx_front_host.cpp (the CPU emulation of the device front end's kernels, which
     the CPU test-suite compares with the host front end).  Lab tools and tests bind it (capi.use_lab()); nothing in the product
     path does."""
     build(force=force, verbose=verbose)

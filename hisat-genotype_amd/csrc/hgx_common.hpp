@@ -81,7 +81,6 @@ struct hgx_classes {
     int64_t *d_count;        // [n_classes]
     int64_t *d_first_row;    // [n_classes]
     uint64_t *d_bitsT;       // lazily built [a_pad][c64]
-    uint64_t *d_prow = nullptr, *d_pcol = nullptr;   // lazily built MFMA-operand orders of the compact matrices (hgx_em.hip)
     // lazily built by the EM (hgx_em.hip): the matrices restricted to the alleles that occur in some class
     int32_t n_act = -1, a1p = 0;                     // active alleles, padded to a multiple of 512
     int32_t *d_act = nullptr;                        // [n_act] ascending allele ids
@@ -124,6 +123,12 @@ struct DevBuf {
             hgx_set_error("device allocation of %zu bytes failed", (size_t)(bytes));   \
             return HGX_ENOMEM;                                         \
         }                                                              \
+    } while (0)
+// a call that returns HGX_OK or an error code which the caller passes on
+#define TRY(expr)                                                      \
+    do {                                                               \
+        const int rc_ = (expr);                                        \
+        if (rc_) return rc_;                                           \
     } while (0)
 
 // a function that queues work on `s` over buffers of its own frame: whatever way it returns, the stream has run dry before they go

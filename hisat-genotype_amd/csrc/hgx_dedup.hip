@@ -942,7 +942,6 @@ extern "C" int hgx_classes_destroy(hgx_classes *c) {
     if (c->ready) (void)hipEventSynchronize(c->ready);
     else if (c->made_on) (void)hipStreamSynchronize(c->made_on);
     hgx_pool_free(c->d_bits); hgx_pool_free(c->d_count); hgx_pool_free(c->d_first_row); hgx_pool_free(c->d_bitsT);
-    hgx_pool_free(c->d_prow); hgx_pool_free(c->d_pcol);
     hgx_pool_free(c->d_act); hgx_pool_free(c->d_bitsC); hgx_pool_free(c->d_bitsTC);
     hgx_pool_free(c->d_wrow); hgx_pool_free(c->d_wcol);
     hgx_pool_free(c->d_setup0); hgx_pool_free(c->d_setup1);

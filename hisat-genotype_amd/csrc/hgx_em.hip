@@ -940,19 +940,6 @@ __device__ __forceinline__ double lut_row(const double *T, const uint64_t (&w)[8
     }
     return acc;
 }
-// lut_row for matrix words that live in registers across many passes (k_em_grid): the words are passed through an empty
-// asm so that the compiler cannot hoist the 64 table addresses of a row out of the iteration loop (it did: 128 loop-invariant
-// VGPRs, spilled to scratch and re-loaded before every lookup)
-[[maybe_unused]] __device__ __forceinline__ double lut_row_resident(const double *T, const uint64_t (&w)[8]) {
-    uint64_t v[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        uint32_t lo = (uint32_t)w[i], hi = (uint32_t)(w[i] >> 32);
-        asm volatile("" : "+v"(lo), "+v"(hi));
-        v[i] = (uint64_t)hi << 32 | lo;
-    }
-    return lut_row(T, v);
-}
 template <int MODE>
 __global__ __launch_bounds__(BLOCK) void k_lutmatvec(const uint64_t *__restrict__ M, int N, int Npad, int n_k,
                                                      const double *__restrict__ vec, const uint8_t *__restrict__ vec_pres,
@@ -1250,29 +1237,6 @@ __global__ __launch_bounds__(BLOCK) void k_lut_rows_fused(const uint64_t *__rest
     if (n < Npad) part[(size_t)slab * Npad + n] = acc2;      // the cols pass adds the slabs
 }
 
-
-
-// arguments of the resident-block EM (k_em_grid, lab build): the host code that prepares them is shared
-struct GkArgs {
-    const uint64_t *Mr, *Mc;          // word-transposed matrices [w64c][Cp], [c64][A]
-    int C, Cp, A;                     // classes, padded classes (multiple of 512), compact padded alleles (multiple of 512)
-    int R, K;                         // class chunks of 1024, allele slabs of 512
-    const int64_t *count;
-    const double *len;
-    double *p;                        // estimate in / out
-    uint8_t *pr;
-    double *part_r, *part_c, *Y;      // [2][K][Cp], [2][Cp/512][A], [2][R][A]
-    unsigned *flags;                  // [3][R*K] words, 128 bytes apart, zero at launch
-    double *scal;
-    int *abort_flag;
-    int remove_low, n_iters, do_init;
-    unsigned long long *stamps;       // HGX_GRID_STAMPS=1: wall_clock64() of thread 0 at the phase boundaries, [R*K][GK_STAMPS]
-};
-constexpr int GK_STAMPS = 128;
-[[maybe_unused]] constexpr long GK_SPIN_LIMIT = 1500000;     // bounded spin (~0.5 s): an error code, never a hung GPU
-constexpr int GK_FLAG_STRIDE = 32;
-[[maybe_unused]] constexpr size_t GK_LDS = (size_t)(LUT_G * 256 + BLOCK) * 8;
-
 // u64-element transpose: out[c][r] = in[r][c]  (in [n_rows][n_cols])
 __global__ __launch_bounds__(256) void k_word_transpose(const uint64_t *__restrict__ in, int n_rows, int n_cols,
                                                         uint64_t *__restrict__ out) {
@@ -1293,36 +1257,18 @@ __global__ __launch_bounds__(256) void k_word_transpose(const uint64_t *__restri
 struct MatVec {
     const uint64_t *B;
     int n_rows, n_words, n_k;
-    const uint64_t *P = nullptr;    // MFMA operand order of B (k_permute_mfma), or nullptr -> VALU kernel
-    int n_super = 0;
-    const uint64_t *M = nullptr;    // word-transposed B [n_words][n_pad] for the table-lookup kernel, or nullptr
+    const uint64_t *M = nullptr;    // word-transposed B [n_words][n_pad] for the table-lookup kernel, or nullptr -> VALU kernel (lab build)
     int n_pad = 0;
     double *part = nullptr;         // [n_words / 8][n_pad] slab partials
     unsigned *counters = nullptr;   // [ceil(n_rows / 1024)], zero between launches
     // table-lookup EM only: the rows pass leaves its partials for the cols pass to add (see k_lutmatvec)
-    int narrow = 0;                 // the narrow-table form (k_lut4): a workgroup owns its rows for the whole of K
     int defer_combine = 0;
     const double *src_part = nullptr;
     int src_slabs = 0, src_pad = 0;
     const int64_t *src_count = nullptr;
 };
 
-int g_backend = 0;                  // 0 auto, 1 VALU (EXEC-masked FP64), 2 MFMA (int8 fixed point), 3 table lookup
-
-inline bool use_mfma(const MatVec &m) {
-    if (!m.P) return false;
-    if (g_backend == 1) return false;
-    if (g_backend == 2) return true;
-    return false;   // auto: at one-sample problem sizes the VALU kernel is faster; MFMA is opt-in
-}
-
-template <int MODE>
-int launch_mfma(const MatVec &m, hipStream_t st, const double *vec, const uint8_t *vec_pres, int x_mode, const int64_t *count,
-                const double *q_in, const uint8_t *pres_in, const double *len, double *y, uint8_t *pres_out, double *scal,
-                int gate) {
-    hgx_set_error("this EM back-end is lab code: build libhgx_lab.so (hisat-genotype_amd/build.py build_lab) -- libhgx.so ships the table-lookup and reference-order paths only");
-    return HGX_EINVAL;
-}
+int g_backend = 0;                  // 0 auto (table lookup), 1 VALU (EXEC-masked FP64; lab build), 3 table lookup
 
 // events that the next table-lookup launch attaches to its own dispatch (hipExtLaunchKernelGGL: the runtime timestamps the
 // kernel's begin and end, like rocprofv3 does, instead of bracketing it with separately queued event records)
@@ -1333,8 +1279,6 @@ int launch_matvec(const MatVec &m, hipStream_t st, const double *vec, const uint
                   const int64_t *count, const double *q_in, const uint8_t *pres_in, const double *len, double *y,
                   uint8_t *pres_out, double *scal, int gate) {
     if constexpr (MODE == MODE_ROWS || MODE == MODE_COLS) {
-        if (use_mfma(m))
-            return launch_mfma<MODE>(m, st, vec, vec_pres, x_mode, count, q_in, pres_in, len, y, pres_out, scal, gate);
         if (m.M) {
             HGX_ONCE_PER_DEVICE({
                 HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_lutmatvec<MODE>),
@@ -1373,7 +1317,7 @@ int launch_matvec(const MatVec &m, hipStream_t st, const double *vec, const uint
 // Per-kernel timing for bench.py's roofline object.  When enabled (hgx_em_set_timing) every bit-mat-vec launch of
 // hgx_em is bracketed by HIP events on its stream; totals accumulate per kernel instantiation until reset.
 struct PassStats { double ms = 0; int64_t launches = 0, executed = 0, bytes = 0; };
-thread_local PassStats g_stats[5];   // [0] <8,ROWS> [1] <16,ROWS> [2] <8,COLS> [3] <16,COLS> [4] k_em_grid (executed = applications)
+thread_local PassStats g_stats[4];   // [0] <8,ROWS> [1] <16,ROWS> [2] <8,COLS> [3] <16,COLS>
 thread_local int g_timing = 0;
 struct Timed { hipEvent_t a, b; int slot; };
 thread_local std::vector<hipEvent_t> g_event_pool;     // recycled HIP events (creating one per launch is not free)
@@ -1499,8 +1443,8 @@ static int hgx_ensure_compact(hgx_classes *c, hipStream_t st) {
         hipLaunchKernelGGL(k_act_from_mask, dim3(1), dim3(512), 0, st, b_mask.as<unsigned long long>(), w64, b_base.as<int32_t>(), c->d_act);
     HIPCHK(hipGetLastError());
     std::vector<uint64_t> h_mask(w64);
-    { int rc_ = hgx_d2h(h_mask.data(), b_mask.p, (size_t)w64 * 8, st); if (rc_) return rc_; }
-    { int rc_ = hgx_sync(st); if (rc_) return rc_; }
+    TRY(hgx_d2h(h_mask.data(), b_mask.p, (size_t)w64 * 8, st));
+    TRY(hgx_sync(st));
     std::vector<int32_t> h_base(w64);
     c->h_act = new int32_t[A];
     int32_t n = 0;
@@ -1509,8 +1453,8 @@ static int hgx_ensure_compact(hgx_classes *c, hipStream_t st) {
         for (uint64_t m = h_mask[w]; m; m &= m - 1) c->h_act[n++] = 64 * w + __builtin_ctzll(m);
     }
     if (!dev_tables) {
-        { int rc_ = hgx_h2d(b_base.p, h_base.data(), (size_t)w64 * 4, st); if (rc_) return rc_; }
-        { int rc_ = hgx_h2d(c->d_act, c->h_act, (size_t)std::max(n, 1) * 4, st); if (rc_) return rc_; }
+        TRY(hgx_h2d(b_base.p, h_base.data(), (size_t)w64 * 4, st));
+        TRY(hgx_h2d(c->d_act, c->h_act, (size_t)std::max(n, 1) * 4, st));
     }
     const int a1p = std::max(512, (n + 511) / 512 * 512);
     c->d_bitsTC = (uint64_t *)hgx_pool_alloc((size_t)a1p * c->c64 * 8);
@@ -1550,13 +1494,13 @@ extern "C" int hgx_em_last_order(int32_t *order_host, int32_t n) {
     return 1;
 }
 extern "C" int hgx_em_set_fast(int on) { const int old = g_em_fast; g_em_fast = on > 0 ? 1 : (on < 0 ? -1 : 0); return old; }
-static thread_local bool g_no_grid = false;      // set while an EM is re-run after a resident-block launch was abandoned
 extern "C" int hgx_em_last_exact(void) { return g_last_exact; }
 
 extern "C" int hgx_em_set_backend(int backend) {
+    if (backend == 2) { hgx_set_error("EM back-end 2 (the int8-MFMA mat-vec) was removed: measured slower twice; 0 and 3 are the table lookup, 1 the VALU mat-vec of the lab build"); return HGX_EINVAL; }
     ARGCHK(backend >= 0 && backend <= 3);
 #ifndef HGX_LAB
-    if (backend == 1 || backend == 2) { hgx_set_error("this EM back-end is lab code: build libhgx_lab.so (hisat-genotype_amd/build.py build_lab) -- libhgx.so ships the table-lookup and reference-order paths only"); return HGX_EINVAL; }
+    if (backend == 1) { hgx_set_error("this EM back-end is lab code: build libhgx_lab.so (hisat-genotype_amd/build.py build_lab) -- libhgx.so ships the table-lookup and reference-order paths only"); return HGX_EINVAL; }
 #endif
     g_backend = backend;
     return HGX_OK;
@@ -1568,9 +1512,9 @@ extern "C" int hgx_em_set_timing(int on) {
     g_timing = on;
     return HGX_OK;
 }
-// slot: 0 <8,ROWS>, 1 <16,ROWS>, 2 <8,COLS>, 3 <16,COLS>, 4 k_em_grid (whole launches; executed = applications of the EM map)
+// slot: 0 <8,ROWS>, 1 <16,ROWS>, 2 <8,COLS>, 3 <16,COLS>
 extern "C" int hgx_em_get_timing(int slot, double *ms_total, int64_t *launches, int64_t *executed, int64_t *bytes_total) {
-    ARGCHK(slot >= 0 && slot < 5);
+    ARGCHK(slot >= 0 && slot < 4);
     if (ms_total) *ms_total = g_stats[slot].ms;
     if (launches) *launches = g_stats[slot].launches;
     if (executed) *executed = g_stats[slot].executed;
@@ -1647,14 +1591,14 @@ static int em_uncertain_near_tie(hgx_classes *c, int32_t n_alleles, const double
     DevBuf b_ids, b_rows;
     ALLOC(b_ids, ids.size() * 4);
     ALLOC(b_rows, ids.size() * c64 * 8);
-    { int rc_ = hgx_h2d(b_ids.p, ids.data(), ids.size() * 4, st); if (rc_) return rc_; }
+    TRY(hgx_h2d(b_ids.p, ids.data(), ids.size() * 4, st));
     const long n_words = (long)ids.size() * (long)c64;
     hipLaunchKernelGGL(k_gather_rows, dim3(nblk(n_words, 256)), dim3(256), 0, st, (const uint64_t *)c->d_bitsT, (int)c64, b_ids.as<int32_t>(), (int)ids.size(),
                        b_rows.as<uint64_t>());
     HIPCHK(hipGetLastError());
     std::vector<uint64_t> rows(ids.size() * c64);
-    { int rc_ = hgx_d2h(rows.data(), b_rows.p, rows.size() * 8, st); if (rc_) return rc_; }
-    { int rc_ = hgx_sync(st); if (rc_) return rc_; }
+    TRY(hgx_d2h(rows.data(), b_rows.p, rows.size() * 8, st));
+    TRY(hgx_sync(st));
     for (size_t k = 0; k < pairs.size(); ++k)
         if (memcmp(&rows[(2 * k) * c64], &rows[(2 * k + 1) * c64], c64 * 8) != 0) { *uncertain = true; return HGX_OK; }     // different membership, too close to call
     return HGX_OK;
@@ -1679,203 +1623,198 @@ static int em_impl(const hgx_classes *cc, int32_t n_alleles, int32_t remove_low,
     return rc;
 }
 
-static int em_impl_inner(const hgx_classes *cc, int32_t n_alleles, int32_t remove_low, const int32_t *allele_len, double *prob_host,
-                         int32_t *first_host, int32_t *n_iter_host, void *stream) {
-    ARGCHK(cc && prob_host && n_alleles > 0 && n_alleles <= cc->a_pad);
-    g_last_exact = 0;
-    g_last_near = 0;
-    g_last_order.clear();
-    hgx_classes_order_after(cc, (hipStream_t)stream);
-    if (first_host) for (int a = 0; a < n_alleles; ++a) first_host[a] = -1;
-    hgx_classes *c = const_cast<hgx_classes *>(cc);
-    hipStream_t st = (hipStream_t)stream;
-    int A = c->a_pad;
-    const int C = c->n_classes;
-    if (n_iter_host) *n_iter_host = 0;
-    if (C == 0) {
-        // single_abundance({}): `diff` starts at 1.0, so the loop makes ONE pass over the empty dict before it stops
-        // (typing_common.py:1351-1404) -- an empty result after 1 iteration (tools/fuzz_many.py: a hand-off that leaves no class)
-        for (int a = 0; a < n_alleles; ++a) prob_host[a] = -1.0;
-        if (n_iter_host) *n_iter_host = 1;
+// ---- the EM host driver ------------------------------------------------------------------------------------------------------------
+// em_impl_inner offers one call to its stages in turn; a stage returns HGX_OK (it took the problem, the results are in place),
+// EM_DECLINED (the next stage is asked) or an error.
+namespace {
+
+constexpr int EM_DECLINED = 1;
+
+struct EmCall {
+    hgx_classes *c;
+    int32_t n_alleles;
+    int remove_low;                    // 0 / 1, as the kernels take it
+    const int32_t *allele_len;         // or NULL
+    double *prob;                      // [n_alleles] results
+    int32_t *first, *n_iter;           // [n_alleles] first class of every returned allele, iteration count (either may be NULL)
+    hipStream_t st;
+};
+
+int em_key_error() {
+    hgx_set_error("EM: allele missing from the next estimate (the reference raises KeyError here, common:1365-1369)");
+    return HGX_EKEY;
+}
+
+// allele lengths as the kernels read them: doubles over a vector space of A elements, 1.0 where no allele stands.  The host copy lives
+// as long as the device one (an upload too large for the staging buffer is read from it by the stream).
+struct Lengths {
+    DevBuf dev;
+    std::vector<double> host;
+    // element j < n is allele act[j] (act == NULL: allele j)
+    int upload(const EmCall &e, int A, int n, const int32_t *act) {
+        host.assign((size_t)A, 1.0);
+        for (int j = 0; j < n; ++j) {
+            const int a = act ? act[j] : j;
+            if (a < e.n_alleles) host[j] = (double)e.allele_len[a];
+        }
+        ALLOC(dev, (size_t)A * 8);
+        return hgx_h2d(dev.p, host.data(), (size_t)A * 8, e.st);
+    }
+    double *ptr() { return dev.as<double>(); }
+};
+
+// The one-launch EMs (k_em_wave; lab build: k_em_ref, k_em_small) share their host side: operands up, ONE kernel that runs the whole EM
+// over the full allele space, abundances + state words (+ first classes) down in one round trip.  A stage calls the upload steps its
+// kernel needs, in its own order, launches, and closes.
+struct OneLaunch {
+    const EmCall &e;
+    const int A;
+    Lengths len;
+    DevBuf b_scal, b_out, b_first, b_rank;
+    explicit OneLaunch(const EmCall &e_) : e(e_), A(e_.c->a_pad) {}
+    int open() {
+        ALLOC(b_scal, S_N * 8); ALLOC(b_out, (size_t)A * 8);
+        if (e.allele_len) TRY(len.upload(e, A, e.n_alleles, nullptr));
         return HGX_OK;
     }
-    if (C <= 64 && c->w64 <= 128 && !hgx_switch_has("em_skip", "wave")) {
-        // single-wavefront path (<= 64 classes over <= 64 distinct alleles); falls through if more alleles occur
-        DevBuf b_len, b_scal, b_out;
-        ALLOC(b_scal, S_N * 8); ALLOC(b_out, A * 8);
-        double *d_len = nullptr;
-        if (allele_len) {
-            std::vector<double> l(A, 1.0);
-            for (int a = 0; a < n_alleles; ++a) l[a] = (double)allele_len[a];
-            ALLOC(b_len, A * 8);
-            { int rc_ = hgx_h2d(b_len.p, l.data(), A * 8, st); if (rc_) return rc_; }
-            d_len = b_len.as<double>();
-        }
-        HIPCHK(hipMemsetAsync(b_scal.p, 0, S_N * 8, st));
-        DevBuf b_first;
-        std::vector<int32_t> h_first;
-        if (first_host) {
+    int zero_state() {                 // state words 0; first classes -1 where the caller wants them
+        HIPCHK(hipMemsetAsync(b_scal.p, 0, S_N * 8, e.st));
+        if (e.first) {
             ALLOC(b_first, (size_t)A * 4);
-            HIPCHK(hipMemsetAsync(b_first.p, 0xFF, (size_t)A * 4, st));
-            h_first.resize(A);
+            HIPCHK(hipMemsetAsync(b_first.p, 0xFF, (size_t)A * 4, e.st));
         }
-        DevBuf b_rank;
-        if (c->h_rank && !hgx_switch_has("em_skip", "exact")) {
-            ALLOC(b_rank, (size_t)A * 4);
-            { int rc_ = hgx_h2d(b_rank.p, c->h_rank, (size_t)A * 4, st); if (rc_) return rc_; }
-        }
-        hipLaunchKernelGGL(k_em_wave, dim3(1), dim3(64), 0, st, c->d_bits, C, c->w64, A, c->d_count, d_len, remove_low ? 1 : 0,
-                           b_out.as<double>(), b_scal.as<double>(), first_host ? b_first.as<int32_t>() : nullptr,
-                           b_rank.as<int32_t>());
+        return HGX_OK;
+    }
+    int put_rank() {                   // the alleles' name order: the kernel then sums in the reference's order
+        ALLOC(b_rank, (size_t)A * 4);
+        return hgx_h2d(b_rank.p, e.c->h_rank, (size_t)A * 4, e.st);
+    }
+    // one round trip; may_decline: the kernel says in S_FALLBACK that the problem is not its size
+    int close(bool may_decline) {
         HIPCHK(hipGetLastError());
         std::vector<double> out(A);
+        std::vector<int32_t> h_first(b_first.p ? A : 0);
         double h_scal[S_N];
-        if (first_host) { int rc_ = hgx_d2h(h_first.data(), b_first.p, (size_t)A * 4, st); if (rc_) return rc_; }
-        { int rc_ = hgx_d2h(out.data(), b_out.p, A * 8, st); if (rc_) return rc_; }
-        { int rc_ = hgx_d2h(h_scal, b_scal.p, S_N * 8, st); if (rc_) return rc_; }
-        { int rc_ = hgx_sync(st); if (rc_) return rc_; }
-        if (h_scal[S_FALLBACK] == 0.0) {
-            if (h_scal[S_KEYERR] != 0.0) {
-                hgx_set_error("EM: allele missing from the next estimate (the reference raises KeyError here, common:1365-1369)");
-                return HGX_EKEY;
-            }
-            for (int a = 0; a < n_alleles; ++a) prob_host[a] = out[a];
-            if (first_host) for (int a = 0; a < n_alleles; ++a) first_host[a] = h_first[a];
-            if (n_iter_host) *n_iter_host = (int)h_scal[S_ITER];
-            g_last_exact = b_rank.p != nullptr;
-            return HGX_OK;
-        }
-    }
-    if (C <= (g_em_fast < 0 ? HGX_EMX_HARD_MAX_CLASSES : HGX_EMX_MAX_CLASSES) && c->w64 <= 128 && c->h_rank && !hgx_switch_has("em_skip", "exact") &&
-        !hgx_switch_has("em_skip", "emx")) {
-        // problems of up to 4096 classes over up to 8192 distinct alleles in the reference's own order of operations
-        // (k_emx, hgx_emx.hip: one workgroup, one launch, bit-identical abundances); falls through if it does not take the problem
-        DevBuf b_rank, b_len;
-        ALLOC(b_rank, (size_t)A * 4);
-        { int rc_ = hgx_h2d(b_rank.p, c->h_rank, (size_t)A * 4, st); if (rc_) return rc_; }
-        if (allele_len) {
-            std::vector<double> l(A, 1.0);
-            for (int a = 0; a < n_alleles; ++a) l[a] = (double)allele_len[a];
-            ALLOC(b_len, (size_t)A * 8);
-            { int rc_ = hgx_h2d(b_len.p, l.data(), (size_t)A * 8, st); if (rc_) return rc_; }
-        }
-        hgx_emx_job job{};
-        job.bits = c->d_bits; job.count = c->d_count; job.rank = b_rank.as<int32_t>(); job.len = allele_len ? b_len.as<double>() : nullptr;
-        job.C = C; job.w64 = c->w64; job.a_pad = A; job.remove_low = remove_low ? 1 : 0;
-        job.fast = g_em_fast > 0 ? 1 : 0;
-        job.any_size = g_em_fast < 0 ? 1 : 0;
-        std::vector<int32_t> order((size_t)n_alleles, -1);
-        job.prob = prob_host; job.first = first_host; job.order = order.data(); job.n_out = n_alleles;
-        { int rc_ = hgx_emx_run(&job, 1, st); if (rc_) return rc_; }
-        if (job.status == 2) {
-            hgx_set_error("EM: allele missing from the next estimate (the reference raises KeyError here, common:1365-1369)");
-            return HGX_EKEY;
-        }
-        if (job.status == 0) {
-            if (n_iter_host) *n_iter_host = job.n_iter;
-            g_last_exact = job.fast ? 0 : 1;
-            if (!job.fast) g_last_order.swap(order);
-            return HGX_OK;
-        }
-        for (int a = 0; a < n_alleles; ++a) prob_host[a] = 0.0;
-        if (first_host) for (int a = 0; a < n_alleles; ++a) first_host[a] = -1;
-    }
-#ifdef HGX_LAB
-#include "lab/hgx_em_impl_mid.inc"        // round 2's mid-size reference-order EM (k_em_ref)
-#endif
-    // helper for the paths that do not carry the first-class information: look it up for the survivors afterwards
-    [[maybe_unused]] auto first_for_present = [&]() -> int {
-        if (!first_host) return HGX_OK;
-        std::vector<int32_t> al;
-        for (int a = 0; a < n_alleles; ++a) if (prob_host[a] >= 0.0) al.push_back(a);
-        if (al.empty()) return HGX_OK;
-        std::vector<int32_t> f(al.size());
-        int rc_ = hgx_first_classes(cc, al.data(), (int32_t)al.size(), f.data(), stream);
-        if (rc_) return rc_;
-        for (size_t i = 0; i < al.size(); ++i) first_host[al[i]] = f[i];
+        if (b_first.p) TRY(hgx_d2h(h_first.data(), b_first.p, (size_t)A * 4, e.st));
+        TRY(hgx_d2h(out.data(), b_out.p, (size_t)A * 8, e.st));
+        TRY(hgx_d2h(h_scal, b_scal.p, S_N * 8, e.st));
+        TRY(hgx_sync(e.st));
+        if (may_decline && h_scal[S_FALLBACK] != 0.0) return EM_DECLINED;
+        if (h_scal[S_KEYERR] != 0.0) return em_key_error();
+        for (int a = 0; a < e.n_alleles; ++a) e.prob[a] = out[a];
+        if (b_first.p) for (int a = 0; a < e.n_alleles; ++a) e.first[a] = h_first[a];
+        if (e.n_iter) *e.n_iter = (int)h_scal[S_ITER];
+        g_last_exact = b_rank.p != nullptr;
         return HGX_OK;
-    };
-#ifdef HGX_LAB
-#include "lab/hgx_em_impl_small.inc"        // round 1's one-workgroup EM (k_em_small)
-#endif
-    int rc = hgx_ensure_compact(c, st);
-    if (rc) return rc;
-    // from here on every vector lives in the compact allele space: element j is allele c->h_act[j]
-    const int A_full = A;
-    A = c->a1p;
-    const int w64c = A / 64;
-    DevBuf b_p, b_q1, b_q2, b_q3, b_wc, b_pr, b_pr1, b_pr2, b_pr3, b_len, b_scal, b_out;
-    ALLOC(b_p, A * 8); ALLOC(b_q1, A * 8); ALLOC(b_q2, A * 8); ALLOC(b_q3, A * 8); ALLOC(b_out, (A + 1) * 8);   // (+ k_em_finish's count)
-    const size_t n_cnt_all = (size_t)std::max((C + BLOCK - 1) / BLOCK, (A + BLOCK - 1) / BLOCK);
-    ALLOC(b_wc, (size_t)C * 8); ALLOC(b_pr, A); ALLOC(b_pr1, A); ALLOC(b_pr2, A); ALLOC(b_pr3, A); ALLOC(b_scal, S_N * 8 + n_cnt_all * 4);       // (scalars + the passes' slab counters: one block, one memset)
-    double *d_len = nullptr;
-    if (allele_len) {
-        std::vector<double> l(A, 1.0);
-        for (int j = 0; j < c->n_act; ++j) if (c->h_act[j] < n_alleles) l[j] = (double)allele_len[c->h_act[j]];
-        ALLOC(b_len, A * 8);
-        { int rc_ = hgx_h2d(b_len.p, l.data(), A * 8, st); if (rc_) return rc_; }
-        { int rc_ = hgx_sync(st); if (rc_) return rc_; }
-        d_len = b_len.as<double>();
     }
-    double *p = b_p.as<double>(), *q1 = b_q1.as<double>(), *q2 = b_q2.as<double>(), *q3 = b_q3.as<double>();
-    uint8_t *pr = b_pr.as<uint8_t>(), *pr1 = b_pr1.as<uint8_t>(), *pr2 = b_pr2.as<uint8_t>(), *pr3 = b_pr3.as<uint8_t>();
-    double *wc = b_wc.as<double>(), *scal = b_scal.as<double>();
-    HIPCHK(hipMemsetAsync(scal, 0, S_N * 8 + n_cnt_all * 4, st));
-    // tie order of the result (first class containing each allele): independent of the EM, queued before it
-    DevBuf b_fc;
-    std::vector<int32_t> h_fc;
-    if (first_host) {
-        ALLOC(b_fc, (size_t)A * 4);
-        h_fc.resize(A);
-        hipLaunchKernelGGL(k_first_set_rows, dim3(nblk((long)A * 64, 256)), dim3(256), 0, st, c->d_bitsTC, A, c->c64, b_fc.as<int32_t>());
-    }
-    MatVec rows{c->d_bitsC, C, w64c, A};
-    MatVec cols{c->d_bitsTC, A, c->c64, C};
+};
 
-    DevBuf b_part, b_part_c;
-    if (g_backend == 0 || g_backend == 3) {
-        // table-lookup kernels: word-transposed copies of both matrices, built once per class set
-        const int Cp = c->c64 * 64;
-        if (!c->d_wrow) {
-            c->d_wrow = (uint64_t *)hgx_pool_alloc((size_t)w64c * Cp * 8);
-            c->d_wcol = (uint64_t *)hgx_pool_alloc((size_t)c->c64 * A * 8);
-            if (!c->d_wrow || !c->d_wcol) { hgx_set_error("device allocation failed"); return HGX_ENOMEM; }
-            hipLaunchKernelGGL(k_word_transpose, dim3((w64c + 31) / 32, (Cp + 31) / 32), dim3(256), 0, st, c->d_bitsC, Cp, w64c, c->d_wrow);
-            hipLaunchKernelGGL(k_word_transpose, dim3((c->c64 + 31) / 32, (A + 31) / 32), dim3(256), 0, st, c->d_bitsTC, A, c->c64, c->d_wcol);
-        }
-        const size_t n_part_r = (size_t)(w64c / 8) * Cp, n_part_c = (size_t)(c->c64 / 8) * A;
-        ALLOC(b_part, std::max(n_part_r, n_part_c) * 8); ALLOC(b_part_c, n_part_c * 8);
-        unsigned *const slab_counters = (unsigned *)(scal + S_N);                   // zeroed with the scalars above
-        rows.M = c->d_wrow; rows.n_pad = Cp; rows.part = b_part.as<double>(); rows.counters = slab_counters;
-        cols.M = c->d_wcol; cols.n_pad = A; cols.part = b_part_c.as<double>(); cols.counters = slab_counters;
-        if (!rows.narrow && !HGX_LAB_SWITCH("em_persist") && !hgx_switch_has("em_skip", "defer")) {
-            // the rows pass stops at its slab partials; the cols pass turns them into w_c in its prologue
-            rows.defer_combine = 1;
-            cols.src_part = rows.part; cols.src_slabs = w64c / 8; cols.src_pad = Cp; cols.src_count = c->d_count;
-        }
+int em_empty(const EmCall &e) {
+    if (e.c->n_classes != 0) return EM_DECLINED;
+    // single_abundance({}): `diff` starts at 1.0, so the loop makes ONE pass over the empty dict before it stops
+    // (typing_common.py:1351-1404) -- an empty result after 1 iteration (tools/fuzz_many.py: a hand-off that leaves no class)
+    for (int a = 0; a < e.n_alleles; ++a) e.prob[a] = -1.0;
+    if (e.n_iter) *e.n_iter = 1;
+    return HGX_OK;
+}
+
+// single wavefront (k_em_wave): <= 64 classes over <= 64 distinct alleles; the kernel declines if more alleles occur
+int em_wave(const EmCall &e) {
+    hgx_classes *c = e.c;
+    if (c->n_classes > 64 || c->w64 > 128 || hgx_switch_has("em_skip", "wave")) return EM_DECLINED;
+    OneLaunch o(e);
+    TRY(o.open());
+    TRY(o.zero_state());
+    if (c->h_rank && !hgx_switch_has("em_skip", "exact")) TRY(o.put_rank());
+    hipLaunchKernelGGL(k_em_wave, dim3(1), dim3(64), 0, e.st, c->d_bits, c->n_classes, c->w64, o.A, c->d_count,
+                       o.len.ptr(), e.remove_low, o.b_out.as<double>(), o.b_scal.as<double>(),
+                       o.b_first.as<int32_t>(), o.b_rank.as<int32_t>());
+    return o.close(true);
+}
+
+// reference order (k_emx, hgx_emx.hip): up to 4096 classes over up to 8192 distinct alleles in the reference's own order of operations
+// -- one workgroup, one launch, bit-identical abundances; declines if hgx_emx_run does not take the problem
+int em_reference_order(const EmCall &e) {
+    hgx_classes *c = e.c;
+    const int A = c->a_pad;
+    if (c->n_classes > (g_em_fast < 0 ? HGX_EMX_HARD_MAX_CLASSES : HGX_EMX_MAX_CLASSES) || c->w64 > 128 || !c->h_rank ||
+        hgx_switch_has("em_skip", "exact") || hgx_switch_has("em_skip", "emx"))
+        return EM_DECLINED;
+    DevBuf b_rank;
+    Lengths len;
+    ALLOC(b_rank, (size_t)A * 4);
+    TRY(hgx_h2d(b_rank.p, c->h_rank, (size_t)A * 4, e.st));
+    if (e.allele_len) TRY(len.upload(e, A, e.n_alleles, nullptr));
+    hgx_emx_job job{};
+    job.bits = c->d_bits; job.count = c->d_count; job.rank = b_rank.as<int32_t>(); job.len = len.ptr();
+    job.C = c->n_classes; job.w64 = c->w64; job.a_pad = A; job.remove_low = e.remove_low;
+    job.fast = g_em_fast > 0 ? 1 : 0;
+    job.any_size = g_em_fast < 0 ? 1 : 0;
+    std::vector<int32_t> order((size_t)e.n_alleles, -1);
+    job.prob = e.prob; job.first = e.first; job.order = order.data(); job.n_out = e.n_alleles;
+    TRY(hgx_emx_run(&job, 1, e.st));
+    if (job.status == 2) return em_key_error();
+    if (job.status == 0) {
+        if (e.n_iter) *e.n_iter = job.n_iter;
+        g_last_exact = job.fast ? 0 : 1;
+        if (!job.fast) g_last_order.swap(order);
+        return HGX_OK;
     }
-    // ---- resident-block path (k_em_grid): the block grid must be co-resident, one workgroup per CU ----------------
-    // two resident grids that together need more CUs than the chip has could each hold a part and wait forever: grids reserve
-    // their CUs from a process-wide budget and one that does not fit runs per pass instead
-    static std::atomic<int> grid_cus{0};
-    struct GridHold {
-        int g = 0;
-        void release() { if (g) grid_cus.fetch_sub(g); g = 0; }
-        ~GridHold() { release(); }
-    } grid_hold;
-    GkArgs ga{};
-    DevBuf b_gpr, b_gpc, b_gy, b_gfl, b_gst;
-    bool grid = false;
-    // opt-in (HGX_EM_GRID=1), or for small block grids only (HGX_EM_GRID_MAX workgroups: many small tasks in flight are bound by
-    // the launch rate, and one launch replaces ~66)
-    int grid_launches = 0;
-    std::vector<Timed> timed;
-    const int slot_rows = A <= 8 * BLOCK ? 0 : 1, slot_cols = C <= 8 * BLOCK ? 2 : 3;
+    for (int a = 0; a < e.n_alleles; ++a) e.prob[a] = 0.0;
+    if (e.first) for (int a = 0; a < e.n_alleles; ++a) e.first[a] = -1;
+    return EM_DECLINED;
+}
+
+#ifdef HGX_LAB
+#include "lab/hgx_em_impl_mid.inc"          // em_lab_mid: round 2's mid-size reference-order EM (k_em_ref)
+#include "lab/hgx_em_impl_small.inc"        // em_lab_small: round 1's one-workgroup EM (k_em_small)
+#endif
+
+// a captured batch (lab switch em_graph): destroyed only once the stream has run it
+struct GraphDrop {
+    hipStream_t s;
+    hipGraphExec_t exec = nullptr;
+    hipGraph_t graph = nullptr;
+    ~GraphDrop() {
+        if (exec) { (void)hipStreamSynchronize(s); (void)hipGraphExecDestroy(exec); }
+        if (graph) (void)hipGraphDestroy(graph);
+    }
+};
+
+// table lookup: the chip-wide EM of every problem the stages above declined (k_lutmatvec, k_lut_rows_fused; lab back-end 1: the VALU
+// bit mat-vec).  Every vector lives in the compact allele space: element j is allele c->h_act[j].  run(), at the end, is the list of steps.
+struct TableEM {
+    const EmCall &e;
+    hgx_classes *const c;
+    const hipStream_t st;
+    const int C;
+    int A = 0;                         // c->a1p
+    DevBuf b_p, b_q1, b_q2, b_q3, b_wc, b_pr, b_pr1, b_pr2, b_pr3, b_scal, b_out, b_fc, b_part, b_part_c;
+    DevBuf b_palt, b_pralt, b_q2x, b_prx, b_scal2;                        // fused steps only
+    Lengths len;
+    double *p = nullptr, *q1 = nullptr, *q2 = nullptr, *q3 = nullptr, *wc = nullptr, *d_len = nullptr;
+    uint8_t *pr = nullptr, *pr1 = nullptr, *pr2 = nullptr, *pr3 = nullptr;
+    double *scal = nullptr, *scal_alt = nullptr;                          // state words: swapped by every fused launch
+    double *p_alt = nullptr, *q2x = nullptr;
+    uint8_t *pr_alt = nullptr, *prx = nullptr;
+    MatVec rows{}, cols{};
+    bool fuse = false;                 // SQUAREM and the advance step ride in the rows pass that follows them (k_lut_rows_fused)
     // timing: g_timing == 1 samples every 4th ungated rows pass of a call and the cols pass that follows it; g_timing == 2
     // times every plain rows / cols pass (bench.py turns it on for the last steps of the timed region only)
-    int n_rows_seen = 0;
+    std::vector<Timed> timed;
+    int slot_rows = 0, slot_cols = 0, n_rows_seen = 0;
     bool stamping = false;
-    auto stamp = [&](int slot, bool begin, int gate) {
+    // what the host has read back
+    double h_scal[S_N];
+    std::vector<double> out;           // [A] abundances (+ k_em_finish's count of decisions on a threshold)
+    std::vector<int32_t> h_fc;         // [A] first classes
+    bool tail_done = false;            // the compact tail kernel finished the EM
+    bool results_fetched = false;      // ... and its results came back with its status word
+
+    explicit TableEM(const EmCall &e_) : e(e_), c(e_.c), st(e_.st), C(e_.c->n_classes) {}
+
+    // brackets one mat-vec launch with a pair of events when it is one of those the timing mode picks
+    void stamp(int slot, bool begin, int gate) {
         if (!g_timing) return;
         if (begin) {
             if (g_timing == 2) stamping = true;
@@ -1890,43 +1829,77 @@ static int em_impl_inner(const hgx_classes *cc, int32_t n_alleles, int32_t remov
             else (void)hipEventRecord(t.a, st);
             timed.push_back(t);
         } else if (stamping && !rows.M) (void)hipEventRecord(timed.back().b, st);
-    };
-    auto cols_pass = [&](const double *vec, const uint8_t *pres_v, int x_mode, double *q_out, uint8_t *pres_out, int gate,
-                         bool after_timed_rows) -> int {
+    }
+    int cols_pass(const double *vec, const uint8_t *pres_v, int x_mode, double *q_out, uint8_t *pres_out, int gate, bool after_timed_rows) {
         stamp(slot_cols, true, (g_timing == 2 || after_timed_rows) ? 0 : 1);
         const int r = launch_matvec<MODE_COLS>(cols, st, wc, nullptr, x_mode == 2 ? 2 : 0, nullptr, vec, pres_v, d_len, q_out, pres_out, scal, gate);
         stamp(slot_cols, false, gate);
         return r;
-    };
+    }
     // one application of the EM map: (vec, pres_v) -> (q_out, pres_out)
-    auto next_prob = [&](const double *vec, const uint8_t *pres_v, int x_mode, double *q_out, uint8_t *pres_out, int gate) -> int {
+    int next_prob(const double *vec, const uint8_t *pres_v, int x_mode, double *q_out, uint8_t *pres_out, int gate) {
         stamp(slot_rows, true, gate);
-        int r = launch_matvec<MODE_ROWS>(rows, st, vec, pres_v, x_mode, c->d_count, nullptr, nullptr, nullptr, wc, nullptr, scal, gate);
+        const int r = launch_matvec<MODE_ROWS>(rows, st, vec, pres_v, x_mode, c->d_count, nullptr, nullptr, nullptr, wc, nullptr, scal, gate);
         stamp(slot_rows, false, gate);
         if (r) return r;
         return cols_pass(vec, pres_v, x_mode, q_out, pres_out, gate, stamping);
-    };
-    // initial mass sum_c n_c / |S_c|, normalised (common:1299-1309); the resident-block kernel does it in its first launch
-    if (!grid) {
-        rc = next_prob(p, pr, 2, p, pr, 0);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_em_init_norm, dim3(1), dim3(BLOCK), 0, st, p, pr, A);
     }
-    double h_scal[S_N];
-    int h_abort = 0;
-    std::vector<double> out(A + 1);
-    bool results_fetched = false;         // the speculative tail's results came back with its status word
-    const int batch = 4;
-    int launched_iters = 0;
-    double tail_failed_at = 1e300;
-    bool tail_done = false;
-    const bool use_tail = !hgx_switch_has("em_skip", "tail");
-    // ---- fused vector steps (k_lut_rows_fused): ping-pong estimate, extrapolated vector and state words -----------
-    const bool fuse = (rows.defer_combine || rows.narrow) && A <= EPT * BLOCK && !hgx_switch_has("em_skip", "fuse");
-    DevBuf b_palt, b_pralt, b_q2x, b_prx, b_scal2;
-    double *p_alt = nullptr, *q2x = nullptr, *scal_alt = nullptr;
-    uint8_t *pr_alt = nullptr, *prx = nullptr;
-    if (fuse) {
+    // buffers, and the operands that are built once per class set
+    int setup() {
+        TRY(hgx_ensure_compact(c, st));
+        A = c->a1p;
+        const int w64c = A / 64;
+        ALLOC(b_p, A * 8); ALLOC(b_q1, A * 8); ALLOC(b_q2, A * 8); ALLOC(b_q3, A * 8); ALLOC(b_out, (A + 1) * 8);   // (+ k_em_finish's count)
+        const size_t n_cnt_all = (size_t)std::max((C + BLOCK - 1) / BLOCK, (A + BLOCK - 1) / BLOCK);
+        ALLOC(b_wc, (size_t)C * 8); ALLOC(b_pr, A); ALLOC(b_pr1, A); ALLOC(b_pr2, A); ALLOC(b_pr3, A);
+        ALLOC(b_scal, S_N * 8 + n_cnt_all * 4);       // (scalars + the passes' slab counters: one block, one memset)
+        if (e.allele_len) {
+            TRY(len.upload(e, A, c->n_act, c->h_act));
+            TRY(hgx_sync(st));
+            d_len = len.ptr();
+        }
+        p = b_p.as<double>(); q1 = b_q1.as<double>(); q2 = b_q2.as<double>(); q3 = b_q3.as<double>();
+        pr = b_pr.as<uint8_t>(); pr1 = b_pr1.as<uint8_t>(); pr2 = b_pr2.as<uint8_t>(); pr3 = b_pr3.as<uint8_t>();
+        wc = b_wc.as<double>(); scal = b_scal.as<double>();
+        HIPCHK(hipMemsetAsync(scal, 0, S_N * 8 + n_cnt_all * 4, st));
+        // tie order of the result (first class containing each allele): independent of the EM, queued before it
+        if (e.first) {
+            ALLOC(b_fc, (size_t)A * 4);
+            h_fc.resize(A);
+            hipLaunchKernelGGL(k_first_set_rows, dim3(nblk((long)A * 64, 256)), dim3(256), 0, st, c->d_bitsTC, A, c->c64, b_fc.as<int32_t>());
+        }
+        rows = MatVec{c->d_bitsC, C, w64c, A};
+        cols = MatVec{c->d_bitsTC, A, c->c64, C};
+        slot_rows = A <= 8 * BLOCK ? 0 : 1;
+        slot_cols = C <= 8 * BLOCK ? 2 : 3;
+        if (g_backend == 0 || g_backend == 3) {
+            // table-lookup kernels: word-transposed copies of both matrices, built once per class set
+            const int Cp = c->c64 * 64;
+            if (!c->d_wrow) {
+                c->d_wrow = (uint64_t *)hgx_pool_alloc((size_t)w64c * Cp * 8);
+                c->d_wcol = (uint64_t *)hgx_pool_alloc((size_t)c->c64 * A * 8);
+                if (!c->d_wrow || !c->d_wcol) { hgx_set_error("device allocation failed"); return HGX_ENOMEM; }
+                hipLaunchKernelGGL(k_word_transpose, dim3((w64c + 31) / 32, (Cp + 31) / 32), dim3(256), 0, st, c->d_bitsC, Cp, w64c, c->d_wrow);
+                hipLaunchKernelGGL(k_word_transpose, dim3((c->c64 + 31) / 32, (A + 31) / 32), dim3(256), 0, st, c->d_bitsTC, A, c->c64, c->d_wcol);
+            }
+            const size_t n_part_r = (size_t)(w64c / 8) * Cp, n_part_c = (size_t)(c->c64 / 8) * A;
+            ALLOC(b_part, std::max(n_part_r, n_part_c) * 8); ALLOC(b_part_c, n_part_c * 8);
+            unsigned *const slab_counters = (unsigned *)(scal + S_N);                   // zeroed with the scalars above
+            rows.M = c->d_wrow; rows.n_pad = Cp; rows.part = b_part.as<double>(); rows.counters = slab_counters;
+            cols.M = c->d_wcol; cols.n_pad = A; cols.part = b_part_c.as<double>(); cols.counters = slab_counters;
+            if (!hgx_switch_has("em_skip", "defer")) {
+                // the rows pass stops at its slab partials; the cols pass turns them into w_c in its prologue
+                rows.defer_combine = 1;
+                cols.src_part = rows.part; cols.src_slabs = w64c / 8; cols.src_pad = Cp; cols.src_count = c->d_count;
+            }
+        }
+        return HGX_OK;
+    }
+
+    // the fused steps' buffers: ping-pong estimate, extrapolated vector and state words (queued work is already running meanwhile)
+    int setup_fused() {
+        fuse = rows.defer_combine && A <= EPT * BLOCK && !hgx_switch_has("em_skip", "fuse");
+        if (!fuse) return HGX_OK;
         ALLOC(b_palt, A * 8); ALLOC(b_pralt, A); ALLOC(b_q2x, A * 8); ALLOC(b_prx, A); ALLOC(b_scal2, S_N * 8);
         p_alt = b_palt.as<double>(); pr_alt = b_pralt.as<uint8_t>(); q2x = b_q2x.as<double>(); prx = b_prx.as<uint8_t>();
         scal_alt = b_scal2.as<double>();
@@ -1936,190 +1909,181 @@ static int em_impl_inner(const hgx_classes *cc, int32_t n_alleles, int32_t remov
             HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_lut_rows_fused<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)LUT_LDS));
         });
-    }
-    auto rows_fused = [&](int fm, const double *qb, const uint8_t *prb, double *out_v, uint8_t *out_p) -> int {
-        FuseArgs fz{q1, qb, pr1, prb, out_v, out_p, scal, scal_alt, remove_low ? 1 : 0};
-        const dim3 grid(rows.n_words / 8, (rows.n_rows + BLOCK - 1) / BLOCK);
-        if (fm == 0) hipLaunchKernelGGL(k_lut_rows_fused<0>, grid, dim3(BLOCK), LUT_LDS, st, rows.M, rows.n_pad, A, p, pr, fz, rows.part);
-        else hipLaunchKernelGGL(k_lut_rows_fused<1>, grid, dim3(BLOCK), LUT_LDS, st, rows.M, rows.n_pad, A, p, pr, fz, rows.part);
-        std::swap(scal, scal_alt);           // every later launch reads the state this one wrote
         return HGX_OK;
-    };
-    for (;;) {
-        // with pruning, look at the survivor count right after the first pruning iteration (iteration index 10).
-        // A first batch of 4 tells whether the EM is still far from converged (diff 10x above the stopping rule); if so the
-        // remaining 7 iterations up to that point go out in one batch: every host sync is a ~40 us bubble in the chain.
-        int nb = batch;
-        if (use_tail && remove_low && launched_iters < 11) {
-            nb = std::min(batch, 11 - launched_iters);
-            if (launched_iters == batch && h_scal[S_DIFF] > 0.001) nb = 11 - launched_iters;
-        }
-        if (grid && use_tail && remove_low && launched_iters < 11) nb = 11 - launched_iters;    // no host sync inside: up to the first pruning
-        launched_iters += nb;
-        if (grid) {
-            const int G = ga.R * ga.K;
-            ga.p = p; ga.pr = pr; ga.scal = scal;
-            ga.n_iters = nb;
-            ga.do_init = grid_launches == 0 ? 1 : 0;
-            ++grid_launches;
-            HIPCHK(hipMemsetAsync(b_gfl.p, 0, ((size_t)3 * G * GK_FLAG_STRIDE + 32) * 4, st));
-            Timed t{nullptr, nullptr, 4};
-            if (g_timing) { t.a = pool_event(); t.b = pool_event(); timed.push_back(t); }
-            HIPCHK(hipGetLastError());
-        }
+    }
+    // a fused step: the vector step FM (0 = SQUAREM over q1, qb; 1 = the advance over q1, qb) and the rows pass over its result
+    template <int FM> void rows_fused(const double *qb, const uint8_t *prb, double *out_v, uint8_t *out_p) {
+        FuseArgs fz{q1, qb, pr1, prb, out_v, out_p, scal, scal_alt, e.remove_low};
+        hipLaunchKernelGGL(k_lut_rows_fused<FM>, dim3(rows.n_words / 8, (rows.n_rows + BLOCK - 1) / BLOCK), dim3(BLOCK), LUT_LDS, st, rows.M,
+                           rows.n_pad, A, p, pr, fz, rows.part);
+        std::swap(scal, scal_alt);           // every later launch, and the host's read-back, take the state this one wrote
+    }
+    void advance() { hipLaunchKernelGGL(k_em_advance, dim3(1), dim3(BLOCK), 0, st, p, pr, q1, pr1, q3, pr3, A, e.remove_low, scal); }
+
+    // nb iterations queued without a host look at the state in between
+    int batch(int nb, GraphDrop &graph) {
         // test switch em_graph: the batch's launches captured into a hipGraph and launched as one (measurement of what a graph
         // buys a chain of dependent 15 us kernels; NOTEBOOK.md section 10) -- capture, instantiation and launch are all inside the call
-        const bool as_graph = !grid && !g_timing && HGX_LAB_SWITCH("em_graph") != nullptr;
+        const bool as_graph = !g_timing && HGX_LAB_SWITCH("em_graph") != nullptr;
         if (as_graph) HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-        for (int b = 0; b < (grid ? 0 : nb); ++b) {
+        for (int b = 0; b < nb; ++b) {
             if (fuse) {
                 // six launches per iteration: SQUAREM and the advance step ride in the prologue of the rows pass that follows
                 if (b == 0) {
-                    if ((rc = next_prob(p, pr, 0, q1, pr1, 0))) return rc;
+                    TRY(next_prob(p, pr, 0, q1, pr1, 0));
                 } else {
-                    if ((rc = rows_fused(1, q3, pr3, p_alt, pr_alt))) return rc;      // advance of the previous iteration + rows(p)
+                    rows_fused<1>(q3, pr3, p_alt, pr_alt);                 // advance of the previous iteration + rows(p)
                     std::swap(p, p_alt);
                     std::swap(pr, pr_alt);
-                    if ((rc = cols_pass(p, pr, 0, q1, pr1, 0, false))) return rc;
+                    TRY(cols_pass(p, pr, 0, q1, pr1, 0, false));
                 }
-                if ((rc = next_prob(q1, pr1, 1, q2, pr2, 0))) return rc;
-                if ((rc = rows_fused(0, q2, pr2, q2x, prx))) return rc;               // SQUAREM + rows(q2')
-                if ((rc = cols_pass(q2x, prx, 0, q3, pr3, 1, false))) return rc;
-                if (b == nb - 1)   // the host looks at the state after the batch: close it with the standalone step
-                    hipLaunchKernelGGL(k_em_advance, dim3(1), dim3(BLOCK), 0, st, p, pr, q1, pr1, q3, pr3, A, remove_low ? 1 : 0, scal);
+                TRY(next_prob(q1, pr1, 1, q2, pr2, 0));
+                rows_fused<0>(q2, pr2, q2x, prx);                          // SQUAREM + rows(q2')
+                TRY(cols_pass(q2x, prx, 0, q3, pr3, 1, false));
+                if (b == nb - 1) advance();      // the host looks at the state after the batch: close it with the standalone step
                 continue;
             }
-            if ((rc = next_prob(p, pr, 0, q1, pr1, 0))) return rc;        // Gene_prob_next  (p is used raw)
-            if ((rc = next_prob(q1, pr1, 1, q2, pr2, 0))) return rc;      // Gene_prob_next2 (normalised on the fly)
+            TRY(next_prob(p, pr, 0, q1, pr1, 0));        // Gene_prob_next  (p is used raw)
+            TRY(next_prob(q1, pr1, 1, q2, pr2, 0));      // Gene_prob_next2 (normalised on the fly)
             hipLaunchKernelGGL(k_em_squarem, dim3(1), dim3(BLOCK), 0, st, p, pr, q1, pr1, q2, pr2, A, scal);
-            if ((rc = next_prob(q2, pr2, 0, q3, pr3, 1))) return rc;      // only if extrapolated
-            hipLaunchKernelGGL(k_em_advance, dim3(1), dim3(BLOCK), 0, st, p, pr, q1, pr1, q3, pr3, A, remove_low ? 1 : 0, scal);
+            TRY(next_prob(q2, pr2, 0, q3, pr3, 1));      // only if extrapolated
+            advance();
         }
-        hipGraphExec_t gexec = nullptr;
-        hipGraph_t gcap = nullptr;
         if (as_graph) {
-            HIPCHK(hipStreamEndCapture(st, &gcap));
-            HIPCHK(hipGraphInstantiate(&gexec, gcap, nullptr, nullptr, 0));
-            HIPCHK(hipGraphLaunch(gexec, st));
+            HIPCHK(hipStreamEndCapture(st, &graph.graph));
+            HIPCHK(hipGraphInstantiate(&graph.exec, graph.graph, nullptr, nullptr, 0));
+            HIPCHK(hipGraphLaunch(graph.exec, st));
         }
-        struct GraphDrop { hipGraphExec_t &e; hipGraph_t &g; hipStream_t s; ~GraphDrop() { if (e) { (void)hipStreamSynchronize(s); (void)hipGraphExecDestroy(e); } if (g) (void)hipGraphDestroy(g); } } graph_drop{gexec, gcap, st};
-        // Pruning has started (iteration index >= 10): the compact tail kernel goes out speculatively right behind the batch --
-        // it checks the survivor count itself -- so that batch result and tail result come back in ONE host round trip.
-        const bool spec_tail = use_tail && remove_low && launched_iters >= 11 && tail_failed_at == 1e300;
-        if (spec_tail)
-            hipLaunchKernelGGL(k_em_tail, dim3(1), dim3(BLOCK), 0, st, c->d_bitsTC, C, c->c64, A, c->d_count, p, pr, d_len,
-                               remove_low ? 1 : 0, b_out.as<double>(), scal);
-        if (spec_tail) {      // if the tail takes over, these ARE the results: fetch them in the same round trip
-            if (first_host) { int rc_ = hgx_d2h(h_fc.data(), b_fc.p, (size_t)A * 4, st); if (rc_) return rc_; }
-            { int rc_ = hgx_d2h(out.data(), b_out.p, A * 8, st); if (rc_) return rc_; }
-        }
-        { int rc_ = hgx_d2h(h_scal, scal, S_N * 8, st); if (rc_) return rc_; }
-        if (grid) { int rc_ = hgx_d2h(&h_abort, ga.abort_flag, 4, st); if (rc_) return rc_; }
-        { int rc_ = hgx_sync(st); if (rc_) return rc_; }
-        if (grid && ga.stamps && grid_launches == 1) {
-            // phase profile of the first launch: per workgroup, 11 stamps per application (see apply); printed as the mean over
-            // applications 2.. of the time between consecutive stamps, for the first, a middle and the last workgroup, and the
-            // maximum over all workgroups
-            const int G = ga.R * ga.K;
-            std::vector<unsigned long long> hs((size_t)G * GK_STAMPS);
-            (void)hipMemcpy(hs.data(), ga.stamps, hs.size() * 8, hipMemcpyDeviceToHost);
-            static const char *nm[11] = {"lut+rows", "publish A", "wait A", "sum A -> w", "cols (2 tables)", "publish B", "wait B",
-                                         "reduce B -> q", "publish C", "wait C", "gather + vector step"};
-            const int apps = (GK_STAMPS - 1) / 11;
-            fprintf(stderr, "[k_em_grid] %d x %d workgroups; us per phase (wg 0 | wg %d | wg %d | max over wgs), applications 2..%d\n",
-                    ga.R, ga.K, G / 2, G - 1, apps);
-            double tot[4] = {0, 0, 0, 0};
-            for (int ph = 0; ph < 11; ++ph) {
-                double v[4] = {0, 0, 0, 0};
-                for (int g = 0; g < G; ++g) {
-                    double sum = 0;
-                    int cnt = 0;
-                    for (int ap = 1; ap < apps; ++ap) {
-                        const unsigned long long t0 = hs[(size_t)g * GK_STAMPS + 1 + ap * 11 + ph];
-                        const unsigned long long t1 = ph < 10 ? hs[(size_t)g * GK_STAMPS + 1 + ap * 11 + ph + 1]
-                                                              : (ap + 1 < apps ? hs[(size_t)g * GK_STAMPS + 1 + (ap + 1) * 11] : 0);
-                        if (!t0 || !t1) continue;
-                        sum += (double)(t1 - t0) * 0.01;
-                        ++cnt;
-                    }
-                    const double m = cnt ? sum / cnt : 0.0;
-                    if (g == 0) v[0] = m;
-                    if (g == G / 2) v[1] = m;
-                    if (g == G - 1) v[2] = m;
-                    v[3] = std::max(v[3], m);
-                }
-                for (int k = 0; k < 4; ++k) tot[k] += v[k];
-                fprintf(stderr, "  %-22s %6.2f %6.2f %6.2f %6.2f\n", nm[ph], v[0], v[1], v[2], v[3]);
+        return HGX_OK;
+    }
+
+    // few survivors: the rest of the EM on one wavefront (k_em_tail checks the survivor count and the distinct class masks itself)
+    void launch_tail() {
+        hipLaunchKernelGGL(k_em_tail, dim3(1), dim3(BLOCK), 0, st, c->d_bitsTC, C, c->c64, A, c->d_count, p, pr, d_len, e.remove_low,
+                           b_out.as<double>(), scal);
+    }
+    int fetch_results(size_t n_out) {
+        if (e.first) TRY(hgx_d2h(h_fc.data(), b_fc.p, (size_t)A * 4, st));
+        return hgx_d2h(out.data(), b_out.p, n_out * 8, st);
+    }
+
+    // the host loop: batches until the state words say done or the tail kernel has taken over
+    int iterate() {
+        const int batch_iters = 4;
+        out.resize(A + 1);
+        const bool use_tail = !hgx_switch_has("em_skip", "tail");
+        int launched_iters = 0;
+        double tail_failed_at = 1e300;
+        for (;;) {
+            // with pruning, look at the survivor count right after the first pruning iteration (iteration index 10).
+            // A first batch of 4 tells whether the EM is still far from converged (diff 10x above the stopping rule); if so the
+            // remaining 7 iterations up to that point go out in one batch: every host sync is a ~40 us bubble in the chain.
+            int nb = batch_iters;
+            if (use_tail && e.remove_low && launched_iters < 11) {
+                nb = std::min(batch_iters, 11 - launched_iters);
+                if (launched_iters == batch_iters && h_scal[S_DIFF] > 0.001) nb = 11 - launched_iters;
             }
-            fprintf(stderr, "  %-22s %6.2f %6.2f %6.2f %6.2f\n", "application", tot[0], tot[1], tot[2], tot[3]);
-            unsigned long long first = ~0ull, last_start = 0;
-            for (int g = 0; g < G; ++g) { first = std::min(first, hs[(size_t)g * GK_STAMPS]); last_start = std::max(last_start, hs[(size_t)g * GK_STAMPS]); }
-            fprintf(stderr, "  first workgroup -> last workgroup started: %.2f us\n", (double)(last_start - first) * 0.01);
-        }
-        if (grid && h_abort) {
-            // a workgroup of the block grid never became resident (bounded spin): run this EM again, one launch per pass
-            grid_hold.release();
-            g_no_grid = true;
-            const int r = em_impl(cc, n_alleles, remove_low, allele_len, prob_host, first_host, n_iter_host, stream);
-            g_no_grid = false;
-            return r;
-        }
-        if (spec_tail) {
-            if (h_scal[S_TAIL] == 1.0) { tail_done = true; results_fetched = true; break; }
-            if (h_scal[S_TAIL] == -1.0) tail_failed_at = h_scal[S_NPRES];
-        }
-        if (h_scal[S_DONE] != 0.0) break;
-        if (!spec_tail && use_tail && h_scal[S_NPRES] <= 64.0 && h_scal[S_NPRES] < tail_failed_at) {
-            // few survivors: finish on one wavefront (k_em_tail) unless too many distinct class masks remain
-            hipLaunchKernelGGL(k_em_tail, dim3(1), dim3(BLOCK), 0, st, c->d_bitsTC, C, c->c64, A, c->d_count, p, pr, d_len,
-                               remove_low ? 1 : 0, b_out.as<double>(), scal);
-            const double rows_ran = h_scal[S_NROWS], cols_ran = h_scal[S_NCOLS];
-            { int rc_ = hgx_d2h(h_scal, scal, S_N * 8, st); if (rc_) return rc_; }
-            { int rc_ = hgx_sync(st); if (rc_) return rc_; }
-            h_scal[S_NROWS] = rows_ran; h_scal[S_NCOLS] = cols_ran;
-            if (h_scal[S_TAIL] == 1.0) { tail_done = true; break; }
-            tail_failed_at = h_scal[S_NPRES];
+            launched_iters += nb;
+            GraphDrop graph{st};
+            TRY(batch(nb, graph));
+            // Pruning has started (iteration index >= 10): the compact tail kernel goes out speculatively right behind the batch --
+            // it checks the survivor count itself -- so that batch result and tail result come back in ONE host round trip.
+            const bool spec_tail = use_tail && e.remove_low && launched_iters >= 11 && tail_failed_at == 1e300;
+            if (spec_tail) {      // if the tail takes over, these ARE the results: fetch them in the same round trip
+                launch_tail();
+                TRY(fetch_results(A));
+            }
+            TRY(hgx_d2h(h_scal, scal, S_N * 8, st));
+            TRY(hgx_sync(st));
+            if (spec_tail) {
+                if (h_scal[S_TAIL] == 1.0) { tail_done = true; results_fetched = true; return HGX_OK; }
+                if (h_scal[S_TAIL] == -1.0) tail_failed_at = h_scal[S_NPRES];
+            }
+            if (h_scal[S_DONE] != 0.0) return HGX_OK;
+            if (!spec_tail && use_tail && h_scal[S_NPRES] <= 64.0 && h_scal[S_NPRES] < tail_failed_at) {
+                launch_tail();
+                const double rows_ran = h_scal[S_NROWS], cols_ran = h_scal[S_NCOLS];
+                TRY(hgx_d2h(h_scal, scal, S_N * 8, st));
+                TRY(hgx_sync(st));
+                h_scal[S_NROWS] = rows_ran; h_scal[S_NCOLS] = cols_ran;
+                if (h_scal[S_TAIL] == 1.0) { tail_done = true; return HGX_OK; }
+                tail_failed_at = h_scal[S_NPRES];
+            }
         }
     }
-    if (g_timing) {
-        const int64_t rows_bytes = (int64_t)C * w64c * 8 + (int64_t)A * 9 + (int64_t)C * 16;
+
+    void fold_timing() {
+        if (!g_timing) return;
+        const int64_t rows_bytes = (int64_t)C * (A / 64) * 8 + (int64_t)A * 9 + (int64_t)C * 16;
         const int64_t cols_bytes = (int64_t)A * c->c64 * 8 + (int64_t)C * 8 + (int64_t)A * 26;
+        // bytes describe the TIMED launches (all ungated: they did the full pass); executed = every pass of the call
         for (auto &t : timed) {
             float ms = 0.f;
             (void)hipEventElapsedTime(&ms, t.a, t.b);
             g_stats[t.slot].ms += ms;
             g_stats[t.slot].launches += 1;
+            g_stats[t.slot].bytes += t.slot == slot_rows ? rows_bytes : cols_bytes;
             g_event_pool.push_back(t.a);
             g_event_pool.push_back(t.b);
         }
-        // bytes describe the TIMED launches (all ungated: they did the full pass); executed = every pass of the call
-        if (grid) {       // SURVEY 8d's bytes of one application (both mat-vecs) x the applications the launches ran
-            g_stats[4].executed += (int64_t)h_scal[S_NROWS];
-            g_stats[4].bytes += (int64_t)h_scal[S_NROWS] * (rows_bytes + cols_bytes);
-        } else {
-            for (auto &t : timed) g_stats[t.slot].bytes += t.slot == slot_rows ? rows_bytes : cols_bytes;
-            g_stats[slot_rows].executed += (int64_t)h_scal[S_NROWS];
-            g_stats[slot_cols].executed += (int64_t)h_scal[S_NCOLS];
+        g_stats[slot_rows].executed += (int64_t)h_scal[S_NROWS];
+        g_stats[slot_cols].executed += (int64_t)h_scal[S_NCOLS];
+    }
+
+    // final selection (unless the tail kernel made it), then from the compact allele space back to the caller's
+    int scatter_results() {
+        if (!tail_done) hipLaunchKernelGGL(k_em_finish, dim3(1), dim3(BLOCK), 0, st, p, pr, d_len, A, e.remove_low, b_out.as<double>(), scal);
+        HIPCHK(hipGetLastError());
+        if (!results_fetched) {
+            TRY(fetch_results(tail_done ? A : A + 1));
+            TRY(hgx_sync(st));
         }
+        g_last_near = (long long)(tail_done ? h_scal[S_NEAR] : out[A]);      // (the tail kernel counted into the state words)
+        for (int a = 0; a < e.n_alleles; ++a) e.prob[a] = -1.0;
+        for (int j = 0; j < c->n_act; ++j) {
+            const int a = c->h_act[j];
+            if (a >= e.n_alleles) continue;
+            e.prob[a] = out[j];
+            if (e.first) e.first[a] = h_fc[j];
+        }
+        if (e.n_iter) *e.n_iter = (int)h_scal[S_ITER];
+        return HGX_OK;
     }
-    if (h_scal[S_KEYERR] != 0.0) {
-        hgx_set_error("EM: allele missing from the next estimate (the reference raises KeyError here, common:1365-1369)");
-        return HGX_EKEY;
+
+    int run() {
+        TRY(setup());
+        // initial mass sum_c n_c / |S_c|, normalised (common:1299-1309)
+        TRY(next_prob(p, pr, 2, p, pr, 0));
+        hipLaunchKernelGGL(k_em_init_norm, dim3(1), dim3(BLOCK), 0, st, p, pr, A);
+        TRY(setup_fused());
+        TRY(iterate());
+        fold_timing();
+        if (h_scal[S_KEYERR] != 0.0) return em_key_error();
+        return scatter_results();
     }
-    if (!tail_done) hipLaunchKernelGGL(k_em_finish, dim3(1), dim3(BLOCK), 0, st, p, pr, d_len, A, remove_low ? 1 : 0, b_out.as<double>(), scal);
-    HIPCHK(hipGetLastError());
-    if (!results_fetched) {
-        if (first_host) { int rc_ = hgx_d2h(h_fc.data(), b_fc.p, (size_t)A * 4, st); if (rc_) return rc_; }
-        { int rc_ = hgx_d2h(out.data(), b_out.p, (size_t)(tail_done ? A : A + 1) * 8, st); if (rc_) return rc_; }
-        { int rc_ = hgx_sync(st); if (rc_) return rc_; }
-    }
-    g_last_near = (long long)(tail_done ? h_scal[S_NEAR] : out[A]);      // (the tail kernel counted into the state words)
-    for (int a = 0; a < n_alleles; ++a) prob_host[a] = -1.0;
-    for (int j = 0; j < c->n_act; ++j) if (c->h_act[j] < n_alleles) prob_host[c->h_act[j]] = out[j];
-    if (first_host) for (int j = 0; j < c->n_act; ++j) if (c->h_act[j] < n_alleles) first_host[c->h_act[j]] = h_fc[j];
-    (void)A_full;
-    if (n_iter_host) *n_iter_host = (int)h_scal[S_ITER];
-    return HGX_OK;
+};
+
+}   // namespace
+
+static int em_impl_inner(const hgx_classes *cc, int32_t n_alleles, int32_t remove_low, const int32_t *allele_len, double *prob_host,
+                         int32_t *first_host, int32_t *n_iter_host, void *stream) {
+    ARGCHK(cc && prob_host && n_alleles > 0 && n_alleles <= cc->a_pad);
+    g_last_exact = 0;
+    g_last_near = 0;
+    g_last_order.clear();
+    const EmCall e{const_cast<hgx_classes *>(cc), n_alleles, remove_low ? 1 : 0, allele_len, prob_host, first_host, n_iter_host, (hipStream_t)stream};
+    hgx_classes_order_after(cc, e.st);
+    if (first_host) for (int a = 0; a < n_alleles; ++a) first_host[a] = -1;
+    if (n_iter_host) *n_iter_host = 0;
+    int rc;
+    if ((rc = em_empty(e)) != EM_DECLINED) return rc;
+    if ((rc = em_wave(e)) != EM_DECLINED) return rc;
+    if ((rc = em_reference_order(e)) != EM_DECLINED) return rc;
+#ifdef HGX_LAB
+    if ((rc = em_lab_mid(e)) != EM_DECLINED) return rc;
+    if ((rc = em_lab_small(e)) != EM_DECLINED) return rc;
+#endif
+    return TableEM(e).run();
 }
 
 // Gene_cmpt2 + EM #2 (core:1752-1782) without materialising the filtered class set when <= 64 alleles pass the filter
@@ -2154,7 +2118,7 @@ extern "C" int hgx_em_masked(const hgx_classes *cc, const uint64_t *mask_host, i
         for (int j = 0; j < 64; ++j) { up.al[j] = j < A1 ? al[j] : 0; up.len[j] = (allele_len && j < A1) ? (double)allele_len[al[j]] : 1.0; }
         DevBuf b_up, b_down, b_pub;
         ALLOC(b_up, sizeof(Up)); ALLOC(b_down, sizeof(Down));
-        { int rc_ = hgx_h2d(b_up.p, &up, sizeof(Up), st); if (rc_) return rc_; }
+        TRY(hgx_h2d(b_up.p, &up, sizeof(Up), st));
         HIPCHK(hipMemsetAsync(b_down.p, 0, offsetof(Down, out), st));
         const int nb = std::max(1, std::min(64, (C + 511) / 512));
         ALLOC(b_pub, (size_t)nb * 64 * sizeof(MaskedEntry));
@@ -2164,15 +2128,12 @@ extern "C" int hgx_em_masked(const hgx_classes *cc, const uint64_t *mask_host, i
                            allele_len ? d_up->len : nullptr, remove_low ? 1 : 0, d_down->out, d_down->first, d_down->scal,
                            (MaskedEntry *)b_pub.p, d_down->ticket, exact ? 1 : 0);
         HIPCHK(hipGetLastError());
-        { int rc_ = hgx_d2h(&down, b_down.p, sizeof(Down), st); if (rc_) return rc_; }
-        { int rc_ = hgx_sync(st); if (rc_) return rc_; }
+        TRY(hgx_d2h(&down, b_down.p, sizeof(Down), st));
+        TRY(hgx_sync(st));
         const double *h_scal = down.scal, *out = down.out;
         const int32_t *first = down.first;
         if (h_scal[S_FALLBACK] == 0.0) {
-            if (h_scal[S_KEYERR] != 0.0) {
-                hgx_set_error("EM: allele missing from the next estimate (the reference raises KeyError here, common:1365-1369)");
-                return HGX_EKEY;
-            }
+            if (h_scal[S_KEYERR] != 0.0) return em_key_error();
             for (int j = 0; j < A1; ++j) {
                 prob_host[al[j]] = out[j];
                 first_class_host[al[j]] = out[j] >= 0.0 ? first[j] : -1;
@@ -2186,7 +2147,7 @@ extern "C" int hgx_em_masked(const hgx_classes *cc, const uint64_t *mask_host, i
     // general path: materialise the filtered, merged class set and run the ordinary EM on it
     DevBuf b_mask;
     ALLOC(b_mask, (size_t)cc->w64 * 8);
-    { int rc_ = hgx_h2d(b_mask.p, mask_host, (size_t)cc->w64 * 8, st); if (rc_) return rc_; }
+    TRY(hgx_h2d(b_mask.p, mask_host, (size_t)cc->w64 * 8, st));
     hgx_classes *sub = nullptr;
     int rc = hgx_dedup_classes(&sub, cc->d_bits, nullptr, cc->d_count, C, cc->a_pad, b_mask.as<uint64_t>(), stream);
     if (rc == HGX_OK) {

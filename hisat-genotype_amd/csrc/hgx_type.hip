@@ -1282,7 +1282,7 @@ struct ClassesView {
         c.d_bitsT = nullptr;
     }
     ~ClassesView() {
-        hgx_pool_free(c.d_bitsT); hgx_pool_free(c.d_prow); hgx_pool_free(c.d_pcol); hgx_pool_free(c.d_act); hgx_pool_free(c.d_bitsC);
+        hgx_pool_free(c.d_bitsT); hgx_pool_free(c.d_act); hgx_pool_free(c.d_bitsC);
         hgx_pool_free(c.d_bitsTC); hgx_pool_free(c.d_wrow); hgx_pool_free(c.d_wcol); hgx_pool_free(c.d_setup0); hgx_pool_free(c.d_setup1);
         delete[] c.h_act;
         delete[] c.h_rank;

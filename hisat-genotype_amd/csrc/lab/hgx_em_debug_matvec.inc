@@ -17,7 +17,6 @@
     double one = 1.0;
     HIPCHK(hipMemcpy(b_scal.as<double>() + S_TOT_A, &one, 8, hipMemcpyHostToDevice));
     MatVec m = which == 0 ? MatVec{c->d_bits, C, c->w64, A} : MatVec{c->d_bitsT, A, c->c64, C};
-    DevBuf b_P;
     if (backend == 2) { hgx_set_error("hgx_debug_matvec: back-end 2 (int8 MFMA) was measured slower twice and removed in round 6"); return HGX_EINVAL; }
     DevBuf b_M, b_part, b_cnt;
     if (backend == 3) {

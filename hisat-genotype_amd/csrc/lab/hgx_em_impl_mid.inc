@@ -1,59 +1,31 @@
-// Lab build only (-DHGX_LAB): a block of hgx_em.hip, included where it stood -- round 2's mid-size reference-order EM (k_em_ref).
-    if (C <= MR_C && c->w64 <= 128 && c->h_rank && !hgx_switch_has("em_skip", "exact") && !hgx_test_switch("em_no_mid")) {
-        // mid-size problems in the reference's own order of operations (k_em_ref): one workgroup, one launch, bit-identical
-        // abundances; falls through if more than MR_A distinct alleles occur
-        DevBuf b_len, b_scal, b_out, b_first, b_rank, b_rm, b_km;
-        ALLOC(b_scal, S_N * 8); ALLOC(b_out, A * 8); ALLOC(b_rank, (size_t)A * 4);
-        ALLOC(b_rm, (size_t)std::max(C, 1) * MR_AW * 8); ALLOC(b_km, (size_t)MR_A * ((C + 63) / 64) * 8);
-        double *d_len = nullptr;
-        if (allele_len) {
-            std::vector<double> l(A, 1.0);
-            for (int a = 0; a < n_alleles; ++a) l[a] = (double)allele_len[a];
-            ALLOC(b_len, A * 8);
-            { int rc_ = hgx_h2d(b_len.p, l.data(), A * 8, st); if (rc_) return rc_; }
-            d_len = b_len.as<double>();
-        }
-        { int rc_ = hgx_h2d(b_rank.p, c->h_rank, (size_t)A * 4, st); if (rc_) return rc_; }
-        HIPCHK(hipMemsetAsync(b_scal.p, 0, S_N * 8, st));
-        std::vector<int32_t> h_first;
-        if (first_host) {
-            ALLOC(b_first, (size_t)A * 4);
-            HIPCHK(hipMemsetAsync(b_first.p, 0xFF, (size_t)A * 4, st));
-            h_first.resize(A);
-        }
-        HGX_ONCE_PER_DEVICE({
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_em_ref), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(MrLds)));
-        });
-        DevBuf b_dbg;
-        const int max_nnz = hgx_test_switch("em_mid_nnz") ? atoi(hgx_test_switch("em_mid_nnz")) : 65536;
-        const bool stamps = hgx_test_switch("mid_stamps") != nullptr;
-        if (stamps) ALLOC(b_dbg, 64);
-        hipLaunchKernelGGL(k_em_ref, dim3(1), dim3(BLOCK), sizeof(MrLds), st, c->d_bits, C, c->w64, A, c->d_count, d_len, b_rank.as<int32_t>(),
-                           remove_low ? 1 : 0, b_rm.as<uint64_t>(), b_km.as<uint64_t>(), b_out.as<double>(), b_scal.as<double>(),
-                           first_host ? b_first.as<int32_t>() : nullptr, max_nnz, stamps ? b_dbg.as<unsigned long long>() : nullptr);
-        HIPCHK(hipGetLastError());
-        if (stamps) {
-            unsigned long long h[8] = {0};
-            (void)hipStreamSynchronize(st);
-            (void)hipMemcpy(h, b_dbg.p, 56, hipMemcpyDeviceToHost);
-            fprintf(stderr, "[k_em_ref] C %d: set-up %.1f us | rows %.1f | cols %.1f | orders %.1f (%llu derived) | normalise %.1f | sums %.1f\n", C,
-                    h[0] * 0.01, h[1] * 0.01, h[2] * 0.01, h[3] * 0.01, h[6], h[4] * 0.01, h[5] * 0.01);
-        }
-        std::vector<double> out(A);
-        double h_scal[S_N];
-        if (first_host) { int rc_ = hgx_d2h(h_first.data(), b_first.p, (size_t)A * 4, st); if (rc_) return rc_; }
-        { int rc_ = hgx_d2h(out.data(), b_out.p, A * 8, st); if (rc_) return rc_; }
-        { int rc_ = hgx_d2h(h_scal, b_scal.p, S_N * 8, st); if (rc_) return rc_; }
-        { int rc_ = hgx_sync(st); if (rc_) return rc_; }
-        if (h_scal[S_FALLBACK] == 0.0) {
-            if (h_scal[S_KEYERR] != 0.0) {
-                hgx_set_error("EM: allele missing from the next estimate (the reference raises KeyError here, common:1365-1369)");
-                return HGX_EKEY;
-            }
-            for (int a = 0; a < n_alleles; ++a) prob_host[a] = out[a];
-            if (first_host) for (int a = 0; a < n_alleles; ++a) first_host[a] = h_first[a];
-            if (n_iter_host) *n_iter_host = (int)h_scal[S_ITER];
-            g_last_exact = 1;
-            return HGX_OK;
-        }
+// Lab build only (-DHGX_LAB): a stage of hgx_em.hip's EM driver -- round 2's mid-size reference-order EM (k_em_ref).
+// Mid-size problems in the reference's own order of operations: one workgroup, one launch, bit-identical abundances; the kernel
+// declines if more than MR_A distinct alleles occur.
+int em_lab_mid(const EmCall &e) {
+    hgx_classes *c = e.c;
+    const int C = c->n_classes;
+    if (C > MR_C || c->w64 > 128 || !c->h_rank || hgx_switch_has("em_skip", "exact") || hgx_test_switch("em_no_mid")) return EM_DECLINED;
+    OneLaunch o(e);
+    DevBuf b_rm, b_km, b_dbg;
+    ALLOC(b_rm, (size_t)std::max(C, 1) * MR_AW * 8); ALLOC(b_km, (size_t)MR_A * ((C + 63) / 64) * 8);
+    TRY(o.open());
+    TRY(o.put_rank());
+    TRY(o.zero_state());
+    HGX_ONCE_PER_DEVICE({
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_em_ref), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(MrLds)));
+    });
+    const int max_nnz = hgx_test_switch("em_mid_nnz") ? atoi(hgx_test_switch("em_mid_nnz")) : 65536;
+    const bool stamps = hgx_test_switch("mid_stamps") != nullptr;
+    if (stamps) ALLOC(b_dbg, 64);
+    hipLaunchKernelGGL(k_em_ref, dim3(1), dim3(BLOCK), sizeof(MrLds), e.st, c->d_bits, C, c->w64, o.A, c->d_count, o.len.ptr(), o.b_rank.as<int32_t>(),
+                       e.remove_low, b_rm.as<uint64_t>(), b_km.as<uint64_t>(), o.b_out.as<double>(), o.b_scal.as<double>(),
+                       o.b_first.as<int32_t>(), max_nnz, b_dbg.as<unsigned long long>());
+    if (stamps) {
+        unsigned long long h[8] = {0};
+        (void)hipStreamSynchronize(e.st);
+        (void)hipMemcpy(h, b_dbg.p, 56, hipMemcpyDeviceToHost);
+        fprintf(stderr, "[k_em_ref] C %d: set-up %.1f us | rows %.1f | cols %.1f | orders %.1f (%llu derived) | normalise %.1f | sums %.1f\n", C,
+                h[0] * 0.01, h[1] * 0.01, h[2] * 0.01, h[3] * 0.01, h[6], h[4] * 0.01, h[5] * 0.01);
     }
+    return o.close(true);
+}

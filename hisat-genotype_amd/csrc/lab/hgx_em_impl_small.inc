@@ -1,34 +1,30 @@
-// Lab build only (-DHGX_LAB): a block of hgx_em.hip, included where it stood -- round 1's one-workgroup EM (k_em_small).
-    if (C <= SMALL_C && A <= EPT * BLOCK && !hgx_test_switch("em_no_small")) {
-        // single-workgroup path: one launch, one sync
-        DevBuf b_len, b_scal, b_out;
-        ALLOC(b_scal, S_N * 8); ALLOC(b_out, A * 8);
-        double *d_len = nullptr;
-        if (allele_len) {
-            std::vector<double> l(A, 1.0);
-            for (int a = 0; a < n_alleles; ++a) l[a] = (double)allele_len[a];
-            ALLOC(b_len, A * 8);
-            { int rc_ = hgx_h2d(b_len.p, l.data(), A * 8, st); if (rc_) return rc_; }
-            d_len = b_len.as<double>();
-        }
-        const size_t lds = (size_t)C * c->w64 * 8;
-        HGX_ONCE_PER_DEVICE({
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_em_small), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       SMALL_C * (EPT * BLOCK / 64) * 8));
-        });
-        hipLaunchKernelGGL(k_em_small, dim3(1), dim3(BLOCK), lds, st, c->d_bits, C, c->w64, A, c->d_count, d_len, remove_low ? 1 : 0,
-                           b_out.as<double>(), b_scal.as<double>());
-        HIPCHK(hipGetLastError());
-        std::vector<double> out(A);
-        double h_scal[S_N];
-        { int rc_ = hgx_d2h(out.data(), b_out.p, A * 8, st); if (rc_) return rc_; }
-        { int rc_ = hgx_d2h(h_scal, b_scal.p, S_N * 8, st); if (rc_) return rc_; }
-        { int rc_ = hgx_sync(st); if (rc_) return rc_; }
-        if (h_scal[S_KEYERR] != 0.0) {
-            hgx_set_error("EM: allele missing from the next estimate (the reference raises KeyError here, common:1365-1369)");
-            return HGX_EKEY;
-        }
-        for (int a = 0; a < n_alleles; ++a) prob_host[a] = out[a];
-        if (n_iter_host) *n_iter_host = (int)h_scal[S_ITER];
-        return first_for_present();
-    }
+// Lab build only (-DHGX_LAB): a stage of hgx_em.hip's EM driver -- round 1's one-workgroup EM (k_em_small): one launch, one sync.
+
+// k_em_small does not carry the first-class information: looked up for the survivors afterwards
+int first_for_present(const EmCall &e) {
+    if (!e.first) return HGX_OK;
+    std::vector<int32_t> al;
+    for (int a = 0; a < e.n_alleles; ++a) if (e.prob[a] >= 0.0) al.push_back(a);
+    if (al.empty()) return HGX_OK;
+    std::vector<int32_t> f(al.size());
+    TRY(hgx_first_classes(e.c, al.data(), (int32_t)al.size(), f.data(), e.st));
+    for (size_t i = 0; i < al.size(); ++i) e.first[al[i]] = f[i];
+    return HGX_OK;
+}
+
+int em_lab_small(const EmCall &e) {
+    hgx_classes *c = e.c;
+    const int C = c->n_classes;
+    if (C > SMALL_C || c->a_pad > EPT * BLOCK || hgx_test_switch("em_no_small")) return EM_DECLINED;
+    OneLaunch o(e);
+    TRY(o.open());                     // (the kernel writes every state word the host reads: nothing to zero)
+    const size_t lds = (size_t)C * c->w64 * 8;
+    HGX_ONCE_PER_DEVICE({
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_em_small), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   SMALL_C * (EPT * BLOCK / 64) * 8));
+    });
+    hipLaunchKernelGGL(k_em_small, dim3(1), dim3(BLOCK), lds, e.st, c->d_bits, C, c->w64, o.A, c->d_count, o.len.ptr(), e.remove_low,
+                       o.b_out.as<double>(), o.b_scal.as<double>());
+    TRY(o.close(false));
+    return first_for_present(e);
+}

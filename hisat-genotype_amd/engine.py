@@ -611,12 +611,12 @@ def em_set_timing(on):
 
 
 def em_get_timing():
-    """{kernel name: (ms_total, launches, executed, bytes_total)} accumulated since em_set_timing(True)."""
+    """{kernel name: (ms_total, launches, executed, bytes_total)} accumulated since em_set_timing(True), for the rows pass
+    (k_lutmatvec<0>) and the cols pass (k_lutmatvec<1>) of the table-lookup EM."""
     out = {}
     # slots 0/1 = rows pass (vector <= 8192 / larger), 2/3 = cols pass; the default (table-lookup) backend runs both sizes
     # with the same kernel, k_lutmatvec<0> / k_lutmatvec<1> in rocprofv3's naming
-    # slot 4 = the resident-block EM (k_em_grid): whole launches; executed = applications of the EM map they ran
-    for name, slots in (("k_lutmatvec<0>", (0, 1)), ("k_lutmatvec<1>", (2, 3)), ("k_em_grid", (4,))):
+    for name, slots in (("k_lutmatvec<0>", (0, 1)), ("k_lutmatvec<1>", (2, 3))):
         tot = [0.0, 0, 0, 0]
         for slot in slots:
             ms, n, ex, by = C.c_double(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
@@ -650,8 +650,8 @@ class test_switches:
 
 
 def em_set_backend(backend):
-    """0 = auto (table lookup), 1 = EXEC-masked FP64 VALU mat-vec, 3 = table-lookup mat-vec (256 subset sums per 8 columns in
-    LDS); 2 = int8 MFMA mat-vec (128-bit fixed point), lab build only (capi.use_lab())."""
+    """0 = auto (table lookup), 3 = table-lookup mat-vec (256 subset sums per 8 columns in LDS), 1 = EXEC-masked FP64 VALU
+    mat-vec, lab build only (capi.use_lab()).  2 (the int8 MFMA mat-vec) was removed: both builds refuse it."""
     capi.check(capi.lib().hgx_em_set_backend(C.c_int(backend)))
 
 

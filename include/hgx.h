@@ -702,12 +702,13 @@ int hgx_bam_splice(const void *src, size_t src_bytes, const uint64_t *seg_off, c
  * test that uses it states.  Environment variables the library does read: HGX_THREADS, HGX_PIN, HGX_THP, HGX_NO_LIBDEFLATE,
  * HGX_MALLOC_TUNE, HGX_READ_PHASES, HGX_PINNED_IDLE_MB (host tuning) and HGX_PARSE_PROFILE, HGX_TYPE_PROFILE (timing prints on stderr).                                            */
 int hgx_test_switch_set(const char *name, const char *value);
-/* mat-vec backend of hgx_em: 0 = auto (table lookup), 1 = EXEC-masked FP64 VALU kernel, 3 = table-lookup kernel (256 subset
- * sums per 8 matrix columns in LDS; one lookup per 8 matrix bits); 2 = int8 MFMA kernel, in the lab build only (libhgx_lab.so,
- * -DHGX_LAB: the MFMA, persistent and resident-grid EM back-ends measured in rounds 1-2 and kept out of the product library) */
+/* mat-vec backend of hgx_em: 0 = auto (table lookup), 3 = table-lookup kernel (256 subset sums per 8 matrix columns in LDS; one
+ * lookup per 8 matrix bits), 1 = EXEC-masked FP64 VALU kernel, in the lab build only (libhgx_lab.so, -DHGX_LAB: comparison forms kept
+ * out of the product library).  2 was the int8 MFMA kernel: measured slower twice and removed, so 2 is refused (HGX_EINVAL) by both
+ * builds, with a message that says so. */
 int hgx_em_set_backend(int backend);
 /* test aid: one rows pass (which = 0: y[c] = count[c] / sum_a B[c][a] x[a]) or cols pass (which = 1: y[a] = sum_c
- * B[c][a] x[c]) with backend 1 or 2; x and y are host arrays of a_pad / n_classes doubles                        */
+ * B[c][a] x[c]) with backend 1 or 3 (lab build); x and y are host arrays of a_pad / n_classes doubles                        */
 int hgx_debug_matvec(const hgx_classes *c, int which, int backend, const double *x_host, double *y_host);
 int hgx_em_set_timing(int on);
 /* the one-workgroup EM kernel (k_emx: hgx_em / hgx_type_* on problems of up to 4096 classes, every EM of hgx_type_many): HIP
@@ -741,6 +742,7 @@ int hgx_stream_sets_info(int32_t *n_sets, int32_t *n_classes, int32_t *n_probes,
  * these on its own doubles), plus the typing calls that ran EM #1 again for the same reason (hand-off cut, report lines), since the
  * library was loaded.  A direct hgx_em call checks the whole result list; the typing calls check the prefix they read.          */
 long long hgx_em_tie_reruns(void);
+/* totals of hgx_em_set_timing (above) for slot 0..3; any other slot is refused (HGX_EINVAL) */
 int hgx_em_get_timing(int slot, double *ms_total, int64_t *launches, int64_t *executed, int64_t *bytes_total);
 
 /* ---- linear-index typing (--linear-index, --aligners hisat2.linear / bowtie2.linear) --------------------------------------

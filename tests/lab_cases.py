@@ -1,5 +1,5 @@
-"""Lab build only (libhgx_lab.so, -DHGX_LAB): the opt-in EM back-ends of rounds 1-2 -- int8-MFMA mat-vec, persistent kernel,
-resident-grid kernel (csrc/lab/*.inc) -- against the product's default path.  Not collected by the suite itself (the product
+"""Lab build only (libhgx_lab.so, -DHGX_LAB): the comparison forms of rounds 1-3 that are still kept -- the VALU bit mat-vec, k_em_ref,
+k_em_small, the fused gene-level form (csrc/lab/*.inc) -- against the product's default path.  Not collected by the suite itself (the product
 library is what the suite's process has loaded): tests/test_gpu_lab.py runs this file with pytest in a child process."""
 import numpy as np
 import pytest
@@ -55,6 +55,15 @@ def test_em_backends_agree(name):
                 assert np.max(np.abs(p1 - p2)) <= 1e-11, (backend, np.max(np.abs(p1 - p2)))
     finally:
         engine.em_set_backend(0)
+
+
+def test_removed_mfma_back_end_is_refused_here_too():
+    """Back-end 2 is refused by the lab library as well, and not with advice to build the library that is already loaded."""
+    with pytest.raises(capi.HgxError) as e:
+        engine.em_set_backend(2)
+    assert "removed" in str(e.value) and "build_lab" not in str(e.value)
+    engine.em_set_backend(1)
+    engine.em_set_backend(0)
 
 
 def test_round2_mid_size_em_is_the_reference_bit_for_bit(orc):

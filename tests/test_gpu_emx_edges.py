@@ -252,6 +252,30 @@ def test_keyerror(orc, x):
         cl.close()
 
 
+def test_a_table_lookup_call_forgets_the_reference_order_call_before_it():
+    """State a call leaves for its thread (em_last_exact, em_last_order) is reset by the next call, whichever path that one takes: C65
+    of this table on k_emx (exact, with an order), then C65 of em_edge_cases without a rank on the table-lookup path."""
+    import em_edge_cases as ec
+    x = xc.BY_ID["C65"]
+    b = xc.xbuild(x)
+    assert len(b.counts) == 65                                 # the smallest class count k_em_wave does not take
+    cl = _classes(x)
+    try:
+        cl.em_ordered(b.n_alleles, x.base.remove_low, b.lengths)
+        assert engine.em_last_exact() and engine.em_last_order(b.n_alleles) is not None
+    finally:
+        cl.close()
+    c = next(c for c in ec.CASES if c.id == "C65")
+    t = ec.build(c)
+    cl = engine.Classes.from_host(t.rows(c.a_pad), t.counts, c.a_pad)
+    try:
+        cl.em_ordered(c.n_alleles, c.remove_low, t.lengths)
+        assert not engine.em_last_exact()
+        assert engine.em_last_order(c.n_alleles) is None
+    finally:
+        cl.close()
+
+
 def test_report_largest_differences():
     """Prints what the cases above measured, family by family (run with -s; profiles/emx_edges_mi355x.txt keeps one such run)."""
     for fam, err in sorted(WORST.items()):

@@ -26,6 +26,19 @@ def test_product_library_has_no_lab_backend():
     engine.em_set_backend(0)
 
 
+def test_removed_back_end_and_timing_slot_are_refused():
+    """Back-end 2 (the int8-MFMA mat-vec) is gone from both builds and the message says so; the EM's timing has slots 0..3."""
+    import ctypes as C
+    from hisatgenotype_amd import capi, engine
+    with pytest.raises(capi.HgxError) as e:
+        engine.em_set_backend(2)
+    assert "removed" in str(e.value) and "lab code" not in str(e.value)
+    ms, n, ex, by = C.c_double(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    assert capi.lib().hgx_em_get_timing(C.c_int(3), C.byref(ms), C.byref(n), C.byref(ex), C.byref(by)) == 0
+    assert capi.lib().hgx_em_get_timing(C.c_int(4), C.byref(ms), C.byref(n), C.byref(ex), C.byref(by)) == -1         # HGX_EINVAL
+    assert set(engine.em_get_timing()) == {"k_lutmatvec<0>", "k_lutmatvec<1>"}
+
+
 def test_product_library_has_no_fused_gene_level_form():
     """hgx_pair_classes_dedup (round 2's fused gene-level form, measured slower) lives in the lab library; libhgx.so says so."""
     import ctypes as C
