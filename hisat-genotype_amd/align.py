@@ -5,7 +5,8 @@ dialect the front end consumes (NM, MD, Zs, NH, YT as simulate._truth_record ren
 It is NOT HISAT2 and its output is not compared with HISAT2's anywhere: no whole-genome index, no secondary records; mates placed
 independently unless pair="aware" (tests/align_pair_ref.py); soft clips only with clip=N, and only for a read that has no
 end-to-end alignment (tests/align_clip_ref.py); a novel indel only with gap=N, one per read, and only for a read that has no
-end-to-end alignment (tests/align_gap_ref.py).  The rules are stated in plain Python in tests/align_ref.py; the kernels
+end-to-end alignment (tests/align_gap_ref.py); both of these in one call, the cheaper rescue per read, only with rescue=(G, C)
+(tests/align_rescue_ref.py).  The rules are stated in plain Python in tests/align_ref.py; the kernels
 (csrc/hgx_align.hip) and the host route (csrc/hgx_align_host.cpp) run one shared core (csrc/hgx_align_core.hpp, and csrc/hgx_align_states.hpp for the search over states).
 """
 import ctypes as C
@@ -20,6 +21,7 @@ NAMED_CLIP = 32                      # the clip budget of the aligner name "hgx.
 CLIP_MAX, CLIP_MAX_EDITS = 255, 4    # HGX_ALN_CLIP_MAX, HGX_ALN_CLIP_EDITS of csrc/hgx_align_core.hpp
 NAMED_GAP = 16                       # the longest novel gap of the aligner name "hgx.gap"
 GAP_MAX = 16                         # HGX_ALN_GAP_MAX of include/hgx.h
+NAMED_RESCUE = (NAMED_GAP, NAMED_CLIP)   # (gap, clip) of the aligner name "hgx.rescue"
 
 
 class AlignOpts(C.Structure):
@@ -30,6 +32,11 @@ class AlignOpts(C.Structure):
 class AlignMore(C.Structure):
     """hgx_align_more: the options behind hgx_align_opts (which keeps its seven words); `bytes` = sizeof."""
     _fields_ = [("bytes", C.c_int32), ("gap", C.c_int32)]
+
+
+class AlignMoreRescue(C.Structure):
+    """hgx_align_more with its third word (12 bytes): passed only where rescue= is given; AlignMore stays the 8-byte first version."""
+    _fields_ = [("bytes", C.c_int32), ("gap", C.c_int32), ("rescue_clip", C.c_int32)]
 
 
 class AlignIndex:
@@ -57,7 +64,7 @@ class AlignIndex:
             (C.c_char_p * max(n, 1))(*vdata), (C.c_char_p * max(n, 1))(*vid)))
 
     def align(self, reads, max_edits=2, max_fragment=1000, fastq=None, route="auto", search="ways", pair="independent",
-              clip=0, gap=0):
+              clip=0, gap=0, rescue=None):
         """SAM text (bytes) for `reads` = one or two FASTA / FASTQ[.gz] paths (str) or in-memory texts (bytes).  `search`: "ways"
         (per anchor, the ways through the known indels), "states" (reads that pass the kernels' anchor slots, stack or step limit
         -- on the host route: every read -- are searched over (read base, backbone position) states instead), "states_all" (every
@@ -72,11 +79,20 @@ class AlignIndex:
         WITHOUT an end-to-end alignment may be written with ONE novel deletion of up to N backbone bases or insertion of up to N read
         bases, its length counted into NM <= max_edits, by the order of tests/align_gap_ref.py (the usual key, then the leftmost
         gap); a read that aligns end to end is written as with 0, except for the mate fields of a record whose mate is aligned only
-        now.  Needs search="ways", pair="independent" and clip=0."""
+        now.  Needs search="ways", pair="independent" and clip=0.  `rescue`: None, or (G, C) = both tiers in one call, the gap tier with
+        gap=G and the clip tier with clip=C: a read WITHOUT an end-to-end alignment is written from the clip tier's result unless the
+        gap tier's costs fewer read bases given up or edited (NM with the gap counted < clipped bases + NM of the clipped record; a
+        tie goes to the clip), by tests/align_rescue_ref.py; no record carries both.  Needs search="ways", pair="independent",
+        max_edits <= 4, and gap=0 and clip=0 (they stay mutually exclusive and keep their meaning)."""
         assert len(reads) in (1, 2)
         opts = AlignOpts(int(max_edits), int(max_fragment), -1 if fastq is None else int(bool(fastq)), ROUTES[route],
                          search if isinstance(search, int) else SEARCHES[search], pair if isinstance(pair, int) else PAIRS[pair], int(clip))
-        more = AlignMore(C.sizeof(AlignMore), int(gap))
+        if rescue is None:
+            more = AlignMore(C.sizeof(AlignMore), int(gap))
+        else:
+            if gap:
+                raise ValueError("rescue=(G, C) names the gap tier's budget itself: gap= stays 0")
+            more = AlignMoreRescue(C.sizeof(AlignMoreRescue), int(rescue[0]), int(rescue[1]))
         out_p, n = C.c_void_p(), C.c_size_t(0)
         if all(isinstance(r, str) for r in reads):
             paths = (C.c_char_p * len(reads))(*[r.encode() for r in reads])
@@ -113,7 +129,9 @@ def align_last():
     pairs_placed / pairs_changed (pair="aware") = pairs with candidates on both mates, with a concordant combination, and with a
     record that differs from the independent one in alignment or NH; clip_searched / clip_clipped / clip_bases (clip=N) = reads
     without an end-to-end alignment that the clip tier searched, reads written with a clip, bases clipped; gap_searched /
-    gap_gapped / gap_bases (gap=N) = the same of the gap tier: reads searched, reads written with a novel gap, gap bases."""
+    gap_gapped / gap_bases (gap=N) = the same of the gap tier: reads searched, reads written with a novel gap, gap bases.  With
+    rescue=(G, C) both groups are set: clip_searched = reads without an end-to-end alignment that have an anchor, gap_searched =
+    those of them the clip tier left unaligned or with a cost of 2 or more; clipped / gapped and bases = the reads WRITTEN so."""
     route, dec = C.c_int32(0), C.c_int32(0)
     reads, aligned, conc = C.c_int64(0), C.c_int64(0), C.c_int64(0)
     capi.check(capi.lib().hgx_align_last(C.byref(route), C.byref(reads), C.byref(aligned), C.byref(conc), C.byref(dec)))

@@ -12,7 +12,8 @@
 //                  read off the mate's pick
 //   (opts.clip > 0 or hgx_align_more.gap > 0 only) the FALLBACK TIER between the picks and k_aln_emit, for the reads with anchors and
 //                  no alignment: k_aln_tier_mark / _fill / _extend<T> / _pick<T>, below.  One tier, two instances: T = ClipTier or
-//                  GapTier names the canon, the pick, the lane's scratch and what a read's extra word means; a call runs one of them
+//                  GapTier names the canon, the pick, the lane's scratch and what a read's extra word means; a call runs one of them,
+//                  or (hgx_align_more.rescue_clip > 0) both as two passes with k_aln_tier_keep / k_aln_tier_choose around the second
 // Every write is bounds-checked by construction: slots < HGX_ALN_DEV_ANCHORS, a record's bytes = the size the same code counted.
 //
 // opts.search != 0 adds a second tier, the search over STATES (hgx_align_states.hpp), for the reads of a chunk that are MARKED: in
@@ -60,6 +61,11 @@ struct Chunk {
     void *scan;                       // hgx_scan_u32_dev's scratch
     int *decline;                     // the chunk's decline word
     uint32_t *total;                  // a scan's total
+    // both tiers (rescue_clip > 0; nullptr otherwise): read_word holds 2 * nc words of a chunk, the clip pass's and, nc words
+    // behind them, the gap pass's
+    uint32_t *nslot2;                 // per read: slots of the gap pass (0: the cost rule or the first mark kept it out)
+    DevRes *kept;                     // per read: the clip pass's pick, kept while the gap pass reuses the read's slots of res[]
+    int32_t *kept_nh, *cost;          // per read: its NH and cost(C) = clipL + clipR + NM (RESCUE_NONE: the clip pass left it unaligned)
 };
 
 __global__ void __launch_bounds__(256)
@@ -245,7 +251,8 @@ k_aln_pair_pick(int nc, int max_fragment, const int32_t *cnt, const DevRes *res,
 
 // out == nullptr: sizes[i] and flags[i] (1 aligned, 2 = mate 1 of a concordant pair); else the line at out + off[i].  word[i] = the
 // read's extra word from the fallback tier (nullptr without one).  CLIP (opts.clip > 0): its clip counts for the S ops; GAP (gap > 0):
-// its gap descriptor (0: none).
+// its gap descriptor (0: none).  CLIP and GAP (both tiers): two word arrays, the clip counts in word[0 .. nc) and the gap descriptors
+// in word[nc .. 2 nc); at most one of a read's two is non-zero.
 template <bool CLIP, bool GAP = false> __global__ void __launch_bounds__(64)
 k_aln_emit(hgx_aln_view V, DevReads rd, long first, int nc, int max_fragment, const DevRes *res, const int32_t *best, const int32_t *nh,
            uint32_t *sizes, int32_t *flags, const uint32_t *off, char *out, const uint32_t *word) {
@@ -266,9 +273,11 @@ k_aln_emit(hgx_aln_view V, DevReads rd, long first, int nc, int max_fragment, co
     const long r = first + i;
     hgx_aln_out w{out ? out + off[i] : nullptr, 0};
     const uint32_t cc = CLIP || GAP ? word[i] : 0;
+    uint32_t gd = GAP ? cc : 0;
+    if constexpr (CLIP && GAP) gd = word[(long)nc + i];
     hgx_aln_line<HGX_ALN_DEV_VARS, CLIP, GAP>(V, rd.text + rd.name_off[r], rd.name_len[r], rd.text + rd.seq_off[r],
                                               rd.qual_off[r] >= 0 ? rd.text + rd.qual_off[r] : nullptr, rd.len[r], a, nh[i], mate, i & 1,
-                                              max_fragment, w, CLIP ? hgx_aln_clip_l(cc) : 0, CLIP ? hgx_aln_clip_r(cc) : 0, GAP ? cc : 0);
+                                              max_fragment, w, CLIP ? hgx_aln_clip_l(cc) : 0, CLIP ? hgx_aln_clip_r(cc) : 0, gd);
     if (!out) {
         sizes[i] = (uint32_t)w.n;
         flags[i] = 1 | ((rd.paired && !(i & 1) && hgx_aln_concordant(a, *mate, max_fragment)) ? 2 : 0);
@@ -284,8 +293,8 @@ k_aln_emit(hgx_aln_view V, DevReads rd, long first, int nc, int max_fragment, co
 //   k_aln_tier_extend<T>  a lane per compacted slot: T's canon into res[] and slot_word[]; a limit reached raises the decline word
 //   k_aln_tier_pick<T>    a lane per read with nslot[i] > 0: T's pick and NH over its slots, best[], nh[], read_word[]
 // A tier T names: canon() with the lane's private scratch as its own arrays (arrays, not one struct: as a struct the compiler lays
-// the lane's memory out otherwise and the kernels' registers and occupancy move), pick(), budget() (its argument of the call) and
-// bases() (what a read's word counts for, the third counter).  Every loop bound is the read length, the slot count, max_edits + 1,
+// the lane's memory out otherwise and the kernels' registers and occupancy move), pick() and bases() (what a read's word counts
+// for, the third counter).  Every loop bound is the read length, the slot count, max_edits + 1,
 // the longest gap, the options at a position or the step limit; every index is a slot below nc * HGX_ALN_DEV_ANCHORS or a compacted
 // slot below the scan's total.
 //
@@ -302,7 +311,6 @@ struct ClipTier {
     static __device__ int pick(const DevRes *res, int n, int *nh, const uint32_t *words) {
         return hgx_aln_pick<HGX_ALN_DEV_VARS, true>(res, n, nh, words);
     }
-    static int budget(const hgx_align_opts *opts, int) { return opts->clip; }
     static int bases(uint32_t word) { return hgx_aln_clip_total(word); }
 };
 // GapTier: the gap canon by the core's GAP walks; the word = the gap descriptor.  Scratch: the outer and the inner walks' stacks
@@ -318,7 +326,6 @@ struct GapTier {
                                                                    word);
     }
     static __device__ int pick(const DevRes *res, int n, int *nh, const uint32_t *words) { return hgx_aln_gap_pick(res, n, nh, words); }
-    static int budget(const hgx_align_opts *, int gap) { return gap; }
     static int bases(uint32_t word) { return hgx_aln_gap_len(word); }
 };
 
@@ -368,37 +375,131 @@ k_aln_tier_pick(int nc, const uint32_t *nslot, const DevRes *res, const uint32_t
     read_word[i] = b >= 0 ? slot_word[(long)i * HGX_ALN_DEV_ANCHORS + b] : 0u;
 }
 
-// the fallback tier of one chunk, behind k_aln_pick: *decline != 0: the call goes to the host route.  counts[0 .. 2]: reads searched,
-// reads the tier aligned, the bases their words stand for.
+// ---- both tiers in one call (hgx_align_more.rescue_clip > 0; the rule in plain Python: tests/align_rescue_ref.py) ----------------
+// The clip pass runs first (the cheap one) over the reads k_aln_tier_mark marks, then, a lane per read:
+//   k_aln_tier_keep     for a marked read: the clip pick's DevRes and NH into kept[] / kept_nh[] (the gap pass writes its canons into
+//                       the same slots of res[]) and cost[i] = clipL + clipR + NM, RESCUE_NONE if the clip pass left it unaligned;
+//                       for every read: nslot2[i], the gap pass's mark = the read's slots if it is marked and cost[i] >= 2 (a gap
+//                       costs at least 1 and a tie goes to the clip), else 0
+//   (the gap pass)      scan, fill, extend, pick over nslot2[] as they are, with the gap words behind the clip words
+//   k_aln_tier_choose   for a read of the gap pass: the gap's pick stands iff it exists and its NM < cost[i] (the clip word is
+//                       zeroed); else, if the clip pass aligned the read, kept[i] goes back into the read's slot 0 with best[],
+//                       nh[] and the gap word zeroed; else the read stays unaligned
+// Every index is a read below nc or the read's own slot 0 of res[].
+constexpr int32_t RESCUE_NONE = INT32_MAX;
+
+__global__ void __launch_bounds__(64)
+k_aln_tier_keep(int nc, const uint32_t *nslot, const DevRes *res, const int32_t *best, const int32_t *nh, const uint32_t *clip_word, DevRes *kept,
+                int32_t *kept_nh, int32_t *cost, uint32_t *nslot2) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nc) return;
+    uint32_t n2 = 0;
+    if (nslot[i] > 0) {
+        int32_t c = RESCUE_NONE;
+        if (best[i] >= 0) {
+            const DevRes &a = res[(long)i * HGX_ALN_DEV_ANCHORS + best[i]];
+            kept[i] = a;
+            kept_nh[i] = nh[i];
+            c = hgx_aln_clip_total(clip_word[i]) + a.nm;
+        }
+        cost[i] = c;
+        if (c >= 2) n2 = nslot[i];
+    }
+    nslot2[i] = n2;
+}
+
+__global__ void __launch_bounds__(64)
+k_aln_tier_choose(int nc, const uint32_t *nslot2, const DevRes *kept, const int32_t *kept_nh, const int32_t *cost, DevRes *res, int32_t *best,
+                  int32_t *nh, uint32_t *clip_word, uint32_t *gap_word) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nc || nslot2[i] == 0) return;                 // (not in the gap pass: the clip pass's pick, or none, stands)
+    const int32_t c = cost[i];
+    if (best[i] >= 0 && res[(long)i * HGX_ALN_DEV_ANCHORS + best[i]].nm < c) clip_word[i] = 0;
+    else if (c != RESCUE_NONE) {
+        res[(long)i * HGX_ALN_DEV_ANCHORS] = kept[i];
+        best[i] = 0;
+        nh[i] = kept_nh[i];
+        gap_word[i] = 0;
+    }
+}
+
+// one pass of tier T over the reads `nslot` marks, into `read_word`: scan, fill, extend, pick.  *total = 0: no read is marked and
+// nothing ran; *decline != 0: a limit was reached.
 template <class T>
-int fallback_tier(hgx_align_index *ix, const DevReads &rd, const hgx_align_opts *opts, int gap, long first, int nc, const Chunk &c, hipStream_t st,
-                  int64_t *counts, int *decline) {
-    HIPCHK(hipMemsetAsync(c.read_word, 0, (size_t)nc * 4, st));
-    k_aln_tier_mark<<<nblk(nc, 256), 256, 0, st>>>(nc, c.cnt, c.best, c.nslot);
-    HIPCHK(hipGetLastError());
-    const int rc = hgx_scan_u32_dev(c.nslot, c.soff, nc, c.scan, c.total, st);
+int tier_pass(hgx_align_index *ix, const DevReads &rd, int max_edits, int budget, long first, int nc, const Chunk &c, const uint32_t *nslot,
+              uint32_t *read_word, hipStream_t st, uint32_t *total, int *decline) {
+    const int rc = hgx_scan_u32_dev(nslot, c.soff, nc, c.scan, c.total, st);
     if (rc) return rc;
-    uint32_t total = 0;
-    HIPCHK(hipMemcpy(&total, c.total, 4, hipMemcpyDeviceToHost));
-    if (!total) return HGX_OK;
-    k_aln_tier_fill<<<nblk((long)nc * HGX_ALN_DEV_ANCHORS, 256), 256, 0, st>>>(nc, c.nslot, c.soff, total, c.compact);
-    k_aln_tier_extend<T><<<nblk(total, 64), 64, 0, st>>>(ix->dv, rd, first, total, opts->max_edits, T::budget(opts, gap), c.compact, c.anch, c.res,
-                                                         c.slot_word, c.decline);
+    *total = 0;
+    HIPCHK(hipMemcpy(total, c.total, 4, hipMemcpyDeviceToHost));
+    if (!*total) return HGX_OK;
+    k_aln_tier_fill<<<nblk((long)nc * HGX_ALN_DEV_ANCHORS, 256), 256, 0, st>>>(nc, nslot, c.soff, *total, c.compact);
+    k_aln_tier_extend<T><<<nblk(*total, 64), 64, 0, st>>>(ix->dv, rd, first, *total, max_edits, budget, c.compact, c.anch, c.res, c.slot_word,
+                                                          c.decline);
     HIPCHK(hipGetLastError());
     int dec = 0;
     HIPCHK(hipMemcpy(&dec, c.decline, 4, hipMemcpyDeviceToHost));
     if (dec) { *decline = dec; return HGX_OK; }
-    k_aln_tier_pick<T><<<nblk(nc, 64), 64, 0, st>>>(nc, c.nslot, c.res, c.slot_word, c.best, c.nh, c.read_word);
+    k_aln_tier_pick<T><<<nblk(nc, 64), 64, 0, st>>>(nc, nslot, c.res, c.slot_word, c.best, c.nh, read_word);
     HIPCHK(hipGetLastError());
+    return HGX_OK;
+}
+
+// what a chunk's tiers counted: [tier][reads searched, reads the tier wrote, the bases their words stand for]
+typedef int64_t TierCounts[HGX_ALN_N_TIERS][3];
+
+template <class T> void tier_sum(int nc, const uint32_t *nslot, const uint32_t *word, TierCounts counts) {
+    for (int i = 0; i < nc; ++i) {
+        if (!nslot[i]) continue;
+        counts[T::id][0] += 1;
+        counts[T::id][1] += word[i] != 0;
+        counts[T::id][2] += T::bases(word[i]);
+    }
+}
+
+// the fallback tier of one chunk, behind k_aln_pick: *decline != 0: the call goes to the host route.  budgets[0 .. 1]: the clip
+// tier's and the gap tier's.
+template <class T>
+int fallback_tier(hgx_align_index *ix, const DevReads &rd, int max_edits, const int *budgets, long first, int nc, const Chunk &c, hipStream_t st,
+                  TierCounts counts, int *decline) {
+    HIPCHK(hipMemsetAsync(c.read_word, 0, (size_t)nc * 4, st));
+    k_aln_tier_mark<<<nblk(nc, 256), 256, 0, st>>>(nc, c.cnt, c.best, c.nslot);
+    HIPCHK(hipGetLastError());
+    uint32_t total = 0;
+    const int rc = tier_pass<T>(ix, rd, max_edits, budgets[T::id == GapTier::id], first, nc, c, c.nslot, c.read_word, st, &total, decline);
+    if (rc || !total || *decline) return rc;
     std::vector<uint32_t> nslot((size_t)nc), word((size_t)nc);
     HIPCHK(hipMemcpy(nslot.data(), c.nslot, (size_t)nc * 4, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(word.data(), c.read_word, (size_t)nc * 4, hipMemcpyDeviceToHost));
-    for (int i = 0; i < nc; ++i) {
-        if (!nslot[i]) continue;
-        counts[0] += 1;
-        counts[1] += word[i] != 0;
-        counts[2] += T::bases(word[i]);
+    tier_sum<T>(nc, nslot.data(), word.data(), counts);
+    return HGX_OK;
+}
+
+// both tiers of one chunk: the clip pass, the gap pass over the reads the cost rule leaves to it, the choice; the counters are
+// summed from what is copied back after the choice
+int rescue_tiers(hgx_align_index *ix, const DevReads &rd, int max_edits, const int *budgets, long first, int nc, const Chunk &c, hipStream_t st,
+                 TierCounts counts, int *decline) {
+    uint32_t *clip_word = c.read_word, *gap_word = c.read_word + nc;
+    HIPCHK(hipMemsetAsync(c.read_word, 0, (size_t)nc * 8, st));
+    k_aln_tier_mark<<<nblk(nc, 256), 256, 0, st>>>(nc, c.cnt, c.best, c.nslot);
+    HIPCHK(hipGetLastError());
+    uint32_t total = 0, total2 = 0;
+    int rc = tier_pass<ClipTier>(ix, rd, max_edits, budgets[0], first, nc, c, c.nslot, clip_word, st, &total, decline);
+    if (rc || !total || *decline) return rc;
+    k_aln_tier_keep<<<nblk(nc, 64), 64, 0, st>>>(nc, c.nslot, c.res, c.best, c.nh, clip_word, c.kept, c.kept_nh, c.cost, c.nslot2);
+    HIPCHK(hipGetLastError());
+    rc = tier_pass<GapTier>(ix, rd, max_edits, budgets[1], first, nc, c, c.nslot2, gap_word, st, &total2, decline);
+    if (rc || *decline) return rc;
+    if (total2) {
+        k_aln_tier_choose<<<nblk(nc, 64), 64, 0, st>>>(nc, c.nslot2, c.kept, c.kept_nh, c.cost, c.res, c.best, c.nh, clip_word, gap_word);
+        HIPCHK(hipGetLastError());
     }
+    std::vector<uint32_t> nslot((size_t)nc), nslot2((size_t)nc), word((size_t)nc * 2);
+    HIPCHK(hipMemcpy(nslot.data(), c.nslot, (size_t)nc * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(nslot2.data(), c.nslot2, (size_t)nc * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(word.data(), c.read_word, (size_t)nc * 8, hipMemcpyDeviceToHost));
+    tier_sum<ClipTier>(nc, nslot.data(), word.data(), counts);
+    tier_sum<GapTier>(nc, nslot2.data(), word.data() + nc, counts);
     return HGX_OK;
 }
 
@@ -706,8 +807,8 @@ void hgx_align_device_free(hgx_align_index *ix) {
     ix->dev_ready = -1;
 }
 
-int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_align_opts *opts, int gap, std::string &body, int64_t *aligned,
-                     int64_t *concordant, int *decline) {
+int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_align_opts *opts, int gap, int rescue_clip, std::string &body,
+                     int64_t *aligned, int64_t *concordant, int *decline) {
     *decline = 0;
     const size_t body0 = body.size();
     const int64_t aligned0 = *aligned, concordant0 = *concordant;
@@ -741,19 +842,26 @@ int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
     ALLOC(d_flags, (size_t)cmax * 4);
     ALLOC(d_scan, hgx_scan_u32_scratch_bytes(cmax) + 16);
     ALLOC(d_misc, 48);                       // [0] decline code, [1] total bytes, [2] reads marked for the second tier; pair mode: bytes 16 .. 40 = pairs searched, placed, changed
-    // the call's fallback tier (at most one: hgx_align_reads_x) and the k_aln_emit that reads its word, chosen here once
+    // the call's fallback tier (one, or both with rescue_clip > 0: hgx_align_reads_x) and the k_aln_emit that reads its words, chosen
+    // here once
     const int clip = opts->clip;
-    const auto tier = clip > 0 ? fallback_tier<ClipTier> : gap > 0 ? fallback_tier<GapTier> : nullptr;
-    const auto emit = clip > 0 ? k_aln_emit<true> : gap > 0 ? k_aln_emit<false, true> : k_aln_emit<false>;
-    const int tier_id = clip > 0 ? ClipTier::id : gap > 0 ? GapTier::id : HGX_ALN_TIER_NONE;
-    DevBuf d_read_word, d_nslot, d_soff, d_slot_word, d_compact;
+    const bool rescue = rescue_clip > 0 && gap > 0;
+    const auto tier = rescue ? rescue_tiers : clip > 0 ? fallback_tier<ClipTier> : gap > 0 ? fallback_tier<GapTier> : nullptr;
+    const auto emit = rescue ? k_aln_emit<true, true> : clip > 0 ? k_aln_emit<true> : gap > 0 ? k_aln_emit<false, true> : k_aln_emit<false>;
+    const int budgets[2] = {rescue ? rescue_clip : clip, gap};
+    DevBuf d_read_word, d_nslot, d_soff, d_slot_word, d_compact, d_nslot2, d_kept, d_kept_nh, d_cost;
     if (tier) {
-        ALLOC(d_read_word, (size_t)cmax * 4); ALLOC(d_nslot, (size_t)cmax * 4); ALLOC(d_soff, (size_t)cmax * 4);
+        ALLOC(d_read_word, (size_t)cmax * (rescue ? 8 : 4)); ALLOC(d_nslot, (size_t)cmax * 4); ALLOC(d_soff, (size_t)cmax * 4);
         ALLOC(d_slot_word, (size_t)cmax * HGX_ALN_DEV_ANCHORS * 4); ALLOC(d_compact, (size_t)cmax * HGX_ALN_DEV_ANCHORS * 4);
+    }
+    if (rescue) {
+        ALLOC(d_nslot2, (size_t)cmax * 4); ALLOC(d_kept, (size_t)cmax * sizeof(DevRes)); ALLOC(d_kept_nh, (size_t)cmax * 4);
+        ALLOC(d_cost, (size_t)cmax * 4);
     }
     const Chunk c{d_cnt.as<int32_t>(), d_anch.as<int2>(), d_res.as<DevRes>(), d_best.as<int32_t>(), d_nh.as<int32_t>(),
                   search ? d_mark.as<int32_t>() : nullptr, d_slot_word.as<uint32_t>(), d_read_word.as<uint32_t>(), d_nslot.as<uint32_t>(),
-                  d_soff.as<uint32_t>(), d_compact.as<int32_t>(), d_scan.p, d_misc.as<int>(), d_misc.as<uint32_t>() + 1};
+                  d_soff.as<uint32_t>(), d_compact.as<int32_t>(), d_scan.p, d_misc.as<int>(), d_misc.as<uint32_t>() + 1,
+                  d_nslot2.as<uint32_t>(), d_kept.as<DevRes>(), d_kept_nh.as<int32_t>(), d_cost.as<int32_t>()};
     auto launch_emit = [&](long first, int nc, uint32_t *sizes, int32_t *flags, const uint32_t *off, char *out) {      // either pass
         emit<<<nblk(nc, 64), 64, 0, st>>>(ix->dv, rd, first, nc, opts->max_fragment, c.res, c.best, c.nh, sizes, flags, off, out, c.read_word);
         return hipGetLastError();
@@ -765,7 +873,7 @@ int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
         *decline = dec;
         return HGX_OK;
     };
-    int64_t tier_counts[3] = {0, 0, 0};
+    TierCounts tier_counts = {};
     const bool pair_aware = reads.paired && opts->pair == 1;
     const size_t misc_bytes = pair_aware ? 40 : 16;
     int64_t pairs[3] = {0, 0, 0};
@@ -800,7 +908,7 @@ int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
             k_aln_pair_pick<<<nc / 2, 64, 0, st>>>(nc, opts->max_fragment, c.cnt, c.res, c.best, c.nh,
                                                    (unsigned long long *)(d_misc.as<char>() + 16));
         if (tier) {
-            rc = tier(ix, rd, opts, gap, first, nc, c, st, tier_counts, &dec);
+            rc = tier(ix, rd, opts->max_edits, budgets, first, nc, c, st, tier_counts, &dec);
             if (rc) return rc;
             if (dec) return declined(dec);
         }
@@ -828,6 +936,6 @@ int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
     }
     HIPCHK(hipStreamSynchronize(st));
     if (pair_aware) hgx_align_pairs_count(pairs[0], pairs[1], pairs[2]);
-    if (tier) hgx_align_tier_count(tier_id, tier_counts[0], tier_counts[1], tier_counts[2]);
+    for (int t = 1; tier && t < HGX_ALN_N_TIERS; ++t) hgx_align_tier_count(t, tier_counts[t][0], tier_counts[t][1], tier_counts[t][2]);
     return HGX_OK;
 }

@@ -37,16 +37,17 @@ struct hgx_aln_reads {
 
 // the kernels' route: the records of `reads` appended to `body`, per-read flags (1 aligned, 2 concordant).  *decline != 0: nothing
 // was appended and the host route finishes the call.
-// `gap`: hgx_align_more.gap (0: no gap tier).
-int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_align_opts *opts, int gap, std::string &body,
-                     int64_t *aligned, int64_t *concordant, int *decline);
+// `gap`: hgx_align_more.gap (0: no gap tier).  `rescue_clip`: hgx_align_more.rescue_clip (> 0, with gap > 0: both tiers, the clip
+// tier with this budget).
+int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_align_opts *opts, int gap, int rescue_clip,
+                     std::string &body, int64_t *aligned, int64_t *concordant, int *decline);
 void hgx_align_device_free(hgx_align_index *ix);
 
 // what the states form took in the calling thread's current call (hgx_align_last_states): added to by either route
 void hgx_align_states_count(int64_t reads, int64_t anchors, int64_t cells);
 // what the pair pick did in the calling thread's current call (hgx_align_last_pairs): added to by the route that gives the bytes
 void hgx_align_pairs_count(int64_t searched, int64_t placed, int64_t changed);
-// what the call's fallback tier (a call runs at most one) did in the calling thread's current call: added to by the route that
-// gives the bytes; hgx_align_last_clip / hgx_align_last_gap report it for their tier and zeros for the other
-enum { HGX_ALN_TIER_NONE = 0, HGX_ALN_TIER_CLIP = 1, HGX_ALN_TIER_GAP = 2 };
+// what a fallback tier did in the calling thread's current call (one triple per tier: a rescue call runs both): added to by the
+// route that gives the bytes; hgx_align_last_clip / hgx_align_last_gap report their tier's, zeros where it did not run
+enum { HGX_ALN_TIER_NONE = 0, HGX_ALN_TIER_CLIP = 1, HGX_ALN_TIER_GAP = 2, HGX_ALN_N_TIERS = 3 };
 void hgx_align_tier_count(int tier, int64_t searched, int64_t found, int64_t bases);

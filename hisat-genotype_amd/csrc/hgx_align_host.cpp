@@ -24,8 +24,7 @@ thread_local int g_route = 0, g_decline = 0;
 thread_local int64_t g_reads = 0, g_aligned = 0, g_conc = 0;
 thread_local int64_t g_st_reads = 0, g_st_anchors = 0, g_st_cells = 0;
 thread_local int64_t g_pr_searched = 0, g_pr_placed = 0, g_pr_changed = 0;
-thread_local int g_tier = HGX_ALN_TIER_NONE;                             // the fallback tier the counters below are of
-thread_local int64_t g_tr_searched = 0, g_tr_found = 0, g_tr_bases = 0;
+thread_local int64_t g_tr[HGX_ALN_N_TIERS][3] = {};                      // per fallback tier: reads searched, reads written, their bases
 
 template <class T> void csr(const std::vector<std::pair<int32_t, int32_t>> &items, int32_t n_pos, std::vector<T> &off, std::vector<T> &list) {
     off.assign((size_t)n_pos + 1, 0);
@@ -244,12 +243,13 @@ int align_one(const hgx_aln_view &V, const char *seq, int L, int max_edits, Host
     return HGX_OK;
 }
 
-// ---- the fallback tier (opts.clip > 0: ClipTier; hgx_align_more.gap > 0: GapTier) for a read align_one found nothing for: a dearer
+// ---- the fallback tier (opts.clip > 0: ClipTier; hgx_align_more.gap > 0: GapTier; rescue_clip > 0: RescueTier, both) for a read
+// align_one found nothing for: a dearer
 // canon over the same anchors, the tier's pick, one extra word for the record.  A tier names its canon, its pick, the scratch it
 // needs besides HostScratch's stack and list, its argument of the call and the bases a word counts for, as the kernels' tiers do.
 // Both run without the memo: it drops an arrival that a plain search never needs, and that arrival may be the prefix of the
 // smallest way with a clip or a gap (hgx_align_core.hpp).
-struct NoTier { static constexpr int id = HGX_ALN_TIER_NONE; static constexpr bool CLIP = false, GAP = false; struct Scratch {}; };
+struct NoTier { static constexpr int id = HGX_ALN_TIER_NONE; static constexpr bool CLIP = false, GAP = false; };
 struct ClipTier {
     static constexpr int id = HGX_ALN_TIER_CLIP;
     static constexpr bool CLIP = true, GAP = false;                      // (hgx_aln_line's)
@@ -263,7 +263,6 @@ struct ClipTier {
                                                                        X.left.data(), X.right.data(), res, word);
     }
     static int pick(const HostRes *res, int n, int *nh, const uint32_t *words) { return hgx_aln_pick<HGX_ALN_HOST_VARS, true>(res, n, nh, words); }
-    static int budget(const hgx_align_opts *o, int) { return o->clip; }
     static int bases(uint32_t word) { return hgx_aln_clip_total(word); }
 };
 struct GapTier {
@@ -281,7 +280,6 @@ struct GapTier {
                                                                       X.stk2.data(), X.cur2.data(), X.sides.data(), res, word);
     }
     static int pick(const HostRes *res, int n, int *nh, const uint32_t *words) { return hgx_aln_gap_pick(res, n, nh, words); }
-    static int budget(const hgx_align_opts *, int gap) { return gap; }
     static int bases(uint32_t word) { return hgx_aln_gap_len(word); }
 };
 template <class T> struct TierScratch {
@@ -290,9 +288,10 @@ template <class T> struct TierScratch {
     std::vector<uint32_t> words;
 };
 
-// *word = 0 and best.ok = 0 where the tier finds nothing or passes a limit (*gave_up); a read with an anchor counts as searched
+// *word = 0 and best.ok = 0 where the tier finds nothing or passes a limit (*gave_up); true: the read has an anchor (it counts as
+// searched)
 template <class T>
-void align_one_tier(const hgx_aln_view &V, const char *seq, int L, int max_edits, int budget, HostScratch &S, TierScratch<T> &X, HostRes &best,
+bool align_one_tier(const hgx_aln_view &V, const char *seq, int L, int max_edits, int budget, HostScratch &S, TierScratch<T> &X, HostRes &best,
                     int *nh, uint32_t *word, int *gave_up) {
     X.res.clear();
     X.words.clear();
@@ -313,8 +312,49 @@ void align_one_tier(const hgx_aln_view &V, const char *seq, int L, int max_edits
         const int b = T::pick(X.res.data(), (int)X.res.size(), nh, X.words.data());
         if (b >= 0) { best = X.res[(size_t)b]; *word = X.words[(size_t)b]; }
     }
-    if (n_anchors > 0) hgx_align_tier_count(T::id, 1, *word != 0, T::bases(*word));
+    return n_anchors > 0;
 }
+
+// what the host route runs per read that align_one found nothing for.  rescue(): best / nh / the read's two words (at most one of
+// them non-zero: which tier wrote the record); the counters are added to here.
+template <class T> struct SingleTier : T {
+    TierScratch<T> X;
+    void rescue(const hgx_aln_view &V, const char *seq, int L, int max_edits, const int *budgets, HostScratch &S, HostRes &best, int *nh,
+                uint32_t *clip_word, uint32_t *gap_word, int *gave_up) {
+        uint32_t &word = T::CLIP ? *clip_word : *gap_word;
+        if (align_one_tier<T>(V, seq, L, max_edits, budgets[T::CLIP ? 0 : 1], S, X, best, nh, &word, gave_up))
+            hgx_align_tier_count(T::id, 1, word != 0, T::bases(word));
+    }
+};
+// both tiers (hgx_align_more.rescue_clip > 0; the rule in plain Python: tests/align_rescue_ref.py): the clip tier's result C, then --
+// unless cost(C) = clipL + clipR + NM_c <= 1, which no gap undercuts -- the gap tier's G; G is the record iff NM_g < cost(C)
+struct RescueTier {
+    static constexpr int id = HGX_ALN_TIER_CLIP | HGX_ALN_TIER_GAP;
+    static constexpr bool CLIP = true, GAP = true;
+    TierScratch<ClipTier> XC;
+    TierScratch<GapTier> XG;
+    HostRes g;
+    void rescue(const hgx_aln_view &V, const char *seq, int L, int max_edits, const int *budgets, HostScratch &S, HostRes &best, int *nh,
+                uint32_t *clip_word, uint32_t *gap_word, int *gave_up) {
+        *gap_word = 0;
+        if (!align_one_tier<ClipTier>(V, seq, L, max_edits, budgets[0], S, XC, best, nh, clip_word, gave_up)) return;
+        const int cost = best.ok ? hgx_aln_clip_total(*clip_word) + best.nm : INT_MAX;
+        bool searched = false;
+        if (cost >= 2 && !*gave_up) {
+            int gnh = 0;
+            uint32_t gw = 0;
+            searched = align_one_tier<GapTier>(V, seq, L, max_edits, budgets[1], S, XG, g, &gnh, &gw, gave_up);
+            if (g.ok && g.nm < cost) {
+                best = g;
+                *nh = gnh;
+                *gap_word = gw;
+                *clip_word = 0;
+            }
+        }
+        hgx_align_tier_count(HGX_ALN_TIER_CLIP, 1, *clip_word != 0, hgx_aln_clip_total(*clip_word));
+        hgx_align_tier_count(HGX_ALN_TIER_GAP, searched, *gap_word != 0, hgx_aln_gap_len(*gap_word));
+    }
+};
 
 // ---- the host route's states form (hgx_align_states.hpp): the same cells as the kernels, in loops --------------------------------
 struct StatesScratch {
@@ -444,16 +484,17 @@ bool pair_pick(PairScratch &S, int max_fragment, int *b1, int *b2, int *nh) {
     return true;
 }
 
-// T: the call's fallback tier (NoTier: none); it also settles which hgx_aln_line writes the records
+// T: what the call runs for a read without an end-to-end alignment (NoTier: nothing; SingleTier<ClipTier>, SingleTier<GapTier>,
+// RescueTier); it also settles which hgx_aln_line writes the records.  budgets[0 .. 1]: the clip tier's and the gap tier's.
 template <class T>
-int host_route(const hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_align_opts *o, int gap, std::string &body, int64_t *aligned,
-               int64_t *conc, int *gave_up) {
+int host_route(const hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_align_opts *o, const int *budgets, std::string &body,
+               int64_t *aligned, int64_t *conc, int *gave_up) {
     const hgx_aln_view &V = ix->hv;
     HostScratch S;
     StatesScratch SS;
     PairScratch PS;
-    TierScratch<T> TS;
-    uint32_t word[2] = {0, 0};                           // the tier's extra word of each mate (0: the tier did not align it)
+    T TS;
+    uint32_t cw[2] = {0, 0}, gw[2] = {0, 0};             // each mate's clip counts and gap descriptor (0: that tier did not write it)
     const int per = reads.paired ? 2 : 1;
     const bool pair_aware = per == 2 && o->pair == 1;
     std::vector<HostRes> best(per);
@@ -467,10 +508,10 @@ int host_route(const hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
                                      : align_one(V, seq, reads.len[k + m], o->max_edits, S, best[m], &nh[m], &gu);
             if (rc) return rc;
             if (pair_aware) PS.cand[m].swap(S.res);      // (a mate that gave up: none)
-            word[m] = 0;
+            cw[m] = gw[m] = 0;
             if constexpr (T::id != HGX_ALN_TIER_NONE)
-                if (!best[m].ok && !gu)                  // no end-to-end alignment: the tier over the same anchors
-                    align_one_tier<T>(V, seq, reads.len[k + m], o->max_edits, T::budget(o, gap), S, TS, best[m], &nh[m], &word[m], &gu);
+                if (!best[m].ok && !gu)                  // no end-to-end alignment: the tier(s) over the same anchors
+                    TS.rescue(V, seq, reads.len[k + m], o->max_edits, budgets, S, best[m], &nh[m], &cw[m], &gw[m], &gu);
             if (gu) *gave_up = gu;
         }
         if (pair_aware && best[0].ok && best[1].ok) {
@@ -495,11 +536,11 @@ int host_route(const hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
             const HostRes *mate = per == 2 ? &best[1 - m] : nullptr;
             hgx_aln_out cnt{nullptr, 0}, w{nullptr, 0};
             for (int pass = 0; pass < 2; ++pass) {       // the size, then the bytes
-                // (a word of 0, a read aligned end to end, gives the plain line with either tier's arguments, as in k_aln_emit)
+                // (words of 0, a read aligned end to end, give the plain line with any tier's arguments, as in k_aln_emit)
                 hgx_aln_line<HGX_ALN_HOST_VARS, T::CLIP, T::GAP>(V, reads.text.data() + reads.name_off[i], reads.name_len[i],
                                                                  reads.text.data() + reads.seq_off[i], qual, reads.len[i], best[m], nh[m], mate, m,
-                                                                 o->max_fragment, pass ? w : cnt, T::CLIP ? hgx_aln_clip_l(word[m]) : 0,
-                                                                 T::CLIP ? hgx_aln_clip_r(word[m]) : 0, T::GAP ? word[m] : 0);
+                                                                 o->max_fragment, pass ? w : cnt, hgx_aln_clip_l(cw[m]), hgx_aln_clip_r(cw[m]),
+                                                                 gw[m]);
                 if (!pass) {
                     line.resize((size_t)cnt.n);
                     w.p = line.data();
@@ -518,10 +559,9 @@ void hgx_align_states_count(int64_t reads, int64_t anchors, int64_t cells) {
     g_st_cells += cells;
 }
 void hgx_align_tier_count(int tier, int64_t searched, int64_t found, int64_t bases) {
-    g_tier = tier;
-    g_tr_searched += searched;
-    g_tr_found += found;
-    g_tr_bases += bases;
+    g_tr[tier][0] += searched;
+    g_tr[tier][1] += found;
+    g_tr[tier][2] += bases;
 }
 void hgx_align_pairs_count(int64_t searched, int64_t placed, int64_t changed) {
     g_pr_searched += searched;
@@ -534,7 +574,8 @@ void hgx_align_pairs_count(int64_t searched, int64_t placed, int64_t changed) {
 extern "C" void hgx_set_error(const char *fmt, ...) { va_list ap; va_start(ap, fmt); vfprintf(stderr, fmt, ap); va_end(ap); fputc('\n', stderr); }
 extern "C" const char *hgx_test_switch(const char *) { return "host"; }
 void *hgx_host_alloc(size_t bytes) { return malloc(bytes); }
-int hgx_align_device(hgx_align_index *, const hgx_aln_reads &, const hgx_align_opts *, int, std::string &, int64_t *, int64_t *, int *decline) {
+int hgx_align_device(hgx_align_index *, const hgx_aln_reads &, const hgx_align_opts *, int, int, std::string &, int64_t *, int64_t *,
+                     int *decline) {
     *decline = HGX_ALN_DECLINE_SWITCH;
     return HGX_OK;
 }
@@ -650,14 +691,20 @@ extern "C" int hgx_align_reads(hgx_align_index *ix, int32_t n_inputs, const char
 extern "C" int hgx_align_reads_x(hgx_align_index *ix, int32_t n_inputs, const char *const *paths, const char *const *texts,
                                  const size_t *text_bytes, const hgx_align_opts *opts, const hgx_align_more *more, char **sam_out,
                                  size_t *n_bytes_out) {
-    // (`more` is read up to the fields this build knows and no further than more->bytes)
-    if (more && more->bytes < (int32_t)sizeof(hgx_align_more)) {
+    // (`more` is read up to the fields this build knows and no further than more->bytes: 8 = the first version, `gap` alone)
+    if (more && more->bytes < 8) {
         hgx_set_error("invalid argument: hgx_align_reads_x (more.bytes)");
         return HGX_EINVAL;
     }
     const int gap = more ? more->gap : 0;
-    if (opts && (gap < 0 || gap > HGX_ALN_GAP_MAX || (gap && (opts->search || opts->pair || opts->clip)))) {      // (one fallback tier per call)
+    const int rescue = more && more->bytes >= 12 ? more->rescue_clip : 0;
+    if (opts && (gap < 0 || gap > HGX_ALN_GAP_MAX || (gap && (opts->search || opts->pair || opts->clip)))) {      // (both tiers: rescue_clip)
         hgx_set_error("invalid argument: hgx_align_reads_x (gap)");
+        return HGX_EINVAL;
+    }
+    // (rescue_clip > 0 with search, pair or opts.clip: gap == 0 or refused above)
+    if (opts && (rescue < 0 || rescue > HGX_ALN_CLIP_MAX || (rescue && (gap <= 0 || opts->max_edits > HGX_ALN_CLIP_EDITS)))) {
+        hgx_set_error("invalid argument: hgx_align_reads_x (rescue_clip)");
         return HGX_EINVAL;
     }
     if (!ix || (n_inputs != 1 && n_inputs != 2) || (!paths && !(texts && text_bytes)) || !opts || !sam_out || !n_bytes_out ||
@@ -673,8 +720,7 @@ extern "C" int hgx_align_reads_x(hgx_align_index *ix, int32_t n_inputs, const ch
     g_route = 0; g_decline = 0; g_reads = g_aligned = g_conc = 0;
     g_st_reads = g_st_anchors = g_st_cells = 0;
     g_pr_searched = g_pr_placed = g_pr_changed = 0;
-    g_tier = HGX_ALN_TIER_NONE;
-    g_tr_searched = g_tr_found = g_tr_bases = 0;
+    memset(g_tr, 0, sizeof g_tr);
     try {
         hgx_aln_reads reads;
         int rc = load_reads(n_inputs, paths, texts, text_bytes, opts->fastq, reads);
@@ -687,18 +733,19 @@ extern "C" int hgx_align_reads_x(hgx_align_index *ix, int32_t n_inputs, const ch
         if (opts->route == 1 || (opts->route == 0 && sw && !strcmp(sw, "host"))) decline = HGX_ALN_DECLINE_SWITCH;
         else if (opts->route == 0 && !(sw && !strcmp(sw, "device")) && reads.n() < 1000) decline = HGX_ALN_DECLINE_GATE;
         if (!decline && reads.n() > 0) {
-            if ((rc = hgx_align_device(ix, reads, opts, gap, body, &aligned, &conc, &decline))) return rc;
+            if ((rc = hgx_align_device(ix, reads, opts, gap, rescue, body, &aligned, &conc, &decline))) return rc;
         }
         if (decline) {
             body.clear();
             aligned = conc = 0;
             g_st_reads = g_st_anchors = g_st_cells = 0;          // what the kernels took before they declined is not this call's answer
             g_pr_searched = g_pr_placed = g_pr_changed = 0;
-            g_tier = HGX_ALN_TIER_NONE;
-            g_tr_searched = g_tr_found = g_tr_bases = 0;
+            memset(g_tr, 0, sizeof g_tr);
             int gave_up = 0;
-            const auto route = opts->clip > 0 ? host_route<ClipTier> : gap > 0 ? host_route<GapTier> : host_route<NoTier>;
-            if ((rc = route(ix, reads, opts, gap, body, &aligned, &conc, &gave_up))) return rc;
+            const auto route = rescue > 0 ? host_route<RescueTier> : opts->clip > 0 ? host_route<SingleTier<ClipTier>>
+                               : gap > 0 ? host_route<SingleTier<GapTier>> : host_route<NoTier>;
+            const int budgets[2] = {rescue > 0 ? rescue : opts->clip, gap};
+            if ((rc = route(ix, reads, opts, budgets, body, &aligned, &conc, &gave_up))) return rc;
             if (gave_up) fprintf(stderr, "[hgx_align_reads] a read's search passed the host route's limits (code %d): left unaligned\n", gave_up);
         }
         g_route = decline ? 0 : 2;
@@ -743,12 +790,11 @@ extern "C" int hgx_align_last_pairs(int64_t *searched, int64_t *placed, int64_t 
     return HGX_OK;
 }
 
-// the last call's tier counters if `tier` is the one it ran, else zeros
+// the last call's counters of `tier` (zeros if it did not run)
 static int tier_last(int tier, int64_t *searched, int64_t *found, int64_t *bases) {
-    const bool ran = g_tier == tier;
-    if (searched) *searched = ran ? g_tr_searched : 0;
-    if (found) *found = ran ? g_tr_found : 0;
-    if (bases) *bases = ran ? g_tr_bases : 0;
+    if (searched) *searched = g_tr[tier][0];
+    if (found) *found = g_tr[tier][1];
+    if (bases) *bases = g_tr[tier][2];
     return HGX_OK;
 }
 extern "C" int hgx_align_last_clip(int64_t *searched, int64_t *clipped, int64_t *bases) {

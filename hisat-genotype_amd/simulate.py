@@ -323,8 +323,8 @@ def align_reads(aligner, simulation, index_name, index_type, base_fname, read_fn
     out; real reads cannot be aligned here.  aligner "hgx" (align.py; simulated or real reads of the loci in `truth`, variants in
     `var_list` order, at most `max_edits` unknown mismatches): its SAM text, stored like the reference stores HISAT2's.
     "hgx.states" is the same aligner with search="states", "hgx.pairs" with pair="aware", "hgx.clip" with clip=32,
-    "hgx.gap" with gap=16 (align.AlignIndex.align)."""
-    if aligner in ("hgx", "hgx.states", "hgx.pairs", "hgx.clip", "hgx.gap"):
+    "hgx.gap" with gap=16, "hgx.rescue" with rescue=(16, 32): both tiers, the cheaper rescue per read (align.AlignIndex.align)."""
+    if aligner in ("hgx", "hgx.states", "hgx.pairs", "hgx.clip", "hgx.gap", "hgx.rescue"):
         if index_type != "graph" or truth is None or var_list is None:
             raise NotImplementedError("the hgx aligner aligns to the loci's backbones through their known variants (graph) only")
         from . import align
@@ -333,7 +333,8 @@ def align_reads(aligner, simulation, index_name, index_type, base_fname, read_fn
                                                                        search="states" if aligner == "hgx.states" else "ways",
                                                                        pair="aware" if aligner == "hgx.pairs" else "independent",
                                                                        clip=align.NAMED_CLIP if aligner == "hgx.clip" else 0,
-                                                                       gap=align.NAMED_GAP if aligner == "hgx.gap" else 0)
+                                                                       gap=align.NAMED_GAP if aligner == "hgx.gap" else 0,
+                                                                       rescue=align.NAMED_RESCUE if aligner == "hgx.rescue" else None)
         _store_as_the_reference_does(out_fname, text.decode())
         return
     if shutil.which(aligner):

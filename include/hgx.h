@@ -900,7 +900,8 @@ int hgx_extract_close(hgx_extract *h);
  * that the tier searched (they have an anchor), reads written with a clip, bases clipped; 0 with clip = 0.
  * align_reads_x: align_reads with further options in `more` (hgx_align_opts keeps its seven words: a caller compiled against them
  * never has an eighth read).  more == NULL is align_reads; more->bytes = sizeof(hgx_align_more) of the caller's build, so that later
- * options join without a new entry point (bytes smaller than the fields of this header: HGX_EINVAL).
+ * options join without a new entry point.  bytes < 8 (the first version's size) is HGX_EINVAL; bytes of 8 .. 11 reads `gap` only,
+ * bytes >= 12 also reads `rescue_clip`.
  * more.gap: 0 (the default: every byte, every word of hgx_align_last*, every kernel launched and every byte copied as before) or
  * N <= 16 (the rule in plain Python: tests/align_gap_ref.py).  A read that has an end-to-end alignment is searched and written as
  * with 0, NH included.  A read that has none may be written with ONE novel gap: on entry to a state (r, p), 0 < r < L, in front of
@@ -912,12 +913,26 @@ int hgx_extract_close(hgx_extract *h);
  * the smallest NM.  The record is the one synth._align_read writes: I / D in the CIGAR, ^bases in MD for a deletion, no Zs item
  * for the gap (inserted bases count into the next item's gap).  A record that 0 writes can change only in FLAG 0x8 / 0x20 / 0x2,
  * RNEXT, PNEXT and YT, where its mate is aligned only now.
- * gap < 0, gap > 16 and gap with search != 0, pair != 0 or clip != 0 (one fallback tier per call) are HGX_EINVAL.
+ * gap < 0, gap > 16 and gap with search != 0, pair != 0 or clip != 0 are HGX_EINVAL (both tiers in one call: more.rescue_clip).
  * On the kernels' route the tier runs per chunk for the reads with anchors that the pick left unaligned (k_aln_gap_extend /
  * k_aln_gap_pick behind the clip tier's mark and fill); a read past a device limit declines with today's codes and the host route
  * gives the bytes.  NOT HISAT2's gap scoring (--rdg / --rfg), and not compared with it.
  * align_last_gap: of the calling thread's last call, on the route that gave the bytes -- reads without an end-to-end alignment
- * that the tier searched (they have an anchor), reads written with a gap, gap bases; 0 with gap = 0. */
+ * that the tier searched (they have an anchor), reads written with a gap, gap bases; 0 with gap = 0.
+ * more.rescue_clip: 0 (the default: every byte, every word of hgx_align_last*, every kernel launched and every byte copied as with
+ * bytes = 8) or N <= 255: BOTH fallback tiers in one call, the cheaper rescue per read (the rule in plain Python:
+ * tests/align_rescue_ref.py).  A read that has an end-to-end alignment is searched and written as with 0, NH included.  A read that
+ * has none gets the clip tier's result C (opts.clip = N: clipL, clipR, NM_c) and the gap tier's result G (more.gap: NM_g, the gap
+ * counted).  cost(C) = clipL + clipR + NM_c, cost(G) = NM_g: read bases given up or edited.  The record is G if G exists and (C does
+ * not exist or NM_g < cost(C)), else C if C exists, else the read is unaligned; a tie goes to the clip, which claims no variant.
+ * Each tier keeps its own order, pick, NH and rendering; no record carries both a clip and a novel gap.  NM_g >= 1, so a read with
+ * cost(C) <= 1 is not searched by the gap tier on either route.  Mate fields and concordance come from the mates' final alignments.
+ * rescue_clip > 0 needs gap > 0, opts.clip = 0, search = 0, pair = 0, max_edits <= 4 and rescue_clip <= 255; anything else, and
+ * rescue_clip < 0, is HGX_EINVAL (the message names the field).  opts.clip > 0 with gap > 0 stays HGX_EINVAL.
+ * align_last_clip / align_last_gap then both report: clip searched = reads without an end-to-end alignment that have an anchor, gap
+ * searched = those of them that the clip tier left unaligned or with cost(C) >= 2; clipped / gapped and bases = the reads WRITTEN
+ * with a clip / a gap.  On the kernels' route: the clip pass, k_aln_tier_keep, the gap pass over the reads kept for it,
+ * k_aln_tier_choose, k_aln_emit<true, true>; a device limit reached in either pass declines the call with today's codes. */
 typedef struct hgx_align_opts {
     int32_t max_edits, max_fragment, fastq, route;
     int32_t search;            /* 0 ways (the default), 1 states, 2 states_all */
@@ -928,6 +943,7 @@ typedef struct hgx_align_opts {
 typedef struct hgx_align_more {
     int32_t bytes;             /* sizeof(hgx_align_more) of the caller's build */
     int32_t gap;               /* 0 no novel gaps (the default); N: a read without an end-to-end alignment may be written with one novel gap of up to N bases */
+    int32_t rescue_clip;       /* (bytes >= 12) 0: as without it; N: with gap > 0, both tiers in one call, the clip tier with a budget of N, the cheaper rescue per read */
 } hgx_align_more;
 typedef struct hgx_align_index hgx_align_index;
 int hgx_align_index_create(hgx_align_index **out, int32_t n_loci, const char *const *names, const char *const *backbones,

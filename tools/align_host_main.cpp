@@ -1,9 +1,9 @@
 // align_host_main.cpp -- the host route of the "hgx" aligner as a stand-alone program, for sanitizer builds:
 //   g++ -std=c++17 -g -O1 -fsanitize=address,undefined -DHGX_ALIGN_STANDALONE -I include -I hisat-genotype_amd/csrc \
 //       hisat-genotype_amd/csrc/hgx_align_host.cpp tools/align_host_main.cpp -lz -o align_host_main
-//   align_host_main <index file> <max_edits> <reads> [<mate reads>] [search=0|1|2] [pair=0|1] [fragment=N] [clip=N] [gap=N]  > out.sam
-//   (search, pair, fragment, clip: hgx_align_opts.search, .pair, .max_fragment, .clip; gap: hgx_align_more.gap; in any order behind the
-//   read files)
+//   align_host_main <index file> <max_edits> <reads> [<mate reads>] [search=0|1|2] [pair=0|1] [fragment=N] [clip=N] [gap=N] [rescue=G,C]  > out.sam
+//   (search, pair, fragment, clip: hgx_align_opts.search, .pair, .max_fragment, .clip; gap: hgx_align_more.gap; rescue: hgx_align_more.gap
+//   and .rescue_clip; in any order behind the read files)
 // The index file is text: "<n_loci>", then per locus "<name> <backbone> <n_vars>" followed by one "<type 0|1|2> <pos> <data> <id>"
 // line per variant in Var_list order.  Nothing of the GPU library is linked.
 #include <cstdio>
@@ -17,7 +17,7 @@
 #include "hgx.h"
 
 int main(int argc, char **argv) {
-    int search = 0, pair = 0, fragment = 1000, clip = 0, gap = 0;
+    int search = 0, pair = 0, fragment = 1000, clip = 0, gap = 0, rescue_clip = 0;
     for (; argc > 4; --argc) {
         const char *a = argv[argc - 1];
         if (!strncmp(a, "search=", 7)) search = atoi(a + 7);
@@ -25,10 +25,11 @@ int main(int argc, char **argv) {
         else if (!strncmp(a, "fragment=", 9)) fragment = atoi(a + 9);
         else if (!strncmp(a, "clip=", 5)) clip = atoi(a + 5);
         else if (!strncmp(a, "gap=", 4)) gap = atoi(a + 4);
+        else if (!strncmp(a, "rescue=", 7) && strchr(a, ',')) { gap = atoi(a + 7); rescue_clip = atoi(strchr(a, ',') + 1); }
         else break;
     }
     if (argc < 4 || argc > 5) {
-        fprintf(stderr, "usage: %s index max_edits reads [mate reads] [search=0|1|2] [pair=0|1] [fragment=N] [clip=N] [gap=N]\n", argv[0]);
+        fprintf(stderr, "usage: %s index max_edits reads [mate reads] [search=0|1|2] [pair=0|1] [fragment=N] [clip=N] [gap=N] [rescue=G,C]\n", argv[0]);
         return 2;
     }
     std::ifstream in(argv[1]);
@@ -61,8 +62,8 @@ int main(int argc, char **argv) {
     const char *paths[2] = {argv[3], argc == 5 ? argv[4] : nullptr};
     char *sam = nullptr;
     size_t n = 0;
-    const hgx_align_more more{(int32_t)sizeof(hgx_align_more), gap};
-    const int rc = hgx_align_reads_x(ix, argc - 3, paths, nullptr, nullptr, &o, gap ? &more : nullptr, &sam, &n);
+    const hgx_align_more more{(int32_t)sizeof(hgx_align_more), gap, rescue_clip};
+    const int rc = hgx_align_reads_x(ix, argc - 3, paths, nullptr, nullptr, &o, gap || rescue_clip ? &more : nullptr, &sam, &n);
     if (rc == 0) fwrite(sam, 1, n, stdout);
     free(sam);
     hgx_align_index_free(ix);

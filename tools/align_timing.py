@@ -1,8 +1,8 @@
 """Time the "hgx" aligner's device route against its host route: reads/s of AlignIndex.align, upload and copy
 back included, at a few read counts.
 
-    python tools/align_timing.py [--workload synth|tandem|paralog|overhang|novel] [--search ways|states|states_all] [--pair] [--clip N]
-                                 [--gap N]
+    python tools/align_timing.py [--workload synth|tandem|paralog|overhang|novel|mixed] [--search ways|states|states_all] [--pair]
+                                 [--clip N] [--gap N] [--rescue G,C]
                                  [--err 0.5] [--reps 5] [--sizes 250,500,1000,2000,4000,16000,64000] [--tandem-indels 12] [--no-host]
 
 --workload synth   simulated 100-base pairs of a synth HLA-like locus, at read counts round the route gate
@@ -17,6 +17,12 @@ back included, at a few read counts.
 --workload novel   100-base pairs of synth.simulate_pairs over the synth locus, a tenth of the reads with a novel one-base deletion
                    (novel_del_frac) and a tenth with a novel one- or two-base insertion (novel_ins_frac), --err errors, cycled to
                    the read count (default --sizes 16000,64000): the reads the gap tier exists for
+--workload mixed   single reads over the synth locus: half of them the overhang workload's tiled reads, half the novel workload's
+                   pairs (both mates), --err errors (default --sizes 16000,64000): the reads both tiers in one call exist for
+--rescue G,C       time both routes with gap=G alone, with clip=C alone and with rescue=(G, C) (hgx_align_more.rescue_clip) beside
+                   the default, and print, per route: reads aligned under each of the three, both counter triples of the rescue
+                   call, the reads the cost rule kept out of its gap pass (clip searched - gap searched), the cost per 8 192-read
+                   chunk of each against the default, and the ratio of the rescue call's cost to the sum of the two tiers' costs
 --gap N            time both routes with gap=N (hgx_align_more.gap) beside gap=0 and print the counters of hgx_align_last_gap and the
                    cost per 8 192-read chunk; the two gap texts are compared with each other, not with the gap=0 texts
 --clip N           time both routes with clip=N (hgx_align_opts.clip) beside clip=0 and print the counters of hgx_align_last_clip and
@@ -152,6 +158,16 @@ def novel_reads(err_percent, n_pairs, pool_pairs=2000, read_len=100):
     return d, texts
 
 
+def mixed_reads(err_percent, n_reads):
+    """(reference dicts, [one FASTA text]): overhang_reads and novel_reads (both build the same locus), half and half, shuffled."""
+    d, (over,) = overhang_reads(err_percent, n_reads // 2)
+    _, novel = novel_reads(err_percent, (n_reads - n_reads // 2 + 1) // 2)
+    seqs = [t.decode().split("\n")[1::2] for t in (over, novel[0], novel[1])]
+    pool = (seqs[0] + seqs[1] + seqs[2])[:n_reads]
+    random.Random(17).shuffle(pool)
+    return d, ["".join(">m%d\n%s\n" % (k, s) for k, s in enumerate(pool)).encode()]
+
+
 def timed(ix, texts, reps, **kw):
     out = ix.align(texts, **kw)                                       # warm-up
     last = align.align_last()
@@ -165,10 +181,11 @@ def timed(ix, texts, reps, **kw):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=("synth", "tandem", "paralog", "overhang", "novel"), default="synth")
+    ap.add_argument("--workload", choices=("synth", "tandem", "paralog", "overhang", "novel", "mixed"), default="synth")
     ap.add_argument("--pair", action="store_true", help="also time the device route with pair=\"aware\"")
     ap.add_argument("--clip", type=int, default=0, help="also time both routes with clip=N")
     ap.add_argument("--gap", type=int, default=0, help="also time both routes with gap=N")
+    ap.add_argument("--rescue", default=None, help="G,C: also time both routes with gap=G, with clip=C and with rescue=(G, C)")
     ap.add_argument("--search", choices=sorted(align.SEARCHES), default="ways")
     ap.add_argument("--err", type=float, default=0.5)
     ap.add_argument("--reps", type=int, default=5)
@@ -177,7 +194,7 @@ def main():
     ap.add_argument("--no-host", action="store_true", help="time the device-route call only")
     args = ap.parse_args()
     sizes = args.sizes or {"synth": "250,500,1000,2000,4000,16000,64000", "tandem": "64", "paralog": "16000,64000",
-                           "overhang": "16000,64000", "novel": "16000,64000"}[args.workload]
+                           "overhang": "16000,64000", "novel": "16000,64000", "mixed": "16000,64000"}[args.workload]
     capi.set_device(0)
     search = {} if args.search == "ways" else {"search": args.search}
     configs = [("device " + args.search, dict(route="device", **search))]
@@ -198,16 +215,43 @@ def main():
         configs.append(("device ways gap", dict(route="device", gap=args.gap)))
         if not args.no_host:
             configs.append(("host ways gap", dict(route="host", gap=args.gap)))
+    rescue = None
+    if args.rescue:
+        assert not search and not args.pair and not args.clip and not args.gap, "rescue needs --search ways and none of --pair, --clip, --gap"
+        rescue = tuple(int(x) for x in args.rescue.split(","))
+        for route in ["device"] + ([] if args.no_host else ["host"]):
+            configs.append(("%s ways gap" % route, dict(route=route, gap=rescue[0])))
+            configs.append(("%s ways clip" % route, dict(route=route, clip=rescue[1])))
+            configs.append(("%s ways rescue" % route, dict(route=route, rescue=rescue)))
     rows = []
     for n in [int(x) for x in sizes.split(",")]:
         d, texts = (reads_of(args.err, n // 2) if args.workload == "synth" else paralog_reads(n // 2) if args.workload == "paralog"
                     else overhang_reads(args.err, n) if args.workload == "overhang" else novel_reads(args.err, n // 2)
-                    if args.workload == "novel" else tandem_reads(args.tandem_indels, n))
+                    if args.workload == "novel" else mixed_reads(args.err, n) if args.workload == "mixed"
+                    else tandem_reads(args.tandem_indels, n))
         ix = align.AlignIndex(d["Genes"], d["Vars"], d["Var_list"], d["refGenes"])
-        outs, clip_outs, med = [], [], {}
+        outs, clip_outs, med, rescue_outs = [], [], {}, {}
         for name, kw in configs:
             out, last, ts = timed(ix, texts, args.reps, **kw)
-            if kw.get("clip"):
+            if rescue:
+                base, tier = name.rsplit(" ", 1) if name.split()[-1] in ("gap", "clip", "rescue") else (name, None)
+                chunks = -(-n // 8192)
+                if tier is None:
+                    outs.append(out)
+                else:
+                    rescue_outs.setdefault(tier, []).append(out)
+                    cost = (statistics.median(ts) - med[base]) * 1e3 / chunks
+                    med[name + " cost"] = cost
+                    print("%7d reads  %-18s aligned %d; clip: searched %d clipped %d bases %d; gap: searched %d gapped %d bases %d; %+.3f ms per "
+                          "8 192-read chunk against %s" % (n, name, last["aligned"], last["clip_searched"], last["clip_clipped"],
+                                                          last["clip_bases"], last["gap_searched"], last["gap_gapped"], last["gap_bases"], cost,
+                                                          base), flush=True)
+                    if tier == "rescue":
+                        both = med[base + " gap cost"] + med[base + " clip cost"]
+                        print("%7d reads  %-18s kept out of the gap pass by the cost rule: %d of %d; cost / (gap cost + clip cost) = %.3f" % (
+                            n, name, last["clip_searched"] - last["gap_searched"], last["clip_searched"], cost / both if both else float("nan")),
+                            flush=True)
+            elif kw.get("clip"):
                 base = name[:-5]
                 chunks = -(-n // 8192)
                 clip_outs.append(out)
@@ -235,6 +279,7 @@ def main():
                       last["aligned"], last["states_reads"], last["states_anchors"], last["states_cells"]),
                   flush=True)
         assert all(o == outs[0] for o in outs) and all(o == clip_outs[0] for o in clip_outs)
+        assert all(o == v[0] for v in rescue_outs.values() for o in v)
         rows.append((n, med[configs[0][0]], med.get("host ways")))
         ix.close()
     if args.workload == "synth" and not args.no_host:
