@@ -39,6 +39,14 @@ class AlignMoreRescue(C.Structure):
     _fields_ = [("bytes", C.c_int32), ("gap", C.c_int32), ("rescue_clip", C.c_int32)]
 
 
+class AlignMoreOrder(C.Structure):
+    """hgx_align_more with its fourth word (16 bytes): passed only where order="coordinate" or align_resident() is asked for."""
+    _fields_ = [("bytes", C.c_int32), ("gap", C.c_int32), ("rescue_clip", C.c_int32), ("order", C.c_int32)]
+
+
+ORDERS = {"read": 0, "coordinate": 1}
+
+
 class AlignIndex:
     """The loci of `Genes` (in its order) with their variants in `Var_list` order, ready for align()."""
 
@@ -63,8 +71,45 @@ class AlignIndex:
             (C.c_int32 * len(off))(*off), (C.c_int32 * max(n, 1))(*vtype), (C.c_int32 * max(n, 1))(*vpos),
             (C.c_char_p * max(n, 1))(*vdata), (C.c_char_p * max(n, 1))(*vid)))
 
+    @staticmethod
+    def _call_args(reads, max_edits, max_fragment, fastq, route, search, pair, clip, gap, rescue, order):
+        """(opts, more, n, paths, texts, sizes, what keeps them alive) of one hgx_align_reads_x / hgx_align_reads_resident call."""
+        assert len(reads) in (1, 2)
+        opts = AlignOpts(int(max_edits), int(max_fragment), -1 if fastq is None else int(bool(fastq)), ROUTES[route],
+                         search if isinstance(search, int) else SEARCHES[search], pair if isinstance(pair, int) else PAIRS[pair], int(clip))
+        order = order if isinstance(order, int) else ORDERS[order]
+        if rescue is not None and gap:
+            raise ValueError("rescue=(G, C) names the gap tier's budget itself: gap= stays 0")
+        if order:
+            more = AlignMoreOrder(C.sizeof(AlignMoreOrder), int(rescue[0] if rescue is not None else gap),
+                                  int(rescue[1]) if rescue is not None else 0, order)
+        elif rescue is None:
+            more = AlignMore(C.sizeof(AlignMore), int(gap))
+        else:
+            more = AlignMoreRescue(C.sizeof(AlignMoreRescue), int(rescue[0]), int(rescue[1]))
+        if all(isinstance(r, str) for r in reads):
+            paths = (C.c_char_p * len(reads))(*[r.encode() for r in reads])
+            return opts, more, C.c_int32(len(reads)), paths, None, None, None
+        bufs = [bytes(r) for r in reads]
+        texts = (C.c_char_p * len(bufs))(*bufs)
+        sizes = (C.c_size_t * len(bufs))(*[len(b) for b in bufs])
+        return opts, more, C.c_int32(len(bufs)), None, texts, sizes, bufs
+
+    def align_resident(self, reads, max_edits=2, max_fragment=1000, fastq=None, route="auto", search="ways", pair="independent",
+                       clip=0, gap=0, rescue=None, stream=None):
+        """align(..., order="coordinate") whose text is NOT copied back: an engine.Alignment over the ordered text in HBM
+        (hgx_align_reads_resident), ready for parse_dev(locus, regions) per locus -- what the coordinate-sorted BAM between aligner
+        and front end gave them, without the file.  `.text()` copies the text back, `.save(path)` writes that BAM; `.close()` frees
+        it (and removes the temporary BAM a per-path fallback may have written).  align_last() reports as for align()."""
+        from . import engine
+        opts, more, n, paths, texts, sizes, _keep = self._call_args(reads, max_edits, max_fragment, fastq, route, search, pair, clip, gap,
+                                                                    rescue, "coordinate")
+        h = C.c_void_p()
+        capi.check(capi.lib().hgx_align_reads_resident(self.h, n, paths, texts, sizes, C.byref(opts), C.byref(more), C.byref(h), stream))
+        return engine.Alignment.from_handle(h)
+
     def align(self, reads, max_edits=2, max_fragment=1000, fastq=None, route="auto", search="ways", pair="independent",
-              clip=0, gap=0, rescue=None):
+              clip=0, gap=0, rescue=None, order="read"):
         """SAM text (bytes) for `reads` = one or two FASTA / FASTQ[.gz] paths (str) or in-memory texts (bytes).  `search`: "ways"
         (per anchor, the ways through the known indels), "states" (reads that pass the kernels' anchor slots, stack or step limit
         -- on the host route: every read -- are searched over (read base, backbone position) states instead), "states_all" (every
@@ -83,27 +128,14 @@ class AlignIndex:
         gap=G and the clip tier with clip=C: a read WITHOUT an end-to-end alignment is written from the clip tier's result unless the
         gap tier's costs fewer read bases given up or edited (NM with the gap counted < clipped bases + NM of the clipped record; a
         tie goes to the clip), by tests/align_rescue_ref.py; no record carries both.  Needs search="ways", pair="independent",
-        max_edits <= 4, and gap=0 and clip=0 (they stay mutually exclusive and keep their meaning)."""
-        assert len(reads) in (1, 2)
-        opts = AlignOpts(int(max_edits), int(max_fragment), -1 if fastq is None else int(bool(fastq)), ROUTES[route],
-                         search if isinstance(search, int) else SEARCHES[search], pair if isinstance(pair, int) else PAIRS[pair], int(clip))
-        if rescue is None:
-            more = AlignMore(C.sizeof(AlignMore), int(gap))
-        else:
-            if gap:
-                raise ValueError("rescue=(G, C) names the gap tier's budget itself: gap= stays 0")
-            more = AlignMoreRescue(C.sizeof(AlignMoreRescue), int(rescue[0]), int(rescue[1]))
+        max_edits <= 4, and gap=0 and clip=0 (they stay mutually exclusive and keep their meaning).  `order`: "read" (the records in
+        input order, mate 1 before mate 2: the 8- and 12-byte hgx_align_more are passed as before) or "coordinate" (stable-sorted by
+        (locus in @SQ order, POS), the order of the BAM that simulate._store_as_the_reference_does writes:
+        tests/align_resident_ref.py); an int is passed through as hgx_align_more.order.  Valid with every form above."""
+        opts, more, n_in, paths, texts, sizes, _keep = self._call_args(reads, max_edits, max_fragment, fastq, route, search, pair, clip, gap,
+                                                                       rescue, order)
         out_p, n = C.c_void_p(), C.c_size_t(0)
-        if all(isinstance(r, str) for r in reads):
-            paths = (C.c_char_p * len(reads))(*[r.encode() for r in reads])
-            rc = capi.lib().hgx_align_reads_x(self.h, C.c_int32(len(reads)), paths, None, None, C.byref(opts), C.byref(more), C.byref(out_p),
-                                              C.byref(n))
-        else:
-            bufs = [bytes(r) for r in reads]
-            texts = (C.c_char_p * len(bufs))(*bufs)
-            sizes = (C.c_size_t * len(bufs))(*[len(b) for b in bufs])
-            rc = capi.lib().hgx_align_reads_x(self.h, C.c_int32(len(bufs)), None, texts, sizes, C.byref(opts), C.byref(more), C.byref(out_p),
-                                              C.byref(n))
+        rc = capi.lib().hgx_align_reads_x(self.h, n_in, paths, texts, sizes, C.byref(opts), C.byref(more), C.byref(out_p), C.byref(n))
         capi.check(rc)
         try:
             return C.string_at(out_p.value, n.value)

@@ -85,6 +85,7 @@ SYMBOLS = [
     "hgx_extract_open", "hgx_extract_feed", "hgx_extract_feed_bam", "hgx_extract_file", "hgx_extract_take", "hgx_extract_stats", "hgx_extract_close",
     "hgx_align_index_create", "hgx_align_index_free", "hgx_align_reads", "hgx_align_last", "hgx_align_last_states",
     "hgx_align_last_pairs", "hgx_align_last_clip", "hgx_align_reads_x", "hgx_align_last_gap",
+    "hgx_align_reads_resident", "hgx_alignment_text", "hgx_alignment_save_bam",
 ]
 
 _lib = None

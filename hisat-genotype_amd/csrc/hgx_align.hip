@@ -31,6 +31,8 @@
 // Tables live in HBM / L2 (16 B per cell): a row reads the rows within the longest known insertion + 1 of it, and the lists are
 // read back from any row, so an LDS ring would not spare the table.  Every index into the scratch is bounded by
 // the numbers the host sized it with: the task's window, read length and cell offset.
+#include <hipcub/hipcub.hpp>
+
 #include "hgx_common.hpp"
 #include "hgx_align.hpp"
 
@@ -282,6 +284,49 @@ k_aln_emit(hgx_aln_view V, DevReads rd, long first, int nc, int max_fragment, co
         sizes[i] = (uint32_t)w.n;
         flags[i] = 1 | ((rd.paired && !(i & 1) && hgx_aln_concordant(a, *mate, max_fragment)) ? 2 : 0);
     }
+}
+
+// ---- coordinate order (hgx_align_more.order = 1; the rule in plain Python: tests/align_resident_ref.py) ------------------------------
+// The chunks' text stays in HBM, one buffer per chunk.  Behind a chunk's k_aln_emit passes:
+//   k_aln_rec_keys      a lane per read: entry first + i of the call's record table -- key (index of RNAME << 32 | POS - 1, from the
+//                       pick that k_aln_emit printed: hgx_aln_coord_key; REC_NONE for a read without a record), place (chunk << 32 |
+//                       offset in the chunk's text), length (0 without a record) and the entry's own index
+// and after the last chunk, over the n entries: one stable radix sort of (key, index) -- ties keep input order --,
+//   k_aln_rec_lens      a lane per sorted entry: its length, for the exclusive scan that gives every line's offset in the ordered text
+//   k_aln_gather_lines  a wavefront per sorted entry: the line's bytes from its chunk's text to its offset, lanes across the bytes
+//                       (source and destination are unaligned and unrelated; lines are 150 - 900 bytes)
+// No atomic decides a position and nothing passes between workgroups.  Every table index is below n, every source byte inside its
+// chunk's text (offset + length <= the chunk's total, both from the scan that placed the line), every destination byte below the
+// chunks' totals summed (the scan of the same lengths in another order).
+// A read without a record has the key n_loci << 32, behind every record's: the sort runs over the bits that n_loci << 32 has.
+__global__ void __launch_bounds__(256)
+k_aln_rec_keys(hgx_aln_view V, long first, int nc, uint32_t chunk, const DevRes *res, const int32_t *best, const uint32_t *sizes,
+               const uint32_t *off, unsigned long long *key, unsigned long long *place, uint32_t *len, uint32_t *idx) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nc) return;
+    const long r = first + i;
+    const bool has = best[i] >= 0;
+    key[r] = has ? hgx_aln_coord_key(V, res[(long)i * HGX_ALN_DEV_ANCHORS + best[i]]) : (unsigned long long)V.n_loci << 32;
+    place[r] = ((unsigned long long)chunk << 32) | (has ? off[i] : 0u);
+    len[r] = has ? sizes[i] : 0u;
+    idx[r] = (uint32_t)r;
+}
+
+__global__ void __launch_bounds__(256) k_aln_rec_lens(const uint32_t *sorted, uint32_t n, const uint32_t *len, uint32_t *out) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < n) out[j] = len[sorted[j]];
+}
+
+__global__ void __launch_bounds__(256)
+k_aln_gather_lines(const uint32_t *sorted, uint32_t n, const unsigned long long *place, const uint32_t *len, const uint32_t *dst_off,
+                   const char *const *chunk_text, char *out) {
+    const uint32_t j = blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64;
+    if (j >= n) return;                                                // (the whole wavefront)
+    const uint32_t e = sorted[j], L = len[e];
+    const unsigned long long p = place[e];
+    const char *src = chunk_text[p >> 32] + (uint32_t)p;
+    char *dst = out + dst_off[j];
+    for (uint32_t b = threadIdx.x & 63; b < L; b += 64) dst[b] = src[b];
 }
 
 // ---- the fallback tier (opts.clip > 0: ClipTier, "soft clips"; hgx_align_more.gap > 0: GapTier, "novel gaps"; hgx_align_core.hpp) ----
@@ -799,6 +844,74 @@ int ensure_device_index(hgx_align_index *ix) {
     ix->dev_ready = dev;
     return HGX_OK;
 }
+
+// coordinate order: the call's record table and the chunks' text, both in HBM until the last chunk has run
+struct Ordered {
+    DevBuf key, place, len, idx;               // per read (k_aln_rec_keys)
+    std::vector<void *> text;                  // per chunk: its emitted text (nullptr: none)
+    std::vector<uint32_t> bytes;               // ... and its size
+    hipStream_t st = nullptr;
+    ~Ordered() {                               // (whatever way the call returns: the kernels over these buffers have run)
+        if (!text.empty()) (void)hipStreamSynchronize(st);
+        for (void *p : text) if (p) hgx_pool_free(p);
+    }
+};
+
+// the table sorted, the lines gathered: the ordered text, `header` in front of it and 64 zeroed bytes behind it with ord->keep (left
+// in ord->d_text), else appended to `body`
+int order_text(const hgx_align_index *ix, Ordered &O, long n, std::string &body, hgx_aln_ordered *ord, hipStream_t st) {
+    size_t total = 0;
+    for (uint32_t b : O.bytes) total += b;
+    const size_t head = ord->keep ? ix->header.size() : 0;
+    if (head + total >= ((size_t)1 << 32) - 64 || n >= (1L << 31)) {       // beyond the 32-bit offsets: input order, the caller sorts the lines
+        for (size_t k = 0; k < O.text.size(); ++k) {
+            if (!O.bytes[k]) continue;
+            const size_t at = body.size();
+            body.resize(at + O.bytes[k]);
+            HIPCHK(hipMemcpy(&body[at], O.text[k], O.bytes[k], hipMemcpyDeviceToHost));
+        }
+        ord->unordered = true;
+        return HGX_OK;
+    }
+    const uint32_t nn = (uint32_t)n;
+    DevBuf d_ptrs, d_key2, d_sorted, d_tmp, d_slen, d_dst, d_scan, d_total, d_out;
+    ALLOC(d_ptrs, O.text.size() * sizeof(void *));
+    HIPCHK(hipMemcpy(d_ptrs.p, O.text.data(), O.text.size() * sizeof(void *), hipMemcpyHostToDevice));
+    ALLOC(d_key2, (size_t)nn * 8); ALLOC(d_sorted, (size_t)nn * 4); ALLOC(d_slen, (size_t)nn * 4); ALLOC(d_dst, (size_t)nn * 4);
+    ALLOC(d_scan, hgx_scan_u32_scratch_bytes(nn) + 16);
+    ALLOC(d_total, 16);
+    int end_bit = 33;                                                      // the bits of n_loci << 32, the largest key
+    while (end_bit < 64 && ((unsigned long long)ix->hv.n_loci >> (end_bit - 32))) ++end_bit;
+    size_t tmp_bytes = 0;
+    (void)hipcub::DeviceRadixSort::SortPairs((void *)nullptr, tmp_bytes, (unsigned long long *)nullptr, (unsigned long long *)nullptr, (uint32_t *)nullptr,
+                                             (uint32_t *)nullptr, (int)nn, 0, end_bit, st);
+    ALLOC(d_tmp, std::max<size_t>(tmp_bytes, 256));
+    HIPCHK(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, tmp_bytes, O.key.as<unsigned long long>(), d_key2.as<unsigned long long>(), O.idx.as<uint32_t>(),
+                                              d_sorted.as<uint32_t>(), (int)nn, 0, end_bit, st));
+    k_aln_rec_lens<<<nblk(nn, 256), 256, 0, st>>>(d_sorted.as<uint32_t>(), nn, O.len.as<uint32_t>(), d_slen.as<uint32_t>());
+    HIPCHK(hipGetLastError());
+    TRY(hgx_scan_u32_dev(d_slen.as<uint32_t>(), d_dst.as<uint32_t>(), nn, d_scan.p, d_total.as<uint32_t>(), st));
+    ALLOC(d_out, head + total + 64);
+    HIPCHK(hipMemsetAsync(d_out.as<char>() + head + total, 0, 64, st));
+    if (head) HIPCHK(hipMemcpyAsync(d_out.p, ix->header.data(), head, hipMemcpyHostToDevice, st));
+    k_aln_gather_lines<<<nblk(nn, 4), 256, 0, st>>>(d_sorted.as<uint32_t>(), nn, O.place.as<unsigned long long>(), O.len.as<uint32_t>(),
+                                                    d_dst.as<uint32_t>(), (const char *const *)d_ptrs.p, d_out.as<char>() + head);
+    HIPCHK(hipGetLastError());
+    uint32_t scanned = 0;
+    HIPCHK(hipMemcpy(&scanned, d_total.p, 4, hipMemcpyDeviceToHost));        // (also: the gather has run before its buffers go back to the pool)
+    HIPCHK(hipStreamSynchronize(st));
+    if (scanned != total) { hgx_set_error("hgx_align_reads: the ordered text has %u bytes, the chunks' %zu", scanned, total); return HGX_EHIP; }
+    if (ord->keep) {
+        ord->d_text = d_out.p;
+        ord->n_bytes = head + total;
+        d_out.p = nullptr;
+    } else if (total) {
+        const size_t at = body.size();
+        body.resize(at + total);
+        HIPCHK(hipMemcpy(&body[at], d_out.p, total, hipMemcpyDeviceToHost));
+    }
+    return HGX_OK;
+}
 }      // namespace
 
 void hgx_align_device_free(hgx_align_index *ix) {
@@ -808,7 +921,7 @@ void hgx_align_device_free(hgx_align_index *ix) {
 }
 
 int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_align_opts *opts, int gap, int rescue_clip, std::string &body,
-                     int64_t *aligned, int64_t *concordant, int *decline) {
+                     int64_t *aligned, int64_t *concordant, int *decline, hgx_aln_ordered *ord) {
     *decline = 0;
     const size_t body0 = body.size();
     const int64_t aligned0 = *aligned, concordant0 = *concordant;
@@ -879,6 +992,11 @@ int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
     int64_t pairs[3] = {0, 0, 0};
     std::vector<int32_t> flags(cmax);
     std::string text;
+    Ordered O;                                 // (ord == nullptr: stays empty -- no buffer, no kernel)
+    if (ord) {
+        O.st = st;
+        ALLOC(O.key, (size_t)n * 8); ALLOC(O.place, (size_t)n * 8); ALLOC(O.len, (size_t)n * 4); ALLOC(O.idx, (size_t)n * 4);
+    }
     for (long first = 0; first < n; first += CHUNK) {
         const int nc = (int)std::min<long>(CHUNK, n - first);
         HIPCHK(hipMemsetAsync(d_cnt.p, 0, (size_t)nc * 4, st));
@@ -925,7 +1043,17 @@ int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
         }
         HIPCHK(hipMemcpy(flags.data(), d_flags.p, (size_t)nc * 4, hipMemcpyDeviceToHost));
         for (int i = 0; i < nc; ++i) { *aligned += flags[i] & 1; *concordant += (flags[i] >> 1) & 1; }
-        if (total) {
+        if (ord) {                                                     // coordinate order: the text stays, the chunk's records join the table
+            void *d_keep = total ? hgx_pool_alloc(total) : nullptr;
+            O.text.push_back(d_keep);
+            O.bytes.push_back(total);
+            if (total && !d_keep) { hgx_set_error("device allocation of %u bytes failed", total); return HGX_ENOMEM; }
+            if (total) HIPCHK(launch_emit(first, nc, nullptr, nullptr, d_off.as<uint32_t>(), (char *)d_keep));
+            k_aln_rec_keys<<<nblk(nc, 256), 256, 0, st>>>(ix->dv, first, nc, (uint32_t)(first / CHUNK), c.res, c.best, d_sizes.as<uint32_t>(),
+                                                          d_off.as<uint32_t>(), O.key.as<unsigned long long>(), O.place.as<unsigned long long>(),
+                                                          O.len.as<uint32_t>(), O.idx.as<uint32_t>());
+            HIPCHK(hipGetLastError());
+        } else if (total) {
             DevBuf d_out;
             ALLOC(d_out, (size_t)total);
             HIPCHK(launch_emit(first, nc, nullptr, nullptr, d_off.as<uint32_t>(), d_out.as<char>()));
@@ -933,6 +1061,10 @@ int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
             HIPCHK(hipMemcpy(&text[0], d_out.p, total, hipMemcpyDeviceToHost));
             body += text;
         }
+    }
+    if (ord) {
+        rc = order_text(ix, O, n, body, ord, st);
+        if (rc) { (void)hipStreamSynchronize(st); return rc; }
     }
     HIPCHK(hipStreamSynchronize(st));
     if (pair_aware) hgx_align_pairs_count(pairs[0], pairs[1], pairs[2]);

@@ -39,9 +39,21 @@ struct hgx_aln_reads {
 // was appended and the host route finishes the call.
 // `gap`: hgx_align_more.gap (0: no gap tier).  `rescue_clip`: hgx_align_more.rescue_clip (> 0, with gap > 0: both tiers, the clip
 // tier with this budget).
+// `ord` (nullptr: hgx_align_more.order = 0, nothing below runs): coordinate order.  The chunks' text stays in HBM and is sorted
+// there; with ord->keep the ordered text -- the index's header in front of it, 64 zeroed bytes behind it -- is left in a pool block
+// (ord->d_text, ord->n_bytes without the 64; the caller owns it) and `body` stays as it was, else the ordered body is appended to
+// `body`.  A body of 4 GB or more cannot be ordered there: it is appended in input order and ord->unordered is set.
+struct hgx_aln_ordered {
+    bool keep = false;
+    void *d_text = nullptr;
+    size_t n_bytes = 0;
+    bool unordered = false;
+};
 int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_align_opts *opts, int gap, int rescue_clip,
-                     std::string &body, int64_t *aligned, int64_t *concordant, int *decline);
+                     std::string &body, int64_t *aligned, int64_t *concordant, int *decline, hgx_aln_ordered *ord = nullptr);
 void hgx_align_device_free(hgx_align_index *ix);
+// coordinate order on the host: `body`'s lines stable-sorted by (index of RNAME among the index's loci, POS - 1)
+void hgx_align_order_body(const hgx_align_index *ix, std::string &body);
 
 // what the states form took in the calling thread's current call (hgx_align_last_states): added to by either route
 void hgx_align_states_count(int64_t reads, int64_t anchors, int64_t cells);

@@ -832,6 +832,13 @@ template <class H> HGX_ALN_HD bool hgx_aln_covers(const H &x, int ix, const H &e
     return x.locus == e.locus && x.strand == e.strand && hgx_aln_before(x, ix, e, ie) && x.end > e.pos0;
 }
 
+// where a record stands in coordinate order (hgx_align_more.order = 1; tests/align_resident_ref.py): the index of its RNAME in the
+// header's @SQ order and POS - 1, from the values hgx_aln_line prints -- a clipped record's pos0 is its first ALIGNED base
+template <class H> HGX_ALN_HD inline int32_t hgx_aln_pos_in_locus(const hgx_aln_view &V, const H &a) { return a.pos0 - V.bb_off[a.locus]; }
+template <class H> HGX_ALN_HD inline uint64_t hgx_aln_coord_key(const hgx_aln_view &V, const H &a) {
+    return ((uint64_t)(uint32_t)a.locus << 32) | (uint32_t)hgx_aln_pos_in_locus(V, a);
+}
+
 // the whole line (with its '\n'); `name` / `qual` as the file has them (qual == nullptr: 'I' x L)
 template <int MAXV, bool CLIP = false, bool GAP = false>
 HGX_ALN_HD void hgx_aln_line(const hgx_aln_view &V, const char *name, int name_len, const char *seq, const char *qual, int L,
@@ -857,7 +864,7 @@ HGX_ALN_HD void hgx_aln_line(const hgx_aln_view &V, const char *name, int name_l
     out.str(name, name_len); out.ch('\t');
     out.num(flag); out.ch('\t');
     out.str(V.pool + V.name_off[a.locus], V.name_len[a.locus]); out.ch('\t');
-    out.num(a.pos0 - lo + 1); out.ch('\t');
+    out.num(a.pos0 - lo + 1); out.ch('\t');                     // (= hgx_aln_pos_in_locus + 1; spelled as before: k_aln_emit's code stays the parent's)
     out.num(nh == 1 ? 60 : 1); out.ch('\t');
     hgx_aln_walk_text<CLIP, GAP>(V, R, a.pos0, a.vl, a.nvar, 0, out, clipL, clipR, gd); out.ch('\t');
     if (rnext == 0) out.ch('*');

@@ -18,6 +18,9 @@
 extern "C" void hgx_set_error(const char *fmt, ...);
 extern "C" const char *hgx_test_switch(const char *name);
 void *hgx_host_alloc(size_t bytes);
+#ifndef HGX_ALIGN_STANDALONE
+#include "hgx_internal.hpp"              // hgx_alignment_from_reads: the hook to the front end's hgx_alignment
+#endif
 
 namespace {
 thread_local int g_route = 0, g_decline = 0;
@@ -569,13 +572,41 @@ void hgx_align_pairs_count(int64_t searched, int64_t placed, int64_t changed) {
     g_pr_changed += changed;
 }
 
+// hgx_align_more.order = 1 on the host: what hgx_write_bam's std::stable_sort by (rid, pos0) does to the stored file, on the lines
+void hgx_align_order_body(const hgx_align_index *ix, std::string &body) {
+    struct Line { uint64_t key; size_t off, len; };
+    std::unordered_map<std::string, uint32_t> rid;
+    for (int g = ix->hv.n_loci - 1; g >= 0; --g) rid[std::string(ix->pool.data() + ix->name_off[g], (size_t)ix->name_len[g])] = (uint32_t)g;
+    std::vector<Line> lines;
+    for (size_t at = 0; at < body.size();) {
+        const char *p = body.data() + at, *e = (const char *)memchr(p, '\n', body.size() - at);
+        const size_t len = e ? (size_t)(e - p) + 1 : body.size() - at;
+        const char *f = p, *end = p + len;
+        for (int k = 0; k < 2 && f < end; ++k) { f = (const char *)memchr(f, '\t', (size_t)(end - f)); f = f ? f + 1 : end; }      // RNAME
+        const char *t = (const char *)memchr(f, '\t', (size_t)(end - f));
+        uint64_t key = ~0ull;                                // (a line without the two fields: behind the records, where it stood)
+        if (t) {
+            const auto it = rid.find(std::string(f, (size_t)(t - f)));
+            const uint64_t pos = strtoull(t + 1, nullptr, 10);
+            if (it != rid.end() && pos > 0) key = ((uint64_t)it->second << 32) | (uint32_t)(pos - 1);
+        }
+        lines.push_back(Line{key, at, len});
+        at += len;
+    }
+    std::stable_sort(lines.begin(), lines.end(), [](const Line &a, const Line &b) { return a.key < b.key; });
+    std::string out;
+    out.reserve(body.size());
+    for (const Line &l : lines) out.append(body, l.off, l.len);
+    body.swap(out);
+}
+
 #ifdef HGX_ALIGN_STANDALONE
 // the stand-alone build (tools/align_host_main.cpp) has no kernels and none of the library around it
 extern "C" void hgx_set_error(const char *fmt, ...) { va_list ap; va_start(ap, fmt); vfprintf(stderr, fmt, ap); va_end(ap); fputc('\n', stderr); }
 extern "C" const char *hgx_test_switch(const char *) { return "host"; }
 void *hgx_host_alloc(size_t bytes) { return malloc(bytes); }
 int hgx_align_device(hgx_align_index *, const hgx_aln_reads &, const hgx_align_opts *, int, int, std::string &, int64_t *, int64_t *,
-                     int *decline) {
+                     int *decline, hgx_aln_ordered *) {
     *decline = HGX_ALN_DECLINE_SWITCH;
     return HGX_OK;
 }
@@ -688,9 +719,12 @@ extern "C" int hgx_align_reads(hgx_align_index *ix, int32_t n_inputs, const char
     return hgx_align_reads_x(ix, n_inputs, paths, texts, text_bytes, opts, nullptr, sam_out, n_bytes_out);
 }
 
-extern "C" int hgx_align_reads_x(hgx_align_index *ix, int32_t n_inputs, const char *const *paths, const char *const *texts,
-                                 const size_t *text_bytes, const hgx_align_opts *opts, const hgx_align_more *more, char **sam_out,
-                                 size_t *n_bytes_out) {
+// hgx_align_reads_x (kept == nullptr: the text to *sam_out) and hgx_align_reads_resident (kept != nullptr: coordinate order
+// whatever `more` says, the ordered text -- header in front -- left in HBM by the kernels' route (kept->d_text) or, where the host
+// route gave the bytes, in *host_text)
+static int align_call(hgx_align_index *ix, int32_t n_inputs, const char *const *paths, const char *const *texts, const size_t *text_bytes,
+                      const hgx_align_opts *opts, const hgx_align_more *more, char **sam_out, size_t *n_bytes_out, hgx_aln_ordered *kept,
+                      std::string *host_text) {
     // (`more` is read up to the fields this build knows and no further than more->bytes: 8 = the first version, `gap` alone)
     if (more && more->bytes < 8) {
         hgx_set_error("invalid argument: hgx_align_reads_x (more.bytes)");
@@ -698,6 +732,11 @@ extern "C" int hgx_align_reads_x(hgx_align_index *ix, int32_t n_inputs, const ch
     }
     const int gap = more ? more->gap : 0;
     const int rescue = more && more->bytes >= 12 ? more->rescue_clip : 0;
+    const int order = kept ? 1 : more && more->bytes >= 16 ? more->order : 0;
+    if (order < 0 || order > 1) {
+        hgx_set_error("invalid argument: hgx_align_reads_x (order)");
+        return HGX_EINVAL;
+    }
     if (opts && (gap < 0 || gap > HGX_ALN_GAP_MAX || (gap && (opts->search || opts->pair || opts->clip)))) {      // (both tiers: rescue_clip)
         hgx_set_error("invalid argument: hgx_align_reads_x (gap)");
         return HGX_EINVAL;
@@ -707,7 +746,7 @@ extern "C" int hgx_align_reads_x(hgx_align_index *ix, int32_t n_inputs, const ch
         hgx_set_error("invalid argument: hgx_align_reads_x (rescue_clip)");
         return HGX_EINVAL;
     }
-    if (!ix || (n_inputs != 1 && n_inputs != 2) || (!paths && !(texts && text_bytes)) || !opts || !sam_out || !n_bytes_out ||
+    if (!ix || (n_inputs != 1 && n_inputs != 2) || (!paths && !(texts && text_bytes)) || !opts || (!kept && (!sam_out || !n_bytes_out)) ||
         opts->max_edits < 0 || opts->route < 0 || opts->route > 2 || opts->search < 0 || opts->search > 2 ||
         opts->pair < 0 || opts->pair > 1 || (opts->pair && opts->search) ||      // (the states form keeps no candidates to pair)
         opts->clip < 0 || opts->clip > HGX_ALN_CLIP_MAX ||
@@ -715,8 +754,10 @@ extern "C" int hgx_align_reads_x(hgx_align_index *ix, int32_t n_inputs, const ch
         hgx_set_error("invalid argument: hgx_align_reads");
         return HGX_EINVAL;
     }
-    *sam_out = nullptr;
-    *n_bytes_out = 0;
+    if (!kept) {
+        *sam_out = nullptr;
+        *n_bytes_out = 0;
+    }
     g_route = 0; g_decline = 0; g_reads = g_aligned = g_conc = 0;
     g_st_reads = g_st_anchors = g_st_cells = 0;
     g_pr_searched = g_pr_placed = g_pr_changed = 0;
@@ -732,8 +773,10 @@ extern "C" int hgx_align_reads_x(hgx_align_index *ix, int32_t n_inputs, const ch
         const char *sw = hgx_test_switch("front");
         if (opts->route == 1 || (opts->route == 0 && sw && !strcmp(sw, "host"))) decline = HGX_ALN_DECLINE_SWITCH;
         else if (opts->route == 0 && !(sw && !strcmp(sw, "device")) && reads.n() < 1000) decline = HGX_ALN_DECLINE_GATE;
+        hgx_aln_ordered ord;
+        ord.keep = kept != nullptr;
         if (!decline && reads.n() > 0) {
-            if ((rc = hgx_align_device(ix, reads, opts, gap, rescue, body, &aligned, &conc, &decline))) return rc;
+            if ((rc = hgx_align_device(ix, reads, opts, gap, rescue, body, &aligned, &conc, &decline, order ? &ord : nullptr))) return rc;
         }
         if (decline) {
             body.clear();
@@ -748,10 +791,16 @@ extern "C" int hgx_align_reads_x(hgx_align_index *ix, int32_t n_inputs, const ch
             if ((rc = route(ix, reads, opts, budgets, body, &aligned, &conc, &gave_up))) return rc;
             if (gave_up) fprintf(stderr, "[hgx_align_reads] a read's search passed the host route's limits (code %d): left unaligned\n", gave_up);
         }
+        if (order && (decline || ord.unordered)) hgx_align_order_body(ix, body);
         g_route = decline ? 0 : 2;
         g_decline = decline;
         g_aligned = aligned;
         g_conc = conc;
+        if (kept) {
+            if (ord.d_text) *kept = ord;
+            else *host_text = ix->header + body;
+            return HGX_OK;
+        }
         const size_t total = ix->header.size() + body.size();
         char *out = (char *)hgx_host_alloc(total + 1);
         if (!out) { hgx_set_error("hgx_align_reads: out of memory"); return HGX_ENOMEM; }
@@ -766,6 +815,33 @@ extern "C" int hgx_align_reads_x(hgx_align_index *ix, int32_t n_inputs, const ch
         return HGX_ENOMEM;
     }
 }
+
+extern "C" int hgx_align_reads_x(hgx_align_index *ix, int32_t n_inputs, const char *const *paths, const char *const *texts,
+                                 const size_t *text_bytes, const hgx_align_opts *opts, const hgx_align_more *more, char **sam_out,
+                                 size_t *n_bytes_out) {
+    return align_call(ix, n_inputs, paths, texts, text_bytes, opts, more, sam_out, n_bytes_out, nullptr, nullptr);
+}
+
+#ifndef HGX_ALIGN_STANDALONE
+extern "C" int hgx_align_reads_resident(hgx_align_index *ix, int32_t n_inputs, const char *const *paths, const char *const *texts,
+                                        const size_t *text_bytes, const hgx_align_opts *opts, const hgx_align_more *more,
+                                        hgx_alignment **out, void *stream) {
+    if (!out) { hgx_set_error("invalid argument: hgx_align_reads_resident"); return HGX_EINVAL; }
+    *out = nullptr;
+    hgx_aln_ordered kept;
+    std::string host_text;
+    const int rc = align_call(ix, n_inputs, paths, texts, text_bytes, opts, more, nullptr, nullptr, &kept, &host_text);
+    if (rc) return rc;
+    std::vector<std::string> refs;
+    std::vector<int32_t> lens;
+    for (int g = 0; g < ix->hv.n_loci; ++g) {
+        refs.emplace_back(ix->pool.data() + ix->name_off[g], (size_t)ix->name_len[g]);
+        lens.push_back(ix->bb_off[g + 1] - ix->bb_off[g]);
+    }
+    return hgx_alignment_from_reads(out, kept.d_text, kept.d_text ? kept.n_bytes : host_text.size(), kept.d_text ? nullptr : host_text.data(),
+                                    ix->header.size(), refs, lens, stream);
+}
+#endif
 
 extern "C" int hgx_align_last(int32_t *route, int64_t *reads, int64_t *aligned, int64_t *pairs_concordant, int32_t *decline_code) {
     if (route) *route = g_route;

@@ -1682,8 +1682,100 @@ struct hgx_alignment {
     size_t raw_bytes = 0, body0 = 0;
     std::vector<std::string> refs;
     long long bytes_up = 0;
-    ~hgx_alignment() { if (d_text) hgx_pool_free(d_text); }
+    // an object made from reads (hgx_align_reads_resident): `path` is empty; the per-path fallback reads a temporary BAM that is
+    // written once, on the first fallback (alignment_path)
+    bool from_reads = false;
+    std::vector<int32_t> ref_lens;
+    std::string h_text;                  // the text where it could not be resident (2^32 - 64 bytes or more)
+    std::mutex mu;                       // over tmp_path: loci fall back from several threads
+    std::string tmp_path;
+    ~hgx_alignment() {
+        if (d_text) hgx_pool_free(d_text);
+        if (!tmp_path.empty()) (void)unlink(tmp_path.c_str());
+    }
 };
+
+// the text of an object made from reads, on the host
+static int alignment_host_text(hgx_alignment *al, std::string &text) {
+    if (!al->resident) { text = al->h_text; return HGX_OK; }
+    text.resize(al->raw_bytes);
+    if (al->raw_bytes) HIPCHK(hipMemcpy(&text[0], al->d_text, al->raw_bytes, hipMemcpyDeviceToHost));
+    return HGX_OK;
+}
+
+static int alignment_write_bam(hgx_alignment *al, const char *path, int32_t n_threads) {
+    std::string text, names;
+    TRY(alignment_host_text(al, text));
+    for (const std::string &r : al->refs) { names += r; names += '\n'; }
+    return hgx_write_bam(path, text.data(), text.size(), names.c_str(), al->ref_lens.data(), (int32_t)al->refs.size(), 1, n_threads);
+}
+
+// the file the per-path call reads for `al`: its own, or for an object made from reads its coordinate-sorted BAM in a temporary file
+static int alignment_path(hgx_alignment *al, std::string &path) {
+    if (!al->from_reads) { path = al->path; return HGX_OK; }
+    std::lock_guard<std::mutex> g(al->mu);
+    if (al->tmp_path.empty()) {
+        const char *dir = getenv("TMPDIR");
+        std::string tmpl = std::string(dir && *dir ? dir : "/tmp") + "/hgx_alignment_XXXXXX.bam";
+        const int fd = mkstemps(&tmpl[0], 4);
+        if (fd < 0) { hgx_set_error("hgx_alignment_parse_dev: cannot create %s", tmpl.c_str()); return HGX_EINVAL; }
+        close(fd);
+        const int rc = alignment_write_bam(al, tmpl.c_str(), 0);
+        if (rc) { (void)unlink(tmpl.c_str()); return rc; }
+        al->tmp_path = tmpl;
+    }
+    path = al->tmp_path;
+    return HGX_OK;
+}
+
+int hgx_alignment_from_reads(hgx_alignment **out, void *d_text, size_t n, const char *h_text, size_t body0, const std::vector<std::string> &refs,
+                             const std::vector<int32_t> &ref_lens, void *stream) {
+    DevBuf b_text;
+    b_text.p = d_text;                   // (adopted: freed here where the call fails)
+    hipStream_t st = (hipStream_t)stream;
+    std::unique_ptr<hgx_alignment> A(new hgx_alignment());
+    HIPCHK(hipGetDevice(&A->dev));
+    A->from_reads = true;
+    A->text = true;
+    A->body0 = body0;
+    A->refs = refs;
+    A->ref_lens = ref_lens;
+    A->raw_bytes = n;
+    if (!b_text.p && n < ((size_t)1 << 32) - 64) {       // the host route gave the bytes: they go up, with the 64 zeroed bytes behind them
+        ALLOC(b_text, n + 64);
+        HIPCHK(hipMemsetAsync((char *)b_text.p + n, 0, 64, st));
+        if (n) HIPCHK(hipMemcpyAsync(b_text.p, h_text, n, hipMemcpyHostToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));
+        A->bytes_up = (long long)n;
+    }
+    if (b_text.p) {
+        A->resident = true;
+        A->d_text = b_text.p;
+        b_text.p = nullptr;
+    } else A->h_text.assign(h_text, n);
+    *out = A.release();
+    return HGX_OK;
+}
+
+extern "C" int hgx_alignment_text(hgx_alignment *al, char **text, size_t *n) {
+    ARGCHK(al && text && n && al->from_reads);
+    *text = nullptr;
+    *n = 0;
+    std::string t;
+    TRY(alignment_host_text(al, t));
+    char *p = (char *)hgx_host_alloc(t.size() + 1);
+    if (!p) { hgx_set_error("hgx_alignment_text: out of memory"); return HGX_ENOMEM; }
+    memcpy(p, t.data(), t.size());
+    p[t.size()] = 0;
+    *text = p;
+    *n = t.size();
+    return HGX_OK;
+}
+
+extern "C" int hgx_alignment_save_bam(hgx_alignment *al, const char *path, int32_t n_threads) {
+    ARGCHK(al && path && al->from_reads);
+    return alignment_write_bam(al, path, n_threads);
+}
 
 extern "C" int hgx_alignment_open(hgx_alignment **out, const char *path, int32_t n_threads, void *stream) {
     ARGCHK(out && path);
@@ -1828,7 +1920,9 @@ extern "C" int hgx_alignment_parse_dev(hgx_dbatch **out, hgx_alignment *al, cons
         }
         hgx_dbatch_destroy(made);
     }
-    return hgx_parse_alignment_file_dev(out, loc, al->path.c_str(), regions, opts, stream);
+    std::string path;
+    TRY(alignment_path(al, path));
+    return hgx_parse_alignment_file_dev(out, loc, path.c_str(), regions, opts, stream);
 }
 
 // ---- many alignment files, many loci: the panel's rectangle (hisatgenotype:613-665 pools genotyping_locus over the samples; inside

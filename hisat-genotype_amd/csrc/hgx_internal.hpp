@@ -291,6 +291,13 @@ inline int64_t hgx_bam_cigar_reflen(const unsigned char *r, uint32_t bs) {
     return tot;
 }
 int hgx_deferred_for_regions(const char *regions, bool text, size_t body0, const std::vector<std::string> &refs, hgx_bam_deferred &d);
+// the hgx_alignment of hgx_align_reads_resident (hgx_align_host.cpp -> hgx_front.hip, where the struct lives): SAM text of n bytes,
+// records from body0 on, reference names and lengths in @SQ order.  d_text != NULL: the text is in HBM already, in a pool block of
+// n + 64 bytes with the last 64 zeroed (hgx_align.hip's ordered text) -- adopted, also where the call fails; else h_text is
+// uploaded.  n >= 2^32 - 64: kept on the host, the object is not resident.
+struct hgx_alignment;
+int hgx_alignment_from_reads(hgx_alignment **out, void *d_text, size_t n, const char *h_text, size_t body0, const std::vector<std::string> &refs,
+                             const std::vector<int32_t> &ref_lens, void *stream);
 
 // ---- BAM index (hgx_bai.cpp; the reader's use of it: hgx_bam.cpp) -------------------------------------------------------------------
 struct hgx_bai_chunk { uint64_t beg, end; };         // virtual offsets: (block's file offset << 16) | offset in its payload

@@ -88,6 +88,31 @@ class Alignment:
         capi.check(capi.lib().hgx_alignment_dims(self.h, C.byref(r), C.byref(t), C.byref(nb), C.byref(up)))
         self.resident, self.is_text, self.stream_bytes, self.bytes_to_device = bool(r.value), bool(t.value), nb.value, up.value
 
+    @classmethod
+    def from_handle(cls, h):
+        """Wrap an hgx_alignment made by the library from reads (hgx_align_reads_resident: AlignIndex.align_resident): it has no
+        file (`path` None); text() and save() are its own."""
+        self = cls.__new__(cls)
+        self.path = None
+        self.h = h
+        r, t, nb, up = C.c_int32(), C.c_int32(), C.c_size_t(), C.c_longlong()
+        capi.check(capi.lib().hgx_alignment_dims(self.h, C.byref(r), C.byref(t), C.byref(nb), C.byref(up)))
+        self.resident, self.is_text, self.stream_bytes, self.bytes_to_device = bool(r.value), bool(t.value), nb.value, up.value
+        return self
+
+    def text(self):
+        """The SAM text (bytes) of an alignment made from reads: header, then the records in coordinate order."""
+        p, n = C.c_void_p(), C.c_size_t(0)
+        capi.check(capi.lib().hgx_alignment_text(self.h, C.byref(p), C.byref(n)))
+        try:
+            return C.string_at(p.value, n.value)
+        finally:
+            capi.lib().hgx_free_text(p)
+
+    def save(self, path, n_threads=0):
+        """The coordinate-sorted BAM that the file route stores (simulate._store_as_the_reference_does), of an alignment made from reads."""
+        capi.check(capi.lib().hgx_alignment_save_bam(self.h, path.encode(), C.c_int32(n_threads)))
+
     def parse_dev(self, locus, regions=None, num_editdist=2, error_correction=True, allow_discordant=False, simulation=False, base_locus=0,
                   n_threads=0, stream=None):
         if regions is not None and not isinstance(regions, (str, bytes)):

@@ -315,6 +315,27 @@ def _store_as_the_reference_does(out_fname, sam_text):
     bamio.write_bam_native(out_fname, body, refs, sort_by_coordinate=True)
 
 
+HGX_ALIGNERS = ("hgx", "hgx.states", "hgx.pairs", "hgx.clip", "hgx.gap", "hgx.rescue")
+
+
+def _hgx_form(aligner):
+    """The keywords of align.AlignIndex.align that an aligner name of the hgx family stands for."""
+    from . import align
+    return dict(search="states" if aligner == "hgx.states" else "ways", pair="aware" if aligner == "hgx.pairs" else "independent",
+                clip=align.NAMED_CLIP if aligner == "hgx.clip" else 0, gap=align.NAMED_GAP if aligner == "hgx.gap" else 0,
+                rescue=align.NAMED_RESCUE if aligner == "hgx.rescue" else None)
+
+
+def align_reads_resident(aligner, read_fname, fastq, truth, var_list, max_edits=2):
+    """align_reads for an aligner of the hgx family on a graph index, without the file: the records in the order the stored BAM
+    would have them, resident in HBM -- an engine.Alignment (align.AlignIndex.align_resident) for typing()'s loci."""
+    from . import align
+    assert aligner in HGX_ALIGNERS
+    Genes, Vars, refGenes = truth
+    return align.cached_index(Genes, Vars, var_list, refGenes).align_resident(list(read_fname), max_edits=max_edits, fastq=fastq,
+                                                                             **_hgx_form(aligner))
+
+
 def align_reads(aligner, simulation, index_name, index_type, base_fname, read_fname, fastq, threads, out_fname, verbose,
                 truth=None, var_list=None, max_edits=2):
     """typing_common.align_reads (common:985-1056).  With the aligner on PATH: the reference's command line, SAM text
@@ -324,17 +345,13 @@ def align_reads(aligner, simulation, index_name, index_type, base_fname, read_fn
     `var_list` order, at most `max_edits` unknown mismatches): its SAM text, stored like the reference stores HISAT2's.
     "hgx.states" is the same aligner with search="states", "hgx.pairs" with pair="aware", "hgx.clip" with clip=32,
     "hgx.gap" with gap=16, "hgx.rescue" with rescue=(16, 32): both tiers, the cheaper rescue per read (align.AlignIndex.align)."""
-    if aligner in ("hgx", "hgx.states", "hgx.pairs", "hgx.clip", "hgx.gap", "hgx.rescue"):
+    if aligner in HGX_ALIGNERS:
         if index_type != "graph" or truth is None or var_list is None:
             raise NotImplementedError("the hgx aligner aligns to the loci's backbones through their known variants (graph) only")
         from . import align
         Genes, Vars, refGenes = truth
         text = align.cached_index(Genes, Vars, var_list, refGenes).align(list(read_fname), max_edits=max_edits, fastq=fastq,
-                                                                       search="states" if aligner == "hgx.states" else "ways",
-                                                                       pair="aware" if aligner == "hgx.pairs" else "independent",
-                                                                       clip=align.NAMED_CLIP if aligner == "hgx.clip" else 0,
-                                                                       gap=align.NAMED_GAP if aligner == "hgx.gap" else 0,
-                                                                       rescue=align.NAMED_RESCUE if aligner == "hgx.rescue" else None)
+                                                                       **_hgx_form(aligner))
         _store_as_the_reference_does(out_fname, text.decode())
         return
     if shutil.which(aligner):

@@ -32,6 +32,10 @@ class _TypingOptions:
     em_fast = False
     loci_side_by_side = True       # several loci of one typing() call: a host thread and stream per locus over ONE read of the file
     loci_together = False          # ... their batches typed by ONE hgx_type_many_loci call instead (measured slower at six loci)
+    # opt-in: reads to align (alignment_fname == "") by an aligner of the hgx family on a graph index reach the loci WITHOUT the
+    # alignment file -- the records stay in HBM in the order the stored BAM would have them (align.AlignIndex.align_resident) and
+    # every locus, a lone one too, runs over them.  No file is written unless keep_alignment asks for it.  False: as before
+    align_resident = False
 
 
 typing_options = _TypingOptions()
@@ -739,7 +743,16 @@ def typing(simulation, full_path_base_fname, locus_list, genotype_genome, partia
                 raise NotImplementedError("index type %r is not on the accelerated path" % (index_type,))
             say("\n\t\t%s %s" % (aligner, index_type))
             remove_alignment_file = False
-            if alignment_fname == "":                     # core:346-367: align the reads first
+            al_reads = None
+            from . import simulate
+            if alignment_fname == "" and typing_options.align_resident and aligner in simulate.HGX_ALIGNERS:
+                # the aligner's records stay in HBM, in the stored file's order (common:1038-1051 without the file)
+                al_reads = simulate.align_reads_resident(aligner, read_fname, fastq, truth=(Genes, Vars, refGenes), var_list=Var_list,
+                                                         max_edits=num_editdist)
+                if keep_alignment:
+                    alignment_fname = "%s_output.bam" % base_fname if simulation else "%s.bam" % core_fid
+                    al_reads.save(alignment_fname)
+            elif alignment_fname == "":                   # core:346-367: align the reads first
                 from . import simulate
                 remove_alignment_file = True
                 alignment_fname = "%s_output.bam" % base_fname if simulation else "%s.bam" % core_fid
@@ -773,7 +786,7 @@ def typing(simulation, full_path_base_fname, locus_list, genotype_genome, partia
                     regions, base_locus = ["%s:%d-%d" % (chr_, left + 1, right + 1), refGenes[gene]], left
                 jobs.append([test_Gene_names, pl, regions, base_locus, prof, None, None])
             t_ = time.perf_counter()
-            al = engine.Alignment(alignment_fname) if len(jobs) > 1 else None
+            al = al_reads if al_reads is not None else engine.Alignment(alignment_fname) if len(jobs) > 1 else None
             t_open = (time.perf_counter() - t_) * 1e3
 
             def run_job(job, stream=None):

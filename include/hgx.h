@@ -932,7 +932,15 @@ int hgx_extract_close(hgx_extract *h);
  * align_last_clip / align_last_gap then both report: clip searched = reads without an end-to-end alignment that have an anchor, gap
  * searched = those of them that the clip tier left unaligned or with cost(C) >= 2; clipped / gapped and bases = the reads WRITTEN
  * with a clip / a gap.  On the kernels' route: the clip pass, k_aln_tier_keep, the gap pass over the reads kept for it,
- * k_aln_tier_choose, k_aln_emit<true, true>; a device limit reached in either pass declines the call with today's codes. */
+ * k_aln_tier_choose, k_aln_emit<true, true>; a device limit reached in either pass declines the call with today's codes.
+ * more.order (read only when bytes >= 16: a call with bytes of 8 or 12 behaves exactly as before): 0 (the default: every byte, every
+ * word of hgx_align_last*, every kernel launched and every byte copied as with bytes = 12) = records in input order; 1 = COORDINATE
+ * order, the order hgx_write_bam(sort_by_coordinate) gives the stored file (the rule in plain Python: tests/align_resident_ref.py):
+ * the header lines stay where they are, the records are stable-sorted by (index of RNAME in the header's @SQ order, POS - 1), ties
+ * keep input order, mate 1 before mate 2.  Valid with every combination the call takes otherwise; any other value is HGX_EINVAL (the
+ * message names the field).  The host route sorts its lines after it has finished; on the kernels' route the chunks' text stays in
+ * HBM, k_aln_rec_keys writes (key, place, length) per read beside k_aln_emit, and after the last chunk one stable radix sort, one
+ * scan of the sorted lengths and k_aln_gather_lines (a wavefront per line) give the ordered text; hgx_align_last* report as with 0. */
 typedef struct hgx_align_opts {
     int32_t max_edits, max_fragment, fastq, route;
     int32_t search;            /* 0 ways (the default), 1 states, 2 states_all */
@@ -944,6 +952,7 @@ typedef struct hgx_align_more {
     int32_t bytes;             /* sizeof(hgx_align_more) of the caller's build */
     int32_t gap;               /* 0 no novel gaps (the default); N: a read without an end-to-end alignment may be written with one novel gap of up to N bases */
     int32_t rescue_clip;       /* (bytes >= 12) 0: as without it; N: with gap > 0, both tiers in one call, the clip tier with a budget of N, the cheaper rescue per read */
+    int32_t order;             /* (bytes >= 16) 0: records in input order (the default); 1: coordinate order, as the stored BAM has them */
 } hgx_align_more;
 typedef struct hgx_align_index hgx_align_index;
 int hgx_align_index_create(hgx_align_index **out, int32_t n_loci, const char *const *names, const char *const *backbones,
@@ -960,6 +969,25 @@ int hgx_align_last_states(int64_t *reads, int64_t *anchors, int64_t *cells);
 int hgx_align_last_pairs(int64_t *searched, int64_t *placed, int64_t *changed);
 int hgx_align_last_clip(int64_t *searched, int64_t *clipped, int64_t *bases);
 int hgx_align_last_gap(int64_t *searched, int64_t *gapped, int64_t *bases);
+/* The aligner's records handed to the front end WITHOUT the file between them.  The reference pipes its aligner through `samtools
+ * view -bS - | samtools sort` into a BAM (typing_common.py:1038-1051) and reads that file back per locus with `samtools view F
+ * ref_allele | sort -k 1,1 -s` (typing_core.py:458-468); what the file contributes to the second pipe is that within one read name
+ * the records come in coordinate order.  align_reads_resident: hgx_align_reads_x with more.order forced to 1 (`more` may be NULL),
+ * the ordered text (header + records) NOT copied back but adopted by an hgx_alignment: resident, SAM text, reference names = the
+ * index's loci in @SQ order, on the current device -- hgx_alignment_parse_dev then runs a locus over it as over a file's bytes.
+ * Where the aligner's host route gave the bytes (below its 1 000-read gate, after a decline) the ordered text is uploaded and the
+ * object is resident all the same; a text of 2^32 - 64 bytes or more is kept on the host and every locus takes the fallback below.
+ * hgx_align_last* report as for hgx_align_reads_x.  Such an object has no file: where hgx_alignment_parse_dev falls back to the
+ * per-path call (the kernels decline a locus, test switch front=host), the object writes its coordinate-sorted BAM ONCE to a
+ * temporary file (under a mutex: loci call side by side), keeps the path for later fallbacks and removes the file at close.
+ * alignment_text: the text of an object made from reads (HGX_EINVAL for one opened from a file); release with hgx_free_text.
+ * alignment_save_bam: the coordinate-sorted BAM the file route stores (typing_common.py:1038-1051; hgx_write_bam over the text,
+ * the index's names and lengths). */
+int hgx_align_reads_resident(hgx_align_index *ix, int32_t n_inputs, const char *const *paths, const char *const *texts,
+                             const size_t *text_bytes, const hgx_align_opts *opts, const hgx_align_more *more, hgx_alignment **out,
+                             void *stream);
+int hgx_alignment_text(hgx_alignment *al, char **text, size_t *n);
+int hgx_alignment_save_bam(hgx_alignment *al, const char *path, int32_t n_threads);
 
 #ifdef __cplusplus
 }
