@@ -166,7 +166,8 @@ __global__ void k_lin_bam_records(const char *__restrict__ raw, const uint64_t *
         if (!bad && t0 == 'A' && t1 == 'S') { as_state = integer ? 1 : 2; asv = v; }
     }
     if (bad) { atomicOr(decline, 1u << HGX_LIN_DECLINE_RECORD); return; }
-    if (as_state != 1) { atomicOr(decline, 1u << HGX_LIN_DECLINE_AS); return; }
+    // (a type-I value above INT32_MAX is no int32 AS: declined, as the text kernel declines the same printed number)
+    if (as_state != 1 || asv > INT32_MAX) { atomicOr(decline, 1u << HGX_LIN_DECLINE_AS); return; }
     keep[i] = 1;
     aid[i] = id;
     as_out[i] = (int32_t)asv;

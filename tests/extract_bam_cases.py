@@ -221,11 +221,25 @@ def _base_cases():
     import random
     rnd = random.Random(5)
     recs = []
-    for n in (0, 1, 2, 63, 64, 65, 4097, 5000):
+    # 150, 250: the workload's read lengths; 1023 .. 1025: k_ext_emit stages 1024 bytes a round and writes 256 bytes a round
+    for n in (0, 1, 2, 63, 64, 65, 150, 250, 1023, 1024, 1025, 4097, 5000):
         seq = "".join(rnd.choice("ACGTN") for _ in range(n)) or "*"
         qual = None if n == 0 else "".join(chr(33 + rnd.randrange(0, 60)) for _ in range(n))
         for k, (f1, f2) in enumerate(((0x43, 0x83), (0x53, 0x93), (0x43, 0x93))):
             recs += pair(b"len%d_%d" % (n, k), 2, 1100, flag1=f1, flag2=f2, seq=seq, qual=qual)
+    # Either side of the first length L at which k_ext_emit stops staging a read in LDS (csrc/hgx_extract.hip: staged = span <=
+    # EXT_SRC_MAX = 4096 and pad + total <= EXT_IMG_MAX = 4608), for a name of 8 bytes and l bases.  a = the source's offset in
+    # its 16-byte granule (0 .. 15) and pad = the destination's in its dword (0 .. 3) depend on where a piece pattern puts the
+    # record, so every length from the least L - 1 to the greatest L is here: L - 1 and L are among them whatever a and pad are.
+    #   BAM, FASTQ:  total = 2 l + 14, span = a + ceil(l / 2) + l < 4096 there; pad + 2 l + 14 > 4608  <=>  L = 2298 - ceil(pad / 2)
+    #                (pad 0: 2298, pad 1 and 2: 2297, pad 3: 2296): 2295 .. 2298
+    #   BAM, FASTA:  total = l + 11, span = a + ceil(l / 2) < 4096 there; pad + l + 11 > 4608  <=>  L = 4598 - pad: 4594 .. 4598
+    #   SAM text, FASTQ (SEQ, a tab, QUAL): span = a + 2 l + 1 > 4096  <=>  L = 2048 - floor(a / 2), a = 0 .. 15: 2040 .. 2048
+    #                (total = 2 l + 14 <= 4110 there)
+    for n in list(range(2040, 2049)) + list(range(2295, 2299)) + list(range(4594, 4599)):
+        seq = "".join(rnd.choice("ACGTN") for _ in range(n))
+        qual = "".join(chr(33 + rnd.randrange(0, 60)) for _ in range(n))
+        recs += pair(b"edge%04d" % n, 2, 1100, flag1=0x43, flag2=0x93, seq=seq, qual=qual)
     recs += pair(b"codes", 2, 1100, flag1=0x53, flag2=0x83, codes=list(range(16)))
     recs += pair(b"codes_odd", 2, 1100, flag1=0x53, flag2=0x93, codes=list(range(16)) + [3])
     for n in (1, 7, 100):
