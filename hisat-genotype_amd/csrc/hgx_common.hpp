@@ -80,6 +80,7 @@ struct hgx_classes {
     uint64_t *d_bits;        // [n_classes][w64]
     int64_t *d_count;        // [n_classes]
     int64_t *d_first_row;    // [n_classes]
+    int64_t n_rows_in = 0;   // rows of the dedup that made the set (0: made otherwise) -- what the slice policy goes by
     uint64_t *d_bitsT;       // lazily built [a_pad][c64]
     // lazily built by the EM (hgx_em.hip): the matrices restricted to the alleles that occur in some class
     int32_t n_act = -1, a1p = 0;                     // active alleles, padded to a multiple of 512
@@ -173,6 +174,29 @@ int hgx_level_classes_grouped_seg(hgx_classes **out, const hgx_index *ix, const 
                                   const uint32_t *pair_seg, void *stream);
 int hgx_dedup_classes_seg(hgx_classes **out, const uint64_t *rows, const uint64_t *row_hash, int64_t n_rows, int32_t a_pad,
                           const uint32_t *row_seg, void *stream);
+
+// ---- slices of the gene side's chip-filling launches (hgx_dedup.hip, hgx_counts.hip) ----------------------------
+// Beside EM #1 a pass (1 024-thread workgroups, 135 KB of LDS) is only placed on a CU that has emptied, and a launch that still has
+// workgroups to hand out refills every freed slot: the pass waits for the END of the launch beside it.  Cut into consecutive
+// launches on the one in-order stream, the chip drains at every cut and the waiting pass of the high-priority stream goes first.
+enum { HGX_SLICE_INSERT = 0, HGX_SLICE_VERIFY = 1, HGX_SLICE_GATHER = 2, HGX_SLICE_COUNTS = 3 };
+enum { HGX_SLICES_NEVER = 0,        // exon-level chain, many-task path
+       HGX_SLICES_IF_FORCED = 1,    // the public entry points: whole launches unless the test switch "gene_slices" says otherwise
+       HGX_SLICES_BESIDE_EM = 2 };  // the one-task gene side while EM #1 runs on another stream: the default policy
+// number of launches for kernel `kernel` of a dedup of n_rows rows (the ONE policy: hgx_dedup.hip)
+int hgx_gene_slices(int kernel, long n_rows, int use);
+// fn(first workgroup, workgroups) for the <= `slices` consecutive non-empty ranges of W workgroups
+template <class F> static inline void hgx_for_slices(long W, int slices, F fn) {
+    const long S = slices < 1 ? 1 : ((long)slices < W ? (long)slices : (W > 0 ? W : 1));
+    for (long k = 0; k < S; ++k) {
+        const long g0 = k * W / S, g1 = (k + 1) * W / S;
+        if (g1 > g0) fn(g0, g1 - g0);
+    }
+}
+// hgx_dedup_classes / hgx_allele_counts_on with the use of slices said by the caller (the C entry points: HGX_SLICES_IF_FORCED)
+int hgx_dedup_classes_sliced(hgx_classes **out, const uint64_t *rows, const uint64_t *row_hash, const int64_t *row_weight,
+                             int64_t n_rows, int32_t a_pad, const uint64_t *and_mask, void *stream, int slice_use);
+int hgx_allele_counts_sliced(const hgx_classes *cc, int64_t *count_host, int32_t *first_host, void *stream, int slice_use);
 
 // fused gene-level form (hgx_device.hip): rows are claimed / verified against their class' representative by the wavefront
 // that computed them; hgx_dedup.hip (hgx_pair_classes_dedup) owns the table and turns it into a class set

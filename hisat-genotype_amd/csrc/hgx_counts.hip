@@ -86,18 +86,21 @@ extern "C" int hgx_first_classes(const hgx_classes *c, const int32_t *alleles_ho
 // stores and a second small kernel adds the <= 64 partials per allele (a global atomic per column and workgroup instead --
 // 1 M atomics on 7 168 hot addresses -- was most of a 101 us launch).  Integers: exact.  Needs every class count < 2^24 and
 // their sum < 2^32 (checked on the device; otherwise the mat-vec form below runs).
+// A launch takes the classes [class0, C) -- all of them, or one slice -- and its workgroups write the partials group0 + blockIdx.y:
+// the reduce kernel adds the counts and takes the minimum of the first classes over the partials of all launches, in any order.
 constexpr int AC_WAVES = 4;
 __global__ __launch_bounds__(64 * AC_WAVES) void k_allele_counts_direct(const uint64_t *__restrict__ bits, int C, int w64,
                                                                          const int64_t *__restrict__ count, int per_wave,
                                                                          unsigned long long *__restrict__ cnt_part,
-                                                                         int *__restrict__ first_part, int A) {
+                                                                         int *__restrict__ first_part, int A, int class0, int group0) {
     __shared__ int s_first[AC_WAVES][32][64];                 // [wave][bit][lane]
     __shared__ uint32_t s_cnt[AC_WAVES][32][64];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int n_half = 2 * w64;
     const int hw = blockIdx.x * 64 + lane;                    // my 32-bit half-word of the allele row
     const bool live = hw < n_half;
-    const int c0 = (blockIdx.y * AC_WAVES + wv) * per_wave, c1 = min(C, c0 + per_wave);
+    const int c0 = min(C, class0 + (blockIdx.y * AC_WAVES + wv) * per_wave), c1 = min(C, c0 + per_wave);
+    const size_t part = (size_t)(group0 + blockIdx.y) * A;
     const uint32_t *rows = (const uint32_t *)bits;
     uint32_t acc[32];
 #pragma unroll
@@ -149,8 +152,8 @@ __global__ __launch_bounds__(64 * AC_WAVES) void k_allele_counts_direct(const ui
 #pragma unroll
             for (int q = 0; q < AC_WAVES; ++q) { t += (unsigned long long)s_cnt[q][b][lane]; f = min(f, s_first[q][b][lane]); }
             const int a = hw * 32 + b;
-            cnt_part[(size_t)blockIdx.y * A + a] = t;
-            first_part[(size_t)blockIdx.y * A + a] = f;
+            cnt_part[part + a] = t;
+            first_part[part + a] = f;
         }
     }
 }
@@ -217,6 +220,9 @@ extern "C" int hgx_allele_counts(const hgx_classes *cc, int64_t *count_host, int
     return hgx_allele_counts_on(cc, count_host, first_host, nullptr);
 }
 extern "C" int hgx_allele_counts_on(const hgx_classes *cc, int64_t *count_host, int32_t *first_host, void *stream) {
+    return hgx_allele_counts_sliced(cc, count_host, first_host, stream, HGX_SLICES_IF_FORCED);
+}
+int hgx_allele_counts_sliced(const hgx_classes *cc, int64_t *count_host, int32_t *first_host, void *stream, int slice_use) {
     ARGCHK(cc && count_host && first_host);
     hipStream_t st = (hipStream_t)stream;
     hgx_classes_order_after(cc, st);
@@ -232,13 +238,28 @@ extern "C" int hgx_allele_counts_on(const hgx_classes *cc, int64_t *count_host, 
         ALLOC(b_cnt, (size_t)A * 8); ALLOC(b_first, (size_t)A * 4); ALLOC(b_big, 16);
         HIPCHK(hipMemsetAsync(b_big.p, 0, 16, st));
         hipLaunchKernelGGL(k_allele_counts_check, dim3(nblk(C, 256 * 16)), dim3(256), 0, st, c->d_count, C, b_big.as<unsigned long long>());
-        // ~1024 wavefronts: 64 half-words each, four consecutive class ranges per workgroup
+        // ~1024 wavefronts: 64 half-words each, four consecutive class ranges per workgroup.  In slices (hgx_gene_slices: beside EM #1)
+        // every launch takes a range of consecutive classes, laid out over the chip by the same rule, and owns the partials
+        // [group0, group0 + its groups): nothing is shared between the launches.
         const int spans = (2 * c->w64 + 63) / 64;
-        const int groups = std::max(1, std::min(256 / std::max(spans, 1), (C + 64 * AC_WAVES - 1) / (64 * AC_WAVES)));
-        const int per_wave = (C + groups * AC_WAVES - 1) / (groups * AC_WAVES);
+        const int wg_classes = 64 * AC_WAVES;
+        auto groups_for = [&](long n_cls) {
+            return (int)std::max(1L, std::min((long)(256 / std::max(spans, 1)), (n_cls + wg_classes - 1) / wg_classes));
+        };
+        const int slices = hgx_gene_slices(HGX_SLICE_COUNTS, (long)c->n_rows_in, slice_use);
+        int groups = 0;
+        hgx_for_slices(nblk(C, wg_classes), slices, [&](long g0, long ng) {
+            groups += groups_for(std::min((long)C, (g0 + ng) * wg_classes) - g0 * wg_classes);
+        });
         ALLOC(b_cp, (size_t)groups * A * 8); ALLOC(b_fp, (size_t)groups * A * 4);
-        hipLaunchKernelGGL(k_allele_counts_direct, dim3(spans, groups), dim3(64 * AC_WAVES), 0, st, c->d_bits, C, c->w64, c->d_count,
-                           per_wave, b_cp.as<unsigned long long>(), b_fp.as<int>(), A);
+        int group0 = 0;
+        hgx_for_slices(nblk(C, wg_classes), slices, [&](long g0, long ng) {
+            const int lo = (int)(g0 * wg_classes), hi = (int)std::min((long)C, (g0 + ng) * wg_classes);
+            const int gs = groups_for(hi - lo), per_wave = (hi - lo + gs * AC_WAVES - 1) / (gs * AC_WAVES);
+            hipLaunchKernelGGL(k_allele_counts_direct, dim3(spans, gs), dim3(64 * AC_WAVES), 0, st, c->d_bits, hi, c->w64, c->d_count,
+                               per_wave, b_cp.as<unsigned long long>(), b_fp.as<int>(), A, lo, group0);
+            group0 += gs;
+        });
         hipLaunchKernelGGL(k_allele_counts_reduce, dim3(nblk(A, 64)), dim3(64), 0, st, b_cp.as<unsigned long long>(), b_fp.as<int>(),
                            groups, A, b_cnt.as<int64_t>(), b_first.as<int>());
         HIPCHK(hipGetLastError());

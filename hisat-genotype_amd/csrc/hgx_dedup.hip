@@ -219,9 +219,10 @@ __device__ __forceinline__ uint64_t shfl_u64(uint64_t v, int l) {
 //      their probes together, then the CASes that empty-looking slots need, then the looks at the first row, then min / add --
 //      so a lane has up to 2 * RPT round trips in flight instead of one chain per slot.
 // Sums are integer adds, first rows a min: the result does not depend on the order of anything.
+// A launch takes the rows [row0, n): the whole input (row0 = 0), or one slice of it (dedup_hash_table).
 template <int BS, int RPT>
 __global__ __launch_bounds__(BS) void k_ht_insert(const uint64_t *__restrict__ hash, const int64_t *__restrict__ weight, long n,
-                                                    unsigned long long *__restrict__ keys, uint32_t *__restrict__ first,
+                                                    long row0, unsigned long long *__restrict__ keys, uint32_t *__restrict__ first,
                                                     unsigned long long *__restrict__ cnt, uint32_t tmask,
                                                     uint32_t *__restrict__ slot_of) {
     constexpr int ROWS = BS * RPT, SLOTS = 2 * ROWS, SPT = SLOTS / BS;
@@ -231,7 +232,7 @@ __global__ __launch_bounds__(BS) void k_ht_insert(const uint64_t *__restrict__ h
                                                  // lane reads only the bucket it has just written)
     const int tid = threadIdx.x, lane = tid & 63;
     for (int s = tid; s < SLOTS; s += BS) { lkey[s] = HGX_EMPTY_KEY; lcnt[s] = 0; lmin[s] = HT_NONE; }
-    const long base = (long)blockIdx.x * ROWS;
+    const long base = row0 + (long)blockIdx.x * ROWS;
     uint64_t key[RPT];
     unsigned long long w[RPT];
 #pragma unroll
@@ -353,14 +354,15 @@ __global__ void k_ht_finalize(const unsigned long long *__restrict__ keys, const
 // row per wave the kernel is a chain of three memory round trips per row and runs at a quarter of the bandwidth.
 __global__ __launch_bounds__(256) void k_verify_ht(const uint64_t *__restrict__ rows, int w64, const uint64_t *__restrict__ mask,
                                                    const uint32_t *__restrict__ slot_of, const uint32_t *__restrict__ first, long n,
-                                                   uint32_t *__restrict__ is_first,
+                                                   long row0, uint32_t *__restrict__ is_first,
                                                    int *__restrict__ bad, uint32_t *__restrict__ bad_rows = nullptr,
                                                    uint32_t *__restrict__ n_bad = nullptr, const uint32_t *__restrict__ seg = nullptr) {
     // seg (many tasks in one dedup): rows of different segments never share a class -- their keys are salted with the segment,
-    // and a row whose slot was founded by another segment's row (a 64-bit key collision) counts as different here
+    // and a row whose slot was founded by another segment's row (a 64-bit key collision) counts as different here.
+    // A launch takes the rows [row0, n): the whole input, or one slice of it.
     constexpr int R = 4;
     const int lane = threadIdx.x & 63;
-    const long r0 = (((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6) * R;
+    const long r0 = row0 + (((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6) * R;
     if (r0 >= n) return;
     uint32_t sl[R], h[R];
 #pragma unroll
@@ -512,7 +514,8 @@ static hgx_classes *new_classes(int32_t a_pad);
 // per-pair rows) a 16-wave workgroup waits for a whole CU's worth of wave slots and the insert takes 3-4x longer.
 static int dedup_hash_table(hgx_classes *cl, const uint64_t *rows, const uint64_t *keys_in, const int64_t *row_weight, long n,
                             int w64, const uint64_t *and_mask, hipStream_t st, bool small_blocks = false,
-                            const uint32_t *seg = nullptr) {
+                            const uint32_t *seg = nullptr, int slice_use = HGX_SLICES_NEVER) {
+    cl->n_rows_in = n;
     long T = 1024;
     while (T < 2 * n) T <<= 1;
     DevBuf b_keys, b_first, b_cnt, b_slot, b_flag, b_rank, b_tmp, b_meta, b_bad, b_salted;
@@ -571,14 +574,23 @@ static int dedup_hash_table(hgx_classes *cl, const uint64_t *rows, const uint64_
     hipLaunchKernelGGL(k_ht_init, dim3(nblk(T, 256)), dim3(256), 0, st, b_keys.as<unsigned long long>(),
                        b_first.as<uint32_t>(), b_cnt.as<unsigned long long>(), T, b_meta.as<uint32_t>(),
                        b_tmp.as<unsigned long long>(), (long)(scan_scratch_bytes(n) / 8));
+    // Insert and exact check go out in slices of consecutive rows where the policy says so (hgx_gene_slices: beside EM #1 only).  The
+    // table's CAS / min / add, the first-row flags and the list of collided rows do not depend on the order of the rows, so the
+    // slices leave what the whole launch leaves; every insert slice is complete before the first check reads a first row.
     if (small_blocks)
-        hipLaunchKernelGGL((k_ht_insert<256, 4>), dim3(nblk(n, 1024)), dim3(256), 0, st, keys_in, row_weight, n, b_keys.as<unsigned long long>(),
+        hipLaunchKernelGGL((k_ht_insert<256, 4>), dim3(nblk(n, 1024)), dim3(256), 0, st, keys_in, row_weight, n, 0L, b_keys.as<unsigned long long>(),
                            b_first.as<uint32_t>(), b_cnt.as<unsigned long long>(), (uint32_t)(T - 1), b_slot.as<uint32_t>());
     else
-        hipLaunchKernelGGL((k_ht_insert<1024, 1>), dim3(nblk(n, 1024)), dim3(1024), 0, st, keys_in, row_weight, n, b_keys.as<unsigned long long>(),
-                           b_first.as<uint32_t>(), b_cnt.as<unsigned long long>(), (uint32_t)(T - 1), b_slot.as<uint32_t>());
-    hipLaunchKernelGGL(k_verify_ht, dim3(nblk((n + 3) / 4, 4)), dim3(256), 0, st, rows, w64, and_mask, b_slot.as<uint32_t>(),
-                       b_first.as<uint32_t>(), n, b_flag.as<uint32_t>(), b_meta.as<int>(), b_bad.as<uint32_t>(), b_meta.as<uint32_t>() + 2, seg);
+        hgx_for_slices(nblk(n, 1024), hgx_gene_slices(HGX_SLICE_INSERT, n, slice_use), [&](long g0, long ng) {
+            hipLaunchKernelGGL((k_ht_insert<1024, 1>), dim3((unsigned)ng), dim3(1024), 0, st, keys_in, row_weight, std::min(n, (g0 + ng) * 1024),
+                               g0 * 1024, b_keys.as<unsigned long long>(), b_first.as<uint32_t>(), b_cnt.as<unsigned long long>(),
+                               (uint32_t)(T - 1), b_slot.as<uint32_t>());
+        });
+    hgx_for_slices(nblk(n, 16), hgx_gene_slices(HGX_SLICE_VERIFY, n, slice_use), [&](long g0, long ng) {      // (16 rows per workgroup)
+        hipLaunchKernelGGL(k_verify_ht, dim3((unsigned)ng), dim3(256), 0, st, rows, w64, and_mask, b_slot.as<uint32_t>(), b_first.as<uint32_t>(),
+                           std::min(n, (g0 + ng) * 16), g0 * 16, b_flag.as<uint32_t>(), b_meta.as<int>(), b_bad.as<uint32_t>(),
+                           b_meta.as<uint32_t>() + 2, seg);
+    });
     { int rc_ = scan_classes(b_flag.as<uint32_t>(), b_rank.as<uint32_t>(), n, b_tmp.p, b_meta.as<uint32_t>() + 1,
                              ScanFin{b_slot.as<uint32_t>(), b_cnt.as<unsigned long long>(), cl->d_first_row, cl->d_count}, st); if (rc_) return rc_; }
     // after collisions (forged keys only) the table is final only after the re-keying rounds: first rows / counts again, per slot
@@ -603,8 +615,12 @@ static int dedup_hash_table(hgx_classes *cl, const uint64_t *rows, const uint64_
     if (one_trip)      // gather per table slot (class id = rank of the slot's first row): needs no host-side class count
         hipLaunchKernelGGL(k_ht_gather_slots, dim3(nblk(T, 4)), dim3(256), 0, st, rows, w64, and_mask, b_keys.as<unsigned long long>(),
                            b_first.as<uint32_t>(), b_rank.as<uint32_t>(), T, cl->d_bits);
-    else
-        hipLaunchKernelGGL(k_ht_gather, dim3(nblk(n_alloc, 4)), dim3(256), 0, st, rows, w64, and_mask, cl->d_first_row, n_alloc, cl->d_bits);
+    else      // (in slices of consecutive classes, four per workgroup, where the policy says so)
+        hgx_for_slices(nblk(n_alloc, 4), hgx_gene_slices(HGX_SLICE_GATHER, n, slice_use), [&](long g0, long ng) {
+            const long c0 = g0 * 4, c1 = std::min((long)n_alloc, (g0 + ng) * 4);
+            hipLaunchKernelGGL(k_ht_gather, dim3((unsigned)ng), dim3(256), 0, st, rows, w64, and_mask, cl->d_first_row + c0, (int)(c1 - c0),
+                               cl->d_bits + (size_t)c0 * w64);
+        });
     HIPCHK(hipGetLastError());
     if (one_trip) {
         { int rc_ = hgx_d2h(meta, b_meta.p, 16, st); if (rc_) return rc_; }
@@ -643,7 +659,8 @@ template <class T, class Destroy> static int fail_clean(int rc, T **out, hipStre
 }
 
 static int dedup_classes_impl(hgx_classes **out, const uint64_t *rows, const uint64_t *row_hash, const int64_t *row_weight,
-                              int64_t n_rows, int32_t a_pad, const uint64_t *and_mask, void *stream, const uint32_t *seg = nullptr) {
+                              int64_t n_rows, int32_t a_pad, const uint64_t *and_mask, void *stream, const uint32_t *seg = nullptr,
+                              int slice_use = HGX_SLICES_NEVER) {
     ARGCHK(out && n_rows >= 0 && a_pad > 0 && a_pad % 512 == 0);
     ARGCHK(n_rows < (1ll << 31));
     hipStream_t st = (hipStream_t)stream;
@@ -660,7 +677,34 @@ static int dedup_classes_impl(hgx_classes **out, const uint64_t *rows, const uin
         hipLaunchKernelGGL(k_hash_rows, dim3(nblk(n, 4)), dim3(256), 0, st, rows, n, w64, and_mask, b_hash.as<uint64_t>());
         keys_in = b_hash.as<uint64_t>();
     }
-    return dedup_hash_table(cl, rows, keys_in, row_weight, n, w64, and_mask, st, false, seg);
+    return dedup_hash_table(cl, rows, keys_in, row_weight, n, w64, and_mask, st, false, seg, slice_use);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The slice policy (declared in hgx_common.hpp).  One number, the slices of the exact check of a dedup of n_rows rows
+// -- 50 000 rows each, ~12 us at HLA-A's row width --, and the other launches by their share of it.  Whole, the four take 56 us
+// (insert), 120 us (check), 18 us (gather) and 52 us (Gene_counts) at 500 k rows; the shares are smaller than those lengths because
+// a launch of the insert or of Gene_counts has a fixed part (a slice of Gene_counts takes 27-32 us however few classes it has: seven
+// of them made the step 0.15 ms SLOWER), and the gather is one slice long as it is (profiles/gene_slices_sweep.txt).
+//   "gene_slices" = N        (tests) N launches of each of the four, wherever the entry points are called; N = 1: whole launches
+//   "gene_slices_verify" = N (measurement) N in place of the default, beside EM #1 only -- the sweep that chose the default;
+//                            "i,v,g,c" = the four counts one by one
+// ------------------------------------------------------------------------------------------------
+constexpr long GENE_SLICE_MIN_ROWS = 131072;       // below, the four launches together are shorter than one stretched pass
+constexpr long GENE_SLICE_ROWS = 50000;            // rows per slice of the exact check (0 = whole launches)
+int hgx_gene_slices(int kernel, long n_rows, int use) {
+    if (use == HGX_SLICES_NEVER) return 1;
+    if (const char *sw = hgx_test_switch("gene_slices")) return std::max(1, atoi(sw));
+    if (use != HGX_SLICES_BESIDE_EM) return 1;
+    long nv = 1;
+    if (const char *sw = hgx_test_switch("gene_slices_verify")) {
+        int each[4];                                 // "i,v,g,c": the four launches' slices one by one (which of them pays)
+        if (sscanf(sw, "%d,%d,%d,%d", &each[0], &each[1], &each[2], &each[3]) == 4) return std::max(1, each[kernel]);
+        nv = std::max(1, atoi(sw));
+    }
+    else if (GENE_SLICE_ROWS > 0 && n_rows >= GENE_SLICE_MIN_ROWS) nv = std::min(32L, (n_rows + GENE_SLICE_ROWS - 1) / GENE_SLICE_ROWS);
+    static const long share[4] = {36, 120, 12, 24};        // of 120: ten slices of the check = 3 of the insert, 1 gather, 2 of Gene_counts
+    return (int)std::max(1L, (nv * share[kernel] + share[HGX_SLICE_VERIFY] / 2) / share[HGX_SLICE_VERIFY]);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -796,7 +840,7 @@ static int group_pairs_impl(hgx_groups **out, const int32_t *pair_off, const uin
     hipLaunchKernelGGL(k_sig_keys, dim3(nblk(std::max<long>(n, 1024), 256)), dim3(256), 0, st, pair_off, refs, n_pairs, (uint32_t)level, b_key.as<uint64_t>(),
                        seg, init);
     hipLaunchKernelGGL((k_ht_insert<256, 4>), dim3(nblk(n, 1024)), dim3(256), 0, st, b_key.as<uint64_t>(), (const int64_t *)nullptr, n,
-                       b_keys.as<unsigned long long>(), b_first.as<uint32_t>(), b_cnt.as<unsigned long long>(), (uint32_t)(T - 1),
+                       0L, b_keys.as<unsigned long long>(), b_first.as<uint32_t>(), b_cnt.as<unsigned long long>(), (uint32_t)(T - 1),
                        b_slot.as<uint32_t>());
     hipLaunchKernelGGL(k_sig_verify, dim3(nblk(n, 256)), dim3(256), 0, st, pair_off, refs, n_pairs, (uint32_t)level,
                        b_slot.as<uint32_t>(), b_first.as<uint32_t>(), b_flag.as<uint32_t>(), b_meta.as<int>(), seg);
@@ -918,9 +962,13 @@ int hgx_dedup_classes_seg(hgx_classes **out, const uint64_t *rows, const uint64_
 }
 extern "C" int hgx_dedup_classes(hgx_classes **out, const uint64_t *rows, const uint64_t *row_hash, const int64_t *row_weight,
                                  int64_t n_rows, int32_t a_pad, const uint64_t *and_mask, void *stream) {
+    return hgx_dedup_classes_sliced(out, rows, row_hash, row_weight, n_rows, a_pad, and_mask, stream, HGX_SLICES_IF_FORCED);
+}
+int hgx_dedup_classes_sliced(hgx_classes **out, const uint64_t *rows, const uint64_t *row_hash, const int64_t *row_weight,
+                             int64_t n_rows, int32_t a_pad, const uint64_t *and_mask, void *stream, int slice_use) {
     if (out) *out = nullptr;
-    return fail_clean(dedup_classes_impl(out, rows, row_hash, row_weight, n_rows, a_pad, and_mask, stream), out, (hipStream_t)stream,
-                      hgx_classes_destroy);
+    return fail_clean(dedup_classes_impl(out, rows, row_hash, row_weight, n_rows, a_pad, and_mask, stream, nullptr, slice_use), out,
+                      (hipStream_t)stream, hgx_classes_destroy);
 }
 
 #ifdef HGX_LAB

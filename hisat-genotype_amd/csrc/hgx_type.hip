@@ -191,15 +191,10 @@ static int ss_class_of(DevStreams &D, hipStream_t s) {
 static int make_gene_stream(hipStream_t *out, int least) {
     // The gene side's chip-filling kernels (k_pair_classes_x2, k_verify_ht) run beside the EM chain of the exon level; a 1 024-thread
     // workgroup of an EM pass is only placed on a CU that has sixteen free wave slots and 135 KB of LDS, so with the gene side free to
-    // take every CU the first EM passes wait for it to drain.  HGX_GENE_CUS=n confines the gene-side stream to n CUs (CU mask).
-    const char *gcu = getenv("HGX_GENE_CUS");
-    const int n_gene_cus = gcu ? atoi(gcu) : 0;
-    if (n_gene_cus > 0 && n_gene_cus < 256) {
-        uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (int b = 0; b < n_gene_cus; ++b) mask[b >> 5] |= 1u << (b & 31);
-        HIPCHK(hipExtStreamCreateWithCUMask(out, 8, mask));
-    } else
-        HIPCHK(hipStreamCreateWithPriority(out, hipStreamNonBlocking, least));
+    // take every CU the first EM passes wait for the launch beside them to end.  The answer is in time, not in space: the launches
+    // behind the scoring go out in slices (hgx_gene_slices); a CU mask on this stream (HGX_GENE_CUS, rounds 5-6) gave the passes
+    // their CUs and took as much from the gene side, and is gone.
+    HIPCHK(hipStreamCreateWithPriority(out, hipStreamNonBlocking, least));
     return HGX_OK;
 }
 // One more set for device `dev`.  The EM chain gets the highest priority, the overlapped side work the lowest.
@@ -318,12 +313,17 @@ bool hgx_ss_forget_stream(void *stream) {
     return false;
 }
 namespace {
+// stream sets of a device that callers hold or are waiting for at the moment.  A counter of its own, not read off DevStreams: g_ss_mu
+// is held for the tens of milliseconds it takes to make and place a new set, and a call that is typing must not wait for that.
+std::atomic<int> g_sets_out[64];
 int acquire_streams(StreamSet &s) {
     int dev = 0;
     HIPCHK(hipGetDevice(&dev));
+    g_sets_out[dev & 63].fetch_add(1, std::memory_order_relaxed);
+    struct Uncount { int dev; bool armed; ~Uncount() { if (armed) g_sets_out[dev & 63].fetch_sub(1, std::memory_order_relaxed); } } uncount{dev, true};
     std::lock_guard<std::mutex> g(g_ss_mu);
     DevStreams &D = g_ss[dev];
-    if (!D.free.empty()) { s = D.free.front(); D.free.erase(D.free.begin()); return HGX_OK; }
+    if (!D.free.empty()) { s = D.free.front(); D.free.erase(D.free.begin()); uncount.armed = false; return HGX_OK; }
     // creating (and placing) a set takes milliseconds: done once, then recycled
     StreamSet made;
     const int rc = make_stream_set(dev, D, made);
@@ -334,16 +334,25 @@ int acquire_streams(StreamSet &s) {
         return rc;
     }
     s = made;
+    uncount.armed = false;
     return HGX_OK;
 }
 void release_streams(const StreamSet &s) {
     if (s.dev < 0) return;
+    g_sets_out[s.dev & 63].fetch_sub(1, std::memory_order_relaxed);
     std::lock_guard<std::mutex> g(g_ss_mu);
     DevStreams &D = g_ss[s.dev];
     // sets go back in the order they were made (the first, best-placed ones in front)
     auto it = D.free.begin();
     while (it != D.free.end() && it->id < s.id) ++it;
     D.free.insert(it, s);
+}
+
+// stream sets of the current device that callers hold at the moment (the asking call's own included)
+int stream_sets_in_use() {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 1;
+    return g_sets_out[dev & 63].load(std::memory_order_relaxed);
 }
 
 struct GateHold {                    // a held gate that is released exactly once
@@ -467,12 +476,16 @@ struct GeneSide {                    // what the gene-level side hands back
     char err[512] = "";
 };
 
-int gene_rank(hgx_classes *gcl, int32_t A, int32_t a_pad, hipStream_t st, GeneSide &g);
+int gene_rank(hgx_classes *gcl, int32_t A, int32_t a_pad, hipStream_t st, GeneSide &g, int slice_use);
 
 // Gene_counts (core:1187-1190) and their print order (core:1650-1651): dict insertion order of Gene_counts = (first pair
 // that counted the allele, Gene_names order), then the reference's stable descending sort on the count.
+// beside_em: EM #1 runs on another stream meanwhile -- the dedup's and the counts' chip-filling launches then go out in slices
+// (hgx_gene_slices), so that a pass of EM #1 waits for the end of a slice, not of a launch.  The scoring launch stays whole: it runs
+// beside the front of the exon-level chain, before the first pass.
 int gene_side(const hgx_index *ix, const hgx_dbatch *db, const uint64_t *compat, uint64_t *gene_bits, uint64_t *gene_hash,
-              bool rows_ready, const hgx_type_opts *opts, hipStream_t st, GeneSide &g) {
+              bool rows_ready, const hgx_type_opts *opts, hipStream_t st, GeneSide &g, bool beside_em) {
+    const int slice_use = beside_em ? HGX_SLICES_BESIDE_EM : HGX_SLICES_IF_FORCED;
     int32_t A = 0, a_pad = 0;
     int rc = hgx_index_dims(ix, &A, &a_pad, nullptr, nullptr);
     if (rc) return rc;
@@ -483,7 +496,7 @@ int gene_side(const hgx_index *ix, const hgx_dbatch *db, const uint64_t *compat,
         // collision falls through to the two-call form
         rc = hgx_pair_classes_dedup_ev(&g.gcl, ix, compat, db->d_pair_off, db->d_pair_ref, db->n_pairs, HGX_LEVEL_GENE, gene_bits, st,
                                        opts->ev_pairs_begin, opts->ev_pairs_end);
-        if (rc == HGX_OK) return gene_rank(g.gcl, A, a_pad, st, g);
+        if (rc == HGX_OK) return gene_rank(g.gcl, A, a_pad, st, g, slice_use);
         if (rc != HGX_ECOLLISION) return rc;
     }
 #endif
@@ -493,16 +506,16 @@ int gene_side(const hgx_index *ix, const hgx_dbatch *db, const uint64_t *compat,
         if (rc) return rc;
         if (opts->ev_pairs_end) HIPCHK(hipEventRecord((hipEvent_t)opts->ev_pairs_end, st));
     }
-    rc = hgx_dedup_classes(&g.gcl, gene_bits, gene_hash, nullptr, db->n_pairs, a_pad, nullptr, st);
+    rc = hgx_dedup_classes_sliced(&g.gcl, gene_bits, gene_hash, nullptr, db->n_pairs, a_pad, nullptr, st, slice_use);
     if (rc) return rc;
-    return gene_rank(g.gcl, A, a_pad, st, g);
+    return gene_rank(g.gcl, A, a_pad, st, g, slice_use);
 }
 
-int gene_rank(hgx_classes *gcl, int32_t A, int32_t a_pad, hipStream_t st, GeneSide &g) {
+int gene_rank(hgx_classes *gcl, int32_t A, int32_t a_pad, hipStream_t st, GeneSide &g, int slice_use) {
     int rc;
     std::vector<int64_t> cnt((size_t)a_pad);
     std::vector<int32_t> first((size_t)a_pad);
-    rc = hgx_allele_counts_on(gcl, cnt.data(), first.data(), st);
+    rc = hgx_allele_counts_sliced(gcl, cnt.data(), first.data(), st, slice_use);
     if (rc) return rc;
     int32_t C = 0;
     hgx_classes_dims(gcl, &C, nullptr);
@@ -784,9 +797,14 @@ int type_impl(hgx_typing *t, const hgx_locus *loc, const hgx_index *ix, const hg
         }
         int dev = 0;
         HIPCHK(hipGetDevice(&dev));
-        worker = std::thread([&, dev] {
+        // Slices only for a call that has the chip to itself.  With other samples or loci in flight (they hold stream sets) a pass
+        // waits for THEIR chip-filling kernels whatever this call does, and the extra launches of the slices get in the way of
+        // the other callers' chains: 2 / 3 samples in flight 1.58 / 1.32 -> 1.68-1.97 / 1.38-1.52 ms per sample, class I 4.05 ->
+        // 4.28-5.08 ms with the slices on everywhere.
+        const bool slices = stream_sets_in_use() <= 1;
+        worker = std::thread([&, dev, slices] {
             if (hipSetDevice(dev) != hipSuccess) { gs.rc = HGX_EHIP; snprintf(gs.err, sizeof(gs.err), "hipSetDevice failed on the gene-side thread"); return; }
-            gs.rc = gene_side(ix, db, compat, b_gbits.as<uint64_t>(), b_ghash.as<uint64_t>(), rows_ready, opts, gene_stream, gs);
+            gs.rc = gene_side(ix, db, compat, b_gbits.as<uint64_t>(), b_ghash.as<uint64_t>(), rows_ready, opts, gene_stream, gs, slices);
             if (gs.rc) snprintf(gs.err, sizeof(gs.err), "%s", hgx_last_error());
         });
         if (groups) {
@@ -797,7 +815,7 @@ int type_impl(hgx_typing *t, const hgx_locus *loc, const hgx_index *ix, const hg
         tq1 = now_s();
         HIPCHK(hipStreamWaitEvent(em_stream, ss.fork, 0));
     } else {
-        gs.rc = gene_side(ix, db, compat, b_gbits.as<uint64_t>(), b_ghash.as<uint64_t>(), rows_ready, opts, stream, gs);
+        gs.rc = gene_side(ix, db, compat, b_gbits.as<uint64_t>(), b_ghash.as<uint64_t>(), rows_ready, opts, stream, gs, false);
         if (gs.rc) return gs.rc;
     }
     auto finish_gene = [&]() -> int {
@@ -957,7 +975,7 @@ extern "C" int hgx_type_classes(hgx_typing **out, const hgx_locus *loc, hgx_clas
     hipStream_t st = (hipStream_t)stream;
     EmFastScope em_mode(em_mode_one(opts->em_fast));
     GeneSide gs;
-    int rc = gene_rank(gene_cl, loc->A, loc->a_pad, st, gs);
+    int rc = gene_rank(gene_cl, loc->A, loc->a_pad, st, gs, HGX_SLICES_IF_FORCED);
     if (!rc) {
         t->counted = gs.counted;
         t->cnt = gs.cnt;
