@@ -73,8 +73,10 @@ class AlignIndex:
 
     @staticmethod
     def _call_args(reads, max_edits, max_fragment, fastq, route, search, pair, clip, gap, rescue, order):
-        """(opts, more, n, paths, texts, sizes, what keeps them alive) of one hgx_align_reads_x / hgx_align_reads_resident call."""
-        assert len(reads) in (1, 2)
+        """(opts, more, n, paths, texts, sizes, what keeps them alive) of one hgx_align_reads_x / hgx_align_reads_resident call;
+        `reads` an engine.Reads: (opts, more, None, None, None, None, reads) of one hgx_align_reads_dev / _dev_resident call."""
+        made = hasattr(reads, "n_reads")
+        assert made or len(reads) in (1, 2)
         opts = AlignOpts(int(max_edits), int(max_fragment), -1 if fastq is None else int(bool(fastq)), ROUTES[route],
                          search if isinstance(search, int) else SEARCHES[search], pair if isinstance(pair, int) else PAIRS[pair], int(clip))
         order = order if isinstance(order, int) else ORDERS[order]
@@ -87,6 +89,8 @@ class AlignIndex:
             more = AlignMore(C.sizeof(AlignMore), int(gap))
         else:
             more = AlignMoreRescue(C.sizeof(AlignMoreRescue), int(rescue[0]), int(rescue[1]))
+        if made:
+            return opts, more, None, None, None, None, reads
         if all(isinstance(r, str) for r in reads):
             paths = (C.c_char_p * len(reads))(*[r.encode() for r in reads])
             return opts, more, C.c_int32(len(reads)), paths, None, None, None
@@ -105,12 +109,16 @@ class AlignIndex:
         opts, more, n, paths, texts, sizes, _keep = self._call_args(reads, max_edits, max_fragment, fastq, route, search, pair, clip, gap,
                                                                     rescue, "coordinate")
         h = C.c_void_p()
-        capi.check(capi.lib().hgx_align_reads_resident(self.h, n, paths, texts, sizes, C.byref(opts), C.byref(more), C.byref(h), stream))
+        if n is None:                            # an engine.Reads: the loading step is the object
+            capi.check(capi.lib().hgx_align_reads_dev_resident(self.h, _keep.h, C.byref(opts), C.byref(more), C.byref(h), stream))
+        else:
+            capi.check(capi.lib().hgx_align_reads_resident(self.h, n, paths, texts, sizes, C.byref(opts), C.byref(more), C.byref(h), stream))
         return engine.Alignment.from_handle(h)
 
     def align(self, reads, max_edits=2, max_fragment=1000, fastq=None, route="auto", search="ways", pair="independent",
               clip=0, gap=0, rescue=None, order="read"):
-        """SAM text (bytes) for `reads` = one or two FASTA / FASTQ[.gz] paths (str) or in-memory texts (bytes).  `search`: "ways"
+        """SAM text (bytes) for `reads` = one or two FASTA / FASTQ[.gz] paths (str) or in-memory texts (bytes), or an engine.Reads
+        made of them beforehand (its table is read where it lies; `fastq` is then not looked at).  `search`: "ways"
         (per anchor, the ways through the known indels), "states" (reads that pass the kernels' anchor slots, stack or step limit
         -- on the host route: every read -- are searched over (read base, backbone position) states instead), "states_all" (every
         read is); an int is passed through as hgx_align_opts.search.  The bytes are the same.  `pair`: "independent" (each mate's
@@ -135,7 +143,10 @@ class AlignIndex:
         opts, more, n_in, paths, texts, sizes, _keep = self._call_args(reads, max_edits, max_fragment, fastq, route, search, pair, clip, gap,
                                                                        rescue, order)
         out_p, n = C.c_void_p(), C.c_size_t(0)
-        rc = capi.lib().hgx_align_reads_x(self.h, n_in, paths, texts, sizes, C.byref(opts), C.byref(more), C.byref(out_p), C.byref(n))
+        if n_in is None:                         # an engine.Reads: the loading step is the object
+            rc = capi.lib().hgx_align_reads_dev(self.h, _keep.h, C.byref(opts), C.byref(more), C.byref(out_p), C.byref(n))
+        else:
+            rc = capi.lib().hgx_align_reads_x(self.h, n_in, paths, texts, sizes, C.byref(opts), C.byref(more), C.byref(out_p), C.byref(n))
         capi.check(rc)
         try:
             return C.string_at(out_p.value, n.value)
@@ -196,6 +207,14 @@ def align_last_gap():
 
 DECLINE_GATE, DECLINE_READ_LEN, DECLINE_ANCHORS, DECLINE_STACK, DECLINE_VARS, DECLINE_STEPS, DECLINE_SWITCH = 1, 2, 3, 4, 5, 6, 7
 DECLINE_WINDOW = 8
+
+# the read table made on the device (engine.Reads): HGX_RD_TILE, HGX_RD_GATE and HGX_RD_DECLINE_* of csrc/hgx_reads.hpp
+READS_TILE = 4096                    # bytes per tile of the newline pass
+READS_GATE = 512 << 10               # bytes of inflated text from which the kernels make the table (the measured break-even, rounded up)
+READS_MAX_BYTES = (1 << 32) - 64     # padded text from which the table declines with SIZE (test switch reads_max_bytes=N: another)
+(READS_DECLINE_GATE, READS_DECLINE_SWITCH, READS_DECLINE_EMPTY_LINE, READS_DECLINE_MARKER, READS_DECLINE_TRUNCATED, READS_DECLINE_QUAL_LEN,
+ READS_DECLINE_LOWER, READS_DECLINE_COUNT, READS_DECLINE_READ_LEN, READS_DECLINE_SIZE) = range(1, 11)
+MAX_READ = 1024                      # HGX_ALN_MAX_READ of csrc/hgx_align_core.hpp
 STATES_MAX_WINDOW, STATES_MARGIN = 8192, 128      # HGX_ALN_STATES_MAX_WINDOW, HGX_ALN_STATES_MARGIN of csrc/hgx_align_states.hpp
 
 _INDEX_CACHE = []          # [(Genes, Vars, Var_list, refGenes, AlignIndex)]: typing() runs once per sample on the same dicts

@@ -35,6 +35,7 @@
 
 #include "hgx_common.hpp"
 #include "hgx_align.hpp"
+#include "hgx_reads.hpp"
 
 namespace {
 typedef hgx_aln_res<HGX_ALN_DEV_VARS> DevRes;
@@ -42,12 +43,7 @@ constexpr int CHUNK = 8192;           // reads per chunk (an even number: mates 
 constexpr long ST_ANCHOR_CAP = (long)CHUNK * HGX_ALN_DEV_ANCHORS;      // anchors of a chunk's marked reads, in total
 constexpr size_t ST_CELL_BUDGET = (size_t)1 << 26;                     // table cells of the tasks in flight (1 GiB)
 
-struct DevReads {
-    const char *text;
-    const int64_t *name_off, *seq_off, *qual_off;
-    const int32_t *name_len, *len;
-    int paired;
-};
+typedef hgx_dev_reads DevReads;          // (hgx_reads.hpp: the read table in HBM, uploaded here or made there by hgx_reads.hip)
 
 // the device buffers of one chunk, made once per call (hgx_align_device) and handed to the tiers
 struct Chunk {
@@ -721,7 +717,7 @@ k_aln_states_pick(int n_marked, const int32_t *marked, const int32_t *t_first, c
 }
 
 // the second tier of one chunk: *decline != 0: the call goes to the host route
-int states_tier(hgx_align_index *ix, const hgx_aln_reads &reads, const DevReads &rd, const hgx_align_opts *opts, long first, int nc,
+int states_tier(hgx_align_index *ix, const int32_t *h_len, const DevReads &rd, const hgx_align_opts *opts, long first, int nc,
                 int n_off_max, const Chunk &c, hipStream_t st, int *decline) {
     const hgx_aln_view &V = ix->dv;
     std::vector<int32_t> mark(nc), marked;
@@ -761,7 +757,7 @@ int states_tier(hgx_align_index *ix, const hgx_aln_reads &reads, const DevReads 
     size_t in_batch = 0, largest = 0;
     int64_t cells = 0;
     for (int m = 0; m < nm; ++m) {
-        const int L = reads.len[first + marked[m]];
+        const int L = h_len[first + marked[m]];
         for (int sg = 0; sg < 2 * V.n_loci; ++sg) {
             const StInfo &t = info[(size_t)m * 2 * V.n_loci + sg];
             if (t.n <= 0) continue;
@@ -920,19 +916,19 @@ void hgx_align_device_free(hgx_align_index *ix) {
     ix->dev_ready = -1;
 }
 
+static int align_chunks(hgx_align_index *ix, const hgx_dev_reads &rd, long n, int max_len, const int32_t *h_len, const hgx_align_opts *opts,
+                        int gap, int rescue_clip, std::string &body, int64_t *aligned, int64_t *concordant, int *decline, hgx_aln_ordered *ord);
+
+// the upload half: the loader's table and text copied up, then the chunks over them
 int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_align_opts *opts, int gap, int rescue_clip, std::string &body,
                      int64_t *aligned, int64_t *concordant, int *decline, hgx_aln_ordered *ord) {
     *decline = 0;
-    const size_t body0 = body.size();
-    const int64_t aligned0 = *aligned, concordant0 = *concordant;
     const long n = (long)reads.n();
     int max_len = 0;
     for (long i = 0; i < n; ++i) max_len = std::max(max_len, (int)reads.len[i]);
     if (max_len > HGX_ALN_DEV_MAX_READ) { *decline = HGX_ALN_DECLINE_READ_LEN; return HGX_OK; }
-    const int n_off_max = hgx_aln_n_offsets(max_len);
     int rc = ensure_device_index(ix);
     if (rc) return rc;
-    hipStream_t st = nullptr;
     DevBuf d_text, d_no, d_so, d_qo, d_nl, d_len;
     ALLOC(d_text, reads.text.size() + 16);
     ALLOC(d_no, n * 8); ALLOC(d_so, n * 8); ALLOC(d_qo, n * 8); ALLOC(d_nl, n * 4); ALLOC(d_len, n * 4);
@@ -944,6 +940,30 @@ int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
     HIPCHK(hipMemcpy(d_len.p, reads.len.data(), n * 4, hipMemcpyHostToDevice));
     const DevReads rd{d_text.as<char>(), d_no.as<int64_t>(), d_so.as<int64_t>(), d_qo.as<int64_t>(), d_nl.as<int32_t>(), d_len.as<int32_t>(),
                       reads.paired};
+    return align_chunks(ix, rd, n, max_len, reads.len.data(), opts, gap, rescue_clip, body, aligned, concordant, decline, ord);
+}
+
+// the body: the chunks of a read table that lies in HBM.  h_len (the reads' lengths on the host) is read by the states tier alone:
+// nullptr with opts->search == 0.
+int hgx_align_device_body(hgx_align_index *ix, const hgx_dev_reads &rd, long n, int max_len, const int32_t *h_len, const hgx_align_opts *opts,
+                          int gap, int rescue_clip, std::string &body, int64_t *aligned, int64_t *concordant, int *decline,
+                          hgx_aln_ordered *ord) {
+    *decline = 0;
+    if (max_len > HGX_ALN_DEV_MAX_READ) { *decline = HGX_ALN_DECLINE_READ_LEN; return HGX_OK; }
+    const int rc = ensure_device_index(ix);
+    if (rc) return rc;
+    return align_chunks(ix, rd, n, max_len, h_len, opts, gap, rescue_clip, body, aligned, concordant, decline, ord);
+}
+
+// the chunks themselves: the index is in HBM and no read is longer than the kernels take (either caller has seen to both)
+static int align_chunks(hgx_align_index *ix, const hgx_dev_reads &rd, long n, int max_len, const int32_t *h_len, const hgx_align_opts *opts,
+                        int gap, int rescue_clip, std::string &body, int64_t *aligned, int64_t *concordant, int *decline, hgx_aln_ordered *ord) {
+    *decline = 0;
+    const size_t body0 = body.size();
+    const int64_t aligned0 = *aligned, concordant0 = *concordant;
+    const int n_off_max = hgx_aln_n_offsets(max_len);
+    int rc = HGX_OK;
+    hipStream_t st = nullptr;
     const int cmax = (int)std::min<long>(n, CHUNK);
     DevBuf d_cnt, d_anch, d_res, d_best, d_nh, d_sizes, d_off, d_flags, d_scan, d_misc, d_mark;
     const int search = opts->search;
@@ -987,7 +1007,7 @@ int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
         return HGX_OK;
     };
     TierCounts tier_counts = {};
-    const bool pair_aware = reads.paired && opts->pair == 1;
+    const bool pair_aware = rd.paired && opts->pair == 1;
     const size_t misc_bytes = pair_aware ? 40 : 16;
     int64_t pairs[3] = {0, 0, 0};
     std::vector<int32_t> flags(cmax);
@@ -1017,7 +1037,7 @@ int hgx_align_device(hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
         HIPCHK(hipMemcpy(misc, d_misc.p, search ? 16 : 4, hipMemcpyDeviceToHost));
         int dec = misc[0];
         if (!dec && search && misc[2] > 0) {
-            rc = states_tier(ix, reads, rd, opts, first, nc, n_off_max, c, st, &dec);
+            rc = states_tier(ix, h_len, rd, opts, first, nc, n_off_max, c, st, &dec);
             if (rc) return rc;
         }
         if (dec) return declined(dec);

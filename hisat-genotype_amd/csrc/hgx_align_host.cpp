@@ -20,6 +20,9 @@ extern "C" const char *hgx_test_switch(const char *name);
 void *hgx_host_alloc(size_t bytes);
 #ifndef HGX_ALIGN_STANDALONE
 #include "hgx_internal.hpp"              // hgx_alignment_from_reads: the hook to the front end's hgx_alignment
+#include "hgx_reads.hpp"                 // hgx_reads: a read table made beforehand (hgx_align_reads_dev)
+#else
+struct hgx_reads;
 #endif
 
 namespace {
@@ -131,17 +134,9 @@ int parse_reads(const std::string &t, int fastq, std::vector<Rec> &recs, std::st
     return HGX_OK;
 }
 
-int load_reads(int n_inputs, const char *const *paths, const char *const *texts, const size_t *text_bytes, int fastq, hgx_aln_reads &out) {
-    std::vector<std::string> text(n_inputs), joined(n_inputs);
-    std::vector<std::vector<Rec>> recs(n_inputs);
-    std::vector<std::vector<char>> fj(n_inputs);
-    for (int i = 0; i < n_inputs; ++i) {
-        int rc;
-        if (paths) rc = slurp(paths[i], text[i]);
-        else rc = inflate_text(texts[i], text_bytes[i], text[i]);
-        if (rc) return rc;
-        if ((rc = parse_reads(text[i], fastq, recs[i], joined[i], fj[i]))) return rc;
-    }
+// the parsed inputs' records interleaved into the call's table: names, upper-case bases and qualities re-packed into out.text
+int table_of(int n_inputs, const std::string *text, const std::vector<std::string> &joined, const std::vector<std::vector<Rec>> &recs,
+             const std::vector<std::vector<char>> &fj, hgx_aln_reads &out) {
     if (n_inputs == 2 && recs[0].size() != recs[1].size()) {
         hgx_set_error("hgx_align_reads: %zu reads in the first file, %zu in the second", recs[0].size(), recs[1].size());
         return HGX_EPARSE;
@@ -167,6 +162,20 @@ int load_reads(int n_inputs, const char *const *paths, const char *const *texts,
             } else out.qual_off.push_back(-1);
         }
     return HGX_OK;
+}
+
+int load_reads(int n_inputs, const char *const *paths, const char *const *texts, const size_t *text_bytes, int fastq, hgx_aln_reads &out) {
+    std::vector<std::string> text(n_inputs), joined(n_inputs);
+    std::vector<std::vector<Rec>> recs(n_inputs);
+    std::vector<std::vector<char>> fj(n_inputs);
+    for (int i = 0; i < n_inputs; ++i) {
+        int rc;
+        if (paths) rc = slurp(paths[i], text[i]);
+        else rc = inflate_text(texts[i], text_bytes[i], text[i]);
+        if (rc) return rc;
+        if ((rc = parse_reads(text[i], fastq, recs[i], joined[i], fj[i]))) return rc;
+    }
+    return table_of(n_inputs, text.data(), joined, recs, fj, out);
 }
 
 // ---- the host route ----------------------------------------------------------------------------------------------------------------
@@ -556,6 +565,21 @@ int host_route(const hgx_align_index *ix, const hgx_aln_reads &reads, const hgx_
 }
 }      // namespace
 
+// the loader in its two halves, for a table made ahead of the call (hgx_reads.hpp)
+int hgx_aln_inflate_input(const char *path, const char *text, size_t n, std::string &out) {
+    return path ? slurp(path, out) : inflate_text(text, n, out);
+}
+int hgx_aln_reads_of_texts(int n_inputs, const std::string *text, int fastq, hgx_aln_reads &out) {
+    std::vector<std::string> joined(n_inputs);
+    std::vector<std::vector<Rec>> recs(n_inputs);
+    std::vector<std::vector<char>> fj(n_inputs);
+    for (int i = 0; i < n_inputs; ++i) {
+        const int rc = parse_reads(text[i], fastq, recs[i], joined[i], fj[i]);
+        if (rc) return rc;
+    }
+    return table_of(n_inputs, text, joined, recs, fj, out);
+}
+
 void hgx_align_states_count(int64_t reads, int64_t anchors, int64_t cells) {
     g_st_reads += reads;
     g_st_anchors += anchors;
@@ -721,10 +745,12 @@ extern "C" int hgx_align_reads(hgx_align_index *ix, int32_t n_inputs, const char
 
 // hgx_align_reads_x (kept == nullptr: the text to *sam_out) and hgx_align_reads_resident (kept != nullptr: coordinate order
 // whatever `more` says, the ordered text -- header in front -- left in HBM by the kernels' route (kept->d_text) or, where the host
-// route gave the bytes, in *host_text)
+// route gave the bytes, in *host_text).  dr != nullptr (hgx_align_reads_dev, hgx_align_reads_dev_resident): the loading step is
+// replaced by a table made beforehand -- in HBM (dr->route == 2: the kernels run over it as it lies; where they decline, text and
+// table are copied down for the host route) or the loader's (dr->host).
 static int align_call(hgx_align_index *ix, int32_t n_inputs, const char *const *paths, const char *const *texts, const size_t *text_bytes,
                       const hgx_align_opts *opts, const hgx_align_more *more, char **sam_out, size_t *n_bytes_out, hgx_aln_ordered *kept,
-                      std::string *host_text) {
+                      std::string *host_text, const hgx_reads *dr = nullptr) {
     // (`more` is read up to the fields this build knows and no further than more->bytes: 8 = the first version, `gap` alone)
     if (more && more->bytes < 8) {
         hgx_set_error("invalid argument: hgx_align_reads_x (more.bytes)");
@@ -746,7 +772,7 @@ static int align_call(hgx_align_index *ix, int32_t n_inputs, const char *const *
         hgx_set_error("invalid argument: hgx_align_reads_x (rescue_clip)");
         return HGX_EINVAL;
     }
-    if (!ix || (n_inputs != 1 && n_inputs != 2) || (!paths && !(texts && text_bytes)) || !opts || (!kept && (!sam_out || !n_bytes_out)) ||
+    if (!ix || (!dr && ((n_inputs != 1 && n_inputs != 2) || (!paths && !(texts && text_bytes)))) || !opts || (!kept && (!sam_out || !n_bytes_out)) ||
         opts->max_edits < 0 || opts->route < 0 || opts->route > 2 || opts->search < 0 || opts->search > 2 ||
         opts->pair < 0 || opts->pair > 1 || (opts->pair && opts->search) ||      // (the states form keeps no candidates to pair)
         opts->clip < 0 || opts->clip > HGX_ALN_CLIP_MAX ||
@@ -763,21 +789,41 @@ static int align_call(hgx_align_index *ix, int32_t n_inputs, const char *const *
     g_pr_searched = g_pr_placed = g_pr_changed = 0;
     memset(g_tr, 0, sizeof g_tr);
     try {
-        hgx_aln_reads reads;
-        int rc = load_reads(n_inputs, paths, texts, text_bytes, opts->fastq, reads);
-        if (rc) return rc;
-        g_reads = (int64_t)reads.n();
+        hgx_aln_reads loaded;
+        int rc = HGX_OK;
+        if (!dr && (rc = load_reads(n_inputs, paths, texts, text_bytes, opts->fastq, loaded))) return rc;
+#ifndef HGX_ALIGN_STANDALONE
+        const bool resident = dr && dr->route == 2;          // the table lies in HBM, `loaded` is empty so far
+        const hgx_aln_reads &reads = dr && !resident ? dr->host : loaded;
+        const size_t n_reads = resident ? (size_t)dr->n : reads.n();
+#else
+        const hgx_aln_reads &reads = loaded;
+        const size_t n_reads = reads.n();
+#endif
+        g_reads = (int64_t)n_reads;
         std::string body;
         int64_t aligned = 0, conc = 0;
         int decline = 0;
         const char *sw = hgx_test_switch("front");
         if (opts->route == 1 || (opts->route == 0 && sw && !strcmp(sw, "host"))) decline = HGX_ALN_DECLINE_SWITCH;
-        else if (opts->route == 0 && !(sw && !strcmp(sw, "device")) && reads.n() < 1000) decline = HGX_ALN_DECLINE_GATE;
+        else if (opts->route == 0 && !(sw && !strcmp(sw, "device")) && n_reads < 1000) decline = HGX_ALN_DECLINE_GATE;
         hgx_aln_ordered ord;
         ord.keep = kept != nullptr;
-        if (!decline && reads.n() > 0) {
+        if (!decline && n_reads > 0) {
+#ifndef HGX_ALIGN_STANDALONE
+            if (resident) {
+                std::vector<int32_t> h_len;                  // (the states tier sizes its tables on the host: 4 bytes per read)
+                if (opts->search && (rc = hgx_reads_len_to_host(dr, h_len))) return rc;
+                rc = hgx_align_device_body(ix, dr->dv, (long)dr->n, dr->max_len, opts->search ? h_len.data() : nullptr, opts, gap, rescue, body,
+                                           &aligned, &conc, &decline, order ? &ord : nullptr);
+                if (rc) return rc;
+            } else
+#endif
             if ((rc = hgx_align_device(ix, reads, opts, gap, rescue, body, &aligned, &conc, &decline, order ? &ord : nullptr))) return rc;
         }
+#ifndef HGX_ALIGN_STANDALONE
+        if (decline && resident && (rc = hgx_reads_to_host(dr, loaded))) return rc;      // (offsets into the text as it lies: no re-pack)
+#endif
         if (decline) {
             body.clear();
             aligned = conc = 0;
@@ -823,6 +869,35 @@ extern "C" int hgx_align_reads_x(hgx_align_index *ix, int32_t n_inputs, const ch
 }
 
 #ifndef HGX_ALIGN_STANDALONE
+// the hgx_alignment over what align_call kept
+static int adopt_kept(hgx_align_index *ix, hgx_aln_ordered &kept, const std::string &host_text, hgx_alignment **out, void *stream) {
+    std::vector<std::string> refs;
+    std::vector<int32_t> lens;
+    for (int g = 0; g < ix->hv.n_loci; ++g) {
+        refs.emplace_back(ix->pool.data() + ix->name_off[g], (size_t)ix->name_len[g]);
+        lens.push_back(ix->bb_off[g + 1] - ix->bb_off[g]);
+    }
+    return hgx_alignment_from_reads(out, kept.d_text, kept.d_text ? kept.n_bytes : host_text.size(), kept.d_text ? nullptr : host_text.data(),
+                                    ix->header.size(), refs, lens, stream);
+}
+
+extern "C" int hgx_align_reads_dev(hgx_align_index *ix, const hgx_reads *reads, const hgx_align_opts *opts, const hgx_align_more *more,
+                                   char **sam_out, size_t *n_bytes_out) {
+    if (!reads) { hgx_set_error("invalid argument: hgx_align_reads_dev"); return HGX_EINVAL; }
+    return align_call(ix, reads->n_inputs, nullptr, nullptr, nullptr, opts, more, sam_out, n_bytes_out, nullptr, nullptr, reads);
+}
+
+extern "C" int hgx_align_reads_dev_resident(hgx_align_index *ix, const hgx_reads *reads, const hgx_align_opts *opts, const hgx_align_more *more,
+                                            hgx_alignment **out, void *stream) {
+    if (!out || !reads) { hgx_set_error("invalid argument: hgx_align_reads_dev_resident"); return HGX_EINVAL; }
+    *out = nullptr;
+    hgx_aln_ordered kept;
+    std::string host_text;
+    const int rc = align_call(ix, reads->n_inputs, nullptr, nullptr, nullptr, opts, more, nullptr, nullptr, &kept, &host_text, reads);
+    if (rc) return rc;
+    return adopt_kept(ix, kept, host_text, out, stream);
+}
+
 extern "C" int hgx_align_reads_resident(hgx_align_index *ix, int32_t n_inputs, const char *const *paths, const char *const *texts,
                                         const size_t *text_bytes, const hgx_align_opts *opts, const hgx_align_more *more,
                                         hgx_alignment **out, void *stream) {
@@ -832,14 +907,7 @@ extern "C" int hgx_align_reads_resident(hgx_align_index *ix, int32_t n_inputs, c
     std::string host_text;
     const int rc = align_call(ix, n_inputs, paths, texts, text_bytes, opts, more, nullptr, nullptr, &kept, &host_text);
     if (rc) return rc;
-    std::vector<std::string> refs;
-    std::vector<int32_t> lens;
-    for (int g = 0; g < ix->hv.n_loci; ++g) {
-        refs.emplace_back(ix->pool.data() + ix->name_off[g], (size_t)ix->name_len[g]);
-        lens.push_back(ix->bb_off[g + 1] - ix->bb_off[g]);
-    }
-    return hgx_alignment_from_reads(out, kept.d_text, kept.d_text ? kept.n_bytes : host_text.size(), kept.d_text ? nullptr : host_text.data(),
-                                    ix->header.size(), refs, lens, stream);
+    return adopt_kept(ix, kept, host_text, out, stream);
 }
 #endif
 

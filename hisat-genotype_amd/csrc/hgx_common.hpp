@@ -296,6 +296,16 @@ __device__ __forceinline__ uint64_t wave_transpose64(uint64_t x) {
     x = stage(dpp_u64<0xB1>(x), 1, 0x5555555555555555ull);                   // quad_perm [1,0,3,2]
     return x;
 }
+// inclusive prefix sum over the 64 lanes through the register file (row_shr 1 / 2 / 4 / 8, row_bcast:15, row_bcast:31)
+__device__ __forceinline__ uint32_t wave_incl_scan_u32_front(uint32_t v) {
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, true);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, true);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, true);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, true);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, true);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, true);
+    return v;
+}
 __device__ __forceinline__ uint64_t finish_hash(uint64_t h, bool nonzero) {
     if (!nonzero) return HGX_EMPTY_KEY;
     return h == HGX_EMPTY_KEY ? HGX_EMPTY_KEY - 1 : h;

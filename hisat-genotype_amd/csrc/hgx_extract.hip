@@ -27,6 +27,7 @@
 #include "hgx_common.hpp"
 #include "hgx_internal.hpp"
 #include "hgx_extract.hpp"
+#include "hgx_reads.hpp"
 #include "hgx_records.hpp"
 #include "hgx_bam_walk.hpp"
 
@@ -453,6 +454,10 @@ static int ext_work_alloc(DevBufs &m, ExtWork &w, long N, hipStream_t st) {
     return HGX_OK;
 }
 
+// keep mode (hgx_extract_keep.hpp holds the bookkeeping): host-route chunks' text becomes host segments in front of what follows
+static void ext_keep_flush(hgx_extract &h) { hgx_keep_flush(h.out, h.segs); }
+static void ext_keep_drop(hgx_extract &h, size_t k) { hgx_keep_drop(h.segs, k, [](void *p) { hgx_pool_free(p); }); }
+
 // Behind either record kernel: groups, hits, sizes and the text of the chunk's N records (d_text: the SAM text, or, BAM, the
 // inflated stream).  *declined != 0: nothing was appended.  keep_last (a BAM chunk that is not the stream's last): the last
 // group may go on in the next chunk and stays out -- *n_proc = its first record = the records this call took, *g_first = the
@@ -544,6 +549,24 @@ static int ext_groups_emit(hgx_extract &h, DevBufs &m, const char *d_text, ExtWo
         hipLaunchKernelGGL(k_ext_emit<BAM>, dim3(2 * H), dim3(64), 0, st, d_text, d_hg, (long)H, d_gbits, fams[k], d_gstart, d_r1, d_r2, R, h.fastq,
                            d_off + (2 * k) * Hp, d_off + (2 * k + 1) * Hp, d_out + part[2 * k], h.paired ? d_out + part[2 * k + 1] : (char *)nullptr);
         HIPCHK(hipGetLastError());
+    }
+    if (h.keep) {                                                        // the parts stay in HBM, each a segment of its family and mate
+        ext_keep_flush(h);
+        for (size_t k = 0; k < F; ++k)
+            for (int mate = 0; mate < (h.paired ? 2 : 1); ++mate) {
+                const size_t n = tot[2 * k + mate];
+                if (!n) continue;
+                hgx_keep_seg sg;
+                sg.n = n;
+                sg.d = hgx_pool_alloc(n);
+                if (!sg.d) { hgx_set_error("device allocation of %zu bytes failed", n); return HGX_ENOMEM; }
+                h.segs[2 * fams[k] + mate].push_back(sg);
+                HIPCHK(hipMemcpyAsync(sg.d, d_out + part[2 * k + mate], n, hipMemcpyDeviceToDevice, st));
+            }
+        HIPCHK(hipStreamSynchronize(st));
+        for (size_t k = 0; k < F; ++k) h.written[fams[k]] += (int64_t)cnt[1 + k];
+        h.n_groups += G;
+        return HGX_OK;
     }
     std::vector<char> host(part[2 * F] + 16);
     HIPCHK(hipMemcpyAsync(host.data(), d_out, part[2 * F], hipMemcpyDeviceToHost, st));
@@ -1110,8 +1133,64 @@ extern "C" int hgx_extract_file(hgx_extract *h, const char *path, void *stream) 
     return rc;
 }
 
+extern "C" int hgx_extract_keep(hgx_extract *h, int32_t keep) {
+    ARGCHK(h);
+    if (h->mode != 0 || h->finished) { hgx_set_error("hgx_extract_keep: the handle has been fed already"); return HGX_EINVAL; }
+    h->keep = keep != 0;
+    h->segs.assign(h->keep ? h->out.size() : 0, std::vector<hgx_keep_seg>());
+    return HGX_OK;
+}
+
+extern "C" int hgx_extract_take_reads(hgx_extract *h, int32_t family, hgx_reads **out) {
+    ARGCHK(h && out && family >= 0 && family < h->n_fam);
+    *out = nullptr;
+    if (!h->keep) { hgx_set_error("hgx_extract_take_reads: the handle does not keep its text (hgx_extract_keep)"); return HGX_EINVAL; }
+    hipStream_t st = nullptr;
+    ext_keep_flush(*h);
+    const int ni = h->paired ? 2 : 1;
+    std::unique_ptr<hgx_reads> r(new hgx_reads);
+    r->n_inputs = ni;
+    hgx_keep_plan plan;
+    int bad = 0;
+    size_t bad_bytes = 0;
+    if (!hgx_keep_layout(h->segs, family, ni, plan, &bad, &bad_bytes)) {
+        hgx_set_error("hgx_extract_take_reads: %zu bytes or more of reads for one family and mate %d (take them more often: below 2 GB)",
+                      bad_bytes, bad + 1);
+        return HGX_EINVAL;
+    }
+    for (int i = 0; i < ni; ++i) { r->in_off[i] = plan.in_off[i]; r->in_bytes[i] = plan.in_bytes[i]; }
+    r->text_bytes = plan.text_bytes;
+    r->d_text = hgx_pool_alloc(plan.text_bytes + 64);        // (the object frees it, however this call ends)
+    if (!r->d_text) { hgx_set_error("device allocation of %zu bytes failed", plan.text_bytes + 64); return HGX_ENOMEM; }
+    char *d = (char *)r->d_text;
+    hgx_keep_copy copy;
+    copy.from_dev = [&](size_t at, const void *dev, size_t n) -> int { HIPCHK(hipMemcpyAsync(d + at, dev, n, hipMemcpyDeviceToDevice, st)); return HGX_OK; };
+    copy.from_host = [&](size_t at, const char *host, size_t n) -> int { HIPCHK(hipMemcpyAsync(d + at, host, n, hipMemcpyHostToDevice, st)); return HGX_OK; };
+    copy.zero = [&](size_t at, size_t n) -> int { HIPCHK(hipMemsetAsync(d + at, 0, n, st)); return HGX_OK; };
+    RCHK(hgx_keep_join(h->segs, family, ni, plan, copy));
+    HIPCHK(hipStreamSynchronize(st));
+    // the table where the text lies; the gate does not apply (nothing is left to upload), front=host still sends it to the loader
+    if (hgx_switch_has("front", "host")) r->decline = HGX_RD_DECLINE_SWITCH;
+    else RCHK(hgx_reads_table_dev(r.get(), h->fastq, st));
+    if (r->decline) {                                        // the text copied down once, the table by the host loader
+        std::vector<std::string> text(ni);
+        for (int i = 0; i < ni; ++i) {
+            text[i].resize(r->in_bytes[i]);
+            if (r->in_bytes[i]) RCHK(hgx_reads_text_to_host(r.get(), r->in_off[i], r->in_bytes[i], &text[i][0]));
+        }
+        hgx_reads_dev_free(r.get());
+        RCHK(hgx_reads_host_table(r.get(), text, h->fastq, r->decline));
+    }
+    // the object is complete: only now are the family's segments given up (a failure above leaves them for another call)
+    for (int i = 0; i < ni; ++i) ext_keep_drop(*h, (size_t)(2 * family + i));
+    hgx_reads_set_last(r.get());
+    *out = r.release();
+    return HGX_OK;
+}
+
 extern "C" int hgx_extract_take(hgx_extract *h, int32_t family, int32_t mate, const char **text, size_t *n_bytes) {
     ARGCHK(h && text && n_bytes && family >= 0 && family < h->n_fam && (mate == 0 || mate == 1));
+    if (h->keep) { hgx_set_error("hgx_extract_take: the handle keeps its text in HBM (hgx_extract_take_reads)"); return HGX_EINVAL; }
     std::string &t = h->taken[2 * family + mate];
     t.clear();
     t.swap(h->out[2 * family + mate]);
@@ -1138,6 +1217,7 @@ extern "C" int hgx_extract_close(hgx_extract *h) {
     if (!h) return HGX_OK;
     ext_free_table(*h);
     ext_bam_drop_dev_carry(*h);
+    for (size_t k = 0; k < h->segs.size(); ++k) ext_keep_drop(*h, k);
     delete h;
     return HGX_OK;
 }

@@ -8,6 +8,7 @@
 
 #include "hgx.h"
 #include "hgx_records.hpp"
+#include "hgx_extract_keep.hpp"
 
 enum {
     HGX_EXT_DECLINE_NONE = 0,
@@ -51,6 +52,11 @@ struct hgx_extract {
     int last_decline = 0;
     std::vector<int64_t> written;                                // pairs (reads) written per family
     std::vector<std::string> out, taken;                         // [n_fam * 2]: text not yet taken / the block handed out last
+    // keep mode (hgx_extract_keep): the text is not collected in `out` but stays, per family and mate, as a list of
+    // segments in chunk order -- a device-route chunk's part in a pool block of its own, a host-route chunk's as its string --
+    // until hgx_extract_take_reads joins them in HBM
+    bool keep = false;
+    hgx_keep_lists segs;                                         // [n_fam * 2] (hgx_extract_keep.hpp)
     // a BAM stream (hgx_extract_feed_bam): deflated bytes in, the records read in their binary form
     int mode = 0;                                                // 0 = nothing fed yet, 1 = text, 2 = BAM
     std::vector<unsigned char> comp;                             // BGZF bytes not yet digested (at most one partial block stays)

@@ -536,16 +536,7 @@ __global__ void __launch_bounds__(256) k_fe_pair_emit(const uint32_t *__restrict
     }
 }
 
-// inclusive prefix sum over the 64 lanes through the register file (row_shr 1 / 2 / 4 / 8, row_bcast:15, row_bcast:31)
-__device__ __forceinline__ uint32_t wave_incl_scan_u32_front(uint32_t v) {
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, true);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, true);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, true);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, true);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, true);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, true);
-    return v;
-}
+// (wave_incl_scan_u32_front, the inclusive prefix sum over the 64 lanes through the register file, is in hgx_common.hpp)
 // ---- prefix scans of the front end (round 5: hand-written; the nine hipcub::DeviceScan call sites -- two launches each -- are gone) ----
 // Up to four 32-bit channels over the same n items in ONE single-pass launch (decoupled look-back, as k_scan_u32 of hgx_dedup.hip):
 // exclusive sums, or an exclusive running maximum; a channel may be a field of the pair protocol's packed 64-bit counts.  Tile state =

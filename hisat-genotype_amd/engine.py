@@ -144,6 +144,88 @@ class Alignment:
             pass
 
 
+class Reads:
+    """The aligner's reads as an object (hgx_reads): the inflated FASTA / FASTQ text uploaded once and the read table
+    made from it by kernels, the offsets pointing into the text as it lies (`route` 2) -- or, where the kernels decline (`decline`:
+    align.READS_DECLINE_*), the table of the aligner's host loader (`route` 0): the same records.  AlignIndex.align(reads) /
+    align_resident(reads) take it in place of the list of paths or texts."""
+
+    @classmethod
+    def from_text(cls, texts_or_paths, fastq=None, stream=None):
+        """One or two FASTA / FASTQ[.gz] paths (str) or in-memory texts (bytes, gzip or plain); `fastq` None: by each input's first byte."""
+        items = list(texts_or_paths)
+        assert len(items) in (1, 2)
+        h = C.c_void_p()
+        fq = C.c_int32(-1 if fastq is None else int(bool(fastq)))
+        if all(isinstance(r, str) for r in items):
+            paths = (C.c_char_p * len(items))(*[r.encode() for r in items])
+            capi.check(capi.lib().hgx_reads_from_text(C.byref(h), C.c_int32(len(items)), paths, None, None, fq, stream))
+        else:
+            bufs = [bytes(r) for r in items]
+            texts = (C.c_char_p * len(bufs))(*bufs)
+            sizes = (C.c_size_t * len(bufs))(*[len(b) for b in bufs])
+            capi.check(capi.lib().hgx_reads_from_text(C.byref(h), C.c_int32(len(bufs)), None, texts, sizes, fq, stream))
+        return cls.from_handle(h)
+
+    @classmethod
+    def from_handle(cls, h):
+        self = cls.__new__(cls)
+        self.h = h
+        ni, route, dec, n, ml, tb = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64(), C.c_int32(), C.c_size_t()
+        capi.check(capi.lib().hgx_reads_dims(self.h, C.byref(ni), C.byref(route), C.byref(dec), C.byref(n), C.byref(ml), C.byref(tb)))
+        self.n_inputs, self.route, self.decline, self.n_reads, self.max_len, self._text_bytes = ni.value, route.value, dec.value, n.value, ml.value, tb.value
+        return self
+
+    def table(self):
+        """(text, name_off, seq_off, qual_off, name_len, len): the bytes the table points into and its five arrays, copied back."""
+        n = max(self.n_reads, 1)
+        text = C.create_string_buffer(max(self._text_bytes, 1))
+        arrs = [np.zeros(n, np.int64) for _ in range(3)] + [np.zeros(n, np.int32) for _ in range(2)]
+        capi.check(capi.lib().hgx_reads_table(self.h, text, *[capi.ptr(a) for a in arrs]))
+        return (text.raw[:self._text_bytes],) + tuple(a[:self.n_reads] for a in arrs)
+
+    def records(self):
+        """[(name, seq, qual | None)] in the aligner's order: read 2k + i = record k of input i."""
+        text, no, so, qo, nl, ln = self.table()
+        return [(text[no[i]:no[i] + nl[i]], text[so[i]:so[i] + ln[i]], text[qo[i]:qo[i] + ln[i]] if qo[i] >= 0 else None)
+                for i in range(self.n_reads)]
+
+    def input_text(self, i):
+        """The inflated text of input `i` (bytes)."""
+        n = C.c_size_t(0)
+        capi.check(capi.lib().hgx_reads_input_text(self.h, C.c_int32(i), None, C.byref(n)))
+        buf = C.create_string_buffer(max(n.value, 1))
+        capi.check(capi.lib().hgx_reads_input_text(self.h, C.c_int32(i), buf, C.byref(n)))
+        return buf.raw[:n.value]
+
+    def save(self, paths):
+        """One gzip file per input whose decompressed bytes are the input's text."""
+        import gzip
+        paths = list(paths)
+        assert len(paths) == self.n_inputs
+        for i, path in enumerate(paths):
+            with gzip.open(path, "wb", compresslevel=1) as f:
+                f.write(self.input_text(i))
+
+    def close(self):
+        if self.h:
+            capi.lib().hgx_reads_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def reads_last():
+    """(route, decline, n_reads, max_len) of the calling thread's last Reads.from_text."""
+    route, dec, n, ml = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int32()
+    capi.check(capi.lib().hgx_reads_last(C.byref(route), C.byref(dec), C.byref(n), C.byref(ml)))
+    return route.value, dec.value, n.value, ml.value
+
+
 class AlignmentSet:
     """The alignment files of MANY samples read ONCE (hgx_alignment_set_open): one BAM per sample, each holding the records of every
     locus (hisatgenotype:613-665 pools the samples; typing_core.py:370, 436-468 loops the loci over each sample's one file).  The

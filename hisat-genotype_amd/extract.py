@@ -45,9 +45,10 @@ def read_locus_table(path, database_list):
 
 
 class Extractor:
-    """One sample's stream: feed() bytes, take() the text per family and mate."""
+    """One sample's stream: feed() bytes, take() the text per family and mate.  keep=True: the text stays where the chunks' routes
+    made it (a device chunk's in HBM) and take_reads(family) hands it to the aligner as an engine.Reads; take() then raises."""
 
-    def __init__(self, regions, families, aligner, paired, simulation, fastq, stream=None):
+    def __init__(self, regions, families, aligner, paired, simulation, fastq, stream=None, keep=False):
         self.families = list(families)
         self.paired = bool(paired)
         fam_ix = {f: i for i, f in enumerate(self.families)}
@@ -62,6 +63,9 @@ class Extractor:
         capi.check(capi.lib().hgx_extract_open(C.byref(self.h), C.c_int32(len(regions)), capi.ptr(fam), C.c_char_p(pool),
                                                C.c_size_t(len(pool)), capi.ptr(left), capi.ptr(right), C.c_int32(len(self.families)),
                                                C.byref(opts)))
+        self.keep = bool(keep)
+        if self.keep:
+            capi.check(capi.lib().hgx_extract_keep(self.h, C.c_int32(1)))
 
     def _raise(self, rc):
         if rc == 0:
@@ -91,6 +95,13 @@ class Extractor:
         p, n = C.c_void_p(), C.c_size_t(0)
         capi.check(capi.lib().hgx_extract_take(self.h, C.c_int32(family), C.c_int32(mate), C.byref(p), C.byref(n)))
         return C.string_at(p.value, n.value) if n.value else b""
+
+    def take_reads(self, family):
+        """The reads of `family` kept since the last call, both mates, as an engine.Reads (hgx_extract_take_reads)."""
+        from . import engine
+        h = C.c_void_p()
+        capi.check(capi.lib().hgx_extract_take_reads(self.h, C.c_int32(family), C.byref(h)))
+        return engine.Reads.from_handle(h)
 
     def stats(self):
         rec, grp, ck_d, ck_h = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
@@ -355,6 +366,49 @@ def extract_reads(base_fname, ix_dir, database_list, read_dir, out_dir, suffix, 
                 last_stats = ex.stats()
                 ex.close()
     return fname_list
+
+
+def extract_reads_resident(base_fname, ix_dir, database_list, alignment_fname, fastq, paired, simulation, aligner, stream=None):
+    """One sample's genome-wide alignment stream -> {database: engine.Reads}, no file in between: the extractor keeps each family's
+    FASTA / FASTQ text in HBM (Extractor(keep=True)) and the aligner's read table is made over it where it lies.
+    alignment_fname: a SAM / BAM path, or an open binary pipe of SAM text read in FEED_BYTES blocks.  database_list is filtered and
+    extended as extract_reads does it.  The objects go to typing_options.reads (one family per typing() call); close() them."""
+    global last_stats
+    regions = read_locus_table("%s/%s.locus" % (ix_dir, base_fname), database_list)
+    ex = Extractor(regions, database_list, aligner, paired, simulation, fastq, stream=stream, keep=True)
+    try:
+        if isinstance(alignment_fname, (str, bytes, os.PathLike)):
+            path = os.fspath(alignment_fname)
+            if is_bam(path):
+                with open(path, "rb") as f:
+                    block = f.read(FEED_BYTES)
+                    while True:
+                        nxt = f.read(FEED_BYTES)
+                        ex.feed_bam(block, last=not nxt)
+                        if not nxt:
+                            break
+                        block = nxt
+            else:
+                ex.feed_file(path)
+        else:
+            while True:
+                block = alignment_fname.read(FEED_BYTES)
+                if not block:
+                    break
+                ex.feed(block)
+            ex.feed(b"", last=True)
+        out = {}
+        try:
+            for f, database in enumerate(database_list):
+                out[database] = ex.take_reads(f)
+        except BaseException:
+            for r in out.values():
+                r.close()
+            raise
+        return out
+    finally:
+        last_stats = ex.stats()
+        ex.close()
 
 
 def synth_stream(n_pairs, regions, seed=1, hit_fraction=0.015, read_len=100, chroms=None):

@@ -326,14 +326,15 @@ def _hgx_form(aligner):
                 rescue=align.NAMED_RESCUE if aligner == "hgx.rescue" else None)
 
 
-def align_reads_resident(aligner, read_fname, fastq, truth, var_list, max_edits=2):
+def align_reads_resident(aligner, read_fname, fastq, truth, var_list, max_edits=2, reads=None):
     """align_reads for an aligner of the hgx family on a graph index, without the file: the records in the order the stored BAM
-    would have them, resident in HBM -- an engine.Alignment (align.AlignIndex.align_resident) for typing()'s loci."""
+    would have them, resident in HBM -- an engine.Alignment (align.AlignIndex.align_resident) for typing()'s loci.  `reads`: an
+    engine.Reads made beforehand, aligned in place of the files of read_fname."""
     from . import align
     assert aligner in HGX_ALIGNERS
     Genes, Vars, refGenes = truth
-    return align.cached_index(Genes, Vars, var_list, refGenes).align_resident(list(read_fname), max_edits=max_edits, fastq=fastq,
-                                                                             **_hgx_form(aligner))
+    return align.cached_index(Genes, Vars, var_list, refGenes).align_resident(list(read_fname) if reads is None else reads, max_edits=max_edits,
+                                                                             fastq=fastq, **_hgx_form(aligner))
 
 
 def align_reads(aligner, simulation, index_name, index_type, base_fname, read_fname, fastq, threads, out_fname, verbose,

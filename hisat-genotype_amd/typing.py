@@ -36,6 +36,9 @@ class _TypingOptions:
     # alignment file -- the records stay in HBM in the order the stored BAM would have them (align.AlignIndex.align_resident) and
     # every locus, a lone one too, runs over them.  No file is written unless keep_alignment asks for it.  False: as before
     align_resident = False
+    # the reads of that chain as an engine.Reads made beforehand (extract.extract_reads_resident, engine.Reads.from_text): taken in
+    # place of loading read_fname, which still names the report.  Looked at only where align_resident applies; None: as before
+    reads = None
 
 
 typing_options = _TypingOptions()
@@ -748,7 +751,7 @@ def typing(simulation, full_path_base_fname, locus_list, genotype_genome, partia
             if alignment_fname == "" and typing_options.align_resident and aligner in simulate.HGX_ALIGNERS:
                 # the aligner's records stay in HBM, in the stored file's order (common:1038-1051 without the file)
                 al_reads = simulate.align_reads_resident(aligner, read_fname, fastq, truth=(Genes, Vars, refGenes), var_list=Var_list,
-                                                         max_edits=num_editdist)
+                                                         max_edits=num_editdist, reads=typing_options.reads)
                 if keep_alignment:
                     alignment_fname = "%s_output.bam" % base_fname if simulation else "%s.bam" % core_fid
                     al_reads.save(alignment_fname)

@@ -844,6 +844,16 @@ int hgx_extract_take(hgx_extract *h, int32_t family, int32_t mate, const char **
 int hgx_extract_stats(const hgx_extract *h, int64_t *records, int64_t *groups, int64_t *written /* [n_families] */, int32_t *route,
                       int32_t *decline, int32_t *error_kind, int64_t *chunks_device, int64_t *chunks_host);
 int hgx_extract_close(hgx_extract *h);
+/* The extractor that KEEPS its text for the aligner.  hgx_extract_keep(h, 1), before the first feed: a chunk of the
+ * device route leaves each (family, mate) part of its text in HBM as a segment instead of copying it to the host, a chunk of the
+ * host route keeps its string as one; the segments stay in chunk order.  hgx_extract_take_reads joins the segments of mate 1 and
+ * mate 2 of `family` in one allocation (device to device, host segments uploaded), makes the read table over it where it lies
+ * (hgx_reads, below; the size gate does not apply: nothing is left to upload) and empties the family's lists; a family without a
+ * read gives an object of 0 reads; 2 GB or more for one family and mate is HGX_EINVAL.  On such a handle hgx_extract_take is
+ * HGX_EINVAL; hgx_extract_stats reports as before.  Without hgx_extract_keep nothing changes. */
+typedef struct hgx_reads hgx_reads;
+int hgx_extract_keep(hgx_extract *h, int32_t keep);
+int hgx_extract_take_reads(hgx_extract *h, int32_t family, hgx_reads **out);
 
 /* ---- the "hgx" aligner: reads of a locus family -> SAM text in the front end's dialect ------------------------------
  * Stands in for typing_common.align_reads (common:985-1056) for reads already known to belong to the loci: at most max_edits
@@ -988,6 +998,42 @@ int hgx_align_reads_resident(hgx_align_index *ix, int32_t n_inputs, const char *
                              void *stream);
 int hgx_alignment_text(hgx_alignment *al, char **text, size_t *n);
 int hgx_alignment_save_bam(hgx_alignment *al, const char *path, int32_t n_threads);
+
+/* ---- the aligner's READ TABLE made where the FASTA / FASTQ text lies ------------------------------------------------
+ * hgx_align_reads loads its inputs on one host thread (gzread, a line walk, a re-pack of every base, six uploads).  An hgx_reads
+ * is that loading step as an object of its own: reads_from_text inflates the inputs on the host as hgx_align_reads does (paths, or
+ * texts that may be gzip-compressed), uploads the inflated text -- input 1, then input 2 at the next multiple of 64 bytes -- and
+ * kernels make the five arrays the aligner reads (name / sequence / quality offsets into the text AS IT LIES, name and read
+ * lengths; read 2k + i = record k of input i).  The rules are the loader's (the plain statement: tests/reads_table_ref.py); the
+ * kernels take the inputs where those rules need no re-pack and DECLINE the rest, in which case the loader makes the table from the
+ * same inflated text and the object holds it on the host -- the same records or the loader's own error.  Decline codes
+ * (HGX_RD_DECLINE_* of csrc/hgx_reads.hpp; the smallest that applies): 1 text below the gate (512 KB of inflated text, the measured break-even rounded up; the test
+ * switch front=device / front=host forces either way), 2 front=host, 3 an empty line anywhere, 4 a record's first line without its
+ * marker (multi-line FASTA included), 5 lines no multiple of 4 / 2, 6 quality and sequence lengths differ, 7 a base in a-z, 8 two
+ * inputs with different record counts, 9 a read longer than 1 024 bases, 10 the texts with their padding reach 4 GB - 64 (test switch reads_max_bytes=N: another limit).  fastq: 1, 0, or -1 = by each
+ * input's first byte, as hgx_align_opts.fastq.
+ * reads_dims: the object's inputs, route (2 = the kernels made the table and it lies in HBM, 0 = the loader's), decline code, reads,
+ * longest read, and the bytes of the text its table points into (what reads_table copies).
+ * reads_table: that text and the five arrays (n_reads entries each) copied to the caller's buffers.
+ * reads_input_text: the inflated text of one input (text == NULL: its size alone) -- what a FASTA / FASTQ file of it holds.
+ * reads_last: route, decline code, reads and longest read of the calling thread's last reads_from_text.
+ * align_reads_dev / align_reads_dev_resident: hgx_align_reads_x / hgx_align_reads_resident with the loading step replaced by the
+ * object (opts.fastq is not read): every option combination, the same bytes, hgx_align_last* as before.  Over a route-2 object the
+ * aligner's kernels read the table where it lies (opts.search != 0 copies the read lengths back, 4 bytes per read); where they
+ * decline, text and table are copied down once and the host route runs over them.  The object is not changed and may be aligned
+ * again. */
+int hgx_reads_from_text(hgx_reads **out, int32_t n_inputs, const char *const *paths, const char *const *texts, const size_t *text_bytes,
+                        int32_t fastq, void *stream);
+int hgx_reads_dims(const hgx_reads *r, int32_t *n_inputs, int32_t *route, int32_t *decline, int64_t *n_reads, int32_t *max_len,
+                   size_t *table_text_bytes);
+int hgx_reads_table(const hgx_reads *r, char *text, int64_t *name_off, int64_t *seq_off, int64_t *qual_off, int32_t *name_len, int32_t *len);
+int hgx_reads_input_text(const hgx_reads *r, int32_t input, char *text, size_t *n_bytes);
+int hgx_reads_last(int32_t *route, int32_t *decline, int64_t *n_reads, int32_t *max_len);
+int hgx_reads_free(hgx_reads *r);
+int hgx_align_reads_dev(hgx_align_index *ix, const hgx_reads *reads, const hgx_align_opts *opts, const hgx_align_more *more, char **sam_out,
+                        size_t *n_bytes_out);
+int hgx_align_reads_dev_resident(hgx_align_index *ix, const hgx_reads *reads, const hgx_align_opts *opts, const hgx_align_more *more,
+                                 hgx_alignment **out, void *stream);
 
 #ifdef __cplusplus
 }
