@@ -8,6 +8,13 @@ end-to-end alignment (tests/align_clip_ref.py); a novel indel only with gap=N, o
 end-to-end alignment (tests/align_gap_ref.py); both of these in one call, the cheaper rescue per read, only with rescue=(G, C)
 (tests/align_rescue_ref.py).  The rules are stated in plain Python in tests/align_ref.py; the kernels
 (csrc/hgx_align.hip) and the host route (csrc/hgx_align_host.cpp) run one shared core (csrc/hgx_align_core.hpp, and csrc/hgx_align_states.hpp for the search over states).
+
+LinearAlignIndex is the same family's aligner on a LINEAR index: the reads against the loci's ALLELE SEQUENCES,
+ungapped, end to end, at most `max_edits` mismatches, up to `k` records per read -- what the linear typing (typing.type_locus_linear)
+groups by read.  It is NOT HISAT2 or Bowtie2 either, and its output is compared with neither: no gaps, clips or splices, mates
+placed independently, RNEXT / PNEXT / TLEN left empty on purpose (the linear branch reads none of them).  The rule is stated in plain
+Python in tests/align_linear_ref.py; the kernels (csrc/hgx_align_linear.hip) and the host route (csrc/hgx_align_linear_host.cpp) run
+one shared core (csrc/hgx_align_linear_core.hpp).
 """
 import ctypes as C
 
@@ -231,4 +238,99 @@ def cached_index(Genes, Vars, Var_list, refGenes):
     ix = AlignIndex(Genes, Vars, Var_list, refGenes)
     _INDEX_CACHE.append((Genes, Vars, Var_list, refGenes, ix))
     del _INDEX_CACHE[:-4]
+    return ix
+
+
+# ---- the linear index -----------------------------------------------------------------------------------------------
+LINEAR_MAX_EDITS, LINEAR_MAX_K = 4, 1024         # HGX_ALNL_MAX_EDITS, HGX_ALNL_MAX_K of csrc/hgx_align_linear_core.hpp
+LINEAR_DEV_MAX_READ = 256                        # HGX_ALNL_DEV_MAX_READ: a longer read declines the kernels' route
+(LINEAR_DECLINE_GATE, LINEAR_DECLINE_READ_LEN, LINEAR_DECLINE_BUDGET, LINEAR_DECLINE_LINE) = 1, 2, 3, 4      # HGX_ALNL_DECLINE_*
+LINEAR_DECLINE_SWITCH = 7
+LINEAR_GATE = 16384                              # HGX_ALNL_GATE: reads x alleles from which route="auto" takes the kernels
+
+
+class AlignLinearOpts(C.Structure):
+    """hgx_align_linear_opts (include/hgx.h); `bytes` = sizeof."""
+    _fields_ = [("bytes", C.c_int32), ("max_edits", C.c_int32), ("k", C.c_int32), ("fastq", C.c_int32), ("route", C.c_int32)]
+
+
+def linear_alleles(Genes, refGenes):
+    """[(name, sequence)] in index order: every gene of `Genes` in dict order, its entries in dict order except the backbone
+    refGenes[gene] (the linear typing skips records whose RNAME contains BACKBONE: indexing it would only spend k slots)."""
+    return [(name, seq) for g in Genes for name, seq in Genes[g].items() if name != refGenes[g]]
+
+
+class LinearAlignIndex:
+    """The allele sequences of `Genes` (linear_alleles order) with their seed table, ready for align()."""
+
+    def __init__(self, Genes, refGenes):
+        alleles = linear_alleles(Genes, refGenes)
+        self.names = [n for n, _ in alleles]
+        names = [n.encode() for n, _ in alleles]
+        seqs = [s.encode() for _, s in alleles]
+        self.h = C.c_void_p()
+        capi.check(capi.lib().hgx_align_linear_index_create(C.byref(self.h), C.c_int32(len(names)), (C.c_char_p * max(len(names), 1))(*names),
+                                                            (C.c_char_p * max(len(seqs), 1))(*seqs)))
+
+    def align(self, reads, max_edits=2, k=10, fastq=None, route="auto"):
+        """SAM text (bytes) for `reads` = one or two FASTA / FASTQ[.gz] paths (str) or in-memory texts (bytes), or an engine.Reads made
+        of them beforehand (`fastq` is then not looked at): @HD, an @SQ per allele, and per read up to `k` records (k = 10 is the
+        reference's `-k 10`) of its hits with at most `max_edits` (0 .. 4) mismatches, ordered by (NM, allele, position, strand).
+        `route`: "auto" (the kernels from reads x alleles >= LINEAR_GATE, the measured break-even; the host route below), "host",
+        "device" (the kernels; they decline to the host route with a code of LINEAR_DECLINE_*: align_linear_last()).  The bytes are
+        the same."""
+        made = hasattr(reads, "n_reads")
+        opts = AlignLinearOpts(C.sizeof(AlignLinearOpts), int(max_edits), int(k), -1 if fastq is None else int(bool(fastq)), ROUTES[route])
+        out_p, n = C.c_void_p(), C.c_size_t(0)
+        if made:
+            rc = capi.lib().hgx_align_linear_reads_dev(self.h, reads.h, C.byref(opts), C.byref(out_p), C.byref(n))
+        else:
+            assert len(reads) in (1, 2)
+            if all(isinstance(r, str) for r in reads):
+                paths = (C.c_char_p * len(reads))(*[r.encode() for r in reads])
+                rc = capi.lib().hgx_align_linear_reads(self.h, C.c_int32(len(reads)), paths, None, None, C.byref(opts), C.byref(out_p), C.byref(n))
+            else:
+                bufs = [bytes(r) for r in reads]
+                texts = (C.c_char_p * len(bufs))(*bufs)
+                sizes = (C.c_size_t * len(bufs))(*[len(b) for b in bufs])
+                rc = capi.lib().hgx_align_linear_reads(self.h, C.c_int32(len(bufs)), None, texts, sizes, C.byref(opts), C.byref(out_p), C.byref(n))
+        capi.check(rc)
+        try:
+            return C.string_at(out_p.value, n.value)
+        finally:
+            capi.lib().hgx_free_text(out_p)
+
+    def close(self):
+        if self.h:
+            capi.lib().hgx_align_linear_index_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def align_linear_last():
+    """dict(route, reads, aligned, records, candidates, decline) of the calling thread's last LinearAlignIndex.align(): route 2 = the
+    kernels, 0 = the host route (decline says why); reads given, reads with a record, records written, seed-table entries looked at."""
+    route, dec = C.c_int32(0), C.c_int32(0)
+    reads, aligned, records, cand = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    capi.check(capi.lib().hgx_align_linear_last(C.byref(route), C.byref(reads), C.byref(aligned), C.byref(records), C.byref(cand), C.byref(dec)))
+    return dict(route=route.value, reads=reads.value, aligned=aligned.value, records=records.value, candidates=cand.value, decline=dec.value)
+
+
+_LINEAR_INDEX_CACHE = []   # [(Genes, refGenes, LinearAlignIndex)]
+
+
+def cached_linear_index(Genes, refGenes):
+    """The linear index of these dicts, found again by the IDENTITY of the two dict objects (as cached_index: dicts edited in place
+    return the index of their old content; callers that edit their dicts build a LinearAlignIndex themselves)."""
+    for g, rg, ix in _LINEAR_INDEX_CACHE:
+        if g is Genes and rg is refGenes:
+            return ix
+    ix = LinearAlignIndex(Genes, refGenes)
+    _LINEAR_INDEX_CACHE.append((Genes, refGenes, ix))
+    del _LINEAR_INDEX_CACHE[:-4]
     return ix

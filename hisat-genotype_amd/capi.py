@@ -88,6 +88,8 @@ SYMBOLS = [
     "hgx_align_reads_resident", "hgx_alignment_text", "hgx_alignment_save_bam",
     "hgx_reads_from_text", "hgx_reads_dims", "hgx_reads_table", "hgx_reads_input_text", "hgx_reads_last", "hgx_reads_free",
     "hgx_align_reads_dev", "hgx_align_reads_dev_resident", "hgx_extract_keep", "hgx_extract_take_reads",
+    "hgx_align_linear_index_create", "hgx_align_linear_index_free", "hgx_align_linear_reads", "hgx_align_linear_reads_dev",
+    "hgx_align_linear_last",
 ]
 
 _lib = None

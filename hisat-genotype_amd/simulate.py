@@ -345,10 +345,30 @@ def align_reads(aligner, simulation, index_name, index_type, base_fname, read_fn
     out; real reads cannot be aligned here.  aligner "hgx" (align.py; simulated or real reads of the loci in `truth`, variants in
     `var_list` order, at most `max_edits` unknown mismatches): its SAM text, stored like the reference stores HISAT2's.
     "hgx.states" is the same aligner with search="states", "hgx.pairs" with pair="aware", "hgx.clip" with clip=32,
-    "hgx.gap" with gap=16, "hgx.rescue" with rescue=(16, 32): both tiers, the cheaper rescue per read (align.AlignIndex.align)."""
+    "hgx.gap" with gap=16, "hgx.rescue" with rescue=(16, 32): both tiers, the cheaper rescue per read (align.AlignIndex.align).
+    index_type "linear" with the plain name "hgx" (real reads only): the reads against the allele sequences of `truth`'s Genes
+    (align.LinearAlignIndex: ungapped, at most `max_edits` mismatches, k = 10), stored the same way; the other names of the family
+    raise, since their options need the variant graph."""
+    if aligner in HGX_ALIGNERS and index_type == "linear":
+        # the reads against the loci's allele sequences (align.LinearAlignIndex, DESIGN.md 5.15): `-k 10` of common:1011-1023
+        if aligner != "hgx":
+            raise NotImplementedError("%s on a linear index: the states search, pair-aware placement and the clip / gap tiers walk the "
+                                      "backbone through its known variants -- a linear index has neither; only \"hgx\" aligns to it"
+                                      % aligner)
+        if simulation:
+            raise NotImplementedError("the hgx aligner on a linear index in simulation mode: the report's simulation form of the "
+                                      "linear branch is not built")
+        if truth is None:
+            raise NotImplementedError("the hgx aligner needs the loci's sequences (truth=(Genes, Vars, refGenes))")
+        from . import align
+        Genes, _, refGenes = truth
+        text = align.cached_linear_index(Genes, refGenes).align(list(read_fname), max_edits=max_edits, k=10, fastq=fastq)
+        _store_as_the_reference_does(out_fname, text.decode())
+        return
     if aligner in HGX_ALIGNERS:
         if index_type != "graph" or truth is None or var_list is None:
-            raise NotImplementedError("the hgx aligner aligns to the loci's backbones through their known variants (graph) only")
+            raise NotImplementedError("the hgx aligner aligns to the loci's backbones through their known variants (graph) or to their "
+                                      "allele sequences (linear)")
         from . import align
         Genes, Vars, refGenes = truth
         text = align.cached_index(Genes, Vars, var_list, refGenes).align(list(read_fname), max_edits=max_edits, fastq=fastq,

@@ -39,6 +39,13 @@ class _TypingOptions:
     # the reads of that chain as an engine.Reads made beforehand (extract.extract_reads_resident, engine.Reads.from_text): taken in
     # place of loading read_fname, which still names the report.  Looked at only where align_resident applies; None: as before
     reads = None
+    # opt-in, and a DEPARTURE from the reference: reads to align (alignment_fname == "") by ["hgx", "linear"] are typed in READ
+    # ORDER, straight from the aligner's text in memory (type_locus_linear(pl, sam_text)); no file is written unless keep_alignment.
+    # The reference stores its aligner's output sorted by coordinate and reads that file in file order: a read's records are then
+    # scattered across thousands of references and almost every group of the linear loop is ONE record.  In read order a group is
+    # the whole read, and its class is the set of alleles that reach the read's best AS.  The two forms give different reports by
+    # design.  False (the default): the reference's -- the stored, coordinate-sorted file typed in file order
+    linear_read_order = False
 
 
 typing_options = _TypingOptions()
@@ -713,12 +720,36 @@ def typing(simulation, full_path_base_fname, locus_list, genotype_genome, partia
         say("# HISAT-genotype hot path: hgx %s (MI355X)" % __import__("hisatgenotype_amd").__version__)
         say("# Database - %s" % dbversion)
         say("# COMMAND:\n%s" % " ".join(sys.argv))
-        linear_inputs = {}                                 # region list -> LinearInput (the linear sections' one read of the file)
+        linear_inputs = {}                                 # (file, region list) -> LinearInput (the linear sections' one read of the file)
+        given_alignment_fname = alignment_fname            # (a graph section that aligns the reads itself renames alignment_fname)
         for aligner, index_type in aligners:
             if index_type == "linear":
-                if simulation or alignment_fname == "":
-                    raise NotImplementedError("a linear index without an alignment file (simulation mode, or reads to align) "
-                                              "needs an aligner run: outside the accelerated path")
+                from . import simulate
+                linear_fname, linear_text, remove_linear_file = given_alignment_fname, None, False
+                if simulation:
+                    raise NotImplementedError("a linear index in simulation mode needs an aligner run and the report's simulation "
+                                              "form of the linear branch: outside the accelerated path")
+                if given_alignment_fname == "":
+                    if aligner != "hgx":
+                        raise NotImplementedError("a linear index without an alignment file (reads to align) needs an aligner run: "
+                                                  "only [\"hgx\", \"linear\"] aligns here (%s does not)" % aligner)
+                    if typing_options.align_resident:
+                        raise NotImplementedError("typing_options.align_resident with a linear index: the aligner's records handed to "
+                                                  "the linear typing inside HBM, without the text, is not built")
+                    # core:346-367 with the hgx aligner on the allele sequences (align.LinearAlignIndex)
+                    linear_fname = "%s.linear.bam" % core_fid      # (a graph section of the same call stores <id>.bam)
+                    if typing_options.linear_read_order:
+                        from . import align
+                        text = align.cached_linear_index(Genes, refGenes).align(list(read_fname), max_edits=num_editdist, k=10, fastq=fastq)
+                        if keep_alignment:
+                            simulate._store_as_the_reference_does(linear_fname, text.decode())
+                        # the record stream `samtools view` prints: no header lines
+                        linear_text = b"".join(l + b"\n" for l in text.split(b"\n") if l and not l.startswith(b"@"))
+                    else:
+                        remove_linear_file = not keep_alignment
+                        simulate.align_reads(aligner, simulation, full_path_base_fname + "." + index_type, index_type, base_fname,
+                                             read_fname, fastq, threads, linear_fname, verbose, truth=(Genes, Vars, refGenes),
+                                             var_list=Var_list, max_edits=num_editdist)
                 say("\n\t\t%s %s" % (aligner, index_type))
                 # core:370 + 1597-1677: every locus of the list over the same alignment file, in file order.  The file is read
                 # once for all loci and aligner sections (LinearInput); in genotype-genome mode once per distinct locus region
@@ -730,17 +761,29 @@ def typing(simulation, full_path_base_fname, locus_list, genotype_genome, partia
                     if genotype_genome != "":
                         _, chr_, left, right = refGene_loci[gene][:4]
                         regions = ["%s:%d-%d" % (chr_, left + 1, right + 1)]
-                    key = tuple(regions or ())
-                    if key not in linear_inputs:
-                        linear_inputs[key] = LinearInput(alignment_fname, regions)
+                    key = (linear_fname,) + tuple(regions or ())
+                    if linear_text is None and key not in linear_inputs:
+                        linear_inputs[key] = LinearInput(linear_fname, regions)
                     try:
-                        res = type_locus_linear(pl, None, aligner, linear_input=linear_inputs[key])
+                        # (the records the hgx aligner made here are counted by the hisat2 rule: every group counts; a file that the
+                        # caller gave is counted under the name the caller gave, as before)
+                        rule = "hisat2" if aligner == "hgx" and given_alignment_fname == "" else aligner
+                        if linear_text is not None:
+                            res = type_locus_linear(pl, linear_text, rule)
+                        else:
+                            res = type_locus_linear(pl, None, rule, linear_input=linear_inputs[key])
                     finally:
                         if not getattr(pl, "cached", False):
                             pl.close()
                     say("\n".join(report_lines_linear(res, output_allele_counts, best_alleles)))
                     if res.error is not None:                      # the counts are printed before the abundance step raises
                         raise res.error
+                if remove_linear_file:                             # core:2144-2145
+                    for key in [k_ for k_ in linear_inputs if k_[0] == linear_fname]:
+                        linear_inputs.pop(key).close()
+                    for f in [linear_fname] + [linear_fname + ext for ext in (".bai", ".unsorted")]:
+                        if os.path.exists(f):
+                            os.remove(f)
                 continue
             if index_type != "graph":
                 raise NotImplementedError("index type %r is not on the accelerated path" % (index_type,))

@@ -1035,6 +1035,40 @@ int hgx_align_reads_dev(hgx_align_index *ix, const hgx_reads *reads, const hgx_a
 int hgx_align_reads_dev_resident(hgx_align_index *ix, const hgx_reads *reads, const hgx_align_opts *opts, const hgx_align_more *more,
                                  hgx_alignment **out, void *stream);
 
+/* ---- the "hgx" aligner on a LINEAR index: a family's reads against its ALLELE SEQUENCES -----------------------------
+ * What the reference runs `hisat2 -k 10` / `bowtie2 -k 10` on a linear index for (typing_common.py:610-641, 985-1056): the records the
+ * linear typing (hgx_linear_*) groups by read.  NOT HISAT2 or Bowtie2, and compared with neither: ungapped, end to end, at most
+ * max_edits mismatches, up to k records per read, mates placed independently.  The rule in plain Python: tests/align_linear_ref.py.
+ * A hit is (allele, pos0, strand) with Hamming distance NM <= max_edits (a read N and an allele base outside ACGT mismatch) and one of
+ * the read's first min(max_edits + 1, L / 16) disjoint 16-mers matching exactly at its place; a read's hits are ordered by (NM, allele
+ * index, pos0, strand) and the first min(k, hits) are written: FLAG 0x1 / 0x40 / 0x80 (paired), 0x10, 0x100 (all but the read's first),
+ * 0x8 (the mate wrote nothing); MAPQ 60 for a read with one hit, else 1; CIGAR <L>M; RNEXT *, PNEXT 0, TLEN 0 (the linear typing reads
+ * none of them); tags AS:i:<-6 NM>, NM:i, MD:Z, NH:i:<records of the read>.  Text: @HD, an @SQ per sequence, records in read order.
+ * align_linear_index_create (typing_common.py:610-641, 985-1056): the index of n_seqs named sequences (the caller leaves the backbone
+ * out: the linear typing skips it); fewer than 1 or 2^20 and more sequences, one of 2^20 bases or more, 2^31 bases in all: HGX_EINVAL.
+ * align_linear_reads (typing_common.py:610-641, 985-1056): inputs as hgx_align_reads takes them (one or two FASTA / FASTQ[.gz] paths
+ * or texts).  opts.bytes = sizeof(hgx_align_linear_opts) of the caller's build; max_edits 0 .. 4 and k 1 .. 1024, anything else is
+ * HGX_EINVAL; fastq 1, 0 or -1 (by each input's first byte); route 0 auto (the kernels from reads x sequences >= 16 384, the measured break-even rounded up; the host route below), 1 host,
+ * 2 the kernels (csrc/hgx_align_linear.hip), which decline to the host route with a code of HGX_ALNL_DECLINE_* (csrc/
+ * hgx_align_linear_core.hpp): 2 a read longer than 256 bases, 3 one read's (pair's) candidates alone pass the chunk budget, 4 a record
+ * longer than 4 000 bytes.  The bytes are the same on either route.
+ * align_linear_reads_dev (typing_common.py:610-641, 985-1056): the same over an hgx_reads made beforehand (opts.fastq is not read); a
+ * table in HBM is read where it lies.
+ * align_linear_last (typing_common.py:610-641, 985-1056): of the calling thread's last call -- route (2 the kernels, 0 the host
+ * route), reads given, reads with a record, records written, seed-table entries looked at, decline code. */
+typedef struct hgx_align_linear_opts {
+    int32_t bytes;             /* sizeof(hgx_align_linear_opts) of the caller's build */
+    int32_t max_edits, k, fastq, route;
+} hgx_align_linear_opts;
+typedef struct hgx_align_linear_index hgx_align_linear_index;
+int hgx_align_linear_index_create(hgx_align_linear_index **out, int32_t n_seqs, const char *const *names, const char *const *seqs);
+int hgx_align_linear_index_free(hgx_align_linear_index *ix);
+int hgx_align_linear_reads(hgx_align_linear_index *ix, int32_t n_inputs, const char *const *paths, const char *const *texts,
+                           const size_t *text_bytes, const hgx_align_linear_opts *opts, char **sam_out, size_t *n_bytes_out);
+int hgx_align_linear_reads_dev(hgx_align_linear_index *ix, const hgx_reads *reads, const hgx_align_linear_opts *opts, char **sam_out,
+                               size_t *n_bytes_out);
+int hgx_align_linear_last(int32_t *route, int64_t *reads, int64_t *aligned, int64_t *records, int64_t *candidates, int32_t *decline_code);
+
 #ifdef __cplusplus
 }
 #endif
