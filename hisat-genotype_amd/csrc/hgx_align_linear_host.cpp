@@ -92,8 +92,12 @@ void hgx_alnl_device_free(hgx_align_linear_index *) {}
 
 // typing_common.py:610-641 (the linear index the reference builds from the allele sequences with hisat2-build / bowtie2-build)
 extern "C" int hgx_align_linear_index_create(hgx_align_linear_index **out, int32_t n_seqs, const char *const *names, const char *const *seqs) {
-    if (!out || n_seqs < 1 || n_seqs >= (1 << HGX_ALNL_ALLELE_BITS) || !names || !seqs) {
+    if (!out || n_seqs < 1 || !names || !seqs) {
         hgx_set_error("invalid argument: hgx_align_linear_index_create");
+        return HGX_EINVAL;
+    }
+    if (n_seqs >= (1 << HGX_ALNL_ALLELE_BITS)) {
+        hgx_set_error("hgx_align_linear_index_create: %d sequences (up to 2^20 - 1)", (int)n_seqs);
         return HGX_EINVAL;
     }
     *out = nullptr;

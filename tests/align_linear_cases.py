@@ -1,6 +1,9 @@
 """The case table of the "hgx" aligner on a linear index: the smallest shapes at which it can go wrong, used by
 tests/test_align_linear_ref.py (the statement itself), tests/test_align_linear_host.py (host route == statement) and
-tests/test_gpu_align_linear.py (kernels == statement).  Families have <= 130 alleles of <= 600 bases.
+tests/test_gpu_align_linear.py (kernels == statement).  Most families have <= 130 alleles of <= 600 bases; the cases of WIDE reach
+the upper bits of the key's fields: position 65 536 and the last accepted one (2^20 - 2), allele 65 536 and above.  The top of the
+ALLELE field (2^20 - 1 alleles) would be a header of 20 MB: it is deliberately left to the refusal test of
+tests/test_align_linear_host.py (test_limits_of_the_index).  Every case costs the statement less than about 5 s.
 
 A case: dict(name, Genes, refGenes, reads = [records] or [mate-1 records, mate-2 records] with a record = (qname, seq, qual or None),
 max_edits, k, decline = the code the kernels' route must report (0: it gives the bytes), budget = the value of the test switch
@@ -17,6 +20,14 @@ _OTHER = {"A": "C", "C": "G", "G": "T", "T": "A"}
 def rnd(seed, n):
     r = random.Random(seed)
     return "".join(r.choice("ACGT") for _ in range(n))
+
+
+_ACGT_OF_BYTE = bytes(b"ACGT"[b & 3] for b in range(256))
+
+
+def rnd_long(seed, n):
+    """As rnd() for the sequences of 10^5 .. 10^6 bases (one call of the generator, not one per base)."""
+    return random.Random(seed).randbytes(n).translate(_ACGT_OF_BYTE).decode()
 
 
 def mut(s, positions, to=None):
@@ -77,8 +88,8 @@ def _edit_cases():
     out = [case("edit-positions", fam, reads)]
     w5 = [mut(w, [3, 20, 40, 52, 70][:n]) for n in range(6)] + [mut(w, [90, 91, 92, 93]), mut(w, [3, 20, 40, 52, 90])]
     reads = [("e%d" % n, s, None) for n, s in enumerate(w5)]
-    out.append(case("max-edits-0", fam, reads, max_edits=0))
-    out.append(case("max-edits-4", fam, reads, max_edits=4))
+    for me in (0, 4, 1, 3):
+        out.append(case("max-edits-%d" % me, fam, reads, max_edits=me))
     return out
 
 
@@ -160,7 +171,17 @@ def _chunk_cases():
         out.append(case("cut-records%+d" % d, fam, reads, budget="%d,%d" % (1 << 20, r2 + d)))
     for n in (3, 4, 5, 8, 9):
         out.append(case("span-4-reads-%d" % n, fam, reads[:n], budget="%d,%d,4" % (1 << 20, 1 << 20)))
-    m1 = [(q, s, None) for q, s, _ in reads[:6]]
+    # the same cuts at the other two slot widths: the kernels keep 4 seed slots per read at max_edits 0 and 1, 8 at 2 and 3, 12 at 4,
+    # and a chunk's planes, counts and buckets start at (its first read) x (that width)
+    for me in (1, 4):
+        units = unit_counts(case("probe", fam, reads, max_edits=me))
+        c2 = units[0][0] + units[1][0]
+        assert units[2][0] > 1
+        for d in (-1, 0, 1):
+            out.append(case("cut-candidates%+d-e%d" % (d, me), fam, reads, max_edits=me, budget="%d" % (c2 + d)))
+        for n in (3, 4, 5, 8, 9):
+            out.append(case("span-4-reads-%d-e%d" % (n, me), fam, reads[:n], max_edits=me, budget="%d,%d,4" % (1 << 20, 1 << 20)))
+    m1 =[(q, s, None) for q, s, _ in reads[:6]]
     m2 = [(q, ref.revcomp(a[150 + 5 * i:250 + 5 * i]), None) for i, (q, _, _) in enumerate(m1)]
     pr = case("probe", fam, [m1, m2])
     pu = unit_counts(pr)
@@ -207,9 +228,187 @@ def _size_cases():
     return out
 
 
+def _spoil(s, seeds):
+    """A substitution in the middle of each of the 16-mers `seeds` of s."""
+    return mut(s, [16 * j + 7 for j in seeds])
+
+
+def _border_cases():
+    """Windows that would run over an allele's border: the text is the alleles concatenated, so such a window MATCHES; only the test
+    0 <= pos0 <= len - L keeps it out.  The first exact seed takes a hit, so a read that starts in front of a border carries a
+    substitution in every seed that lies wholly or partly in front of it: else the border-side seeds, which the rule silences, would
+    hide a missing test.  Only `control` hits."""
+    A, B, C = rnd(100, 200), rnd(101, 200), rnd(102, 200)
+    fam = [("A", A), ("B", B), ("C", C)]
+    s20, s40 = _spoil(A[-20:] + B[:80], (0, 1)), _spoil(A[-40:] + B[:60], (0, 1, 2))
+    reads = [("end-ab", A[-60:] + B[:40], None), ("end-bc-rev", ref.revcomp(B[-60:] + C[:40]), None), ("end-a99", A[-99:] + B[:1], None),
+             ("start-20", s20, None), ("start-20-rev", ref.revcomp(s20), None), ("start-40", s40, None), ("start-40-rev", ref.revcomp(s40), None),
+             ("start-1", A[-1:] + B[:99], None), ("start-1-spoiled", _spoil(A[-1:] + B[:99], (0,)), None),
+             ("seed-2-at-0-of-first", rnd(103, 16) + A[:84], None), ("seed-3-at-0-of-first", rnd(104, 32) + A[:68], None),
+             ("past-the-last", C[-60:] + "A" * 40, None), ("past-the-last-rev", ref.revcomp(C[-60:] + "A" * 40), None),
+             ("control", B[50:150], None)]
+    return [case("borders-e%d" % me, fam, reads, max_edits=me) for me in (2, 4)]
+
+
+def _end_seed_cases():
+    """Reads with ONE seed that is an allele's last or first 16-mer: the ends of the seed table, in the bytes."""
+    fam = [("01", rnd(110, 300)), ("02", rnd(111, 250))]
+    X, Y = fam[0][1], fam[1][1]
+    reads = [("last-16", X[-16:], None), ("last-31", X[-31:], None), ("last-31-mm", mut(X[-31:], [30]), None),
+             ("first-16-rev", ref.revcomp(X[:16]), None), ("first-16", X[:16], None), ("last-16-of-2", Y[-16:], None),
+             ("last-16-of-2-rev", ref.revcomp(Y[-16:]), None)]
+    return [case("one-seed-at-the-ends", fam, reads)]
+
+
+MIXED_LENGTHS = (100, 16, 256, 31, 64, 15, 65, 40, 128, 129, 17, 192)
+
+
+def _mixed_length_cases():
+    """Reads of different lengths in ONE call, each with a mismatch at its last base (the 16-base read, whose only seed that would
+    spoil, is exact): a route that takes another read's length sees no mismatch, or a window of junk.  With the library's budgets,
+    with a cut behind (nearly) every read, behind the second read, with spans of 2 and 4 reads; as pairs whose mates differ in length,
+    the 15-base mate (no seed) first in one pair and last in another; and with a last read of 257 bases, which declines."""
+    T = rnd(120, 700)
+    fam = [("01", T), ("02", mut(T, [300])), ("03", rnd(121, 300))]
+    reads = []
+    for n, L in enumerate(MIXED_LENGTHS):
+        w = T[23 * n + 5:23 * n + 5 + L]
+        reads.append(("len%d" % L, w if L == 16 else mut(w, [L - 1]), None))
+    u = unit_counts(case("probe", fam, reads))
+    big = max(c for c, _ in u)
+    assert u[5][0] == 0 and min(c for i, (c, _) in enumerate(u) if i != 5) > 0
+    out = [case("mixed-lengths", fam, reads),
+           case("mixed-lengths-own-chunks", fam, reads, budget="%d" % big),            # (a read without candidates joins the chunk in front)
+           case("mixed-lengths-cut-behind-2", fam, reads, budget="%d" % (u[0][0] + u[1][0])),
+           case("mixed-lengths-span-2", fam, reads, budget="%d,%d,2" % (1 << 20, 1 << 20)),
+           case("mixed-lengths-span-4", fam, reads, budget="%d,%d,4" % (1 << 20, 1 << 20))]
+    # spans of four reads AND a cut behind (nearly) every read, at each slot width (4, 8, 12 slots per read): a chunk that starts
+    # neither at its span's first read nor at the call's -- the only place where (first - span start) x width differs from both
+    for me in (1, 2, 4):
+        big = max(c for c, _ in unit_counts(case("probe", fam, reads, max_edits=me)))
+        out.append(case("mixed-lengths-span-4-cuts-e%d" % me, fam, reads, max_edits=me, budget="%d,%d,4" % (big, 1 << 20)))
+    by = {int(q[3:]): (q, s, None) for q, s, _ in reads}
+    pairs = [(100, 16), (256, 31), (15, 64), (65, 40), (128, 129), (17, 192), (64, 15)]
+    m1 = [("p%d" % i, by[a][1], None) for i, (a, _) in enumerate(pairs)]
+    m2 = [("p%d" % i, ref.revcomp(by[b][1]), None) for i, (_, b) in enumerate(pairs)]
+    pu = unit_counts(case("probe", fam, [m1, m2]))
+    out += [case("mixed-pairs", fam, [m1, m2]),
+            case("mixed-pairs-own-chunks", fam, [m1, m2], budget="%d" % max(c for c, _ in pu)),
+            case("mixed-pairs-span-2", fam, [m1, m2], budget="%d,%d,2" % (1 << 20, 1 << 20))]
+    out.append(case("mixed-257-last", fam, reads[:5] + [("len257", mut(T[40:297], [256]), None)], decline=DECLINE_READ_LEN))
+    return out
+
+
+def _empty_step_cases():
+    """Chunks that append nothing between chunks that do: with spans of two reads, a span whose reads have no candidate (a chunk of
+    no candidates), then a read with candidates and no hit in a chunk of its own (a chunk of no hits), then reads with hits again."""
+    A, B = rnd(130, 200), rnd(131, 200)
+    fam = [("A", A), ("B", B)]
+    reads = [("h0", A[10:110], None), ("h1", B[20:120], None), ("junk0", rnd(132, 100), None), ("junk1", rnd(133, 100), None),
+             ("straddle", A[-60:] + B[:40], None), ("h2", B[60:160], None), ("h3", A[90:190], None), ("junk2", rnd(134, 100), None)]
+    u = [c for c, _ in unit_counts(case("probe", fam, reads))]
+    assert u[2] == u[3] == u[7] == 0 and min(u[0], u[1], u[4], u[5], u[6]) > 0
+    lim = max(u)
+    assert u[0] + u[1] > lim and u[4] + u[5] > lim
+    return [case("empty-steps-between-chunks", fam, reads, budget="%d,%d,2" % (lim, 1 << 20))]
+
+
+def _shift_cases():
+    """Windows at every one of the 64 bit offsets of the plane words, one and two words long and at every word count of a read."""
+    S = rnd(140, 400)
+    fam = [("01", S), ("02", mut(S, [399]))]
+    reads = [("at%d" % p, mut(S[p:p + 70], [69]), None) for p in range(64)]
+    reads += [("len%d" % L, mut(S[37:37 + L], [0, L - 1]), None) for L in (63, 64, 65, 127, 128, 129, 191, 192, 193, 255, 256)]
+    return [case("every-shift", fam, reads)]
+
+
+def _tandem_cases():
+    """Short tandem repeats (the CODIS loci): a read inside the repeat has a candidate at every period of every allele."""
+    f1, f2 = rnd(150, 40), rnd(151, 40)
+    fam = [("%d" % n, f1 + "AGAT" * n + f2) for n in (8, 12, 30, 31)] + [("polyA", "A" * 150)]
+    reads = [("repeat", "AGAT" * 20, None), ("anchored", f1[-20:] + "AGAT" * 15, None), ("through-12", f1[-26:] + "AGAT" * 12 + f2[:26], None),
+             ("poly-a", "A" * 100, None), ("poly-a-mm", mut("A" * 100, [50]), None), ("phase", "GATA" * 20, None)]
+    return [case("tandem", fam, reads), case("tandem-e4-k1000", fam, reads, max_edits=4, k=1000)]
+
+
+def _n_over_a_cases():
+    """A read N where the allele has A (the planes code A as 00: without the mask an N seeds as A), and reads of A alone."""
+    X = rnd(160, 300)
+    w = X[100:200]
+
+    def n_at(seed):
+        return mut(w, [next(i for i in range(16 * seed, 16 * seed + 16) if w[i] == "A")], "N")
+    fam = [("01", X), ("02", mut(X, [250])), ("polyA", "A" * 120), ("A-N-A", "A" * 60 + "N" + "A" * 59)]
+    reads = [("n-seed-0", n_at(0), None), ("n-seed-1", n_at(1), None), ("n-seed-2", n_at(2), None), ("n-seed-0-rev", ref.revcomp(n_at(0)), None),
+             ("n-seed-1-rev", ref.revcomp(n_at(1)), None), ("a16", "A" * 16, None), ("a20", "A" * 20, None), ("a47", "A" * 47, None),
+             ("t20", "T" * 20, None), ("a30n", "A" * 30 + "N", None)]
+    return [case("n-over-a", fam, reads), case("n-over-a-e4-k200", fam, reads, max_edits=4, k=200)]
+
+
+def _k_cap_cases():
+    """k = 1 024, the cap: a read with exactly 1 024 hits, and one with more."""
+    out = []
+    for name, n in (("k-cap-exactly-1024-hits", 1024 + 19), ("k-cap-1081-hits", 1100)):
+        out.append(case(name, [("01", rnd(170, 100)), ("polyA", "A" * n)], [("a20", "A" * 20, None), ("t20", "T" * 20, None)], k=1024))
+    return out
+
+
+def _short_allele_cases():
+    """Alleles of 0, 1, 15 and 16 bases among others (an empty sequence is accepted and gets its @SQ line), lower-case allele text."""
+    X, Y, Z = rnd(180, 200), rnd(181, 120), rnd(182, 120)
+    fam = [("01", X), ("empty", ""), ("one", "C"), ("fifteen", X[:15]), ("sixteen", X[20:36]), ("lower", Y.lower()),
+           ("half-lower", Z[:60].lower() + Z[60:]), ("last", X[100:180])]
+    reads = [("in-sixteen", X[20:36], None), ("at-0", X[:16], None), ("in-lower", Y[30:70], None), ("in-lower-mm", mut(Y[30:90], [59]), None),
+             ("over-the-case-change", Z[30:90], None), ("over-the-case-change-rev", ref.revcomp(Z[20:100]), None), ("in-last", X[100:180], None),
+             ("lower-read", Y[10:60].lower(), None)]
+    return [case("short-and-lower-alleles", fam, reads)]
+
+
+def _wide_cases():
+    """The upper bits of the key's position and allele fields."""
+    out = []
+    W = rnd_long(190, 70000)
+    at = lambda p: W[p:p + 100]
+    reads = [("at-0", at(0), None), ("at-1023", at(1023), None), ("at-1024", at(1024), None), ("at-65535-mm", mut(at(65535), [50]), None),
+             ("at-65536-rev", ref.revcomp(at(65536)), None), ("at-last", W[-100:], None)]
+    out.append(case("wide-pos", [("small", rnd(191, 150)), ("wide", W)], reads))
+    # 66 000 alleles of 20 bases; alleles 3, 300 and 65 999 are equal: with k = 2 the order over the high allele bits decides
+    S = rnd_long(192, 20 * 66000)
+    al = [S[20 * i:20 * i + 20] for i in range(66000)]
+    al[300] = al[65999] = al[3]
+    fam = [("%05d" % i, s) for i, s in enumerate(al)]
+    reads = [("a0", al[0], None), ("a255", al[255], None), ("a256-rev", ref.revcomp(al[256]), None), ("a65535", al[65535], None),
+             ("a65536", al[65536], None), ("triple", al[3], None), ("triple-mm", mut(al[3], [19]), None)]
+    out.append(case("wide-alleles", fam, reads, k=2))
+    # the longest allele the index takes, behind a short one: positions with the field's top bit set, and the last window
+    T = rnd_long(193, (1 << 20) - 1)
+    out.append(case("top-of-pos-field", [("short", rnd(194, 77)), ("longest", T)],
+                    [("at-524288", T[524288:524388], None), ("last-100-rev", ref.revcomp(T[-100:]), None)], max_edits=0))
+    return out
+
+
+LINE_MAX = 4000                # HGX_ALNL_LINE_MAX: the bytes of the longest record, its '\n' counted, that the kernels write
+
+
+def _line_limit_cases():
+    """A record of exactly LINE_MAX bytes (the kernels give the bytes) and of one byte more (LINE), sized from the statement's line."""
+    fam = [("01", rnd(200, 300)), ("02", rnd(201, 300))]
+    a = fam[0][1]
+    front = ("front", a[10:110], None)
+    line = ref.align_text(ref.index_of(*family(fam)), [[("n", a[100:200], None)]]).split("\n")[3]
+    assert line.startswith("n\t0\t")
+    out = []
+    for name, extra, decline in (("line-exactly-at-the-limit", 0, 0), ("line-one-byte-above-the-limit", 1, DECLINE_LINE)):
+        qname = "n" * (LINE_MAX - len(line) - 1 + 1 + extra)
+        out.append(case(name, fam, [front, (qname, a[100:200], None)], decline=decline))
+    return out
+
+
 def _all():
     out = []
-    for f in (_length_cases, _n_cases, _edit_cases, _position_cases, _bucket_cases, _k_cases, _pair_cases, _chunk_cases, _size_cases):
+    for f in (_length_cases, _n_cases, _edit_cases, _position_cases, _bucket_cases, _k_cases, _pair_cases, _chunk_cases, _size_cases,
+              _border_cases, _end_seed_cases, _mixed_length_cases, _empty_step_cases, _shift_cases, _tandem_cases, _n_over_a_cases,
+              _k_cap_cases, _short_allele_cases, _wide_cases, _line_limit_cases):
         out += f()
     return out
 

@@ -88,6 +88,32 @@ def test_refused_options():
         align.LinearAlignIndex({"G": {"G*BACKBONE": "ACGT"}}, {"G": "G*BACKBONE"})        # nothing but the backbone: no sequence to index
 
 
+def test_limits_of_the_index():
+    """The key has 20 bits for the allele and 20 for the position: the index build takes a sequence of 2^20 - 1 bases and refuses one
+    of 2^20; it refuses 2^20 sequences (the table's cases stop at 66 000: 2^20 - 1 sequences would be a header of 20 MB).  An empty
+    sequence is accepted (the case short-and-lower-alleles aligns to such an index)."""
+    import ctypes as C
+
+    def create(names, seqs):
+        h = C.c_void_p()
+        try:
+            capi.check(capi.lib().hgx_align_linear_index_create(C.byref(h), C.c_int32(len(names)), (C.c_char_p * len(names))(*names),
+                                                                (C.c_char_p * len(seqs))(*seqs)))
+        finally:
+            if h:
+                capi.lib().hgx_align_linear_index_free(h)
+    longest = lc.rnd_long(7, (1 << 20) - 1).encode()
+    create([b"short", b"longest"], [b"ACGT" * 5, longest])
+    with pytest.raises(capi.HgxError) as e:
+        create([b"short", b"longer"], [b"ACGT" * 5, longest + b"A"])
+    assert e.value.code == -1 and "sequence 1 has 1048576 bases" in str(e.value) and "2^20 - 1" in str(e.value)
+    create([b"a", b"empty"], [b"ACGT" * 5, b""])
+    n = 1 << 20
+    with pytest.raises(capi.HgxError) as e:
+        create([b"s"] * n, [b"ACGTACGTACGTACGTACGT"] * n)
+    assert e.value.code == -1 and "1048576 sequences" in str(e.value) and "2^20 - 1" in str(e.value)
+
+
 def test_index_order_and_cache():
     Genes = {"B": {"B*BACKBONE": "AC", "B*02": "ACGT", "B*01": "AAAA"}, "A": {"A*01": "CC", "A*BACKBONE": "GG"}}
     refGenes = {"B": "B*BACKBONE", "A": "A*BACKBONE"}

@@ -21,7 +21,41 @@ def test_seeded_hits_equal_the_brute_force_where_seeds_are_implied(name):
                 checked += 1
             else:
                 assert set(ref.hits(alleles, seq, c["max_edits"])) <= set(ref.hits_brute(alleles, seq, c["max_edits"]))
-    assert checked or name in ("length-15", "length-16", "length-47")
+    assert checked or name in ("length-15", "length-16", "length-47", "one-seed-at-the-ends", "k-cap-exactly-1024-hits", "k-cap-1081-hits",
+                               "wide-alleles")           # (every read of these is shorter than 16 (max_edits + 1) bases)
+
+
+def test_the_cases_hold_what_their_names_say():
+    """What the table's border, k-cap, empty-step, wide and record-length cases rest on, stated on the statement's own results."""
+    def hits_by_read(name):
+        c = lc.BY_NAME[name]
+        alleles = ref.index_of(c["Genes"], c["refGenes"])
+        return {q: ref.hits(alleles, s, c["max_edits"]) for recs in c["reads"] for q, s, _ in recs}
+    for name in ("borders-e2", "borders-e4"):
+        h = hits_by_read(name)
+        assert [q for q in h if h[q]] == ["control"] and h["control"] == [(0, 1, 50, 0)]
+        c = lc.BY_NAME[name]                          # ... and every other read's window DOES match where the alleles are one text
+        text = "".join(s for _, s in ref.index_of(c["Genes"], c["refGenes"])) + "A" * 64
+        one = [("all", text)]
+        for q in ("end-ab", "end-bc-rev", "end-a99", "start-20", "start-20-rev", "start-1", "start-1-spoiled", "past-the-last", "past-the-last-rev"):
+            assert ref.hits(one, dict((r[0], r[1]) for r in c["reads"][0])[q], c["max_edits"]), q
+    assert len(hits_by_read("borders-e4")) == 14
+    h = hits_by_read("k-cap-exactly-1024-hits")
+    assert len(h["a20"]) == 1024 == len(h["t20"])
+    assert len(hits_by_read("k-cap-1081-hits")["a20"]) == 1081
+    h = hits_by_read("empty-steps-between-chunks")
+    assert [bool(h[q]) for q in ("h0", "h1", "junk0", "junk1", "straddle", "h2", "h3", "junk2")] == [True, True, False, False, False, True, True, False]
+    h = hits_by_read("wide-pos")
+    assert [h[q][0][1:] for q in h] == [(1, 0, 0), (1, 1023, 0), (1, 1024, 0), (1, 65535, 0), (1, 65536, 1), (1, 69900, 0)]
+    h = hits_by_read("wide-alleles")
+    assert [x[1] for x in h["triple"]] == [3, 300, 65999] and [x[1] for x in h["a65536"]] == [65536]
+    assert hits_by_read("top-of-pos-field") == {"at-524288": [(0, 1, 524288, 0)], "last-100-rev": [(0, 1, (1 << 20) - 1 - 100, 1)]}
+    h = hits_by_read("every-shift")
+    assert all(h["at%d" % p] == [(1, 0, p, 0), (1, 1, p, 0)] for p in range(64))
+    for name, n in (("line-exactly-at-the-limit", lc.LINE_MAX), ("line-one-byte-above-the-limit", lc.LINE_MAX + 1)):
+        assert max(len(l) + 1 for l in lc.ref_text(name).decode().split("\n")[:-1]) == n
+    h = hits_by_read("mixed-lengths")
+    assert [q for q in h if not h[q]] == ["len15"]
 
 
 def test_random_reads_against_the_brute_force():

@@ -41,9 +41,12 @@ def test_kernels_write_the_statements_bytes(name):
         assert last["candidates"] == sum(ref.candidates(alleles, s, c["max_edits"]) for recs in c["reads"] for _, s, _ in recs)
 
 
-@pytest.mark.parametrize("name", ["pairs", "single-end-fastq", "cut-candidates+0"])
+@pytest.mark.parametrize("name", ["pairs", "single-end-fastq", "cut-candidates+0", "mixed-lengths", "mixed-lengths-own-chunks", "mixed-lengths-span-2",
+                                  "mixed-pairs", "mixed-pairs-own-chunks", "tandem", "mixed-257-last"])
 def test_a_read_table_made_on_the_device(name):
-    """engine.Reads.from_text (the table made by the kernels where the text lies) in place of the loader."""
+    """engine.Reads.from_text (the table made by the kernels where the text lies) in place of the loader.  Reads of
+    mixed lengths: the table's len[] is indexed by the read's place in the CALL, not in its chunk.  mixed-257-last: the table is made
+    (257 bases are within the table's limit) and the aligner declines on the table's max_len; text and table are copied down."""
     c = lc.BY_NAME[name]
     capi.set_device(0)
     with engine.test_switches(front="device"):
@@ -53,8 +56,10 @@ def test_a_read_table_made_on_the_device(name):
         got, last = _device(c, reads)
     finally:
         reads.close()
-    assert (last["route"], last["decline"]) == (2, 0), last
+    assert (last["route"], last["decline"]) == ((0, c["decline"]) if c["decline"] else (2, 0)), last
     assert got == lc.ref_text(name)
+    n, aligned, records = ref.counters(ref.index_of(c["Genes"], c["refGenes"]), c["reads"], c["max_edits"], c["k"])
+    assert (last["reads"], last["aligned"], last["records"]) == (n, aligned, records)
 
 
 def test_auto_takes_the_kernels_from_the_gate_on():

@@ -4,8 +4,9 @@
 //       hisat-genotype_amd/csrc/hgx_align_host.cpp hisat-genotype_amd/csrc/hgx_align_linear_host.cpp tools/align_linear_host_main.cpp \
 //       -lz -o align_linear_host_main
 //   align_linear_host_main <index file> <max_edits> <k> <reads> [<mate reads>]  > out.sam
-// The index file is text: "<n_seqs>", then one "<name> <sequence>" line per sequence in index order.  Nothing of the GPU library is
-// linked: the kernels' route is a stub that declines.
+// The index file is text: "<n_seqs>", then one "<name> <length> <sequence>" line per sequence in index order ("<name> 0" for an empty
+// sequence).  Nothing of the GPU library is linked: the kernels' route is a stub that declines.  The last line of stderr holds the
+// call's counters (hgx_align_linear_last).
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -23,8 +24,12 @@ int main(int argc, char **argv) {
     int n = 0;
     in >> n;
     std::vector<std::string> names(n > 0 ? n : 0), seqs(n > 0 ? n : 0);
-    for (int a = 0; a < n; ++a) in >> names[a] >> seqs[a];
-    if (!in) { fprintf(stderr, "bad index file\n"); return 2; }
+    for (int a = 0; a < n; ++a) {
+        long len = -1;
+        in >> names[a] >> len;
+        if (len > 0) in >> seqs[a];                 // (an empty sequence has no third field)
+        if (!in || len < 0 || (long)seqs[a].size() != len) { fprintf(stderr, "bad index file (sequence %d)\n", a); return 2; }
+    }
     std::vector<const char *> c_names, c_seqs;
     for (auto &s : names) c_names.push_back(s.c_str());
     for (auto &s : seqs) c_seqs.push_back(s.c_str());
